@@ -1,16 +1,24 @@
 #!/usr/bin/env python3
 """bench.py — entity-updates/s of the ECS world tick (transform + physics) on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--no-gather] [--no-cpu] [--no-configs]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--no-gather] [--dump-outputs DIR]
+                    [--full [--no-cpu] [--no-configs] [--repeats R]]
 
 A "step" is one fixed-step tick of the whole (sharded) world: the fused integrate + transform-hierarchy
 kernel over every tile, and for N > 1 the packing of this rank's root world matrices plus ONE RCCL
 all-gather of them (BASELINE.json configs[4]).  Inputs are synthetic and resident in
 HBM before the timed region.  Rank 0 prints one JSON line.
 
+A plain run sets up, warms up, times exactly K steps in one region and prints the line (`ms_per_step` = region / K).
+`--full` adds everything else the benchmark measures or checks: the median of R = 5 regions of K steps, the CPU legs
+(`cpu_baseline`, `cpu_allcore`), the sampled parity check against the CPU port and, for N = 1, the `configs` array.
+`--dump-outputs DIR` writes what the last timed step left on the device (rank 0's shard) as DIR/<name>.npy after the
+timed steps: world matrices, positions, rotationEuler and linear velocities of a fixed, seeded sample of at most
+DUMP_SAMPLE entities, and the sample's entity ids (float64).
+
 Workloads (BASELINE.json `configs`):
-    N = 1 : "flat1m"    — configs[1]: 1,000,000 entities, flat, every entity a Dynamic body (the headline line); the
-            same run then measures the other single-GPU configurations into the line's `configs` array: chains4
+    N = 1 : "flat1m"    — configs[1]: 1,000,000 entities, flat, every entity a Dynamic body (the headline line); with
+            --full the same run then measures the other single-GPU configurations into the line's `configs` array: chains4
             (configs[2]), cube4m (configs[3], with the broadphase), flat 16 M (the working set beyond the Infinity
             Cache: the honest HBM figure) and flat1m in Bullet's own orientation scheme.
     N > 1 : "subtree64" — configs[4] (variant 5b): 2,000,000 entities PER GPU in 64-node subtrees whose
@@ -49,6 +57,8 @@ sys.path.insert(0, ROOT)
 # all of them in the first ticks after a re-pose, and every spinning body) — 0.12 x 44 B on top of the default scheme's bytes.
 BASIS_EXTRA_BYTES = 5.3
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md); ~6300 GB/s is the measured copy rate
+DUMP_SAMPLE = 1 << 18  # --dump-outputs: entities sampled from a larger shard (25 floats + 1 double each: 28 MB at most)
+DUMP_SEED = 20240607   # the sample is drawn once from this seed: the same entities in every run of the same arguments
 STUB = os.environ.get("BGE_BENCH_STUB") == "1"  # tests/test_bench_launcher.py only: control flow over gloo, no GPU work
 
 
@@ -71,17 +81,27 @@ def parse_args(argv=None):
     ap.add_argument("--bullet-basis", action="store_true",
                     help="BGE_TICK_BULLET_BASIS: Bullet's basis round trip + euler rewrite for every Dynamic body each tick "
                          "(+44 B per body: quaternion in and out, rotationEuler out); default: zero-spin bodies keep theirs")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg and the sampled parity check")
-    ap.add_argument("--no-configs", action="store_true", help="N = 1: skip the `configs` array (other single-GPU configurations)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: median of --repeats regions, the CPU legs, the sampled parity check and "
+                         "(N = 1) the `configs` array; a plain run times exactly --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (rank 0's shard, a seeded sample of at most "
+                         f"{DUMP_SAMPLE} entities) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the cpu_baseline leg and the sampled parity check")
+    ap.add_argument("--no-configs", action="store_true", help="with --full, N = 1: skip the `configs` array (other single-GPU configurations)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target duration of the cpu_baseline sample")
     ap.add_argument("--cpu-threads", type=int, default=16, help="threads of the all-core CPU leg (a 1-GPU box's CPU share)")
-    ap.add_argument("--repeats", type=int, default=5,
+    ap.add_argument("--repeats", type=int, default=None,
                     help="the K-step timed region is run this many times back to back (each bracketed by barrier + synchronize, "
-                         "max over ranks); the MEDIAN region is reported — a 20-launch region is 0.5 ms, one cold sample of it is noise")
+                         "max over ranks); the MEDIAN region is reported — a 20-launch region is 0.5 ms, one cold sample of it is noise "
+                         "(default: 5 with --full, else 1, so that --steps is the number of timed steps)")
     ap.add_argument("--deadline", type=float, default=180.0,
                     help="seconds any one blocking phase of a rank may take (and, x3 = 540 s, the launcher's limit for the whole job: "
                          "inside the driver's 600 s)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    return args
 
 
 # --------------------------------------------------------------------------------------------------------- launcher
@@ -271,6 +291,34 @@ def load_traffic(workload_name, entities):
         return per_entity * entities, t.get("_provenance", "profiles/traffic.json (committed rocprofv3 --pmc passes, 2 x FETCH_SIZE + WRITE_SIZE)")
     except Exception:
         return None, "no committed PMC measurement for this workload"
+
+
+def dump_outputs(world, out_dir, first, chunk=1 << 20):
+    """--dump-outputs: the state the last timed step left on the device, for a fixed, seeded sample of this shard's entities
+    (all of them when the shard is no larger than DUMP_SAMPLE), read back chunk by chunk so that host memory stays bounded."""
+    import numpy as np
+    n = world.n
+    if n <= DUMP_SAMPLE:
+        idx = np.arange(n, dtype=np.int64)
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_SAMPLE, replace=False))
+    parts = {"world": [], "position": [], "rotation_euler": [], "linvel": []}
+    for c0 in range(0, n, chunk):
+        c1 = min(n, c0 + chunk)
+        lo, hi = np.searchsorted(idx, [c0, c1])
+        if lo == hi:
+            continue
+        rows = idx[lo:hi] - c0
+        pos, euler = world.download_pose(c0, c1 - c0)
+        parts["world"].append(world.download_world(c0, c1 - c0)[rows])
+        parts["position"].append(pos[rows])
+        parts["rotation_euler"].append(euler[rows])
+        parts["linvel"].append(world.download_bodies(c0, c1 - c0)["linvel"][rows])
+    os.makedirs(out_dir, exist_ok=True)
+    for name, chunks in parts.items():
+        arr = np.concatenate(chunks) if chunks else np.zeros((0, 16 if name == "world" else 3), np.float32)
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float32))
+    np.save(os.path.join(out_dir, "entity_id.npy"), (idx + first).astype(np.float64))
 
 
 # ------------------------------------------------------------------------------------------------- one configuration
@@ -680,6 +728,8 @@ def run_rank(args):
             k_ms, k_ticks = world.profile_read()
             assert k_ticks == args.steps, (k_ticks, args.steps)
             region_kernel_ms.append(k_ms / k_ticks)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(world, args.dump_outputs, rank * per_gpu)   # before anything below ticks the world again
     kernel_note = "one HIP event pair around the K launches of the timed region"
     if gather:
         # the collective and the packing kernel share the stream with the tick kernels: time the tick kernels in a
@@ -798,10 +848,10 @@ def run_rank(args):
             out["scaling_efficiency"] = None if STUB else value / (n_gpus * solo_value)
             out["compute_only_ms_per_step"] = solo["region_s_slowest_rank"] / args.steps * 1e3
             out["compute_plus_collective_ms_per_step"] = elapsed_s / args.steps * 1e3
-        if n_gpus == 1 and not args.no_cpu and not STUB:
+        if n_gpus == 1 and args.full and not args.no_cpu and not STUB:
             out["cpu_baseline"] = cpu_baseline(wl, args.cpu_seconds)
             out["cpu_allcore"] = cpu_allcore(wl, args.cpu_seconds / 2, args.cpu_threads)
-    if not args.no_cpu and not STUB and base.shape in (synth.FLAT, synth.CHAINS4, synth.SUBTREE64):
+    if args.full and not args.no_cpu and not STUB and base.shape in (synth.FLAT, synth.CHAINS4, synth.SUBTREE64):
         # every rank checks a sample of ITS shard against the CPU port (outside the timed region); rank 0 reports the worst
         with deadlines.phase("sampled parity check against the CPU port"):
             try:
@@ -833,7 +883,7 @@ def run_rank(args):
         world.comm_destroy()
     world.close()
 
-    if rank == 0 and n_gpus == 1 and not args.no_configs and not STUB and name == "flat1m" and not args.entities:
+    if rank == 0 and n_gpus == 1 and args.full and not args.no_configs and not STUB and name == "flat1m" and not args.entities:
         # The other single-GPU configurations, same process, after the headline's timed region (every
         # single-GPU config in the one driver-timed line).  flat 16 M is the figure without Infinity-Cache help.
         extras = []

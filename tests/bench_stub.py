@@ -98,6 +98,11 @@ class StubWorld:
         c = self.n if count is None else count
         return np.zeros((c, 3), np.float32), np.zeros((c, 3), np.float32)
 
+    def download_bodies(self, first=0, count=None):
+        c = self.n - first if count is None else count
+        return dict(linvel=np.zeros((c, 3), np.float32), angvel=np.zeros((c, 3), np.float32),
+                    quat=np.zeros((c, 4), np.float32), aabb=np.zeros((c, 6), np.float32))
+
     def sync(self):
         pass
 

@@ -23,7 +23,7 @@ def _run(extra_args, extra_env=None, timeout=240, drop=("WORLD_SIZE", "RANK", "L
 
 
 def test_gpus_2_starts_two_ranks_and_reports_them():
-    rc, out, err, _ = _run(["--gpus", "2", "--deadline", "90"])
+    rc, out, err, _ = _run(["--gpus", "2", "--deadline", "90", "--full"])
     assert rc == 0, err[-2000:]
     lines = [ln for ln in out.splitlines() if ln.strip()]
     assert len(lines) == 1, out  # exactly ONE line on stdout
@@ -42,6 +42,52 @@ def test_gpus_2_starts_two_ranks_and_reports_them():
     assert line["compute_only_ms_per_step"] > 0 and line["compute_plus_collective_ms_per_step"] > 0
     assert line["repeats"] == 5 and len(line["region_ms"]) == 5 and "median of 5" in line["timing"]
     assert abs(line["ms_per_step"] - sorted(line["region_ms"])[2] / 5) < 1e-9    # the median region / K
+
+
+def test_a_plain_run_times_exactly_steps_and_dumps_its_outputs(tmp_path):
+    import numpy as np
+    rc, out, err, _ = _run(["--gpus", "1", "--dump-outputs", str(tmp_path)])
+    assert rc == 0, err[-2000:]
+    lines = [ln for ln in out.splitlines() if ln.strip()]
+    assert len(lines) == 1, out
+    line = json.loads(lines[0])
+    assert line["n_gpus"] == 1 and line["steps"] == 5 and line["warmup"] == 2
+    assert line["repeats"] == 1 and len(line["region_ms"]) == 1            # one region of exactly --steps steps
+    assert abs(line["ms_per_step"] - line["region_ms"][0] / 5) < 1e-9
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in line, key
+    assert "configs" not in line and "cpu_baseline" not in line and "parity" not in line
+    shapes = {"world": (6400, 16), "position": (6400, 3), "rotation_euler": (6400, 3), "linvel": (6400, 3), "entity_id": (6400,)}
+    total = 0
+    for name, shape in shapes.items():
+        a = np.load(tmp_path / f"{name}.npy")
+        assert a.shape == shape and a.dtype in (np.float32, np.float64), (name, a.shape, a.dtype)
+        total += a.nbytes
+    assert total <= 64 << 20
+    assert np.array_equal(np.load(tmp_path / "entity_id.npy"), np.arange(6400, dtype=np.float64))
+
+
+def test_dump_sample_is_seeded_and_bounded(tmp_path):
+    """A shard larger than DUMP_SAMPLE: the same sorted sample of entity ids in every run, under 64 MB in all."""
+    sys.path.insert(0, ROOT)
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import numpy as np
+    import bench
+    from bench_stub import StubWorld
+
+    class Wl:
+        n = 3 * bench.DUMP_SAMPLE
+    picks = []
+    for k in range(2):
+        w = StubWorld()
+        w.load(Wl)
+        d = tmp_path / str(k)
+        bench.dump_outputs(w, str(d), 100, chunk=bench.DUMP_SAMPLE)
+        picks.append(np.load(d / "entity_id.npy"))
+        assert len(picks[-1]) == bench.DUMP_SAMPLE and np.load(d / "world.npy").shape == (bench.DUMP_SAMPLE, 16)
+        assert sum(f.stat().st_size for f in d.iterdir()) <= 64 << 20
+    assert np.array_equal(picks[0], picks[1]) and np.all(np.diff(picks[0]) > 0)
+    assert picks[0][0] >= 100 and picks[0][-1] < 100 + Wl.n
 
 
 def test_default_deadline_keeps_the_launcher_inside_the_drivers_limit():
