@@ -18,6 +18,8 @@
 //   reads   flags 4 B (body type, dirty bits, level, in-tile parent index, mass class), pos/euler/scale 12 B
 //           each, vel 12 B (Dynamic bodies only); parent slot 4 B only for nodes whose parent is in an earlier pass
 //   writes  pos 12 B + vel 12 B (Dynamic only), world 64 B; flags only when a bit changed
+//   Waves whose rotation rows are current (WorldView::rs_word) read neither euler nor scale and write only world row 3:
+//   68 B per flat body instead of 140 B.
 //   The world matrices leave through LDS so that every wave-level store instruction writes 1 KiB of
 //   contiguous memory (16 B per lane), whatever the per-node compute layout was.
 //   The kernel is HBM-bound (~250 flop against >= 113 B per entity): no MFMA.
@@ -196,6 +198,18 @@ __global__ void __launch_bounds__(kTile, NORMAL ? 4 : (AABB ? BGE_AABB_MIN_WAVES
     const uint32_t count = (hdr >> kHdrCountShift) & kHdrCountMask;
     const uint32_t max_level = hdr & kHdrLevelMask;
 
+    // Rotation rows current (WorldView::rs_word): a wave whose word equals p.rs_epoch had world rows 0..2 = bx_mtx_srt(scale,
+    // euler) for every valid slot when it last ran, and nothing has written scale, euler or world since (the host bumps the
+    // epoch on every call that could).  Unless a lane re-poses or spins in this tick, rows 0..2 would come out bit for bit as
+    // they are stored: the wave skips the euler / scale loads and bx_mtx_srt and stores the translation row alone (DESIGN.md
+    // §4.1: 68 instead of 140 B per flat body).  The word is loaded as a scalar next to the tile header.
+    constexpr bool kRowsPath = XFORM && !AABB && !NORMAL && !BASIS;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const uint32_t rs_old = (kRowsPath && p.rs_epoch != 0u) ? w.rs_word[tile * 4u + wave] : 0u;
+    // (header: wave-local, max level 0, no frozen root, no external parent)
+    const bool rs_tile = kRowsPath && p.rs_epoch != 0u && (hdr & (kHdrWaveLocal | kHdrFrozen | kHdrExt | kHdrLevelMask)) == kHdrWaveLocal;
+    const bool rs_hint = rs_tile && rs_old == p.rs_epoch;
+
     const uint32_t f0 = w.flags[slot];
     // The component loads do not wait for the flag word: every array is allocated for whole tiles, so the loads of a slot
     // that turns out to be empty (or of a velocity nobody integrates) are harmless, and issuing them together with the flags
@@ -208,8 +222,10 @@ __global__ void __launch_bounds__(kTile, NORMAL ? 4 : (AABB ? BGE_AABB_MIN_WAVES
     F3 pos{0.0f, 0.0f, 0.0f}, eul{0.0f, 0.0f, 0.0f}, scl{1.0f, 1.0f, 1.0f}, vel_early{0.0f, 0.0f, 0.0f};
     if (BGE_SPECULATIVE_LOADS) {
         pos = ld3(w.pos, slot);
-        eul = ld3(w.euler, slot);
-        if (XFORM) scl = ld3(w.scale, slot);
+        if (!rs_hint) {
+            eul = ld3(w.euler, slot);
+            if (XFORM) scl = ld3(w.scale, slot);
+        }
 #ifndef BGE_SPECULATIVE_VEL
 #define BGE_SPECULATIVE_VEL 1
 #endif
@@ -255,8 +271,22 @@ __global__ void __launch_bounds__(kTile, NORMAL ? 4 : (AABB ? BGE_AABB_MIN_WAVES
         }
     } else if (valid || orphan_body) {
         pos = ld3(w.pos, slot);
-        eul = ld3(w.euler, slot);
-        if (XFORM) scl = ld3(w.scale, slot);
+        if (!rs_hint) {
+            eul = ld3(w.euler, slot);
+            if (XFORM) scl = ld3(w.scale, slot);
+        }
+    }
+    // The flags confirm the word: no valid lane re-poses (which rewrites euler), spins (which turns it), has an external parent
+    // or a parent in the tile.  (Orphaned bodies never read euler / scale here.)  Otherwise the lanes load what they skipped.
+    bool rs_fast = false;
+    if (rs_hint) {
+        const bool repose_now = PHYS && p.no_repose == 0u && (f & (kTDirty | kBDirty)) != 0;
+        const bool stale = valid && (repose_now || (PHYS && (f & kSpin)) || (f & (kExtParent | kLevelMask)));
+        rs_fast = __ballot(stale) == 0ull;
+        if (!rs_fast && (valid || orphan_body)) {
+            eul = ld3(w.euler, slot);
+            scl = ld3(w.scale, slot);
+        }
     }
 
     // (AABB variants) this lane's fed box for the wave's broadphase partial: identity when the slot carries no body
@@ -520,7 +550,13 @@ __global__ void __launch_bounds__(kTile, NORMAL ? 4 : (AABB ? BGE_AABB_MIN_WAVES
         }
     }
 
-    if (XFORM) {
+    if (kRowsPath && rs_fast) {
+        // rows 0..2 in memory are what bx_mtx_srt would store; row 3 is (pos, 1) (bx::mtxSRT, m[12..15]).  16 B at a 64-B stride,
+        // plain stores: tools/ubench_world_rows.hip measured non-temporal ones twice as slow for this shape, and the host keeps
+        // the path off where the working set outgrows the Infinity Cache (16 M slots: partially written lines cost 2.7x whole ones)
+        if (valid) reinterpret_cast<float4*>(w.world)[4ull * slot + 3u] = make_float4(pos.x, pos.y, pos.z, 1.0f);
+        f &= ~kTDirty; // transform->dirty = false
+    } else if (XFORM) {
         float local[16];
         bx_mtx_srt(local, scl, eul, pos);
         const uint32_t level = (f & kLevelMask) >> kLevelShift;
@@ -573,6 +609,13 @@ __global__ void __launch_bounds__(kTile, NORMAL ? 4 : (AABB ? BGE_AABB_MIN_WAVES
                 const uint32_t n = wbase + nl;
                 const uint32_t r = (qi & 3u) ^ ((n >> 2) & 3u);
                 if ((valid_mask >> nl) & 1ull) store_out(&dst[n * 4u + r], lds[wbase * 4u + qi], p.nt_out != 0);
+            }
+            if (kRowsPath && p.rs_epoch != 0u) {
+                // the rows just stored are bx_mtx_srt of the scale and euler in memory; the word says so when the next tick can use
+                // it: every valid lane ends the tick without spin in a tile of the fast path's shape (written only when it changes)
+                const bool keeps = rs_tile && __ballot(valid && (f & (kSpin | kExtParent | kLevelMask))) == 0ull;
+                const uint32_t rs_new = keeps ? p.rs_epoch : 0u;
+                if (rs_new != rs_old && (tid & 63u) == 0u) w.rs_word[tile * 4u + wave] = rs_new;
             }
             if (NORMAL) {
                 // render feed: normalMtx = transpose(inverse(world)) (Renderer.cpp:633-636), same LDS round trip

@@ -155,6 +155,18 @@ struct bge_world {
     DevBuf root_worlds, counter, stage, stage2, mass_palette, normal, deact, filter_class, filter_table, grav_palette;
     DevBuf cshape, cmass, cfriction, cinfo, manifold; // ground contact (bge_contact.hip); manifold allocated when the plane is switched on
     DevBuf ground_list, ground_count;                 // slots k_ground_select hands to the solver; count + ticket words
+    // "rotation rows current" words of the tick kernel (WorldView::rs_word, one per wave64, zeroed with every layout) and the
+    // epoch they are compared with.  Every call that can write euler, scale, world, quat, angular velocity, body types or flags —
+    // and every tick whose launches include another kernel that writes them — moves the epoch on, which invalidates all words.
+    DevBuf rs_word;
+    uint32_t rs_epoch = 1;
+    void rs_bump()
+    {
+        if (++rs_epoch == 0) { // (after 2^32 - 1 bumps: a word may still hold the new value)
+            rs_epoch = 1;
+            if (rs_word.p) (void)hipMemsetAsync(rs_word.p, 0, rs_word.bytes, stream);
+        }
+    }
     // Dynamic boxes on the Static / Kinematic box colliders of the scene (round 3, bge_contact.hip): off by default, like the plane
     bool static_contacts = false;
     DevBuf crestitution;                              // RigidBody::restitution per slot (allocated with the layout, zero = the component default)
@@ -354,12 +366,13 @@ struct bge_world {
         view.crestitution = crestitution.as<float>();
         view.bmanifold = bmanifold.as<uint32_t>();
         view.frozen = frozen.as<uint32_t>();
+        view.rs_word = rs_word.as<uint32_t>();
     }
     void release_all()
     {
         for (DevBuf* b : {&flags, &parent, &tile_hdr, &slot_of_entity, &entity_of_slot, &root_slots, &root_index, &pos, &euler, &scale, &world, &vel,
                           &angvel, &quat, &inv_mass, &half_extent, &group, &mask, &aabb, &root_worlds, &counter, &stage,
-                          &stage2, &mass_palette, &normal, &deact, &filter_class, &filter_table, &grav_palette, &bp_partials, &cshape, &cmass, &cfriction, &cinfo, &manifold, &crestitution, &bmanifold, &obstacle_slots, &obstacle_gen, &obstacles, &obstacle_grid, &box_list, &box_count, &frozen, &trig_slot, &trig_entity, &trig_he, &trig_group,
+                          &stage2, &mass_palette, &normal, &deact, &filter_class, &filter_table, &grav_palette, &bp_partials, &cshape, &cmass, &cfriction, &cinfo, &manifold, &crestitution, &bmanifold, &obstacle_slots, &obstacle_gen, &obstacles, &obstacle_grid, &box_list, &box_count, &frozen, &rs_word, &trig_slot, &trig_entity, &trig_he, &trig_group,
                           &trig_mask, &trig_active, &trig_aabb, &trig_pairs, &trig_count, &trig_lists, &ground_list, &ground_count, &trig_tab[0], &trig_tab[1],
                           &trig_delta_dev, &trig_keys_dev}) {
             b->release();
@@ -1323,6 +1336,9 @@ try {
     HIP_TRY(w->flags.ensure(S * 4));
     HIP_TRY(w->parent.ensure(S * 4));
     HIP_TRY(w->tile_hdr.ensure(T * 4));
+    HIP_TRY(w->rs_word.ensure(T * 16));
+    HIP_TRY(hipMemsetAsync(w->rs_word.p, 0, T * 16, w->stream));
+    w->rs_bump();
     HIP_TRY(w->slot_of_entity.ensure(std::max<uint64_t>(n, 1) * 4));
     HIP_TRY(w->entity_of_slot.ensure(S * 4));
     HIP_TRY(w->root_index.ensure(S * 4));
@@ -1459,6 +1475,7 @@ static int upload_trs_impl(bge_world* w, uint64_t first, uint64_t count, const u
                                      w->flags.as<uint32_t>(), bge::kTDirty, di, bge::kValid));
     HIP_TRY(hipStreamSynchronize(w->stream));
     w->maybe_dirty = true;
+    w->rs_bump();
     return BGE_OK;
 }
 
@@ -1487,6 +1504,7 @@ try {
     HIP_TRY(bge::launch_scatter_rows(w->stream, w->slot_of_entity.as<uint32_t>(), first, count, 0, nullptr, nullptr,
                                      w->flags.as<uint32_t>(), bge::kTDirty, nullptr, bge::kValid));
     w->maybe_dirty = true;
+    w->rs_bump();
     return BGE_OK;
 }
 BGE_CATCH_ALL("bge_world_mark_dirty")
@@ -1632,6 +1650,7 @@ static int upload_bodies_impl(bge_world* w, uint64_t first, uint64_t count, cons
                                        d + 12 * count));
     HIP_TRY(hipStreamSynchronize(w->stream));
     w->maybe_dirty = true;
+    w->rs_bump();
     return BGE_OK;
 }
 
@@ -1649,6 +1668,7 @@ try {
     HIP_TRY(bge::launch_scatter_velocities(w->stream, w->slot_of_entity.as<uint32_t>(), first, count, linvel3 ? dl : nullptr,
                                            angvel3 ? da : nullptr, w->view));
     HIP_TRY(hipStreamSynchronize(w->stream));
+    w->rs_bump();
     return BGE_OK;
 }
 BGE_CATCH_ALL("bge_world_set_velocities")
@@ -1777,6 +1797,7 @@ int tick_impl(bge_world* w, uint32_t ticks, float dt, const float gravity[3], ui
                 HIP_TRY(hipEventRecord(w->prof_events[w->prof_used], w->stream));
             }
             for (uint32_t c = 0; c < chunks; ++c) HIP_TRY(hipGraphLaunch(w->graph_exec, w->stream));
+            w->rs_bump(); // (captured with the fast path off: TickParams::rs_epoch 0)
             first_eager = chunks * bge_world::kGraphTicks;
             w->maybe_dirty = phys && !xform;
             if (w->profiling == 1 && first_eager == ticks) {
@@ -1790,6 +1811,15 @@ int tick_impl(bge_world* w, uint32_t ticks, float dt, const float gravity[3], ui
     // fits the 256 MiB Infinity Cache; BGE_NT_STORES=0/1 overrides (experiments)
     bool nt_out = static_cast<double>(w->flat.n_slots) * ((flags & BGE_TICK_NORMAL_MATRICES) ? 204.0 : 140.0) > kNtThresholdBytes;
     if (const char* e = std::getenv("BGE_NT_STORES")) nt_out = std::atoi(e) != 0;
+    // Translation-row fast path of the tick kernel (WorldView::rs_word): only in the variants it exists in (transforms, with or
+    // without the default physics step, nothing else), and only where no other kernel of the tick writes euler, scale, world
+    // or quat (ground plane, obstacles, Dynamic contacts).  Only while the working set fits the Infinity Cache: beyond it a
+    // 16-B store into every 64-B matrix costs more than the whole matrix (tools/ubench_world_rows.hip: 16 M slots, 2.7x).
+    // BGE_WORLD_ROWS=0 turns it off (A/B runs); a tick without it moves the epoch on, so that no word outlives what it vouched for.
+    const bool contacts = phys && (w->ground_plane || w->static_contacts || w->dynamic_contacts);
+    bool rows_path = xform && !contacts && !nt_out &&
+                     !(flags & (BGE_TICK_AABBS | BGE_TICK_BROADPHASE | BGE_TICK_NORMAL_MATRICES | BGE_TICK_BULLET_BASIS | BGE_TICK_GATHER_ROOTS));
+    if (const char* e = std::getenv("BGE_WORLD_ROWS")) rows_path = rows_path && std::atoi(e) != 0;
     for (uint32_t t = first_eager; t < ticks; ++t) {
         if (!phys && !w->maybe_dirty && !(flags & BGE_TICK_NORMAL_MATRICES)) {
             // TransformSystem::Update with nothing dirty: a no-op scan — only the kernel launches are skipped.  The
@@ -1808,6 +1838,8 @@ int tick_impl(bge_world* w, uint32_t ticks, float dt, const float gravity[3], ui
         p.gz = gravity ? gravity[2] : 0.0f;
         p.nt_out = nt_out ? 1u : 0u;
         p.no_repose = sub.no_repose ? 1u : 0u;
+        if (rows_path) p.rs_epoch = w->rs_epoch;
+        else w->rs_bump();
         w->fill_sleep(p);
         const bool with_triggers = (flags & BGE_TICK_BROADPHASE) && !w->triggers.empty();
         if (with_triggers && !sub.ghosts_posed) {
@@ -2044,6 +2076,7 @@ try {
         HIP_TRY(bge::launch_pose_only(w->stream, w->view, static_cast<uint64_t>(w->flat.n_tiles_ticked) * bge::kTile,
                                       (flags & BGE_TICK_BULLET_BASIS) != 0));
         w->maybe_dirty = true;
+        w->rs_bump(); // (k_pose_only re-poses: it writes quat, euler, velocities)
         if (triggers) {
             process_triggers_without_a_step(w);
         }
@@ -2089,6 +2122,7 @@ try {
         w->rebuild_view();
     }
     w->ground_plane = on;
+    w->rs_bump();
     w->drop_graph();
     return BGE_OK;
 }
@@ -2109,6 +2143,7 @@ try {
     w->static_contacts = on;
     w->static_contacts_ever = w->static_contacts_ever || on;
     w->obstacles_stale = true;
+    w->rs_bump();
     w->drop_graph();
     return BGE_OK;
 }
@@ -2131,6 +2166,7 @@ try {
     w->dynamic_contacts = enabled != 0;
     w->isl_n_prev = 0; // (off and on again: the pair cache starts empty)
     w->isl_gen_stale = true;
+    w->rs_bump();
     w->drop_graph();
     return BGE_OK;
 }

@@ -78,7 +78,9 @@ enum bge_tick_flags {
 };
 
 enum bge_device_array {
-    BGE_ARRAY_WORLD = 0,          /* float[n_slots][16], slot order */
+    BGE_ARRAY_WORLD = 0,          /* float[n_slots][16], slot order; READ-ONLY to consumers: a tick rewrites only the
+                                     translation row of a matrix whose rotation rows it knows to be current,
+                                     so a value written here into rows 0..2 may persist */
     BGE_ARRAY_ROOT_WORLDS = 1,    /* float[n_roots][16], filled by bge_world_pack_roots */
     BGE_ARRAY_SLOT_OF_ENTITY = 2, /* uint32[n_entities], BGE_NO_PARENT where the entity has no Transform */
     BGE_ARRAY_POSITION = 3,       /* float[n_slots][3] */

@@ -1,0 +1,233 @@
+// ubench_world_rows.hip — what the store shape of the flat tick's world matrices costs on gfx950.
+//
+// The flat tick rewrites 64 B of world matrix per entity, of which rows 0..2 already hold exactly the bits it stores
+// whenever the body neither re-posed nor spun.  Before the kernel learns to store row 3 alone,
+// this program times the access shapes involved, over N slots of float[16], with plain and non-temporal stores:
+//   a  full rows    64 B per slot, every store instruction 1 KiB contiguous (the tick's wave-local write-out)
+//   b  row 3 only   16 B per slot at a 64-B stride, lane = slot
+//   c  flat tick    read flags, pos, vel, euler, scale (SoA); write pos, vel and the full row (bx_mtx_srt, LDS write-out)
+//   d  fast path    read flags, pos, vel; write pos, vel and row 3
+//   b2 rows 2-3     32 B per slot at a 64-B stride (two 16-B stores per lane: whole 32-B sectors)
+//   e  fast path, whole sectors: read flags, pos, vel and row 2; write pos, vel and rows 2-3
+// Each kernel runs `reps` times back to back between two events after a warm-up; one JSON line per (kernel, store
+// policy, size).  Built by tools/ubench_world_rows.sh; no part of the product library.
+#include <hip/hip_runtime.h>
+
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#include "../banggameengine_amd/csrc/bge_device_math.hpp"
+
+using namespace bge::dev;
+
+#define CK(x)                                                                                          \
+    do {                                                                                               \
+        hipError_t e_ = (x);                                                                           \
+        if (e_ != hipSuccess) {                                                                        \
+            std::fprintf(stderr, "%s:%d %s: %s\n", __FILE__, __LINE__, #x, hipGetErrorString(e_));     \
+            std::exit(1);                                                                              \
+        }                                                                                              \
+    } while (0)
+
+namespace {
+
+constexpr uint32_t kBlock = 256;
+
+template <bool NT> __device__ __forceinline__ void put4(float4* p, const float4& v)
+{
+    if (NT) {
+        __builtin_nontemporal_store(v.x, &p->x);
+        __builtin_nontemporal_store(v.y, &p->y);
+        __builtin_nontemporal_store(v.z, &p->z);
+        __builtin_nontemporal_store(v.w, &p->w);
+    } else {
+        *p = v;
+    }
+}
+
+// (a) one float4 per lane, consecutive lanes consecutive float4s: 64 B per slot
+template <bool NT> __global__ void __launch_bounds__(kBlock) k_full_rows(float4* __restrict__ world, uint32_t n_slots, float salt)
+{
+    const uint64_t i = blockIdx.x * static_cast<uint64_t>(kBlock) + threadIdx.x;
+    if (i >= 4ull * n_slots) return;
+    put4<NT>(world + i, make_float4(salt, static_cast<float>(i & 1023u), 0.0f, 1.0f));
+}
+
+// (b) row 3 of slot = lane: 16 B at a 64-B stride
+template <bool NT> __global__ void __launch_bounds__(kBlock) k_row3(float4* __restrict__ world, uint32_t n_slots, float salt)
+{
+    const uint32_t slot = blockIdx.x * kBlock + threadIdx.x;
+    if (slot >= n_slots) return;
+    put4<NT>(world + 4ull * slot + 3, make_float4(salt, static_cast<float>(slot & 1023u), 0.0f, 1.0f));
+}
+
+// (b2) rows 2 and 3 of slot = lane: the 32-B-aligned upper half of the matrix, whole 32-B sectors
+template <bool NT> __global__ void __launch_bounds__(kBlock) k_rows23(float4* __restrict__ world, uint32_t n_slots, float salt)
+{
+    const uint32_t slot = blockIdx.x * kBlock + threadIdx.x;
+    if (slot >= n_slots) return;
+    put4<NT>(world + 4ull * slot + 2, make_float4(0.0f, 0.0f, salt, 0.0f));
+    put4<NT>(world + 4ull * slot + 3, make_float4(salt, static_cast<float>(slot & 1023u), 0.0f, 1.0f));
+}
+
+struct Soa {
+    uint32_t* flags;
+    float *pos, *vel, *euler, *scale;
+    float4* world;
+};
+
+// (c) the flat tick's traffic and transform work: integrate, bx_mtx_srt, wave-local LDS write-out of 1 KiB per instruction
+template <bool NT> __global__ void __launch_bounds__(kBlock, 8) k_flat_full(Soa s, uint32_t n_slots, float dt)
+{
+    __shared__ float4 lds[kBlock * 4];
+    const uint32_t tid = threadIdx.x;
+    const uint32_t slot = blockIdx.x * kBlock + tid; // n_slots is a multiple of kBlock
+    const uint32_t f = s.flags[slot];
+    F3 pos = ld3(s.pos, slot), vel = ld3(s.vel, slot);
+    const F3 eul = ld3(s.euler, slot), scl = ld3(s.scale, slot);
+    const bool valid = (f & 1u) != 0;
+    if (valid) {
+        vel.y = vel.y + -9.81f * dt;
+        pos.x = pos.x + vel.x * dt;
+        pos.y = pos.y + vel.y * dt;
+        pos.z = pos.z + vel.z * dt;
+        st3(s.vel, slot, vel);
+        st3(s.pos, slot, pos);
+    }
+    float m[16];
+    bx_mtx_srt(m, scl, eul, pos);
+#pragma unroll
+    for (uint32_t r = 0; r < 4; ++r) lds[tid * 4u + (r ^ ((tid >> 2) & 3u))] = make_float4(m[4 * r], m[4 * r + 1], m[4 * r + 2], m[4 * r + 3]);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    const unsigned long long valid_mask = __ballot(valid);
+    const uint32_t lane = tid & 63u, wbase = tid & ~63u;
+    float4* dst = s.world + 4ull * kBlock * blockIdx.x;
+#pragma unroll
+    for (uint32_t k = 0; k < 4; ++k) {
+        const uint32_t qi = lane + 64u * k, nl = qi >> 2, n = wbase + nl;
+        const uint32_t r = (qi & 3u) ^ ((n >> 2) & 3u);
+        if ((valid_mask >> nl) & 1ull) put4<NT>(&dst[n * 4u + r], lds[wbase * 4u + qi]);
+    }
+}
+
+// (d) the proposed fast path: rows 0..2 are current, only the translation row is stored
+template <bool NT> __global__ void __launch_bounds__(kBlock, 8) k_flat_row3(Soa s, uint32_t n_slots, float dt)
+{
+    const uint32_t slot = blockIdx.x * kBlock + threadIdx.x;
+    const uint32_t f = s.flags[slot];
+    F3 pos = ld3(s.pos, slot), vel = ld3(s.vel, slot);
+    if (f & 1u) {
+        vel.y = vel.y + -9.81f * dt;
+        pos.x = pos.x + vel.x * dt;
+        pos.y = pos.y + vel.y * dt;
+        pos.z = pos.z + vel.z * dt;
+        st3(s.vel, slot, vel);
+        st3(s.pos, slot, pos);
+        put4<NT>(s.world + 4ull * slot + 3, make_float4(pos.x, pos.y, pos.z, 1.0f));
+    }
+}
+
+// (e) as (d), but row 2 is read back and stored again with row 3, so that every written 32-B sector is written whole
+template <bool NT> __global__ void __launch_bounds__(kBlock, 8) k_flat_rows23(Soa s, uint32_t n_slots, float dt)
+{
+    const uint32_t slot = blockIdx.x * kBlock + threadIdx.x;
+    const uint32_t f = s.flags[slot];
+    F3 pos = ld3(s.pos, slot), vel = ld3(s.vel, slot);
+    const float4 row2 = s.world[4ull * slot + 2];
+    if (f & 1u) {
+        vel.y = vel.y + -9.81f * dt;
+        pos.x = pos.x + vel.x * dt;
+        pos.y = pos.y + vel.y * dt;
+        pos.z = pos.z + vel.z * dt;
+        st3(s.vel, slot, vel);
+        st3(s.pos, slot, pos);
+        put4<NT>(s.world + 4ull * slot + 2, row2);
+        put4<NT>(s.world + 4ull * slot + 3, make_float4(pos.x, pos.y, pos.z, 1.0f));
+    }
+}
+
+template <typename F> float time_us(F launch, int warm, int reps)
+{
+    hipEvent_t a, b;
+    CK(hipEventCreate(&a));
+    CK(hipEventCreate(&b));
+    for (int i = 0; i < warm; ++i) launch();
+    CK(hipDeviceSynchronize());
+    CK(hipEventRecord(a, nullptr));
+    for (int i = 0; i < reps; ++i) launch();
+    CK(hipEventRecord(b, nullptr));
+    CK(hipEventSynchronize(b));
+    float ms = 0.0f;
+    CK(hipEventElapsedTime(&ms, a, b));
+    CK(hipEventDestroy(a));
+    CK(hipEventDestroy(b));
+    return 1e3f * ms / static_cast<float>(reps);
+}
+
+void report(const char* kernel, bool nt, uint32_t n, float us, double bytes_per_slot)
+{
+    const double gbs = bytes_per_slot * n / (us * 1e-6) / 1e9;
+    std::printf("{\"kernel\": \"%s\", \"nt\": %d, \"slots\": %u, \"us\": %.3f, \"bytes_per_slot\": %.0f, \"GB_s\": %.1f}\n", kernel, nt ? 1 : 0,
+                n, us, bytes_per_slot, gbs);
+    std::fflush(stdout);
+}
+
+template <bool NT> void run_size(uint32_t n, int reps, Soa s)
+{
+    const int warm = 20;
+    const dim3 blk(kBlock);
+    const dim3 g_full((4ull * n + kBlock - 1) / kBlock), g_slot((n + kBlock - 1) / kBlock);
+    report("a_full_rows", NT, n, time_us([&] { k_full_rows<NT><<<g_full, blk>>>(s.world, n, 1.0f); }, warm, reps), 64.0);
+    report("b_row3", NT, n, time_us([&] { k_row3<NT><<<g_slot, blk>>>(s.world, n, 2.0f); }, warm, reps), 16.0);
+    report("b2_rows23", NT, n, time_us([&] { k_rows23<NT><<<g_slot, blk>>>(s.world, n, 3.0f); }, warm, reps), 32.0);
+    report("c_flat_full", NT, n, time_us([&] { k_flat_full<NT><<<g_slot, blk>>>(s, n, 1.0f / 60.0f); }, warm, reps), 140.0);
+    report("d_flat_row3", NT, n, time_us([&] { k_flat_row3<NT><<<g_slot, blk>>>(s, n, 1.0f / 60.0f); }, warm, reps), 68.0);
+    report("e_flat_rows23", NT, n, time_us([&] { k_flat_rows23<NT><<<g_slot, blk>>>(s, n, 1.0f / 60.0f); }, warm, reps), 100.0);
+    CK(hipGetLastError());
+    CK(hipDeviceSynchronize());
+}
+
+} // namespace
+
+// usage: ubench_world_rows [slots ...]   (default 1048576 16777216; rounded up to whole 256-slot blocks)
+//        env UBENCH_REPS: timed launches per kernel (default 200)
+int main(int argc, char** argv)
+{
+    std::vector<uint32_t> sizes;
+    for (int i = 1; i < argc; ++i) sizes.push_back(static_cast<uint32_t>(std::strtoul(argv[i], nullptr, 10)));
+    if (sizes.empty()) sizes = {1u << 20, 1u << 24};
+    const int reps = std::getenv("UBENCH_REPS") ? std::atoi(std::getenv("UBENCH_REPS")) : 200;
+    for (uint32_t n0 : sizes) {
+        const uint32_t n = (n0 + kBlock - 1) / kBlock * kBlock;
+        Soa s{};
+        CK(hipMalloc(&s.flags, 4ull * n));
+        CK(hipMalloc(&s.pos, 12ull * n));
+        CK(hipMalloc(&s.vel, 12ull * n));
+        CK(hipMalloc(&s.euler, 12ull * n));
+        CK(hipMalloc(&s.scale, 12ull * n));
+        CK(hipMalloc(&s.world, 64ull * n));
+        std::vector<uint32_t> fl(n, 1u);
+        std::vector<float> v3(3ull * n);
+        CK(hipMemcpy(s.flags, fl.data(), 4ull * n, hipMemcpyHostToDevice));
+        for (size_t i = 0; i < v3.size(); ++i) v3[i] = 0.001f * static_cast<float>(i % 997);
+        CK(hipMemcpy(s.pos, v3.data(), 12ull * n, hipMemcpyHostToDevice));
+        CK(hipMemcpy(s.euler, v3.data(), 12ull * n, hipMemcpyHostToDevice));
+        for (size_t i = 0; i < v3.size(); ++i) v3[i] = 1.0f + 0.0001f * static_cast<float>(i % 101);
+        CK(hipMemcpy(s.scale, v3.data(), 12ull * n, hipMemcpyHostToDevice));
+        CK(hipMemset(s.vel, 0, 12ull * n));
+        CK(hipMemset(s.world, 0, 64ull * n));
+        run_size<false>(n, reps, s);
+        run_size<true>(n, reps, s);
+        CK(hipFree(s.flags));
+        CK(hipFree(s.pos));
+        CK(hipFree(s.vel));
+        CK(hipFree(s.euler));
+        CK(hipFree(s.scale));
+        CK(hipFree(s.world));
+    }
+    return 0;
+}

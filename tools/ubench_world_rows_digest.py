@@ -1,0 +1,62 @@
+#!/usr/bin/env python3
+"""Digest of tools/ubench_world_rows.sh: per kernel, store policy and size, the event time, the median traced dispatch time
+and the bytes per slot from the PMC passes.
+
+    python tools/ubench_world_rows_digest.py OUT_DIR
+
+Bytes per slot: 2 x FETCH_SIZE (gfx950 tallies 128-B read requests at 64 B) and WRITE_SIZE as counted, both KiB -> B,
+over the slots of the dispatch (k_full_rows runs four threads per slot)."""
+import csv
+import glob
+import json
+import os
+import statistics
+import sys
+from collections import defaultdict
+
+
+def key(name, grid):
+    name = name.replace("(anonymous namespace)::", "").replace("void ", "").split("(")[0]
+    base, _, arg = name.partition("<")
+    slots = grid // 4 if base == "k_full_rows" else grid
+    return base, arg.rstrip(">") == "true", slots
+
+
+def grid_of(row):
+    return int(row.get("Grid_Size") or row.get("Grid_Size_X") or 0)
+
+
+def main():
+    out = sys.argv[1]
+    times = {}
+    names = {"a_full_rows": "k_full_rows", "b_row3": "k_row3", "c_flat_full": "k_flat_full", "d_flat_row3": "k_flat_row3",
+             "b2_rows23": "k_rows23", "e_flat_rows23": "k_flat_rows23"}
+    for line in open(os.path.join(out, "times.jsonl")):
+        d = json.loads(line)
+        times[(names[d["kernel"]], bool(d["nt"]), d["slots"])] = d["us"]
+    traced = defaultdict(list)
+    for path in glob.glob(os.path.join(out, "stats", "**", "*kernel_trace.csv"), recursive=True):
+        for row in csv.DictReader(open(path)):
+            traced[key(row["Kernel_Name"], grid_of(row))].append((int(row["End_Timestamp"]) - int(row["Start_Timestamp"])) / 1e3)
+    pmc = defaultdict(lambda: defaultdict(list))
+    for c in ("FETCH_SIZE", "WRITE_SIZE"):
+        for path in glob.glob(os.path.join(out, f"pmc_{c}", "**", "*counter_collection.csv"), recursive=True):
+            for row in csv.DictReader(open(path)):
+                if row["Counter_Name"] != c:
+                    continue
+                pmc[key(row.get("Kernel_Name") or row.get("Kernel"), grid_of(row))][c].append(float(row["Counter_Value"]))
+    rows = []
+    print(f"{'kernel':12s} {'nt':>2s} {'slots':>9s} {'event_us':>9s} {'trace_us':>9s} {'read_B':>7s} {'write_B':>7s}")
+    for k in sorted(times, key=lambda k: (k[2], k[1], k[0])):
+        base, nt, slots = k
+        tr = statistics.median(traced[k]) if traced[k] else float("nan")
+        rd = 2 * statistics.median(pmc[k]["FETCH_SIZE"]) * 1024 / slots if pmc[k]["FETCH_SIZE"] else float("nan")
+        wr = statistics.median(pmc[k]["WRITE_SIZE"]) * 1024 / slots if pmc[k]["WRITE_SIZE"] else float("nan")
+        rows.append(dict(kernel=base, nt=nt, slots=slots, event_us=times[k], trace_median_us=round(tr, 3),
+                         read_B_per_slot=round(rd, 2), write_B_per_slot=round(wr, 2)))
+        print(f"{base:12s} {int(nt):2d} {slots:9d} {times[k]:9.2f} {tr:9.2f} {rd:7.2f} {wr:7.2f}")
+    json.dump(rows, open(os.path.join(out, "digest.json"), "w"), indent=1)
+
+
+if __name__ == "__main__":
+    main()
