@@ -212,13 +212,13 @@ __global__ void __launch_bounds__(256) k_bp_bounds(uint64_t n_slots, const uint3
 // extent histogram is then a histogram of WAVE maxima: bin b holds the bodies of the waves whose widest body falls into b
 // (they are all at most that wide) and, as its "large" weight, the number of such waves.  Good enough to choose the cell
 // size — the choice only affects speed: whatever the cell, a body wider than it is treated as large by the sort itself.
-// With `decide` the workgroup that finishes last goes on to choose the grid (decide_grid below) — what a separate
-// k_bp_params launch did: 5.2 + 15.6 us as two kernels at 4 M bodies (profiles/r02/cube4m_kernel_stats.csv).
+// The workgroup that finishes last goes on to choose the grid (decide_grid below) — what a separate k_bp_params launch
+// did: 5.2 + 15.6 us as two kernels at 4 M bodies (profiles/r02/cube4m_kernel_stats.csv; variant removed).
 constexpr uint32_t kReduceBlocks = 128;
 template <uint32_t NS> __device__ void decide_grid(Accum* acc, uint32_t max_cells, uint32_t n_bounds_blocks);
 constexpr uint32_t kReduceShards = 4; // histogram copies the 128 workgroups of k_bp_reduce_partials spread their atomics over
 __global__ void __launch_bounds__(256) k_bp_reduce_partials(const float4* __restrict__ partials, uint32_t n_partials, Accum* acc,
-                                                            uint32_t max_cells, uint32_t decide)
+                                                            uint32_t max_cells)
 {
     __shared__ uint32_t hist[kExtentBins];
     __shared__ uint32_t hwaves[kExtentBins];
@@ -315,7 +315,6 @@ __global__ void __launch_bounds__(256) k_bp_reduce_partials(const float4* __rest
             if (hmax[k]) atomicMax(&acc->extent_max[blockIdx.x % kReduceShards][k], hmax[k]);
         }
     }
-    if (!decide) return;
     // Every thread's stores and atomics are made visible at device scope, then one ticket per workgroup; whoever draws the
     // last one sees all the others' results (acquire: this CU's vector L1 is dropped) and decides.  Every workgroup reaches
     // this point, so the ticket word is back at 0 when the kernel ends.
@@ -552,7 +551,7 @@ template <uint32_t NS> __device__ void decide_grid(Accum* acc, uint32_t max_cell
     acc->grid = g;
 }
 
-// decide_grid as a launch of its own: after k_bp_bounds, and after k_bp_reduce_partials under BGE_BP_PARAMS=split
+// decide_grid as a launch of its own, after k_bp_bounds
 __global__ void __launch_bounds__(kParamsThreads) k_bp_params(Accum* acc, uint32_t max_cells, uint32_t n_bounds_blocks)
 {
     decide_grid<kHistShards>(acc, max_cells, n_bounds_blocks);
@@ -600,7 +599,7 @@ __global__ void __launch_bounds__(256) k_bp_count(uint64_t n_slots, const uint32
 // ---- exclusive scan of cell_count[0..n) into cell_start[0..n], n = padded to kScanBlock multiples by the caller
 constexpr uint32_t kScanBlock = 2048; // 256 threads x 8
 
-// Single-pass scan: one read and one write of the table instead of the three kernels below (76 us -> see DESIGN.md 4.3).
+// Single-pass scan: one read and one write of the table instead of three kernels (variant removed; 76 us -> see DESIGN.md 4.3).
 // The table has at most ~1000 tiles of 8192 cells, so there is no look-back CHAIN: every tile publishes its own sum and
 // then adds up the sums of ALL earlier tiles itself (256 threads x <= 4 status words, one round trip), O(tiles^2 / 2)
 // 8-byte reads in total — 4 MB for 1024 tiles.
@@ -688,77 +687,6 @@ __global__ void __launch_bounds__(256) k_scan_lookback(const uint32_t* __restric
         o.w = o.z + v[k].z;
         run = o.w + v[k].w;
         dst[k] = o;
-    }
-}
-
-__global__ void __launch_bounds__(256) k_scan_blocks(const uint32_t* __restrict__ in, uint32_t* __restrict__ out,
-                                                     uint32_t* __restrict__ block_sums, uint32_t n)
-{
-    __shared__ uint32_t wave_tot[4];
-    const uint32_t base = blockIdx.x * kScanBlock + threadIdx.x * 8;
-    uint32_t v[8];
-    uint32_t sum = 0;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        v[k] = (base + k < n) ? in[base + k] : 0u;
-        sum += v[k];
-    }
-    // inclusive scan of per-thread sums across the wave
-    uint32_t incl = sum;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t t = __shfl_up(incl, off, 64);
-        if ((threadIdx.x & 63u) >= static_cast<uint32_t>(off)) incl += t;
-    }
-    const uint32_t wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63u) == 63u) wave_tot[wave] = incl;
-    __syncthreads();
-    uint32_t wave_base = 0;
-    for (uint32_t k = 0; k < wave; ++k) wave_base += wave_tot[k];
-    uint32_t run = wave_base + incl - sum;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        if (base + k < n) out[base + k] = run;
-        run += v[k];
-    }
-    if (threadIdx.x == 255) block_sums[blockIdx.x] = wave_base + incl;
-}
-
-__global__ void __launch_bounds__(256) k_scan_sums(uint32_t* __restrict__ block_sums, uint32_t n_blocks)
-{
-    // single workgroup: serial over chunks of 256, wave scan inside
-    __shared__ uint32_t wave_tot[4];
-    __shared__ uint32_t carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (uint32_t base = 0; base < n_blocks; base += 256) {
-        const uint32_t i = base + threadIdx.x;
-        const uint32_t v = i < n_blocks ? block_sums[i] : 0u;
-        uint32_t incl = v;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t t = __shfl_up(incl, off, 64);
-            if ((threadIdx.x & 63u) >= static_cast<uint32_t>(off)) incl += t;
-        }
-        const uint32_t wave = threadIdx.x >> 6;
-        if ((threadIdx.x & 63u) == 63u) wave_tot[wave] = incl;
-        __syncthreads();
-        uint32_t wave_base = carry;
-        for (uint32_t k = 0; k < wave; ++k) wave_base += wave_tot[k];
-        if (i < n_blocks) block_sums[i] = wave_base + incl - v;
-        __syncthreads();
-        if (threadIdx.x == 255) carry = wave_base + incl;
-        __syncthreads();
-    }
-}
-
-__global__ void __launch_bounds__(256) k_scan_add(uint32_t* __restrict__ out, const uint32_t* __restrict__ block_sums, uint32_t n)
-{
-    const uint32_t base = blockIdx.x * kScanBlock + threadIdx.x * 8;
-    const uint32_t add = block_sums[blockIdx.x];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        if (base + k < n) out[base + k] += add;
     }
 }
 
@@ -1384,140 +1312,27 @@ __device__ __forceinline__ bool filter_ok(const uint32_t* __restrict__ flags, co
     return !both_static && (group[sa] & mask[sb]) != 0 && (group[sb] & mask[sa]) != 0;
 }
 
-// Pair search, LDS-tiled.  A workgroup owns 256 consecutive sorted bodies.  For each of the 5 neighbour runs the
-// union of its bodies' candidate ranges is one contiguous range of sorted records (records are sorted by cell, x
-// fastest); it is staged through LDS in coalesced chunks of kChunk records, and every lane tests only the part of the
-// chunk that belongs to ITS OWN candidate range.  The first version walked the ranges with dependent global loads
-// (one or two candidates in flight per lane) and was latency-bound at 1.45 ms for 4 M bodies.
-constexpr uint32_t kChunk = 256; // records per staged chunk: 12 KiB of LDS (with 6 KiB of pair staging: 8 workgroups per CU)
-
 __device__ __forceinline__ bool filter_rec(const float4& a2, const float4& b2)
 {
     const bool both_static = __float_as_uint(a2.z) != 0u && __float_as_uint(b2.z) != 0u;
     return !both_static && (__float_as_uint(a2.x) & __float_as_uint(b2.y)) != 0u && (__float_as_uint(b2.x) & __float_as_uint(a2.y)) != 0u;
 }
 
-// WINDOW: apply the slab window of the sharded broadphase (a second instantiation keeps the single-GPU search free of it:
-// the extra sink fields cost ~5 % there, measured)
 __device__ __forceinline__ bool filter_tab(const uint4& a, const uint4& b)
 {
     return !(a.z != 0u && b.z != 0u) && (a.x & b.y) != 0u && (b.x & a.y) != 0u;
 }
 
-template <bool WINDOW, bool COMPACT>
-__global__ void __launch_bounds__(256) k_bp_pairs(const Accum* __restrict__ acc, const uint32_t* __restrict__ cell_start,
-                                                  const float4* __restrict__ sorted, const uint4* __restrict__ filter_table,
-                                                  PairSink sink)
-{
-    constexpr uint32_t RS = COMPACT ? 2u : 3u; // float4 per record
-    __shared__ float4 cand[RS * kChunk];
-    __shared__ uint2 stage_lds[4][kStage];
-    __shared__ uint4 s_tab[COMPACT ? 256 : 1]; // (group, mask, static, 0) per filter class
-    __shared__ uint32_t s_cell_first, s_cell_last;
-
-    const GridParams g = acc->grid;
-    if (COMPACT) s_tab[threadIdx.x] = filter_table[threadIdx.x]; // visible after the first barrier below
-    const uint32_t n_sorted = g.n_bodies - acc->n_large;
-    const uint32_t n_blocks = (n_sorted + 255u) / 256u;
-    WaveStage st{stage_lds[threadIdx.x >> 6], 0u};
-    const uint32_t tid = threadIdx.x;
-
-    for (uint32_t blk = blockIdx.x; blk < n_blocks; blk += gridDim.x) {
-        const uint32_t i = blk * 256u + tid;
-        const bool active = i < n_sorted;
-        float4 lo = make_float4(0, 0, 0, 0), hi = lo, fi = lo;
-        uint32_t cell = 0;
-        if (active) {
-            lo = sorted[static_cast<uint64_t>(RS) * i];
-            hi = sorted[static_cast<uint64_t>(RS) * i + 1];
-            if (COMPACT) {
-                cell = cell_of(g, lo.x, lo.y, lo.z); // the same function of the same bits as in k_bp_count
-            } else {
-                fi = sorted[3ull * i + 2];
-                cell = __float_as_uint(hi.w);
-            }
-        }
-        const uint32_t entity_i = __float_as_uint(lo.w);
-        const uint32_t last_tid = min(255u, n_sorted - 1u - blk * 256u);
-        __syncthreads(); // previous block iteration is done with s_cell_*
-        if (tid == 0) s_cell_first = cell;
-        if (tid == last_tid) s_cell_last = cell;
-        __syncthreads();
-        const uint32_t cell_first = s_cell_first, cell_last = s_cell_last;
-        uint4 own = make_uint4(0, 0, 0, 0);
-        if (COMPACT && active) own = s_tab[__float_as_uint(hi.w) & 255u];
-
-#pragma unroll 1
-        for (int row = 0; row < 5; ++row) {
-            // this lane's candidate range [j, end) and the workgroup's union [r_lo, r_hi)
-            uint32_t j = 0, end = 0, r_lo, r_hi;
-            if (row == 0) {
-                // own cell's later records + the cell to the right
-                if (active) {
-                    j = i + 1;
-                    end = cell_start[cell + 2];
-                }
-                r_lo = blk * 256u + 1u;
-                r_hi = cell_start[cell_last + 2];
-            } else {
-                const int dy = (row == 1) ? 1 : (row - 3); // rows 2,3,4 -> dy = -1,0,1 at dz = 1
-                const int dz = (row == 1) ? 0 : 1;
-                const uint32_t off = static_cast<uint32_t>(dy * static_cast<int>(g.dim_x)) + static_cast<uint32_t>(dz) * g.dim_xy;
-                if (active) {
-                    j = cell_start[cell + off - 1];
-                    end = cell_start[cell + off + 2];
-                }
-                r_lo = cell_start[cell_first + off - 1];
-                r_hi = cell_start[cell_last + off + 2];
-            }
-            for (uint32_t base = r_lo; base < r_hi; base += kChunk) {
-                const uint32_t top = min(base + kChunk, r_hi);
-                // skip chunks no lane needs (sparse worlds: far-apart cells with crowded cells in between)
-                const uint32_t jj0 = max(j, base);
-                const uint32_t e0 = min(end, top);
-                if (!__syncthreads_or(jj0 < e0)) continue;
-                for (uint32_t k = tid; k < RS * (top - base); k += 256u) cand[k] = sorted[static_cast<uint64_t>(RS) * base + k];
-                __syncthreads();
-                uint32_t jj = jj0;
-                while (__any(jj < e0)) {
-                    // two candidates per trip: both LDS fetches are in flight together
-                    bool hit0 = false, hit1 = false;
-                    uint32_t e0j = 0, e1j = 0;
-                    if (jj < e0) {
-                        const uint32_t k0 = RS * (jj - base);
-                        const bool two = jj + 1u < e0;
-                        const uint32_t k1 = two ? k0 + RS : k0;
-                        const float4 alo = cand[k0], ahi = cand[k0 + 1u];
-                        const float4 blo = cand[k1], bhi = cand[k1 + 1u];
-                        if (overlap(lo, hi, alo, ahi)) {
-                            hit0 = (COMPACT ? filter_tab(own, s_tab[__float_as_uint(ahi.w) & 255u]) : filter_rec(fi, cand[k0 + RS - 1u])) &&
-                                   (!WINDOW || in_window(sink, lo, alo));
-                            e0j = __float_as_uint(alo.w);
-                        }
-                        if (two && overlap(lo, hi, blo, bhi)) {
-                            hit1 = (COMPACT ? filter_tab(own, s_tab[__float_as_uint(bhi.w) & 255u]) : filter_rec(fi, cand[k1 + RS - 1u])) &&
-                                   (!WINDOW || in_window(sink, lo, blo));
-                            e1j = __float_as_uint(blo.w);
-                        }
-                        jj += 2u;
-                    }
-                    if (__any(hit0 || hit1)) {
-                        emit_pairs(sink, st, hit0, entity_i, e0j);
-                        emit_pairs(sink, st, hit1, entity_i, e1j);
-                    }
-                }
-                // (the __syncthreads_or at the top of the next iteration protects cand before it is overwritten)
-            }
-        }
-    }
-    if (st.fill) stage_flush(sink, st, st.fill);
-}
-
-// Pair search, wave-granular.  Same algorithm as k_bp_pairs, but the unit of work is ONE WAVE owning 64 consecutive
-// sorted bodies: the candidate chunks are staged in a wave-private LDS region and handed between the lanes of the wave
-// with wave_sync() (a wave's DS operations execute in order), so the kernel has no workgroup barrier at all.  The
-// workgroup version above spent its time waiting — two __syncthreads per staged chunk behind dependent cell_start and
-// record loads — not moving bytes: shrinking the records from 48 to 32 bytes left its 355 us untouched.
+// Pair search, wave-granular.  ONE WAVE owns 64 consecutive sorted bodies.  For each of the 5 neighbour runs the union of its
+// bodies' candidate ranges is one contiguous range of sorted records (records are sorted by cell, x fastest); it is staged
+// through a wave-private LDS region in coalesced chunks, handed between the lanes of the wave with wave_sync() (a wave's DS
+// operations execute in order), and every lane tests only the part of the chunk that belongs to ITS OWN candidate range.
+// The kernel has no workgroup barrier at all.  The first version walked the ranges with dependent global loads (one or two
+// candidates in flight per lane) and was latency-bound at 1.45 ms for 4 M bodies; a workgroup-granular version (256 bodies,
+// chunks of 256 records; variant removed) spent its time waiting — two __syncthreads per staged chunk behind dependent
+// cell_start and record loads — not moving bytes: shrinking the records from 48 to 32 bytes left its 355 us untouched.
+// WINDOW: apply the slab window of the sharded broadphase (a second instantiation keeps the single-GPU search free of it:
+// the extra sink fields cost ~5 % there, measured).
 #ifndef BGE_WAVE_CHUNK
 #define BGE_WAVE_CHUNK 88 /* 8 workgroups per CU (64 VGPRs, 12 B scratch) with 32-byte records; measured at 4 M bodies, step time:
                              96 -> 583 us (7 per CU), 88 -> 577, 80 -> 586, 72 -> 604 (more rows need a second chunk) */
@@ -1906,7 +1721,7 @@ int Broadphase::fail(int code, const char* what, hipError_t e)
 
 void Broadphase::release()
 {
-    for (void** p : {&pairs_, &scan_stage_, &counters_, &cell_count_, &cell_start_, &scan_tmp_, &scan_status_, &sort_matrix_,
+    for (void** p : {&pairs_, &scan_stage_, &counters_, &cell_count_, &cell_start_, &scan_status_, &sort_matrix_,
                      &sort_offsets_, &sort_status_, &coarse_, &sorted_slot_, &sorted_aabb_, &body_cell_,
                      &large_list_}) {
         if (*p) (void)hipFree(*p);
@@ -1944,16 +1759,12 @@ int Broadphase::configure(uint64_t n_slots, uint64_t pair_capacity)
     BP_TRY(hipMalloc(&counters_, sizeof(Accum)));
     BP_TRY(hipMalloc(&cell_count_, (static_cast<size_t>(table_size_) + 2 * kScanTile) * 4)); // whole scan tiles, zero-padded
     BP_TRY(hipMalloc(&cell_start_, (static_cast<size_t>(table_size_) + 2 * kScanTile) * 4));
-    BP_TRY(hipMalloc(&scan_tmp_, (static_cast<size_t>(table_size_) / kScanBlock + 2) * 4));
     BP_TRY(hipMalloc(&scan_status_, (static_cast<size_t>(table_size_) / kScanBlock + 2) * 8));
     BP_TRY(hipMemset(scan_status_, 0, (static_cast<size_t>(table_size_) / kScanBlock + 2) * 8));
     scan_epoch_ = 0;
-    if (const char* e = std::getenv("BGE_BP_SCAN")) three_kernel_scan_ = std::atoi(e) == 3; // A/B: BGE_BP_SCAN=3 keeps the three-kernel scan
-    if (const char* e = std::getenv("BGE_BP_PAIRS")) block_pairs_ = std::string(e) == "block";  // A/B: workgroup-granular pair search
     sort_groups_ = kSortGroups;
     if (const char* e = std::getenv("BGE_BP_SORT_GROUPS")) sort_groups_ = std::min<uint32_t>(kSortGroups, std::max(1, std::atoi(e))); // tests: several passes per workgroup at small n
     if (const char* e = std::getenv("BGE_BP_BOUNDS")) fused_bounds_ = std::string(e) != "pass"; // A/B and tests: k_bp_bounds' own pass over the AABBs
-    if (const char* e = std::getenv("BGE_BP_PARAMS")) fused_params_ = std::string(e) != "split"; // A/B: k_bp_params as its own launch
     if (const char* e = std::getenv("BGE_BP_FILTER")) small_palette_ = std::string(e) != "table"; // A/B and tests: keep the (group, mask) table
     if (const char* e = std::getenv("BGE_BP_COARSE")) transposed_coarse_ = std::string(e) != "scatter"; // A/B: per-thread scattered record writes
     if (const char* e = std::getenv("BGE_BP_RECORDS")) full_records_ = std::atoi(e) == 48;  // A/B: BGE_BP_RECORDS=48 keeps full records
@@ -2018,7 +1829,6 @@ int Broadphase::run(hipStream_t stream, const WorldView& w, uint64_t n, const ui
     Accum* acc = static_cast<Accum*>(counters_);
     uint32_t* cell_count = static_cast<uint32_t*>(cell_count_);
     uint32_t* cell_start = static_cast<uint32_t*>(cell_start_);
-    uint32_t* block_sums = static_cast<uint32_t*>(scan_tmp_);
     uint32_t* body_rank = static_cast<uint32_t*>(sorted_slot_);
     uint32_t* body_cell = static_cast<uint32_t*>(body_cell_);
     uint32_t* large_list = static_cast<uint32_t*>(large_list_);
@@ -2034,7 +1844,6 @@ int Broadphase::run(hipStream_t stream, const WorldView& w, uint64_t n, const ui
     }
     // the scan covers table_size_ + 2 entries (cell_start[c + 2] is read for the last cell)
     const uint32_t scan_n = table_size_ + 2;
-    const uint32_t scan_blocks = blocks_for(scan_n, kScanBlock);
     const uint32_t slot_blocks = blocks_for(n, 256);
 
     uint32_t bounds_blocks = std::min<uint32_t>(slot_blocks, kBoundsBlocks);
@@ -2042,9 +1851,7 @@ int Broadphase::run(hipStream_t stream, const WorldView& w, uint64_t n, const ui
         // the tick kernel left one partial per wave beside the AABBs: 32 bytes per 64 slots instead of 28 per slot
         const uint32_t n_partials = static_cast<uint32_t>(n / 64);
         bounds_blocks = std::min<uint32_t>(kReduceBlocks, blocks_for(n_partials, 256));
-        hipLaunchKernelGGL(k_bp_reduce_partials, dim3(bounds_blocks), dim3(256), 0, stream, wave_partials, n_partials, acc, table_size_,
-                           fused_params_ ? 1u : 0u);
-        if (!fused_params_) hipLaunchKernelGGL(k_bp_params, dim3(1), dim3(kParamsThreads), 0, stream, acc, table_size_, bounds_blocks);
+        hipLaunchKernelGGL(k_bp_reduce_partials, dim3(bounds_blocks), dim3(256), 0, stream, wave_partials, n_partials, acc, table_size_);
     } else {
         hipLaunchKernelGGL(k_bp_bounds, dim3(bounds_blocks), dim3(256), 0, stream, n, w.flags, w.aabb, acc);
         hipLaunchKernelGGL(k_bp_params, dim3(1), dim3(kParamsThreads), 0, stream, acc, table_size_, bounds_blocks);
@@ -2093,16 +1900,10 @@ int Broadphase::run(hipStream_t stream, const WorldView& w, uint64_t n, const ui
         BP_TRY(hipMemsetAsync(cell_count, 0, (static_cast<size_t>(table_size_) + 2 * kScanTile) * 4, stream));
         hipLaunchKernelGGL(k_bp_count, dim3(slot_blocks), dim3(256), 0, stream, n, w.flags, w.aabb, acc, cell_count, body_cell,
                            body_rank, large_list);
-        if (three_kernel_scan_) {
-            hipLaunchKernelGGL(k_scan_blocks, dim3(scan_blocks), dim3(256), 0, stream, cell_count, cell_start, block_sums, scan_n);
-            hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(256), 0, stream, block_sums, scan_blocks);
-            hipLaunchKernelGGL(k_scan_add, dim3(scan_blocks), dim3(256), 0, stream, cell_start, block_sums, scan_n);
-        } else {
-            scan_epoch_ = (scan_epoch_ + 1u) & 0x3fffffffu;
-            if (scan_epoch_ == 0u) scan_epoch_ = 1u; // 0 is what a never-written status word holds
-            hipLaunchKernelGGL(k_scan_lookback, dim3(blocks_for(scan_n, kScanTile)), dim3(256), 0, stream, cell_count, cell_start,
-                               static_cast<unsigned long long*>(scan_status_), acc, scan_n, scan_epoch_, 1u);
-        }
+        scan_epoch_ = (scan_epoch_ + 1u) & 0x3fffffffu;
+        if (scan_epoch_ == 0u) scan_epoch_ = 1u; // 0 is what a never-written status word holds
+        hipLaunchKernelGGL(k_scan_lookback, dim3(blocks_for(scan_n, kScanTile)), dim3(256), 0, stream, cell_count, cell_start,
+                           static_cast<unsigned long long*>(scan_status_), acc, scan_n, scan_epoch_, 1u);
         if (compact_records) {
             hipLaunchKernelGGL(k_bp_scatter<true>, dim3(slot_blocks), dim3(256), 0, stream, n, w.flags, w.aabb, cell_start, body_cell,
                                body_rank, w.group, w.mask, palette->class_of_slot, entity_of_slot, sorted);
@@ -2110,31 +1911,21 @@ int Broadphase::run(hipStream_t stream, const WorldView& w, uint64_t n, const ui
             hipLaunchKernelGGL(k_bp_scatter<false>, dim3(slot_blocks), dim3(256), 0, stream, n, w.flags, w.aabb, cell_start, body_cell,
                                body_rank, w.group, w.mask, static_cast<const uint32_t*>(nullptr), entity_of_slot, sorted);
         }
-        // persistent grid sized to residency: 18 KiB of LDS per workgroup -> 8 per CU on 256 CUs
     }
-    const dim3 pair_grid(std::min<uint32_t>(slot_blocks, 8 * 256));
+    // wave-granular search, persistent grid sized to residency (LDS: 26 KiB per workgroup with 32-byte records, 30 KiB
+    // with full ones).  A software-pipelined variant (all five rows' cell_start loads up front, the next row's chunk
+    // prefetched into registers during the tests) was measured SLOWER: 324 us against 308 us — it needs 95 VGPRs.
     const uint4* no_table = nullptr;
-    if (!block_pairs_) {
-        // wave-granular search, persistent grid sized to residency (LDS: 26 KiB per workgroup with 32-byte records, 30 KiB
-        // with full ones).  A software-pipelined variant (all five rows' cell_start loads up front, the next row's chunk
-        // prefetched into registers during the tests) was measured SLOWER: 324 us against 308 us — it needs 95 VGPRs.
-        const bool small = compact_records && !window && palette->n_classes <= 32u && small_palette_;
-        const dim3 wgrid(std::min<uint32_t>(blocks_for(n, 256), (small ? kWaveResidentSmall : (compact_records ? kWaveResidentCompact : kWaveResidentFull)) * 256));
-        if (window) {
-            hipLaunchKernelGGL((k_bp_pairs_wave<true, false>), wgrid, dim3(256), 0, stream, acc, cell_start, sorted, no_table, sink);
-        } else if (compact_records && palette->n_classes <= 32u && small_palette_) {
-            hipLaunchKernelGGL((k_bp_pairs_wave<false, true, true>), wgrid, dim3(256), 0, stream, acc, cell_start, sorted, palette->table, sink);
-        } else if (compact_records) {
-            hipLaunchKernelGGL((k_bp_pairs_wave<false, true>), wgrid, dim3(256), 0, stream, acc, cell_start, sorted, palette->table, sink);
-        } else {
-            hipLaunchKernelGGL((k_bp_pairs_wave<false, false>), wgrid, dim3(256), 0, stream, acc, cell_start, sorted, no_table, sink);
-        }
-    } else if (window) {
-        hipLaunchKernelGGL((k_bp_pairs<true, false>), pair_grid, dim3(256), 0, stream, acc, cell_start, sorted, no_table, sink);
+    const bool small = compact_records && !window && palette->n_classes <= 32u && small_palette_;
+    const dim3 wgrid(std::min<uint32_t>(blocks_for(n, 256), (small ? kWaveResidentSmall : (compact_records ? kWaveResidentCompact : kWaveResidentFull)) * 256));
+    if (window) {
+        hipLaunchKernelGGL((k_bp_pairs_wave<true, false>), wgrid, dim3(256), 0, stream, acc, cell_start, sorted, no_table, sink);
+    } else if (compact_records && palette->n_classes <= 32u && small_palette_) {
+        hipLaunchKernelGGL((k_bp_pairs_wave<false, true, true>), wgrid, dim3(256), 0, stream, acc, cell_start, sorted, palette->table, sink);
     } else if (compact_records) {
-        hipLaunchKernelGGL((k_bp_pairs<false, true>), pair_grid, dim3(256), 0, stream, acc, cell_start, sorted, palette->table, sink);
+        hipLaunchKernelGGL((k_bp_pairs_wave<false, true>), wgrid, dim3(256), 0, stream, acc, cell_start, sorted, palette->table, sink);
     } else {
-        hipLaunchKernelGGL((k_bp_pairs<false, false>), pair_grid, dim3(256), 0, stream, acc, cell_start, sorted, no_table, sink);
+        hipLaunchKernelGGL((k_bp_pairs_wave<false, false>), wgrid, dim3(256), 0, stream, acc, cell_start, sorted, no_table, sink);
     }
     hipLaunchKernelGGL(k_bp_large, dim3(std::min<uint32_t>(slot_blocks, 1024)), dim3(256), 0, stream, n, acc, large_list,
                        body_cell, w.aabb, w.flags, w.group, w.mask, entity_of_slot, sink);

@@ -78,18 +78,14 @@ private:
     void* counters_ = nullptr;   // device scalars (pair count, bounds, ...)
     void* cell_count_ = nullptr; // uint32[table_size + 1]
     void* cell_start_ = nullptr; // uint32[table_size + 1]
-    void* scan_tmp_ = nullptr;
     void* scan_status_ = nullptr; // uint64[tiles] status words of the single-pass scan
     uint32_t scan_epoch_ = 0;
-    bool three_kernel_scan_ = false;
     bool full_records_ = false;
     // two-level LDS counting sort (k_sort_*)
     bool lds_sort_ = false;
     uint32_t sort_shift_ = 12, sort_buckets_ = 0;
     void *sort_matrix_ = nullptr, *sort_offsets_ = nullptr, *sort_status_ = nullptr, *coarse_ = nullptr;
-    bool block_pairs_ = false;
     bool fused_bounds_ = true;      // grid from the tick kernel's per-wave partials (TickParams::bp_partial) when the caller has them; BGE_BP_BOUNDS=pass for A/B
-    bool fused_params_ = true;      // the last workgroup of k_bp_reduce_partials chooses the grid; BGE_BP_PARAMS=split launches k_bp_params instead
     uint32_t sort_groups_ = 512;    // chunk workgroups of the coarse passes (BGE_BP_SORT_GROUPS lowers it: tests)
     uint32_t fine_window_[2] = {0, 0}; // records in k_sort_fine_t's LDS window: [0] 48-byte records, [1] 32-byte records
     bool small_palette_ = true;     // wave search: one compatibility word per class when the palette has <= 32 classes

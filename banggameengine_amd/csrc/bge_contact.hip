@@ -256,14 +256,10 @@ __global__ void __launch_bounds__(128, BGE_GROUND_MIN_BLOCKS) k_ground(WorldView
     const uint32_t n_list = min(g.list_count[16u * shard], static_cast<uint32_t>(g.shard_cap));
     const uint32_t* list = g.list + static_cast<uint64_t>(shard) * g.shard_cap;
     const uint32_t step = (gridDim.x / kGroundShards) * blockDim.x;
-#ifndef BGE_GROUND_EMPTY /* timing experiment: the launch without the solver (and so without scratch) */
     for (uint32_t i = (blockIdx.x / kGroundShards) * blockDim.x + threadIdx.x; i < n_list; i += step) {
         const uint32_t slot = list[i];
         if (slot < g.n_slots) ground_body<BASIS>(w, g, slot);
     }
-#else
-    if (n_list == 0xffffffffu) w.cinfo[list[step]] = 0;
-#endif
     // the workgroup that draws the shard's last ticket empties its list for the next sub-step's k_ground_select: by then every
     // workgroup of the shard has read the count (it did so before it drew its own ticket).  (One ticket word for all 1024
     // workgroups made an EMPTY launch take 13.6 us: a thousand atomics on one address.)

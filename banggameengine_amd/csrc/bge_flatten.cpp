@@ -2,7 +2,6 @@
 #include "bge_flatten.hpp"
 
 #include <algorithm>
-#include <cstdlib>
 #include <numeric>
 
 namespace bge {
@@ -17,7 +16,6 @@ struct Graph {
     std::vector<uint32_t> child_list;
     std::vector<uint32_t> bfs;         // every node reachable from a root, parents before children
     std::vector<uint32_t> subtree;     // node count of the subtree rooted here (reachable nodes only)
-    std::vector<uint32_t> height;      // levels below this node (leaf = 0)
     std::vector<uint32_t> depth;       // global depth, roots = 0 (kNone if unreachable)
     std::vector<uint32_t> roots;       // in entity order
 };
@@ -69,21 +67,19 @@ void build_graph(uint64_t n, const uint32_t* parent, const uint8_t* has_transfor
         }
     }
     g.subtree.assign(n, 0);
-    g.height.assign(n, 0);
     for (size_t k = g.bfs.size(); k-- > 0;) {
         const uint32_t u = g.bfs[k];
         g.subtree[u] += 1;
         const uint32_t p = g.eff_parent[u];
         if (p != kNone) {
             g.subtree[p] += g.subtree[u];
-            g.height[p] = std::max(g.height[p], g.height[u] + 1);
         }
     }
 }
 
 struct TileBuilder {
     // Nodes of the tile being filled with their in-tile level.  A wave-local tile keeps four groups (one per
-    // wave64) and only ever receives whole subtrees of <= 64 nodes; a block tile uses group 0 as a flat list.
+    // wave64) and only ever receives singletons; a block tile uses group 0 as a flat list.
     std::vector<uint32_t> nodes[4];
     std::vector<uint8_t> levels[4];
     bool wave_local = false;
@@ -115,15 +111,7 @@ struct TileBuilder {
 
 } // namespace
 
-FlattenOptions flatten_options_from_env()
-{
-    FlattenOptions o;
-    if (const char* s = std::getenv("BGE_WAVE_LOCAL_HEIGHT")) o.wave_local_max_height = static_cast<uint32_t>(std::atoi(s));
-    return o;
-}
-
-void flatten_topology(uint64_t n, const uint32_t* parent, const uint8_t* has_transform, Flattened& out,
-                      const FlattenOptions& opt)
+void flatten_topology(uint64_t n, const uint32_t* parent, const uint8_t* has_transform, Flattened& out)
 {
     // Flat scene (no parent links at all, every entity owns a Transform): slot == entity index, wave-local tiles,
     // no graph needed.  (16 M entities: 0.6 s instead of 5-7 s, which was first-touch of ~1.2 GB of temporaries.)
@@ -275,26 +263,12 @@ void flatten_topology(uint64_t n, const uint32_t* parent, const uint8_t* has_tra
                 out.pass_of_entity[r] = pass;
                 continue;
             }
-            // destination of the subtree's nodes
-            std::vector<uint32_t>* dst_nodes;
-            std::vector<uint8_t>* dst_levels;
-            uint32_t budget; // nodes that may still be placed (oversize subtrees are cut when it reaches 0)
-            if (size <= kGroup && g.height[r] <= opt.wave_local_max_height) {
-                int grp = wl.group_with_room(size);
-                if (grp < 0) {
-                    emit_tile(wl, false);
-                    grp = 0;
-                }
-                dst_nodes = &wl.nodes[grp];
-                dst_levels = &wl.levels[grp];
-                budget = size;
-            } else {
-                const bool whole = size <= kTile;
-                if (whole ? size > bk.room() : !bk.empty()) emit_tile(bk, false);
-                dst_nodes = &bk.nodes[0];
-                dst_levels = &bk.levels[0];
-                budget = whole ? size : kTile;
-            }
+            // a block tile takes the subtree
+            const bool whole = size <= kTile;
+            if (whole ? size > bk.room() : !bk.empty()) emit_tile(bk, false);
+            std::vector<uint32_t>* dst_nodes = &bk.nodes[0];
+            std::vector<uint8_t>* dst_levels = &bk.levels[0];
+            uint32_t budget = whole ? size : kTile; // nodes that may still be placed (oversize subtrees are cut when it reaches 0)
             // breadth-first over the subtree; an oversize subtree is cut when its tile is full
             queue.clear();
             queue_level.clear();

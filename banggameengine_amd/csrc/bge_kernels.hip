@@ -149,11 +149,6 @@ template <bool IS_MIN> __device__ __forceinline__ float wave_reduce_to_lane63(fl
     return v;
 }
 
-#ifdef BGE_EXPERIMENT_NO_SLEEP /* timing-only A/B build: bodies never fall asleep */
-constexpr bool kSleepEnabled = false;
-#else
-constexpr bool kSleepEnabled = true;
-#endif
 #ifndef BGE_AABB_MIN_WAVES
 #define BGE_AABB_MIN_WAVES 4 /* waves per SIMD the AABB variant is compiled for: at 8 it spills 20 VGPRs (measured ~2 % slower at 4 M bodies) */
 #endif
@@ -213,24 +208,15 @@ __global__ void __launch_bounds__(kTile, NORMAL ? 4 : (AABB ? BGE_AABB_MIN_WAVES
     const uint32_t f0 = w.flags[slot];
     // The component loads do not wait for the flag word: every array is allocated for whole tiles, so the loads of a slot
     // that turns out to be empty (or of a velocity nobody integrates) are harmless, and issuing them together with the flags
-    // takes one memory round trip instead of two out of a workgroup's life (BGE_SPECULATIVE_LOADS=0: A/B build).  Measured at
+    // takes one memory round trip instead of two out of a workgroup's life.  Measured at
     // 1 M flat bodies: 24.4 -> 23.7 us per tick; velocities are only loaded early in tiles whose slots all carry a Dynamic body
     // (loading them everywhere cost 64-node subtrees, 1 body in 64 entities, 4 % more time)
-#ifndef BGE_SPECULATIVE_LOADS
-#define BGE_SPECULATIVE_LOADS 1
-#endif
-    F3 pos{0.0f, 0.0f, 0.0f}, eul{0.0f, 0.0f, 0.0f}, scl{1.0f, 1.0f, 1.0f}, vel_early{0.0f, 0.0f, 0.0f};
-    if (BGE_SPECULATIVE_LOADS) {
-        pos = ld3(w.pos, slot);
-        if (!rs_hint) {
-            eul = ld3(w.euler, slot);
-            if (XFORM) scl = ld3(w.scale, slot);
-        }
-#ifndef BGE_SPECULATIVE_VEL
-#define BGE_SPECULATIVE_VEL 1
-#endif
-        if (BGE_SPECULATIVE_VEL && PHYS && (hdr & kHdrAllDynamic)) vel_early = ld3(w.vel, slot); // (elsewhere most slots have no velocity to read)
+    F3 pos = ld3(w.pos, slot), eul{0.0f, 0.0f, 0.0f}, scl{1.0f, 1.0f, 1.0f}, vel_early{0.0f, 0.0f, 0.0f};
+    if (!rs_hint) {
+        eul = ld3(w.euler, slot);
+        if (XFORM) scl = ld3(w.scale, slot);
     }
+    if (PHYS && (hdr & kHdrAllDynamic)) vel_early = ld3(w.vel, slot); // (elsewhere most slots have no velocity to read)
     // The mass palette entry (gravity force, inverse mass) is one more dependent round trip behind the flag word.  In tiles whose
     // slots all carry a Dynamic body every lane fetches palette entry (lane) with the loads above and takes its class's entry
     // from lane (class) once the flags are there (classes are < 64; outside any divergent branch: a permute reads active lanes).
@@ -238,11 +224,8 @@ __global__ void __launch_bounds__(kTile, NORMAL ? 4 : (AABB ? BGE_AABB_MIN_WAVES
     // with at least one Dynamic body in eight slots made depth-4 chains (bodies on the roots) 3 % SLOWER (22.5 -> 23.2 us): there
     // the extra loads cost more than the round trip they hide.  Not in the Bullet-basis variant either: 31.9 -> 32.1 us with it (and
     // with the queue counter's barrier moved behind the first loads), three alternating runs.
-#ifndef BGE_PALETTE_SHUFFLE
-#define BGE_PALETTE_SHUFFLE 1
-#endif
     float4 gf_early = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    const bool palette_early = BGE_PALETTE_SHUFFLE && BGE_SPECULATIVE_LOADS && PHYS && !BASIS && (hdr & kHdrAllDynamic);
+    const bool palette_early = PHYS && !BASIS && (hdr & kHdrAllDynamic);
     if (palette_early) {
         const float4 mine = w.grav_palette[tid & 63u];
         const int cls0 = static_cast<int>((f0 >> kMassShift) & 63u);
@@ -252,7 +235,7 @@ __global__ void __launch_bounds__(kTile, NORMAL ? 4 : (AABB ? BGE_AABB_MIN_WAVES
     // are asleep — are two more dependent round trips behind the flag word; in all-dynamic tiles they are requested with the
     // first loads (8 B per body more, only in ticks that follow a k_ground launch).
     uint32_t ci_early = 0, dz_early = 0;
-    const bool ground_early = BGE_SPECULATIVE_LOADS && PHYS && p.cinfo_in != nullptr && (hdr & kHdrAllDynamic);
+    const bool ground_early = PHYS && p.cinfo_in != nullptr && (hdr & kHdrAllDynamic);
     if (ground_early) {
         ci_early = p.cinfo_in[slot];
         dz_early = w.deact[slot];
@@ -264,17 +247,9 @@ __global__ void __launch_bounds__(kTile, NORMAL ? 4 : (AABB ? BGE_AABB_MIN_WAVES
     // removes it while the component exists): it is stepped, collides and enters trigger volumes like any other, but it is
     // never re-posed or re-created and nothing is written back.  Here: the physics part runs, the transform part does not.
     const bool orphan_body = PHYS && !valid && (f & kTypeMask) != 0;
-    if (BGE_SPECULATIVE_LOADS) {
-        if (!valid && !orphan_body) {
-            pos = eul = F3{0.0f, 0.0f, 0.0f};
-            scl = F3{1.0f, 1.0f, 1.0f};
-        }
-    } else if (valid || orphan_body) {
-        pos = ld3(w.pos, slot);
-        if (!rs_hint) {
-            eul = ld3(w.euler, slot);
-            if (XFORM) scl = ld3(w.scale, slot);
-        }
+    if (!valid && !orphan_body) {
+        pos = eul = F3{0.0f, 0.0f, 0.0f};
+        scl = F3{1.0f, 1.0f, 1.0f};
     }
     // The flags confirm the word: no valid lane re-poses (which rewrites euler), spins (which turns it), has an external parent
     // or a parent in the tile.  (Orphaned bodies never read euler / scale here.)  Otherwise the lanes load what they skipped.
@@ -326,7 +301,7 @@ __global__ void __launch_bounds__(kTile, NORMAL ? 4 : (AABB ? BGE_AABB_MIN_WAVES
                     if (!BASIS) turn = false; // its angular velocity is zero now: the default scheme leaves the re-posed quaternion alone
                 }
             } else {
-                if (dynamic) v = (BGE_SPECULATIVE_LOADS && BGE_SPECULATIVE_VEL && (hdr & kHdrAllDynamic)) ? vel_early : ld3(w.vel, slot);
+                if (dynamic) v = (hdr & kHdrAllDynamic) ? vel_early : ld3(w.vel, slot);
                 if (spin) av = ld3(w.angvel, slot);
                 if (turn || AABB) q = ld4(w.quat, slot);
             }
@@ -390,7 +365,7 @@ __global__ void __launch_bounds__(kTile, NORMAL ? 4 : (AABB ? BGE_AABB_MIN_WAVES
                 }
                 // Deactivation record: untouched (and unread) while the body is fast and its timer is zero.
                 // (kDrowsy <=> record != 0; body (re)creation clears the bit: a new btRigidBody is ACTIVE_TAG, timer 0)
-                const uint32_t dz0 = (kSleepEnabled && (f & kDrowsy)) ? (ground_early ? dz_early : w.deact[slot]) : 0u;
+                const uint32_t dz0 = (f & kDrowsy) ? (ground_early ? dz_early : w.deact[slot]) : 0u;
                 uint32_t dz = dz0;
                 // buildIslands: a free body is an island of its own; WANTS_DEACTIVATION -> ISLAND_SLEEPING
                 // (kCiIsland: an island of several bodies with an active body in it keeps this one awake — bge_island.hip k_island_flags)
@@ -441,7 +416,7 @@ __global__ void __launch_bounds__(kTile, NORMAL ? 4 : (AABB ? BGE_AABB_MIN_WAVES
                     // arithmetic too (rounding is monotone and the other two squares are >= 0), i.e. "not slow".
                     // (Measured at 1 M bodies: sleeping support costs 1.4 % of the tick this way, 2.0 % with the full test on
                     // every body, 2.9 % with the record handling moved behind a separate branch.)
-                    if (kSleepEnabled && (!(fabsf(v.y) >= p.sleep_lin) || dz != 0u)) {
+                    if (!(fabsf(v.y) >= p.sleep_lin) || dz != 0u) {
                         const float lin2 = v.x * v.x + v.y * v.y + v.z * v.z;
                         const float ang2 = av.x * av.x + av.y * av.y + av.z * av.z;
                         const bool slow = lin2 < p.sleep_lin2 && ang2 < p.sleep_ang2;
@@ -488,15 +463,12 @@ __global__ void __launch_bounds__(kTile, NORMAL ? 4 : (AABB ? BGE_AABB_MIN_WAVES
         // (rotating the wave that takes the first 64 entries with the workgroup index, so that not every resident workgroup's
         //  wave 0 does this work, changed nothing: 32.1 against 31.8 us)
         const uint32_t et = tid;
-#ifndef BGE_EXPERIMENT_BASIS /* timing-only A/B builds (results are wrong): 1 = no orientation step for the queued bodies, 2 = no euler angles either */
-#define BGE_EXPERIMENT_BASIS 0
-#endif
         if (et < n_queued) {
             const float4 qq = eq_quat[et], aa = eq_av[et];
             const uint32_t in = __float_as_uint(aa.w);
             Q4 q{qq.x, qq.y, qq.z, qq.w};
             uint32_t out = (in & kEqForce) ? kEqStoreEuler : 0u;
-            if ((in & kEqIntegrate) && BGE_EXPERIMENT_BASIS == 0) {
+            if (in & kEqIntegrate) {
                 const Q4 qn = bt_integrate_orientation(bt_quat_from_mat_sel(bt_mat_from_quat(q)), F3{aa.x, aa.y, aa.z}, p.dt);
                 const bool same = !(in & kEqForce) && __float_as_uint(qn.x) == __float_as_uint(q.x) && __float_as_uint(qn.y) == __float_as_uint(q.y) &&
                                   __float_as_uint(qn.z) == __float_as_uint(q.z) && __float_as_uint(qn.w) == __float_as_uint(q.w);
@@ -507,7 +479,7 @@ __global__ void __launch_bounds__(kTile, NORMAL ? 4 : (AABB ? BGE_AABB_MIN_WAVES
                 q = qn;
             }
             F3 e{0.0f, 0.0f, 0.0f};
-            if ((out & kEqStoreEuler) && BGE_EXPERIMENT_BASIS < 2) e = bt_transform_euler_from_mat<true>(bt_mat_from_quat(q));
+            if (out & kEqStoreEuler) e = bt_transform_euler_from_mat<true>(bt_mat_from_quat(q));
             eq_quat[et] = make_float4(q.x, q.y, q.z, q.w);
             eq_av[et] = make_float4(e.x, e.y, e.z, __uint_as_float(out));
         }
@@ -573,8 +545,8 @@ __global__ void __launch_bounds__(kTile, NORMAL ? 4 : (AABB ? BGE_AABB_MIN_WAVES
         }
 
         if (hdr & kHdrWaveLocal) {
-            // Every parent sits in its child's own 64-slot group (one wave64): the level loop and the write-out
-            // need no workgroup barrier — DS operations of one wave execute in order.
+            // Singletons at level 0 only (bge_flatten.hpp kHdrWaveLocal): the write-out needs no workgroup barrier — DS
+            // operations of one wave execute in order.
             if (valid && level == 0) {
                 if (f & kExtParent) {
                     world_mul_put(lds, w.world, w.parent[slot], tid, local);
@@ -585,16 +557,6 @@ __global__ void __launch_bounds__(kTile, NORMAL ? 4 : (AABB ? BGE_AABB_MIN_WAVES
                         if (keep_world) store_root_stored(p.root_out, w.root_index[slot], w.world, slot);
                         else store_root(p.root_out, w.root_index[slot], local);
                     }
-                }
-            }
-            if (max_level != 0) {
-                const uint32_t parent = (f & kParentMask) >> kParentShift;
-                uint32_t wave_max = level;
-#pragma unroll
-                for (int off = 32; off > 0; off >>= 1) wave_max = max(wave_max, static_cast<uint32_t>(__shfl_xor(wave_max, off, 64)));
-                for (uint32_t d = 1; d <= wave_max; ++d) {
-                    wave_lds_sync();
-                    if (valid && level == d) lds_mul_put(lds, parent, tid, local); // parent * local — the reference's order
                 }
             }
             wave_lds_sync();
@@ -655,9 +617,7 @@ __global__ void __launch_bounds__(kTile, NORMAL ? 4 : (AABB ? BGE_AABB_MIN_WAVES
                 }
             }
             for (uint32_t d = 1; d <= max_level; ++d) {
-#ifndef BGE_EXPERIMENT_NO_LEVEL_BARRIER /* timing-only A/B build: results are wrong without the barrier */
                 __syncthreads();
-#endif
                 if (valid && level == d) lds_mul_put(lds, parent, tid, local); // parent * local — the reference's order
             }
             __syncthreads();

@@ -155,7 +155,7 @@ struct IslandParams {
     void* rows;                     // [row_cap] IslRow: the contact rows in [0, row_cap / 2), the friction rows behind them
     void* rows_cold;                // [row_cap / 2] IslRowCold: what only the split-impulse sweeps and the write-back need of a contact row
     uint32_t row_cap;
-    uint32_t iterations;            // 10 (btContactSolverInfo::m_numIterations); BGE_ISLAND_ITERATIONS overrides it for MEASUREMENTS only
+    uint32_t iterations;            // 10 (btContactSolverInfo::m_numIterations)
     // islands too big for one thread's LDS column: k_island_solve lists them, k_island_solve_big takes a workgroup to each
     uint32_t* big_list;             // [n_bodies][2] first body, end (counts[4] of them; counts[5] is the workgroups' ticket)
     uint32_t* mid_list;             // [n_bodies][2] likewise, islands of 5 .. 16 bodies (counts[7] of them): k_island_solve<.., true>

@@ -313,19 +313,6 @@ struct bge_world {
         return t;
     }
 
-    // opt-in hipGraph replay of back-to-back ticks (BGE_USE_GRAPH=1; measured slower than eager launches, see tick_many)
-    static constexpr uint32_t kGraphTicks = 32;
-    static constexpr uint32_t kGraphMaxTiles = 512; // ~131 k entities: above that a tick outlasts a host launch anyway
-    hipGraphExec_t graph_exec = nullptr;
-    uint32_t graph_flags = 0;
-    float graph_dt = 0.0f, graph_g[3] = {0, 0, 0};
-    bool graph_disabled = false;
-    void drop_graph()
-    {
-        if (graph_exec) (void)hipGraphExecDestroy(graph_exec);
-        graph_exec = nullptr;
-    }
-
     // optional event-pair timing of the tick kernels
     int profiling = 0;                   // 0 off, 1 one pair per tick_many call, 2 one pair per tick
     std::vector<hipEvent_t> prof_events; // start/stop pairs
@@ -336,7 +323,6 @@ struct bge_world {
 
     void rebuild_view()
     {
-        drop_graph(); // captured launches hold the old pointers
         view.flags = flags.as<uint32_t>();
         view.parent = parent.as<uint32_t>();
         view.tile_hdr = tile_hdr.as<uint32_t>();
@@ -390,7 +376,6 @@ struct bge_world {
         router.release();
         for (DevBuf* b : {&global_of_slot, &bp_send, &bp_recv, &bp_small, &bp_hist}) b->release();
         comm.destroy();
-        drop_graph();
         for (hipEvent_t e : prof_events) (void)hipEventDestroy(e);
         prof_events.clear();
     }
@@ -1080,7 +1065,6 @@ int island_substep(bge_world* w, bge::GroundParams& gp, uint64_t n_slots, bool b
     ip.int_cap = static_cast<uint32_t>(std::min<uint64_t>(int_cap, 0xffffffffu));
     ip.big_points = w->isl_big_points;
     ip.iterations = 10u;
-    if (const char* e = std::getenv("BGE_ISLAND_ITERATIONS")) ip.iterations = static_cast<uint32_t>(std::strtoul(e, nullptr, 10)); // (measurements: what the set-up costs)
     HIP_TRY(bge::launch_island_solve(w->stream, w->view, gp, ip, bullet_basis));
     return BGE_OK;
 }
@@ -1636,7 +1620,6 @@ static int upload_bodies_impl(bge_world* w, uint64_t first, uint64_t count, cons
         if (changed) {
             HIP_TRY(hipStreamSynchronize(w->stream));
             HIP_TRY(hipMemcpy(w->tile_hdr.p, w->flat.tile_hdr.data(), static_cast<size_t>(w->flat.n_tiles_total) * 4, hipMemcpyHostToDevice));
-            w->drop_graph();
         }
     }
     const size_t bytes = words.size() * 4;
@@ -1680,6 +1663,7 @@ struct SubStep {
     bool ghosts_posed = false; // the trigger ghosts were posed (and their activation rule applied) before the first sub-step
 };
 int tick_impl(bge_world* w, uint32_t ticks, float dt, const float gravity[3], uint32_t flags, SubStep sub);
+uint64_t ticked_slots(const bge_world* w) { return static_cast<uint64_t>(w->flat.n_tiles_ticked) * bge::kTile; }
 } // namespace
 
 int bge_world_tick_many(bge_world* w, uint32_t ticks, float dt, const float gravity[3], uint32_t flags)
@@ -1689,6 +1673,119 @@ try {
 BGE_CATCH_ALL("bge_world_tick_many")
 
 namespace {
+// The sub-step's contacts (ground plane, obstacles, Dynamic pairs).  Bullet's order inside PhysicsSystem::Update: teleport dirty
+// bodies (before stepSimulation), then per sub-step collision detection + solver, then integrateTransforms — so k_ground_select
+// re-poses them (once per stepSimulation call) and picks the bodies at the ground, k_ground collides and solves those, and the
+// tick kernel integrates.
+int contact_substep(bge_world* w, bge::TickParams& p, float dt, const float gravity[3], uint32_t flags, SubStep sub)
+{
+    const uint64_t n_slots = ticked_slots(w);
+    // the solver's work list: slots + its count and ticket words (left at zero by every k_ground)
+    const uint64_t shard_cap = bge::ground_shard_cap(n_slots);
+    const size_t list_bytes = shard_cap * bge::kGroundShards * 4, count_bytes = (bge::kGroundShards + 1) * 64;
+    if (w->ground_list.bytes < list_bytes || !w->ground_count.p) {
+        HIP_TRY(w->ground_list.ensure(list_bytes));
+        HIP_TRY(w->ground_count.ensure(count_bytes));
+        HIP_TRY(hipMemsetAsync(w->ground_count.p, 0, count_bytes, w->stream));
+    }
+    bge::GroundParams gp{};
+    gp.repose = sub.no_repose ? 0u : 1u; // (the teleport rule is part of k_ground_select)
+    gp.list = w->ground_list.as<uint32_t>();
+    gp.list_count = w->ground_count.as<uint32_t>();
+    gp.shard_cap = shard_cap;
+    gp.dt = dt;
+    gp.gx = gravity[0];
+    gp.gy = gravity[1];
+    gp.gz = gravity[2];
+    gp.n_slots = n_slots;
+    gp.want_aabb = (flags & (BGE_TICK_BROADPHASE | BGE_TICK_AABBS)) ? 1u : 0u;
+    gp.plane = w->ground_plane ? 1u : 0u;
+    if (w->static_contacts) {
+        if (int rc = prepare_obstacles(w, n_slots)) return rc;
+        gp.obstacle_slots = w->obstacle_slots.as<uint32_t>();
+        gp.obstacle_gen = w->obstacle_gen.as<uint32_t>();
+        gp.obstacles = w->obstacles.as<bge::ObstacleRec>();
+        gp.n_obstacles = w->n_obstacles;
+        if (w->obstacle_grid_on && w->n_obstacles > bge::kObstacleGridMin) {
+            gp.obstacle_grid = w->obstacle_grid.as<uint32_t>();
+            gp.obstacle_grid_cap = 64u * w->n_obstacles;
+        }
+        gp.entity_of_slot = w->entity_of_slot.as<uint32_t>();
+        gp.box_list = w->box_list.as<uint32_t>();
+        gp.box_count = w->box_count.as<uint32_t>();
+    }
+    if (w->dynamic_contacts) {
+        if (int rc = island_substep(w, gp, n_slots, (flags & BGE_TICK_BULLET_BASIS) != 0, sub.no_repose != 0, (flags & BGE_TICK_BROADPHASE) != 0)) return rc;
+    }
+    HIP_TRY(bge::launch_ground(w->stream, w->view, gp, (flags & BGE_TICK_BULLET_BASIS) != 0));
+    p.no_repose = 1u;
+    p.cinfo_in = w->cinfo.as<uint32_t>();
+    return BGE_OK;
+}
+
+// The tick's broadphase after the tick kernel, and the trigger volumes' overlaps with the new boxes
+int broadphase_and_triggers(bge_world* w, bool with_triggers)
+{
+    // buffers are sized on first use: a world that never asks for pairs does not pay for them
+    const uint64_t cap = w->pair_capacity_req ? w->pair_capacity_req : std::max<uint64_t>(8 * w->flat.n_entities, 4096);
+    int rc = BGE_OK;
+    if (!(w->dynamic_contacts && w->bp_shared)) rc = w->broadphase.configure(std::max<uint64_t>(w->flat.n_slots, bge::kTile), cap);
+    if (rc != BGE_OK) return fail(rc, "broadphase allocation failed: %s", w->broadphase.error());
+    bge::FilterPalette palette{};
+    if (int prc = filter_palette_of(w, &palette)) return prc;
+    if (!(w->dynamic_contacts && w->bp_shared)) { // (else: island_substep ran it on these very boxes)
+        rc = w->broadphase.run(w->stream, w->view, ticked_slots(w), w->entity_of_slot.as<uint32_t>(), nullptr, &palette, w->bp_partials.as<float4>());
+        if (rc != BGE_OK) return fail(rc, "broadphase failed: %s", w->broadphase.error());
+    }
+    w->bp_shared = false;
+    w->pairs_from_slab = false;
+    if (with_triggers) {
+        // counters: [0] overlaps found, [1] ghosts left to the all-bodies pass, [2] ghosts walked through the grid
+        HIP_TRY(hipMemsetAsync(w->trig_count.p, 0, 12, w->stream));
+        const uint32_t n_trig = static_cast<uint32_t>(w->triggers.size());
+        const uint32_t* big_list = nullptr;
+        if (n_trig > w->trigger_grid_min) {
+            // many ghosts: the ones that cover few cells look their bodies up in the broadphase's sorted grid
+            // (n_bodies x n_triggers box tests otherwise: 4 M bodies x 1000 ghosts = 4 G tests a tick)
+            HIP_TRY(w->trig_lists.ensure(static_cast<size_t>(n_trig) * 8));
+            const bge::TriggerView tv = w->trigger_view();
+            const bge::BoxQuery q{n_trig, tv.aabb, tv.group, tv.mask, tv.entity, w->trig_count.as<uint32_t>(),
+                                  w->trig_lists.as<uint32_t>(), w->trig_lists.as<uint32_t>() + n_trig,
+                                  static_cast<uint2*>(w->trig_pairs.p), kTriggerPairCap};
+            rc = w->broadphase.query_boxes(w->stream, w->view, w->entity_of_slot.as<uint32_t>(), &palette, q);
+            if (rc != BGE_OK) return fail(rc, "trigger query failed: %s", w->broadphase.error());
+            big_list = w->trig_lists.as<uint32_t>();
+        }
+        HIP_TRY(bge::launch_trigger_pairs(w->stream, ticked_slots(w), n_trig,
+                                          w->trigger_view(), w->view, w->entity_of_slot.as<uint32_t>(), w->trig_count.as<uint32_t>(),
+                                          w->trig_pairs.p, kTriggerPairCap, big_list,
+                                          big_list ? w->trig_count.as<uint32_t>() + 1 : nullptr));
+        HIP_TRY(bge::launch_trigger_ghost_pairs(w->stream, n_trig, w->trigger_view(), w->trig_count.as<uint32_t>(), w->trig_pairs.p,
+                                                kTriggerPairCap));
+        // The short way needs last tick's table to hold exactly the host's sets and no one-shot volume in the world (one that
+        // fires leaves the world in the middle of ProcessTriggerEvents' loop and takes itself out of the later ghosts' lists:
+        // that order dependence stays on the host)
+        bool short_way = w->trig_device_diff && w->trig_mirror_valid;
+        for (const bge_world::Trigger& t : w->triggers) short_way = short_way && !(t.one_shot && t.runtime_active);
+        int how = 1;
+        if (short_way) {
+            how = process_trigger_pairs_fast(w);
+            if (how < 0) return how;
+        }
+        if (how == 1) {
+            if (int rc2 = process_trigger_pairs(w)) return rc2;
+            ++w->trig_slow_ticks;
+            w->trig_mirror_valid = false;
+            bool one_shot = false;
+            for (const bge_world::Trigger& t : w->triggers) one_shot = one_shot || (t.one_shot && t.runtime_active);
+            if (w->trig_device_diff && !one_shot) {
+                if (int rc2 = rebuild_trigger_mirror(w)) return rc2;
+            }
+        }
+    }
+    return BGE_OK;
+}
+
 int tick_impl(bge_world* w, uint32_t ticks, float dt, const float gravity[3], uint32_t flags, SubStep sub)
 {
     if (!w) return fail(BGE_ERR_INVALID, "world is NULL");
@@ -1732,7 +1829,6 @@ int tick_impl(bge_world* w, uint32_t ticks, float dt, const float gravity[3], ui
         HIP_TRY(hipMemcpy(w->grav_palette.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
         std::memcpy(w->grav_cached, gravity, 12);
         w->grav_palette_stale = false;
-        w->drop_graph();
     }
     if (w->profiling) {
         // room for every pair of this call, so that no mid-run synchronisation is needed
@@ -1741,70 +1837,6 @@ int tick_impl(bge_world* w, uint32_t ticks, float dt, const float gravity[3], ui
             hipEvent_t e = nullptr;
             HIP_TRY(hipEventCreate(&e));
             w->prof_events.push_back(e);
-        }
-    }
-    // Optional (BGE_USE_GRAPH=1): replay a captured hipGraph of 32 ticks instead of issuing every launch from the host.
-    // Same kernels, same order, same results — but MEASURED SLOWER on ROCm 7.2 / MI355X: 10 k entities 5.9 us per tick
-    // against 3.2 us eager, 100 k 7.4 against 4.5, 1 M equal (graph kernel nodes cost more than back-to-back eager
-    // launches on one stream), so it is off by default.
-    uint32_t first_eager = 0;
-    const bool use_graph = std::getenv("BGE_USE_GRAPH") != nullptr;
-    if (use_graph && !sub.no_repose && !w->ground_plane && !w->dynamic_contacts && !w->graph_disabled && phys && ticks >= 2 * bge_world::kGraphTicks && w->profiling != 2 &&
-        !(flags & (BGE_TICK_BROADPHASE | BGE_TICK_AABBS | BGE_TICK_GATHER_ROOTS)) && w->flat.n_tiles_ticked <= bge_world::kGraphMaxTiles &&
-        w->flat.n_tiles_ticked > 0) {
-        const bool same = w->graph_exec && w->graph_flags == flags && w->graph_dt == dt && w->graph_g[0] == gravity[0] &&
-                          w->graph_g[1] == gravity[1] && w->graph_g[2] == gravity[2];
-        if (!same) {
-            w->drop_graph();
-            hipGraph_t graph = nullptr;
-            bool ok = hipStreamBeginCapture(w->stream, hipStreamCaptureModeRelaxed) == hipSuccess;
-            if (ok) {
-                bge::TickParams p{};
-                p.dt = dt;
-                p.gx = gravity[0];
-                p.gy = gravity[1];
-                p.gz = gravity[2];
-                p.nt_out = 0; // graph replay is limited to small scenes
-                w->fill_sleep(p);
-                for (uint32_t t = 0; ok && t < bge_world::kGraphTicks; ++t) {
-                    for (size_t pass = 0; ok && pass + 1 < w->flat.pass_tile_begin.size(); ++pass) {
-                        p.tile_begin = w->flat.pass_tile_begin[pass];
-                        ok = bge::launch_tick(w->stream, w->view, p, w->flat.pass_tile_begin[pass + 1] - p.tile_begin, flags) == hipSuccess;
-                    }
-                }
-                ok = (hipStreamEndCapture(w->stream, &graph) == hipSuccess) && ok && graph != nullptr;
-            }
-            if (ok) ok = hipGraphInstantiate(&w->graph_exec, graph, nullptr, nullptr, 0) == hipSuccess;
-            if (graph) (void)hipGraphDestroy(graph);
-            if (!ok) {
-                (void)hipGetLastError();
-                w->drop_graph();
-                w->graph_disabled = true; // capture is not available here: keep issuing launches eagerly
-            } else {
-                w->graph_flags = flags;
-                w->graph_dt = dt;
-                w->graph_g[0] = gravity[0];
-                w->graph_g[1] = gravity[1];
-                w->graph_g[2] = gravity[2];
-            }
-        }
-        if (w->graph_exec) {
-            const uint32_t chunks = ticks / bge_world::kGraphTicks;
-            if (w->profiling == 1) {
-                if (w->prof_used + 2 > w->prof_events.size()) {
-                    if (int rc = fold_profile(w)) return rc;
-                }
-                HIP_TRY(hipEventRecord(w->prof_events[w->prof_used], w->stream));
-            }
-            for (uint32_t c = 0; c < chunks; ++c) HIP_TRY(hipGraphLaunch(w->graph_exec, w->stream));
-            w->rs_bump(); // (captured with the fast path off: TickParams::rs_epoch 0)
-            first_eager = chunks * bge_world::kGraphTicks;
-            w->maybe_dirty = phys && !xform;
-            if (w->profiling == 1 && first_eager == ticks) {
-                HIP_TRY(hipEventRecord(w->prof_events[w->prof_used + 1], w->stream));
-                w->prof_used += 2;
-                w->prof_ticks_pending.push_back(ticks);
-            }
         }
     }
     // Output stores: non-temporal once the tick's working set (~140 B per slot, 204 B with normal matrices) no longer
@@ -1820,7 +1852,7 @@ int tick_impl(bge_world* w, uint32_t ticks, float dt, const float gravity[3], ui
     bool rows_path = xform && !contacts && !nt_out &&
                      !(flags & (BGE_TICK_AABBS | BGE_TICK_BROADPHASE | BGE_TICK_NORMAL_MATRICES | BGE_TICK_BULLET_BASIS | BGE_TICK_GATHER_ROOTS));
     if (const char* e = std::getenv("BGE_WORLD_ROWS")) rows_path = rows_path && std::atoi(e) != 0;
-    for (uint32_t t = first_eager; t < ticks; ++t) {
+    for (uint32_t t = 0; t < ticks; ++t) {
         if (!phys && !w->maybe_dirty && !(flags & BGE_TICK_NORMAL_MATRICES)) {
             // TransformSystem::Update with nothing dirty: a no-op scan — only the kernel launches are skipped.  The
             // collective is NOT: a peer rank may have dirty transforms and issue its gather, and a rank that stayed
@@ -1860,53 +1892,8 @@ int tick_impl(bge_world* w, uint32_t ticks, float dt, const float gravity[3], ui
             }
             p.bp_partial = w->bp_partials.as<float4>();
         }
-        if (phys && (w->ground_plane || w->static_contacts || w->dynamic_contacts)) {
-            // Ground plane on.  Bullet's order inside PhysicsSystem::Update: teleport dirty bodies (before stepSimulation), then per
-            // sub-step collision detection + solver, then integrateTransforms — so k_ground_select re-poses them (once per
-            // stepSimulation call) and picks the bodies at the ground, k_ground collides and solves those, and the tick kernel
-            // integrates.
-            const uint64_t n_slots = static_cast<uint64_t>(w->flat.n_tiles_ticked) * bge::kTile;
-            // the solver's work list: slots + its count and ticket words (left at zero by every k_ground)
-            const uint64_t shard_cap = bge::ground_shard_cap(n_slots);
-            const size_t list_bytes = shard_cap * bge::kGroundShards * 4, count_bytes = (bge::kGroundShards + 1) * 64;
-            if (w->ground_list.bytes < list_bytes || !w->ground_count.p) {
-                HIP_TRY(w->ground_list.ensure(list_bytes));
-                HIP_TRY(w->ground_count.ensure(count_bytes));
-                HIP_TRY(hipMemsetAsync(w->ground_count.p, 0, count_bytes, w->stream));
-                w->drop_graph();
-            }
-            bge::GroundParams gp{};
-            gp.repose = sub.no_repose ? 0u : 1u; // (the teleport rule is part of k_ground_select)
-            gp.list = w->ground_list.as<uint32_t>();
-            gp.list_count = w->ground_count.as<uint32_t>();
-            gp.shard_cap = shard_cap;
-            gp.dt = dt;
-            gp.gx = gravity[0];
-            gp.gy = gravity[1];
-            gp.gz = gravity[2];
-            gp.n_slots = n_slots;
-            gp.want_aabb = (flags & (BGE_TICK_BROADPHASE | BGE_TICK_AABBS)) ? 1u : 0u;
-            gp.plane = w->ground_plane ? 1u : 0u;
-            if (w->static_contacts) {
-                if (int rc = prepare_obstacles(w, n_slots)) return rc;
-                gp.obstacle_slots = w->obstacle_slots.as<uint32_t>();
-                gp.obstacle_gen = w->obstacle_gen.as<uint32_t>();
-                gp.obstacles = w->obstacles.as<bge::ObstacleRec>();
-                gp.n_obstacles = w->n_obstacles;
-                if (w->obstacle_grid_on && w->n_obstacles > bge::kObstacleGridMin) {
-                    gp.obstacle_grid = w->obstacle_grid.as<uint32_t>();
-                    gp.obstacle_grid_cap = 64u * w->n_obstacles;
-                }
-                gp.entity_of_slot = w->entity_of_slot.as<uint32_t>();
-                gp.box_list = w->box_list.as<uint32_t>();
-                gp.box_count = w->box_count.as<uint32_t>();
-            }
-            if (w->dynamic_contacts) {
-                if (int rc = island_substep(w, gp, n_slots, (flags & BGE_TICK_BULLET_BASIS) != 0, sub.no_repose != 0, (flags & BGE_TICK_BROADPHASE) != 0)) return rc;
-            }
-            HIP_TRY(bge::launch_ground(w->stream, w->view, gp, (flags & BGE_TICK_BULLET_BASIS) != 0));
-            p.no_repose = 1u;
-            p.cinfo_in = w->cinfo.as<uint32_t>();
+        if (contacts) {
+            if (int rc = contact_substep(w, p, dt, gravity, flags, sub)) return rc;
         }
         const size_t n_passes = w->flat.pass_tile_begin.size() - 1;
         // BGE_TICK_GATHER_ROOTS with a transform pass: the roots write the all-gather's send buffer themselves
@@ -1923,7 +1910,7 @@ int tick_impl(bge_world* w, uint32_t ticks, float dt, const float gravity[3], ui
             if (w->comm.begin_frame(w->stream, &send) != BGE_OK) return fail(BGE_ERR_HIP, "%s", w->comm.error());
             p.root_out = send;
         }
-        const bool pair_begins = w->profiling == 2 || (w->profiling == 1 && t == 0); // (t == 0 never happens after graph chunks: their start event is already recorded)
+        const bool pair_begins = w->profiling == 2 || (w->profiling == 1 && t == 0);
         const bool pair_ends = w->profiling == 2 || (w->profiling == 1 && t + 1 == ticks);
         if (pair_begins) {
             if (w->prof_used + 2 > w->prof_events.size()) {
@@ -1942,76 +1929,7 @@ int tick_impl(bge_world* w, uint32_t ticks, float dt, const float gravity[3], ui
             w->prof_ticks_pending.push_back(w->profiling == 2 ? 1u : ticks);
         }
         if (flags & BGE_TICK_BROADPHASE) {
-            // buffers are sized on first use: a world that never asks for pairs does not pay for them
-            const uint64_t cap = w->pair_capacity_req ? w->pair_capacity_req : std::max<uint64_t>(8 * w->flat.n_entities, 4096);
-            int rc = BGE_OK;
-            if (!(w->dynamic_contacts && w->bp_shared)) rc = w->broadphase.configure(std::max<uint64_t>(w->flat.n_slots, bge::kTile), cap);
-            if (rc != BGE_OK) return fail(rc, "broadphase allocation failed: %s", w->broadphase.error());
-            if (w->filter_table_stale && !w->filter_overflow) {
-                std::vector<uint32_t> tab(256 * 4, 0u);
-                for (size_t c = 0; c < w->filter_palette.size(); ++c) {
-                    tab[4 * c] = w->filter_palette[c].group;
-                    tab[4 * c + 1] = w->filter_palette[c].mask;
-                    tab[4 * c + 2] = w->filter_palette[c].is_static;
-                }
-                HIP_TRY(hipMemcpyAsync(w->filter_table.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, w->stream));
-                HIP_TRY(hipStreamSynchronize(w->stream)); // `tab` is a local
-                w->filter_table_stale = false;
-            }
-            const bge::FilterPalette palette{w->filter_overflow ? nullptr : w->filter_class.as<uint32_t>(),
-                                             w->filter_overflow ? nullptr : w->filter_table.as<uint4>(),
-                                             static_cast<uint32_t>(w->filter_palette.size())};
-            if (!(w->dynamic_contacts && w->bp_shared)) { // (else: island_substep ran it on these very boxes)
-                rc = w->broadphase.run(w->stream, w->view, static_cast<uint64_t>(w->flat.n_tiles_ticked) * bge::kTile,
-                                       w->entity_of_slot.as<uint32_t>(), nullptr, &palette, w->bp_partials.as<float4>());
-                if (rc != BGE_OK) return fail(rc, "broadphase failed: %s", w->broadphase.error());
-            }
-            w->bp_shared = false;
-            w->pairs_from_slab = false;
-            if (with_triggers) {
-                // counters: [0] overlaps found, [1] ghosts left to the all-bodies pass, [2] ghosts walked through the grid
-                HIP_TRY(hipMemsetAsync(w->trig_count.p, 0, 12, w->stream));
-                const uint32_t n_trig = static_cast<uint32_t>(w->triggers.size());
-                const uint32_t* big_list = nullptr;
-                if (n_trig > w->trigger_grid_min) {
-                    // many ghosts: the ones that cover few cells look their bodies up in the broadphase's sorted grid
-                    // (n_bodies x n_triggers box tests otherwise: 4 M bodies x 1000 ghosts = 4 G tests a tick)
-                    HIP_TRY(w->trig_lists.ensure(static_cast<size_t>(n_trig) * 8));
-                    const bge::TriggerView tv = w->trigger_view();
-                    const bge::BoxQuery q{n_trig, tv.aabb, tv.group, tv.mask, tv.entity, w->trig_count.as<uint32_t>(),
-                                          w->trig_lists.as<uint32_t>(), w->trig_lists.as<uint32_t>() + n_trig,
-                                          static_cast<uint2*>(w->trig_pairs.p), kTriggerPairCap};
-                    rc = w->broadphase.query_boxes(w->stream, w->view, w->entity_of_slot.as<uint32_t>(), &palette, q);
-                    if (rc != BGE_OK) return fail(rc, "trigger query failed: %s", w->broadphase.error());
-                    big_list = w->trig_lists.as<uint32_t>();
-                }
-                HIP_TRY(bge::launch_trigger_pairs(w->stream, static_cast<uint64_t>(w->flat.n_tiles_ticked) * bge::kTile, n_trig,
-                                                  w->trigger_view(), w->view, w->entity_of_slot.as<uint32_t>(), w->trig_count.as<uint32_t>(),
-                                                  w->trig_pairs.p, kTriggerPairCap, big_list,
-                                                  big_list ? w->trig_count.as<uint32_t>() + 1 : nullptr));
-                HIP_TRY(bge::launch_trigger_ghost_pairs(w->stream, n_trig, w->trigger_view(), w->trig_count.as<uint32_t>(), w->trig_pairs.p,
-                                                        kTriggerPairCap));
-                // The short way needs last tick's table to hold exactly the host's sets and no one-shot volume in the world (one that
-                // fires leaves the world in the middle of ProcessTriggerEvents' loop and takes itself out of the later ghosts' lists:
-                // that order dependence stays on the host)
-                bool short_way = w->trig_device_diff && w->trig_mirror_valid;
-                for (const bge_world::Trigger& t : w->triggers) short_way = short_way && !(t.one_shot && t.runtime_active);
-                int how = 1;
-                if (short_way) {
-                    how = process_trigger_pairs_fast(w);
-                    if (how < 0) return how;
-                }
-                if (how == 1) {
-                    if (int rc2 = process_trigger_pairs(w)) return rc2;
-                    ++w->trig_slow_ticks;
-                    w->trig_mirror_valid = false;
-                    bool one_shot = false;
-                    for (const bge_world::Trigger& t : w->triggers) one_shot = one_shot || (t.one_shot && t.runtime_active);
-                    if (w->trig_device_diff && !one_shot) {
-                        if (int rc2 = rebuild_trigger_mirror(w)) return rc2;
-                    }
-                }
-            }
+            if (int rc = broadphase_and_triggers(w, with_triggers)) return rc;
         }
         w->maybe_dirty = phys && !xform;
         if (fused_gather) {
@@ -2073,8 +1991,7 @@ try {
         // no sub-step: no collision detection, no integration — but the calls around stepSimulation still run
         if (!w->has_topology) return fail(BGE_ERR_STATE, "bge_world_set_topology has not been called");
         DeviceGuard guard(w->device);
-        HIP_TRY(bge::launch_pose_only(w->stream, w->view, static_cast<uint64_t>(w->flat.n_tiles_ticked) * bge::kTile,
-                                      (flags & BGE_TICK_BULLET_BASIS) != 0));
+        HIP_TRY(bge::launch_pose_only(w->stream, w->view, ticked_slots(w), (flags & BGE_TICK_BULLET_BASIS) != 0));
         w->maybe_dirty = true;
         w->rs_bump(); // (k_pose_only re-poses: it writes quat, euler, velocities)
         if (triggers) {
@@ -2123,7 +2040,6 @@ try {
     }
     w->ground_plane = on;
     w->rs_bump();
-    w->drop_graph();
     return BGE_OK;
 }
 BGE_CATCH_ALL("bge_world_set_ground_plane")
@@ -2144,7 +2060,6 @@ try {
     w->static_contacts_ever = w->static_contacts_ever || on;
     w->obstacles_stale = true;
     w->rs_bump();
-    w->drop_graph();
     return BGE_OK;
 }
 BGE_CATCH_ALL("bge_world_set_static_contacts")
@@ -2167,7 +2082,6 @@ try {
     w->isl_n_prev = 0; // (off and on again: the pair cache starts empty)
     w->isl_gen_stale = true;
     w->rs_bump();
-    w->drop_graph();
     return BGE_OK;
 }
 BGE_CATCH_ALL("bge_world_set_dynamic_contacts")
@@ -2496,7 +2410,6 @@ try {
     w->sleep_lin = linear_threshold;
     w->sleep_ang = angular_threshold;
     w->sleep_time = seconds;
-    w->drop_graph();
     return BGE_OK;
 }
 BGE_CATCH_ALL("bge_world_set_sleeping")
@@ -2568,8 +2481,6 @@ BGE_CATCH_ALL("bge_world_pairs")
 
 // ---------------------------------------------------------------- sharded broadphase (bge_route.hip)
 namespace {
-uint64_t ticked_slots(const bge_world* w) { return static_cast<uint64_t>(w->flat.n_tiles_ticked) * bge::kTile; }
-
 int refresh_global_of_slot(bge_world* w)
 {
     if (!w->global_of_slot_stale && w->global_of_slot.p) return BGE_OK;
