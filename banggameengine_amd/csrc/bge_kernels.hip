@@ -892,13 +892,23 @@ __global__ void k_trigger_aabb(uint32_t n_triggers, TriggerView t, WorldView w)
     const F3 pos = ld3(w.pos, slot);
     const F3 eul = ld3(w.euler, slot);
     const F3 he = ld3(t.half_extent, i);
-    const M3 r = bt_mat_from_quat(bt_quat_from_transform_euler(eul));
+    const Q4 q = bt_quat_from_transform_euler(eul);
+    const M3 r = bt_mat_from_quat(q);
     float mn[3], mx[3];
     bt_aabb_of_pose(pos, r, he, mn, mx);
     for (int a = 0; a < 3; ++a) {
         bb[a] = mn[a];
         bb[3 + a] = mx[a];
     }
+    float* ps = t.pose + 8ull * i;
+    ps[0] = pos.x;
+    ps[1] = pos.y;
+    ps[2] = pos.z;
+    ps[3] = 0.0f;
+    ps[4] = q.x;
+    ps[5] = q.y;
+    ps[6] = q.z;
+    ps[7] = q.w;
 }
 
 // every body against every trigger (scenes carry a handful of triggers; n_bodies x n_triggers box tests); hits are

@@ -186,6 +186,7 @@ struct TriggerView {
     const uint32_t* mask;      // [triggers]
     const uint8_t* active;     // [triggers]
     float* aabb;               // [triggers][6]
+    float* pose;               // [triggers][8] origin xyz, 0, quaternion xyzw of the ghost as last posed (the ray queries read it)
 };
 
 struct TickParams {

@@ -25,6 +25,7 @@
 #include "bge_comm.hpp"
 #include "bge_flatten.hpp"
 #include "bge_kernels.hpp"
+#include "bge_raycast.hpp"
 
 namespace {
 
@@ -261,6 +262,7 @@ struct bge_world {
         // removes it, so the ghost stays in the world where it last was and keeps reporting overlaps.
         bool frozen = false;
         float frozen_aabb[6] = {0, 0, 0, 0, 0, 0};
+        float frozen_pose[8] = {0, 0, 0, 0, 0, 0, 0, 1}; // ... and the pose (origin, 0, quaternion) the ray queries see it at
         std::vector<uint32_t> overlaps;       // sorted entity indices of the previous tick: the union of the two lists below
         std::vector<uint32_t> overlap_bodies; // ... met as rigid bodies (of any type: the pair cache pairs a ghost with Static bodies too)
         std::vector<uint32_t> overlap_ghosts; // ... met as other trigger ghosts (each of two overlapping ghosts lists the other)
@@ -281,6 +283,13 @@ struct bge_world {
     bool triggers_device_stale = true;
     bool trig_list_on_device = false; // the device arrays are indexed like `triggers` (false between an upload of the list and the next sync)
     DevBuf trig_slot, trig_entity, trig_he, trig_group, trig_mask, trig_active, trig_aabb, trig_pairs, trig_count, trig_lists;
+    DevBuf trig_pose; // [triggers][8] ghost pose written beside the box by k_trigger_aabb (ray queries)
+    // ray queries (bge_raycast.hip): staging for the host entry points, the per-ray keys (all ones between calls), the all-hits
+    // list, and the ghosts the rays see (rebuilt from `triggers` per query, uploaded when it changed)
+    DevBuf ray_in, ray_out, ray_keys, ray_all, ray_all_count, ray_ghosts;
+    uint64_t ray_keys_n = 0;
+    uint32_t ray_all_cap = 0;
+    std::vector<bge::RayGhost> ray_ghosts_host, ray_ghosts_dev;
     uint32_t trigger_grid_min = 64;       // more ghosts than this: the broadphase grid answers for the small ones
     // Enter / Exit taken on the device (bge_kernels.hpp TriggerDiff): two key tables (this tick's, last tick's), header + deltas in
     // one device buffer with a page-locked copy.  The overlap sets above stay the truth; `trig_mirror_valid` says that last tick's
@@ -310,6 +319,7 @@ struct bge_world {
         t.mask = trig_mask.as<uint32_t>();
         t.active = trig_active.as<uint8_t>();
         t.aabb = trig_aabb.as<float>();
+        t.pose = trig_pose.as<float>();
         return t;
     }
 
@@ -360,7 +370,7 @@ struct bge_world {
                           &angvel, &quat, &inv_mass, &half_extent, &group, &mask, &aabb, &root_worlds, &counter, &stage,
                           &stage2, &mass_palette, &normal, &deact, &filter_class, &filter_table, &grav_palette, &bp_partials, &cshape, &cmass, &cfriction, &cinfo, &manifold, &crestitution, &bmanifold, &obstacle_slots, &obstacle_gen, &obstacles, &obstacle_grid, &box_list, &box_count, &frozen, &rs_word, &trig_slot, &trig_entity, &trig_he, &trig_group,
                           &trig_mask, &trig_active, &trig_aabb, &trig_pairs, &trig_count, &trig_lists, &ground_list, &ground_count, &trig_tab[0], &trig_tab[1],
-                          &trig_delta_dev, &trig_keys_dev}) {
+                          &trig_delta_dev, &trig_keys_dev, &trig_pose, &ray_in, &ray_out, &ray_keys, &ray_all, &ray_all_count, &ray_ghosts}) {
             b->release();
         }
         if (trig_delta_host) (void)hipHostFree(trig_delta_host);
@@ -505,6 +515,7 @@ int sync_triggers_to_device(bge_world* w)
     HIP_TRY(w->trig_mask.ensure(n * 4));
     HIP_TRY(w->trig_active.ensure(n));
     HIP_TRY(w->trig_aabb.ensure(n * 24));
+    HIP_TRY(w->trig_pose.ensure(n * 32));
     HIP_TRY(w->trig_pairs.ensure(static_cast<size_t>(kTriggerPairCap) * 8));
     HIP_TRY(w->trig_count.ensure(64));
     HIP_TRY(hipMemcpyAsync(w->trig_slot.p, slot.data(), n * 4, hipMemcpyHostToDevice, w->stream));
@@ -517,6 +528,7 @@ int sync_triggers_to_device(bge_world* w)
         const bge_world::Trigger& t = w->triggers[i];
         if (t.runtime_active && t.frozen) {
             HIP_TRY(hipMemcpyAsync(static_cast<char*>(w->trig_aabb.p) + 24 * i, t.frozen_aabb, 24, hipMemcpyHostToDevice, w->stream));
+            HIP_TRY(hipMemcpyAsync(static_cast<char*>(w->trig_pose.p) + 32 * i, t.frozen_pose, 32, hipMemcpyHostToDevice, w->stream));
         }
     }
     HIP_TRY(hipStreamSynchronize(w->stream)); // the host vectors die here
@@ -1181,6 +1193,7 @@ try {
             if (t.posed && w->trig_list_on_device && w->trig_aabb.p) {
                 HIP_TRY(hipStreamSynchronize(w->stream));
                 HIP_TRY(hipMemcpy(t.frozen_aabb, static_cast<const char*>(w->trig_aabb.p) + 24 * k, 24, hipMemcpyDeviceToHost));
+                if (w->trig_pose.p) HIP_TRY(hipMemcpy(t.frozen_pose, static_cast<const char*>(w->trig_pose.p) + 32 * k, 32, hipMemcpyDeviceToHost));
                 t.frozen = true;
             } else {
                 t.runtime_active = false; // (never posed: there is no ghost to keep)
@@ -2713,6 +2726,7 @@ try {
                 t.frozen = true;
                 t.runtime_active = true;
                 std::memcpy(t.frozen_aabb, o.frozen_aabb, 24);
+                std::memcpy(t.frozen_pose, o.frozen_pose, 32);
                 t.layer = o.layer;
                 t.mask = o.mask;
                 if (t.overlaps.empty()) {
@@ -2785,6 +2799,197 @@ try {
     return BGE_OK;
 }
 BGE_CATCH_ALL("bge_world_trigger_query_stats")
+
+// ---------------------------------------------------------------- ray queries (bge_raycast.hip)
+static_assert(sizeof(bge_ray) == 32, "bge_ray is 32 bytes (include/bge_world.h)");
+static_assert(sizeof(bge_ray_hit) == 40, "bge_ray_hit is 40 bytes (include/bge_world.h)");
+
+namespace {
+
+// What every query needs: the ghosts the rays see (in the world, posed by a tick into the device arrays as they are indexed
+// now — uploaded only when the list changed), the per-ray keys, the body arrays.
+int ray_prepare(bge_world* w, uint64_t n_rays, bge::RayParams& p)
+{
+    if (!w->has_topology) return fail(BGE_ERR_STATE, "bge_world_set_topology has not been called");
+    if (n_rays > 0x7fffffffull) return fail(BGE_ERR_INVALID, "n_rays = %llu: at most 2^31 - 1 rays per batch", (unsigned long long)n_rays);
+    if (w->flat.n_entities > bge::kRayEntityMask) {
+        return fail(BGE_ERR_UNSUPPORTED, "ray queries need entity indices below 2^30 (world has %llu)", (unsigned long long)w->flat.n_entities);
+    }
+    std::vector<bge::RayGhost>& gh = w->ray_ghosts_host;
+    gh.clear();
+    if (w->trig_list_on_device && w->trig_pose.p) {
+        for (size_t i = 0; i < w->triggers.size(); ++i) {
+            const bge_world::Trigger& t = w->triggers[i];
+            if (!t.runtime_active || !(t.posed || t.frozen)) continue;
+            bge::RayGhost g{};
+            if (t.shape == BGE_SHAPE_CAPSULE) {
+                g.capsule = 1u;
+                g.dims[0] = std::max(t.size[0], 0.01f); // btCapsuleShape(radius, 2 * halfHeight), as for bodies
+                g.dims[1] = 0.5f * (std::max(t.size[1], 0.0f) * 2.0f);
+                g.dims[2] = g.dims[0];
+            } else {
+                collider_half_extents(t.shape, t.size, g.dims);
+            }
+            g.trigger = static_cast<uint32_t>(i);
+            g.entity = t.entity;
+            g.group = t.layer;
+            g.mask = t.mask;
+            gh.push_back(g);
+        }
+    }
+    const bool same = gh.size() == w->ray_ghosts_dev.size() &&
+                      (gh.empty() || std::memcmp(gh.data(), w->ray_ghosts_dev.data(), gh.size() * sizeof(bge::RayGhost)) == 0);
+    if (!same) {
+        w->ray_ghosts_dev = gh;
+        if (!gh.empty()) {
+            HIP_TRY(w->ray_ghosts.ensure(gh.size() * sizeof(bge::RayGhost)));
+            HIP_TRY(hipMemcpyAsync(w->ray_ghosts.p, w->ray_ghosts_dev.data(), gh.size() * sizeof(bge::RayGhost), hipMemcpyHostToDevice,
+                                   w->stream));
+            HIP_TRY(hipStreamSynchronize(w->stream)); // (the list changes when the trigger set does, not per query)
+        }
+    }
+    if (n_rays > w->ray_keys_n) {
+        HIP_TRY(w->ray_keys.ensure(n_rays * 8));
+        HIP_TRY(hipMemsetAsync(w->ray_keys.p, 0xff, n_rays * 8, w->stream));
+        w->ray_keys_n = n_rays;
+    }
+    p = bge::RayParams{};
+    p.n_rays = static_cast<uint32_t>(n_rays);
+    p.n_slots = w->flat.n_slots;
+    p.flags = w->view.flags;
+    p.pos = w->view.pos;
+    p.quat = w->view.quat;
+    p.cshape = w->view.cshape;
+    p.cinfo = w->view.cinfo;
+    p.group = w->view.group;
+    p.mask = w->view.mask;
+    p.entity_of_slot = w->entity_of_slot.as<uint32_t>();
+    p.slot_of_entity = w->slot_of_entity.as<uint32_t>();
+    p.ghosts = w->ray_ghosts.as<bge::RayGhost>();
+    p.n_ghosts = static_cast<uint32_t>(w->ray_ghosts_dev.size());
+    p.ghost_pose = w->trig_pose.as<float>();
+    p.plane = w->ground_plane ? 1u : 0u;
+    p.keys = w->ray_keys.as<unsigned long long>();
+    return BGE_OK;
+}
+
+int ray_upload(bge_world* w, uint64_t n_rays, const bge_ray* rays)
+{
+    HIP_TRY(w->ray_in.ensure(n_rays * sizeof(bge_ray)));
+    HIP_TRY(hipMemcpyAsync(w->ray_in.p, rays, n_rays * sizeof(bge_ray), hipMemcpyHostToDevice, w->stream));
+    return BGE_OK;
+}
+
+} // namespace
+
+int bge_world_raycast(bge_world* w, uint64_t n_rays, const bge_ray* rays, bge_ray_hit* hits)
+try {
+    if (!w) return fail(BGE_ERR_INVALID, "world is NULL");
+    if (n_rays == 0) return BGE_OK;
+    if (!rays || !hits) return fail(BGE_ERR_INVALID, "NULL argument");
+    DeviceGuard guard(w->device);
+    bge::RayParams p;
+    if (int rc = ray_prepare(w, n_rays, p)) return rc;
+    if (int rc = ray_upload(w, n_rays, rays)) return rc;
+    HIP_TRY(w->ray_out.ensure(n_rays * sizeof(bge_ray_hit)));
+    p.rays = w->ray_in.p;
+    p.hits = w->ray_out.p;
+    HIP_TRY(bge::launch_ray_closest(w->stream, p));
+    HIP_TRY(hipMemcpyAsync(hits, w->ray_out.p, n_rays * sizeof(bge_ray_hit), hipMemcpyDeviceToHost, w->stream));
+    HIP_TRY(hipStreamSynchronize(w->stream));
+    return BGE_OK;
+}
+BGE_CATCH_ALL("bge_world_raycast")
+
+int bge_world_raycast_device(bge_world* w, uint64_t n_rays, const void* rays_device, void* hits_device)
+try {
+    if (!w) return fail(BGE_ERR_INVALID, "world is NULL");
+    if (n_rays == 0) return BGE_OK;
+    if (!rays_device || !hits_device) return fail(BGE_ERR_INVALID, "NULL argument");
+    DeviceGuard guard(w->device);
+    bge::RayParams p;
+    if (int rc = ray_prepare(w, n_rays, p)) return rc;
+    p.rays = rays_device;
+    p.hits = hits_device;
+    HIP_TRY(bge::launch_ray_closest(w->stream, p));
+    return BGE_OK;
+}
+BGE_CATCH_ALL("bge_world_raycast_device")
+
+int bge_world_raycast_all(bge_world* w, uint64_t n_rays, const bge_ray* rays, bge_ray_hit* hits, uint64_t cap, uint64_t* offsets,
+                          uint64_t* total)
+try {
+    if (!w || !total) return fail(BGE_ERR_INVALID, "NULL argument");
+    *total = 0;
+    if (n_rays == 0) {
+        if (offsets) offsets[0] = 0;
+        return BGE_OK;
+    }
+    if (!rays) return fail(BGE_ERR_INVALID, "rays is NULL");
+    DeviceGuard guard(w->device);
+    bge::RayParams p;
+    if (int rc = ray_prepare(w, n_rays, p)) return rc;
+    if (int rc = ray_upload(w, n_rays, rays)) return rc;
+    HIP_TRY(w->ray_all_count.ensure(4));
+    p.rays = w->ray_in.p;
+    p.all_count = w->ray_all_count.as<uint32_t>();
+    uint32_t found = 0;
+    // the list's capacity grows to what a batch found: a second run of the same batch fits
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        const uint64_t want = std::max<uint64_t>({w->ray_all_cap, 4096u, 4 * n_rays});
+        if (want > 0x7fffffffull) return fail(BGE_ERR_OOM, "ray hit list of %llu records", (unsigned long long)want);
+        HIP_TRY(w->ray_all.ensure(want * sizeof(bge::RayAllRec)));
+        w->ray_all_cap = static_cast<uint32_t>(want);
+        p.all = w->ray_all.as<bge::RayAllRec>();
+        p.all_cap = w->ray_all_cap;
+        HIP_TRY(hipMemsetAsync(w->ray_all_count.p, 0, 4, w->stream));
+        HIP_TRY(bge::launch_ray_all(w->stream, p));
+        HIP_TRY(hipMemcpyAsync(&found, w->ray_all_count.p, 4, hipMemcpyDeviceToHost, w->stream));
+        HIP_TRY(hipStreamSynchronize(w->stream));
+        if (found <= w->ray_all_cap) break;
+        w->ray_all_cap = found;
+    }
+    if (found > w->ray_all_cap) return fail(BGE_ERR_STATE, "ray hit list overflowed twice");
+    std::vector<bge::RayAllRec> rec(found);
+    if (found) {
+        HIP_TRY(hipMemcpyAsync(rec.data(), w->ray_all.p, found * sizeof(bge::RayAllRec), hipMemcpyDeviceToHost, w->stream));
+        HIP_TRY(hipStreamSynchronize(w->stream));
+    }
+    // each ray's segment in (f, object code) order; the key is a total order, so the result does not depend on append order
+    auto key = [](const bge::RayAllRec& r) {
+        uint32_t fb;
+        std::memcpy(&fb, &r.f, 4);
+        return std::make_pair(static_cast<uint64_t>(r.ray) << 32 | fb, r.code);
+    };
+    std::sort(rec.begin(), rec.end(), [&](const bge::RayAllRec& a, const bge::RayAllRec& b) { return key(a) < key(b); });
+    *total = found;
+    if (offsets) {
+        size_t at = 0;
+        for (uint64_t r = 0; r <= n_rays; ++r) {
+            while (at < rec.size() && rec[at].ray < r) ++at;
+            offsets[r] = at;
+        }
+    }
+    if (!hits) return BGE_OK;
+    if (cap < found) return fail(BGE_ERR_INVALID, "raycast_all: %u hits, room for %llu", found, (unsigned long long)cap);
+    for (size_t i = 0; i < rec.size(); ++i) {
+        const bge::RayAllRec& r = rec[i];
+        const bge_ray& ray = rays[r.ray];
+        bge_ray_hit& h = hits[i];
+        const uint32_t kind = r.code >> 30;
+        h.kind = kind == 0u ? BGE_RAY_BODY : (kind == 1u ? BGE_RAY_TRIGGER : BGE_RAY_GROUND);
+        h.entity = kind == 2u ? BGE_RAY_NO_ENTITY : (r.code & bge::kRayEntityMask);
+        h.fraction = r.f;
+        h.distance = r.f * ray.max_distance;
+        for (int a = 0; a < 3; ++a) {
+            const float delta = ray.direction[a] * ray.max_distance; // the device's arithmetic (bge_raycast.hip ray_prep, k_ray_finish)
+            h.point[a] = ray.origin[a] + delta * r.f;
+            h.normal[a] = r.n[a];
+        }
+    }
+    return BGE_OK;
+}
+BGE_CATCH_ALL("bge_world_raycast_all")
 
 int bge_world_pack_roots(bge_world* w, void* dst_device)
 try {

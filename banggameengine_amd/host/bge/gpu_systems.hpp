@@ -240,6 +240,41 @@ public:
     // Enter / Stay / Exit of the last UpdatePhysics (what ProcessTriggerEvents publishes, PhysicsSystem.cpp:1017-1074)
     const std::vector<GpuTriggerEvent>& TriggerEvents() const { return trigger_events_; }
 
+    // PhysicsSystem::Raycast / RaycastAll (src/physics/PhysicsSystem.cpp:1076-1146) on the device world as the last Update left it
+    // (include/bge_world.h states what a ray sees).  One launch pair and one small read-back per call.  HitT has the members of the
+    // reference's PhysicsRaycastHit (src/physics/PhysicsAPI.h:12-18): entity, point, normal, distance.
+    template <class Vec3, class HitT>
+    bool Raycast(const Vec3& origin, const Vec3& direction, float maxDistance, uint32_t layerMask, HitT& outHit)
+    {
+        if (!ok() || !(maxDistance > 0.0f) || layerMask == 0u) return false;
+        const bge_ray ray = MakeRay(origin, direction, maxDistance, layerMask);
+        bge_ray_hit h{};
+        if (bge_world_raycast(world_, 1, &ray, &h) != BGE_OK) return Log("bge_world_raycast");
+        if (h.kind == BGE_RAY_MISS) return false;
+        FillHit(h, outHit);
+        return true;
+    }
+    template <class HitT, class Vec3>
+    std::vector<HitT> RaycastAll(const Vec3& origin, const Vec3& direction, float maxDistance, uint32_t layerMask)
+    {
+        std::vector<HitT> hits;
+        if (!ok() || !(maxDistance > 0.0f) || layerMask == 0u) return hits;
+        const bge_ray ray = MakeRay(origin, direction, maxDistance, layerMask);
+        uint64_t total = 0;
+        if (bge_world_raycast_all(world_, 1, &ray, nullptr, 0, nullptr, &total) != BGE_OK) {
+            Log("bge_world_raycast_all");
+            return hits;
+        }
+        ray_hits_.resize(total);
+        if (total && bge_world_raycast_all(world_, 1, &ray, ray_hits_.data(), total, nullptr, &total) != BGE_OK) {
+            Log("bge_world_raycast_all");
+            return hits;
+        }
+        hits.resize(total);
+        for (uint64_t i = 0; i < total; ++i) FillHit(ray_hits_[i], hits[i]);
+        return hits;
+    }
+
 private:
     // EnsureTrigger (PhysicsSystem.cpp:523-590): the trigger set is re-sent when a TriggerVolume appeared, vanished or
     // changed; remembered overlaps survive on the device side for unchanged triggers
@@ -655,6 +690,34 @@ private:
     std::vector<uint32_t> t_order_; // EntityIds of the scene's TriggerVolumes, ascending
     std::vector<bge_trigger_event> raw_events_;
     std::vector<GpuTriggerEvent> trigger_events_;
+    std::vector<bge_ray_hit> ray_hits_;
+
+    template <class Vec3> static bge_ray MakeRay(const Vec3& o, const Vec3& d, float maxDistance, uint32_t layerMask)
+    {
+        bge_ray r{};
+        r.origin[0] = o.x;
+        r.origin[1] = o.y;
+        r.origin[2] = o.z;
+        r.direction[0] = d.x;
+        r.direction[1] = d.y;
+        r.direction[2] = d.z;
+        r.max_distance = maxDistance;
+        r.layer_mask = layerMask;
+        return r;
+    }
+    // entity index -> EntityId through the mirror's map; the plane (the reference's Ground object) has no entity: kInvalidEntity (0)
+    template <class HitT> void FillHit(const bge_ray_hit& h, HitT& out) const
+    {
+        const bool has = h.entity != BGE_RAY_NO_ENTITY && h.entity < ids_.size();
+        out.entity = static_cast<decltype(out.entity)>(has ? ids_[h.entity] : Id{0});
+        out.point.x = h.point[0];
+        out.point.y = h.point[1];
+        out.point.z = h.point[2];
+        out.normal.x = h.normal[0];
+        out.normal.y = h.normal[1];
+        out.normal.z = h.normal[2];
+        out.distance = h.distance;
+    }
 };
 
 // One mirror per Scene object, found by address (TransformSystem::Update is a static function without state,
@@ -698,7 +761,11 @@ public:
         GpuSceneMirror<SceneT> probe;
         if (!probe.ok()) std::fprintf(stderr, "[GPU] Initialize: no usable device — %s\n", bge_last_error());
     }
-    void OnSceneReloaded(SceneT& scene) { GpuMirrors<SceneT>::Drop(scene); } // the mirror (and its clock) is rebuilt by the next Update
+    void OnSceneReloaded(SceneT& scene) // the mirror (and its clock) is rebuilt by the next Update
+    {
+        GpuMirrors<SceneT>::Drop(scene);
+        if (lastScene_ == &scene) lastScene_ = nullptr;
+    }
     // mtime poll of the config file, every frame (PhysicsSystem.cpp:216-240)
     bool ReloadConfigIfNeeded(SceneT& scene)
     {
@@ -737,6 +804,21 @@ public:
     int LastSubSteps() const { return lastStepSubsteps_; }
     // trigger events of the last Update (publish them on the engine's EventBus, src/core/EventBus.h)
     const std::vector<GpuTriggerEvent>& TriggerEvents(SceneT& scene) const { return GpuMirrors<SceneT>::Of(scene).TriggerEvents(); }
+
+    // PhysicsSystem::Raycast / RaycastAll (src/physics/PhysicsSystem.h:66-75): the world of the scene of the last Update, as that
+    // Update left it — call after Update and before the next one uploads new poses, as Application::Update does
+    // (src/core/Application.cpp:256-281).  false / empty before the first Update, as the reference without m_world.
+    template <class Vec3, class HitT>
+    bool Raycast(const Vec3& origin, const Vec3& direction, float maxDistance, uint32_t layerMask, HitT& outHit) const
+    {
+        return lastScene_ && GpuMirrors<SceneT>::Of(*lastScene_).Raycast(origin, direction, maxDistance, layerMask, outHit);
+    }
+    template <class HitT, class Vec3>
+    std::vector<HitT> RaycastAll(const Vec3& origin, const Vec3& direction, float maxDistance, uint32_t layerMask) const
+    {
+        if (!lastScene_) return {};
+        return GpuMirrors<SceneT>::Of(*lastScene_).template RaycastAll<HitT>(origin, direction, maxDistance, layerMask);
+    }
 
     // PhysicsSystem::Config (src/physics/PhysicsSystem.h:85-95); the character fields are read and kept, nothing here uses them
     struct Config {
@@ -789,6 +871,7 @@ private:
     void Step(SceneT& scene, double dt)
     {
         auto& m = GpuMirrors<SceneT>::Of(scene);
+        lastScene_ = &scene;
         m.gravity[0] = 0.0f;
         m.gravity[1] = config_.gravity; // m_world->setGravity(btVector3(0, m_config.gravity, 0)), PhysicsSystem.cpp:130, 292
         m.gravity[2] = 0.0f;
@@ -814,6 +897,7 @@ private:
     Config config_{};
     bool bulletBasis_ = false;
     bool groundPlane_ = true;
+    SceneT* lastScene_ = nullptr; // the scene whose world the ray queries read
     double lastStepDurationMs_ = 0.0, lastStepDt_ = 0.0;
     int lastStepSubsteps_ = 0, lastBodies_ = 0;
 };

@@ -15,6 +15,34 @@ TICK_PHYSICS, TICK_TRANSFORMS, TICK_BROADPHASE, TICK_ALL, TICK_GATHER_ROOTS, TIC
 TICK_BULLET_BASIS = 64
 ARRAY_WORLD, ARRAY_ROOT_WORLDS, ARRAY_SLOT_OF_ENTITY, ARRAY_POSITION, ARRAY_PAIRS = 0, 1, 2, 3, 4
 
+# ray queries (bge_world_raycast*): the C records as numpy dtypes
+RAY_MISS, RAY_BODY, RAY_TRIGGER, RAY_GROUND = 0, 1, 2, 3
+RAY_NO_ENTITY = 0xFFFFFFFF
+RAY_DTYPE = np.dtype([("origin", "<f4", (3,)), ("direction", "<f4", (3,)), ("max_distance", "<f4"), ("layer_mask", "<u4")])
+RAY_HIT_DTYPE = np.dtype([("kind", "<u4"), ("entity", "<u4"), ("fraction", "<f4"), ("distance", "<f4"), ("point", "<f4", (3,)),
+                          ("normal", "<f4", (3,))])
+assert RAY_DTYPE.itemsize == 32 and RAY_HIT_DTYPE.itemsize == 40
+
+
+def make_rays(origins, directions, max_distance=200.0, layer_mask=0xFFFFFFFF):
+    """bge_ray records: origins / directions (n, 3); max_distance and layer_mask a scalar or one value per ray."""
+    o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+    d = np.ascontiguousarray(directions, np.float32).reshape(-1, 3)
+    if len(o) != len(d):
+        raise ValueError(f"{len(o)} origins, {len(d)} directions")
+    rays = np.zeros(len(o), RAY_DTYPE)
+    rays["origin"] = o
+    rays["direction"] = d
+    rays["max_distance"] = np.broadcast_to(np.asarray(max_distance, np.float32), (len(o),))
+    rays["layer_mask"] = np.broadcast_to(np.asarray(layer_mask, np.uint64).astype(np.uint32), (len(o),))
+    return rays
+
+
+def _hit_fields(h):
+    return {"kind": h["kind"].copy(), "entity": h["entity"].copy(), "fraction": h["fraction"].copy(),
+            "distance": h["distance"].copy(), "point": h["point"].copy(), "normal": h["normal"].copy()}
+
+
 # fixed step and gravity of the reference (assets/config/physics.json:2-3)
 FIXED_DT = float(np.float32(0.0083333333))
 GRAVITY = (0.0, -9.81, 0.0)
@@ -310,6 +338,42 @@ class World:
         return a.value, b.value
 
     # -- multi-GPU support / device-resident consumers
+    # -- ray queries (PhysicsSystem::Raycast / RaycastAll for a batch; include/bge_world.h states what a ray sees)
+    def raycast(self, origins, directions, max_distance=200.0, layer_mask=0xFFFFFFFF):
+        """Closest hit per ray: dict of numpy arrays kind, entity, fraction, distance, point (n, 3), normal (n, 3).
+        max_distance and layer_mask take a scalar or one value per ray."""
+        rays = make_rays(origins, directions, max_distance, layer_mask)
+        hits = np.zeros(len(rays), RAY_HIT_DTYPE)
+        check(lib().bge_world_raycast(self._h, len(rays), _p(rays), _p(hits)))
+        return _hit_fields(hits)
+
+    def raycast_all(self, origins, directions, max_distance=200.0, layer_mask=0xFFFFFFFF):
+        """Every hit per ray: the arrays of raycast() over all hits plus offsets (n + 1): ray i's hits are
+        [offsets[i], offsets[i + 1]), in (fraction, object code) order."""
+        rays = make_rays(origins, directions, max_distance, layer_mask)
+        total = C.c_uint64(0)
+        offsets = np.zeros(len(rays) + 1, np.uint64)
+        check(lib().bge_world_raycast_all(self._h, len(rays), _p(rays), None, 0, _p(offsets), C.byref(total)))
+        hits = np.zeros(max(int(total.value), 1), RAY_HIT_DTYPE)
+        check(lib().bge_world_raycast_all(self._h, len(rays), _p(rays), _p(hits), len(hits), _p(offsets), C.byref(total)))
+        out = _hit_fields(hits[:int(total.value)])
+        out["offsets"] = offsets
+        return out
+
+    def raycast_device(self, rays, hits):
+        """Closest hit per ray between device tensors: rays holds n bge_ray records (32 bytes each, e.g. a uint8 / float32 /
+        int32 tensor made from make_rays()), hits room for n bge_ray_hit records (40 bytes each).  Enqueued on the world's
+        stream without synchronisation: call sync() (or order the stream yourself) before reading hits."""
+        nb = rays.numel() * rays.element_size()
+        if nb % 32:
+            raise ValueError(f"rays holds {nb} bytes, not a whole number of 32-byte records")
+        n = nb // 32
+        if hits.numel() * hits.element_size() < 40 * n:
+            raise ValueError(f"hits has room for {hits.numel() * hits.element_size()} bytes, {40 * n} needed")
+        if not (rays.is_cuda and hits.is_cuda and rays.is_contiguous() and hits.is_contiguous()):
+            raise ValueError("rays and hits must be contiguous device tensors")
+        check(lib().bge_world_raycast_device(self._h, n, C.c_void_p(rays.data_ptr()), C.c_void_p(hits.data_ptr())))
+
     def pack_roots(self, dst_device_ptr: int | None = None):
         check(lib().bge_world_pack_roots(self._h, C.c_void_p(dst_device_ptr) if dst_device_ptr else None))
 

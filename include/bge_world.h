@@ -380,6 +380,66 @@ BGE_API int bge_world_trigger_diff_stats(bge_world* world, uint64_t* device_tick
 BGE_API int bge_world_trigger_active(bge_world* world, uint64_t count, const uint32_t* entity_index, uint8_t* active);
 BGE_API int bge_world_trigger_query_stats(bge_world* world, uint32_t* through_grid, uint32_t* against_all_bodies);
 
+/*
+ * Ray queries: PhysicsSystem::Raycast / RaycastAll (src/physics/PhysicsSystem.cpp:1076-1146), i.e. Bullet's rayTest with a
+ * ClosestRayResultCallback / AllHitsRayResultCallback of group -1 and mask layer_mask, for a batch of rays at once.
+ * Parity with the reference's compiled caster is NOT pinned for this path; the rules below are the specification.
+ *   Segment   from = origin, to = origin + direction * max_distance (direction is not normalised, as in the reference); a hit
+ *             has fraction f in [0, 1], point = from + (to - from) * f, distance = f * max_distance (the reference's definition,
+ *             not the Euclidean length), normal = outward unit normal of the surface hit, world space.
+ *   No hit    when !(max_distance > 0), layer_mask == 0, direction == (0, 0, 0), or any input is not finite (NaN, inf).
+ *   Filter    an object is a candidate when (objGroup & layer_mask) != 0 && objMask != 0.
+ *   Objects   - every rigid body (Static, Dynamic, Kinematic; asleep or awake) at the pose Bullet holds after the last physics
+ *               tick: position + quaternion (bge_world_download_pose / _bodies).  A box is the SHARP box of its half extents
+ *               with margin (max(size, 0.01)); a capsule is Bullet's Y-axis capsule (radius, half height).  Bodies uploaded
+ *               since the last physics tick (Bullet creates them in the next Update) and removed bodies are not in the world.
+ *             - every trigger ghost that is in the world at the pose the last BGE_TICK_BROADPHASE tick gave it (EnsureTrigger poses it
+ *               from the Transform as it was before the step): the entity is the trigger's.  Inactive ghosts, ghosts of fired
+ *               one-shots and ghosts never posed (or not posed since the last bge_world_upload_triggers) are not hit.
+ *             - the ground plane when bge_world_set_ground_plane is on: group StaticFilter (2), mask all-ones, hit from either side
+ *               (btTriangleRaycastCallback without back-face filtering): normal +y from above, -y from below; a segment that does
+ *               not cross y = 0 strictly (parallel, or an end point on the plane) does not hit it.  entity = BGE_RAY_NO_ENTITY.
+ *   Closest   smallest f; ties go to the lowest object code: bodies by entity index, then ghosts by entity index, then the plane.
+ *   All hits  one record per object crossed, each ray's list sorted by (f, object code) (Bullet's order is its dbvt traversal
+ *             order, which depends on history: this order is a specification choice).
+ *   Choices   - a ray that starts inside or on the surface of a box or capsule does not hit that shape;
+ *             - boxes are sharp: Bullet's GJK caster rounds a box's edges by its 0.04 margin, so a ray grazing within 0.04 of an
+ *               edge may differ from the reference;
+ *             - Bullet also culls bodies whose fed AABB of the last sub-step misses the ray; here the shape at its current pose
+ *               alone decides.
+ *   Call order  the query reads the device state as it is: call it after a physics tick and before new poses are uploaded, as
+ *             Application::Update does (src/core/Application.cpp:256-281).  A Transform uploaded between the tick and the query
+ *             moves the body's position for the query (its orientation stays the one the tick left).
+ *   bge_world_raycast         hits[i] for rays[i]; a miss is kind BGE_RAY_MISS, entity BGE_RAY_NO_ENTITY, all floats 0.
+ *                             Synchronises the world's stream.
+ *   bge_world_raycast_all     offsets[0..n_rays] (offsets[i + 1] - offsets[i] hits of ray i at hits[offsets[i]..]) and *total,
+ *                             the convention of bge_world_pairs: hits = NULL queries only the counts (offsets may be NULL too);
+ *                             BGE_ERR_INVALID when cap < *total, *total (and offsets) still filled in.
+ *   bge_world_raycast_device  device pointers: rays_device = bge_ray[n_rays], hits_device = bge_ray_hit[n_rays]; enqueued on the
+ *                             world's stream, no synchronisation (the caller orders its own use of hits_device after it).
+ *   n_rays = 0 is a no-op.  The entity indices of the world must stay below 2^30.
+ */
+typedef struct bge_ray {
+    float origin[3];
+    float direction[3];
+    float max_distance;
+    uint32_t layer_mask;
+} bge_ray; /* 32 bytes */
+enum bge_ray_kind { BGE_RAY_MISS = 0, BGE_RAY_BODY = 1, BGE_RAY_TRIGGER = 2, BGE_RAY_GROUND = 3 };
+#define BGE_RAY_NO_ENTITY 0xffffffffu
+typedef struct bge_ray_hit {
+    uint32_t kind;   /* bge_ray_kind */
+    uint32_t entity; /* entity index of the body or trigger; BGE_RAY_NO_ENTITY for the plane and for a miss */
+    float fraction;
+    float distance;
+    float point[3];
+    float normal[3];
+} bge_ray_hit; /* 40 bytes */
+BGE_API int bge_world_raycast(bge_world* world, uint64_t n_rays, const bge_ray* rays, bge_ray_hit* hits);
+BGE_API int bge_world_raycast_all(bge_world* world, uint64_t n_rays, const bge_ray* rays, bge_ray_hit* hits, uint64_t cap,
+                                  uint64_t* offsets, uint64_t* total);
+BGE_API int bge_world_raycast_device(bge_world* world, uint64_t n_rays, const void* rays_device, void* hits_device);
+
 /* Multi-GPU support: compact the world matrices of all roots (entity order) into one buffer that the
  * caller all-gathers across ranks (one collective per frame).  dst = NULL packs into the world's own
  * BGE_ARRAY_ROOT_WORLDS buffer; otherwise dst is a device pointer with room for n_roots*16 floats. */

@@ -1,0 +1,493 @@
+"""Ray queries (include/bge_world.h bge_world_raycast*) without a GPU: the float64 reference the GPU tests compare against, checked
+on hand-worked cases; the exported symbols; the C99 view of the records; the adapter's Raycast / RaycastAll on the reference's
+types (C++20, -Werror)."""
+from __future__ import annotations
+
+import ctypes as C
+import math
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CPP = os.path.join(ROOT, "tests", "cpp")
+LIBDIR = os.path.join(ROOT, "banggameengine_amd")
+
+RAY_MISS, RAY_BODY, RAY_TRIGGER, RAY_GROUND = 0, 1, 2, 3
+NO_ENTITY = 0xFFFFFFFF
+CODE_GHOST, CODE_PLANE = 1 << 30, (2 << 30) | ((1 << 30) - 1)
+
+# ------------------------------------------------------------------------------------------------ float64 reference
+
+
+def quat_to_mat(q):
+    """btMatrix3x3::setRotation in float64 (s = 2 / |q|^2)."""
+    x, y, z, w = (float(v) for v in q)
+    s = 2.0 / (x * x + y * y + z * z + w * w)
+    xs, ys, zs = x * s, y * s, z * s
+    wx, wy, wz = w * xs, w * ys, w * zs
+    xx, xy, xz = x * xs, x * ys, x * zs
+    yy, yz, zz = y * ys, y * zs, z * zs
+    return np.array([[1 - (yy + zz), xy - wz, xz + wy], [xy + wz, 1 - (xx + zz), yz - wx], [xz - wy, yz + wx, 1 - (xx + yy)]])
+
+
+def quat_from_euler(e):
+    """ToBtQuaternion(euler) = setEulerZYX(yaw = e.y, pitch = e.x, roll = e.z), float64."""
+    hy, hp, hr = e[1] * 0.5, e[0] * 0.5, e[2] * 0.5
+    cy, sy, cp, sp, cr, sr = math.cos(hy), math.sin(hy), math.cos(hp), math.sin(hp), math.cos(hr), math.sin(hr)
+    return np.array([sr * cp * cy - cr * sp * sy, cr * sp * cy + sr * cp * sy, cr * cp * sy - sr * sp * cy, cr * cp * cy + sr * sp * sy])
+
+
+def box_half_extents(size):
+    """collider_half_extents for a box, in binary32 as the library computes it (btBoxShape: implicit = he - 0.04, safe margin)."""
+    h = np.maximum(np.asarray(size, np.float32), np.float32(0.01))
+    m0 = np.float32(0.04)
+    inner = (h - m0).astype(np.float32)
+    safe = np.float32(0.1) * h.min()
+    if safe < m0:
+        return (((inner + m0).astype(np.float32) - safe).astype(np.float32) + safe).astype(np.float32)
+    return (inner + m0).astype(np.float32)
+
+
+def capsule_dims(size):
+    r = max(np.float32(size[0]), np.float32(0.01))
+    return np.array([r, max(np.float32(size[1]), np.float32(0.0)), r], np.float32)
+
+
+def ray_box(o, d, h):
+    """Sharp box: (f, local normal) of the first entry, None on a miss or when o is inside / on the box."""
+    if all(abs(o[a]) <= h[a] for a in range(3)):
+        return None
+    tn, tf, ax = -math.inf, math.inf, -1
+    for a in range(3):
+        if d[a] == 0.0:
+            if abs(o[a]) > h[a]:
+                return None
+            continue
+        t1, t2 = (-h[a] - o[a]) / d[a], (h[a] - o[a]) / d[a]
+        near, far = min(t1, t2), max(t1, t2)
+        if near > tn:
+            tn, ax = near, a
+        tf = min(tf, far)
+    if ax < 0 or not (tn <= tf) or not (0.0 <= tn <= 1.0):
+        return None
+    n = np.zeros(3)
+    n[ax] = -1.0 if d[ax] > 0 else 1.0
+    return tn, n
+
+
+def ray_capsule(o, d, r, hh):
+    """Y-axis capsule (radius r, half height hh): (f, local normal) or None (miss, or o inside / on it)."""
+    cy = min(max(o[1], -hh), hh)
+    if o[0] ** 2 + (o[1] - cy) ** 2 + o[2] ** 2 <= r * r:
+        return None
+    best, bn = math.inf, None
+    a = d[0] ** 2 + d[2] ** 2
+    if a > 0:
+        b = o[0] * d[0] + o[2] * d[2]
+        c = o[0] ** 2 + o[2] ** 2 - r * r
+        disc = b * b - a * c
+        if disc >= 0:
+            t = (-b - math.sqrt(disc)) / a
+            y = o[1] + d[1] * t
+            if 0 <= t <= 1 and abs(y) <= hh:
+                best, bn = t, np.array([o[0] + d[0] * t, 0.0, o[2] + d[2] * t])
+    aa = float(np.dot(d, d))
+    for c0 in (-hh, hh):
+        m = np.array([o[0], o[1] - c0, o[2]])
+        bb, cc = float(np.dot(m, d)), float(np.dot(m, m)) - r * r
+        disc = bb * bb - aa * cc
+        if disc >= 0:
+            t = (-bb - math.sqrt(disc)) / aa
+            if 0 <= t <= 1 and t < best:
+                best, bn = t, m + d * t
+    if bn is None:
+        return None
+    return best, bn / np.linalg.norm(bn)
+
+
+def ray_plane(from_y, to_y):
+    """y = 0 from either side (btTriangleRaycastCallback, no back-face filter): ends strictly on opposite sides."""
+    if not ((from_y > 0 and to_y < 0) or (from_y < 0 and to_y > 0)):
+        return None
+    return from_y / (from_y - to_y), np.array([0.0, 1.0 if from_y > 0 else -1.0, 0.0])
+
+
+class Obj:
+    """A collision object of the query's world: kind RAY_BODY / RAY_TRIGGER, entity, filter words, shape, pose."""
+
+    def __init__(self, kind, entity, group, mask, capsule, dims, origin, quat):
+        self.kind, self.entity, self.group, self.mask = kind, int(entity), int(group), int(mask)
+        self.capsule, self.dims = bool(capsule), np.asarray(dims, np.float64)
+        self.origin, self.basis = np.asarray(origin, np.float64), quat_to_mat(quat)
+
+    @property
+    def code(self):
+        return self.entity if self.kind == RAY_BODY else CODE_GHOST | self.entity
+
+    def cast(self, frm, delta, grow=0.0):
+        o = self.basis.T @ (frm - self.origin)
+        d = self.basis.T @ delta
+        if self.capsule:
+            r = ray_capsule(o, d, self.dims[0] + grow, self.dims[1])
+        else:
+            r = ray_box(o, d, self.dims + grow)
+        return None if r is None else (r[0], self.basis @ r[1])
+
+
+def ray_valid(origin, direction, max_distance, mask):
+    o, d = np.asarray(origin, np.float32), np.asarray(direction, np.float32)
+    md = np.float32(max_distance)
+    with np.errstate(all="ignore"):
+        delta = d * md
+        ok = (np.isfinite(o).all() and np.isfinite(d).all() and np.isfinite(md) and md > 0 and int(mask) != 0 and (d != 0).any()
+              and np.isfinite(delta).all() and np.isfinite(np.float32(np.dot(delta, delta))))
+    return bool(ok)
+
+
+def cast_all(objs, origin, direction, max_distance, mask, plane, grow=0.0):
+    """Every hit of one ray: sorted list of (f, code, kind, entity, normal)."""
+    if not ray_valid(origin, direction, max_distance, mask):
+        return []
+    frm = np.asarray(origin, np.float32).astype(np.float64)
+    delta = (np.asarray(direction, np.float32) * np.float32(max_distance)).astype(np.float64)
+    out = []
+    for ob in objs:
+        if (ob.group & int(mask)) == 0 or ob.mask == 0:
+            continue
+        r = ob.cast(frm, delta, grow)
+        if r is not None:
+            out.append((r[0], ob.code, ob.kind, ob.entity, r[1]))
+    if plane and (int(mask) & 2):
+        r = ray_plane(frm[1], frm[1] + delta[1])
+        if r is not None:
+            out.append((r[0], CODE_PLANE, RAY_GROUND, NO_ENTITY, r[1]))
+    out.sort(key=lambda h: (h[0], h[1]))
+    return out
+
+
+def cast_closest(objs, origin, direction, max_distance, mask, plane):
+    hits = cast_all(objs, origin, direction, max_distance, mask, plane)
+    return hits[0] if hits else None
+
+
+def clear_decision(objs, origin, direction, max_distance, mask, plane, eps=1e-4):
+    """The closest object is well defined: the runner-up is more than eps further along in f, and growing or shrinking every
+    shape by eps (a ray grazing an edge, a near miss, an origin near a surface) does not change which objects are hit."""
+    base = cast_all(objs, origin, direction, max_distance, mask, plane)
+    if len(base) > 1 and base[1][0] - base[0][0] <= eps:
+        return False
+    codes = [h[1] for h in base]
+    for g in (eps, -eps):
+        if [h[1] for h in cast_all(objs, origin, direction, max_distance, mask, plane, grow=g)] != codes:
+            return False
+    return True
+
+
+class World64:
+    """The same reference, vectorised over the objects (the GPU tests cast thousands of rays at thousands of objects)."""
+
+    def __init__(self, objs, plane):
+        self.plane = bool(plane)
+        n = len(objs)
+        self.kind = np.array([o.kind for o in objs], np.int64).reshape(n)
+        self.entity = np.array([o.entity for o in objs], np.int64).reshape(n)
+        self.group = np.array([o.group for o in objs], np.int64).reshape(n)
+        self.omask = np.array([o.mask for o in objs], np.int64).reshape(n)
+        self.capsule = np.array([o.capsule for o in objs], bool).reshape(n)
+        self.dims = np.array([o.dims for o in objs], np.float64).reshape(n, 3)
+        self.origin = np.array([o.origin for o in objs], np.float64).reshape(n, 3)
+        self.basis = np.array([o.basis for o in objs], np.float64).reshape(n, 3, 3)
+        self._derive()
+
+    @classmethod
+    def from_arrays(cls, kind, entity, group, mask, capsule, dims, origin, quat, plane):
+        """Same world from per-object arrays (quat (n, 4) xyzw) without a Python object per body."""
+        w = cls([], plane)
+        w.kind, w.entity = np.asarray(kind, np.int64), np.asarray(entity, np.int64)
+        w.group, w.omask = np.asarray(group, np.int64), np.asarray(mask, np.int64)
+        w.capsule, w.dims, w.origin = np.asarray(capsule, bool), np.asarray(dims, np.float64), np.asarray(origin, np.float64)
+        q = np.asarray(quat, np.float64)
+        x, y, z, ww = q[:, 0], q[:, 1], q[:, 2], q[:, 3]
+        s = 2.0 / (x * x + y * y + z * z + ww * ww)
+        xs, ys, zs = x * s, y * s, z * s
+        wx, wy, wz, xx, xy, xz, yy, yz, zz = ww * xs, ww * ys, ww * zs, x * xs, x * ys, x * zs, y * ys, y * zs, z * zs
+        w.basis = np.stack([np.stack([1 - (yy + zz), xy - wz, xz + wy], 1), np.stack([xy + wz, 1 - (xx + zz), yz - wx], 1),
+                            np.stack([xz - wy, yz + wx, 1 - (xx + yy)], 1)], 1)
+        w._derive()
+        return w
+
+    def _derive(self):
+        self.code = np.where(self.kind == RAY_BODY, self.entity, CODE_GHOST | self.entity)
+        # bounding spheres: a cull before the exact tests (shapes grown by at most 1e-3 stay inside)
+        self.radius = np.where(self.capsule, self.dims[:, 0] + self.dims[:, 1], np.linalg.norm(self.dims, axis=1)) + 2e-3
+        self._min_dim = None
+
+    def min_dim(self, code):
+        """Smallest half extent (box) or radius (capsule) of the object with this code; 1 for the plane."""
+        if self._min_dim is None:
+            small = np.where(self.capsule, self.dims[:, 0], self.dims.min(axis=1))
+            self._min_dim = dict(zip(self.code.tolist(), small.tolist()))
+        return self._min_dim.get(int(code), 1.0)
+
+    def cast_all(self, origin, direction, max_distance, mask, grow=0.0):
+        if not ray_valid(origin, direction, max_distance, mask):
+            return []
+        frm = np.asarray(origin, np.float32).astype(np.float64)
+        delta = (np.asarray(direction, np.float32) * np.float32(max_distance)).astype(np.float64)
+        w = self.origin - frm
+        t = np.clip((w @ delta) / float(delta @ delta), 0.0, 1.0)
+        e = w - t[:, None] * delta
+        near = (e * e).sum(axis=1) <= self.radius ** 2
+        sel = np.nonzero(near & ((self.group & int(mask)) != 0) & (self.omask != 0))[0]
+        out = []
+        if len(sel):
+            B = self.basis[sel]
+            o = np.einsum("nji,nj->ni", B, frm - self.origin[sel])
+            d = np.einsum("nji,j->ni", B, delta)
+            h = self.dims[sel] + grow
+            cap = self.capsule[sel]
+            f = np.full(len(sel), np.inf)
+            nl = np.zeros((len(sel), 3))
+            with np.errstate(all="ignore"):
+                # boxes
+                inside = (np.abs(o) <= h).all(axis=1)
+                par = d == 0
+                bad = (par & (np.abs(o) > h)).any(axis=1)
+                t1, t2 = (-h - o) / d, (h - o) / d
+                near = np.where(par, -np.inf, np.minimum(t1, t2))
+                far = np.where(par, np.inf, np.maximum(t1, t2))
+                ax = np.argmax(near, axis=1)
+                tn = near[np.arange(len(sel)), ax]
+                tf = far.min(axis=1)
+                hit = ~cap & ~inside & ~bad & (tn > -np.inf) & (tn <= tf) & (tn >= 0) & (tn <= 1)
+                f = np.where(hit, tn, f)
+                sgn = np.where(d[np.arange(len(sel)), ax] > 0, -1.0, 1.0)
+                nb = np.zeros((len(sel), 3))
+                nb[np.arange(len(sel)), ax] = sgn
+                nl = np.where(hit[:, None], nb, nl)
+                # capsules: side, then the two cap spheres
+                r, hh = h[:, 0], self.dims[sel][:, 1]
+                cy = np.clip(o[:, 1], -hh, hh)
+                cin = o[:, 0] ** 2 + (o[:, 1] - cy) ** 2 + o[:, 2] ** 2 <= r * r
+                a = d[:, 0] ** 2 + d[:, 2] ** 2
+                b = o[:, 0] * d[:, 0] + o[:, 2] * d[:, 2]
+                c = o[:, 0] ** 2 + o[:, 2] ** 2 - r * r
+                disc = b * b - a * c
+                t = (-b - np.sqrt(disc)) / a
+                y = o[:, 1] + d[:, 1] * t
+                side = cap & ~cin & (a > 0) & (disc >= 0) & (t >= 0) & (t <= 1) & (np.abs(y) <= hh)
+                best = np.where(side, t, np.inf)
+                bn = np.where(side[:, None], np.stack([o[:, 0] + d[:, 0] * t, np.zeros_like(t), o[:, 2] + d[:, 2] * t], 1), 0.0)
+                aa = (d * d).sum(axis=1)
+                for c0 in (-1.0, 1.0):
+                    m = o - np.stack([np.zeros_like(hh), c0 * hh, np.zeros_like(hh)], 1)
+                    bb, cc = (m * d).sum(axis=1), (m * m).sum(axis=1) - r * r
+                    ds = bb * bb - aa * cc
+                    ts = (-bb - np.sqrt(ds)) / aa
+                    ok = cap & ~cin & (ds >= 0) & (ts >= 0) & (ts <= 1) & (ts < best)
+                    best = np.where(ok, ts, best)
+                    bn = np.where(ok[:, None], m + d * ts[:, None], bn)
+                bn = bn / np.linalg.norm(bn, axis=1, keepdims=True)
+                f = np.where(cap, best, f)
+                nl = np.where(cap[:, None], bn, nl)
+            for k in np.nonzero(np.isfinite(f))[0]:
+                i = sel[k]
+                out.append((float(f[k]), int(self.code[i]), int(self.kind[i]), int(self.entity[i]), B[k] @ nl[k]))
+        if self.plane and (int(mask) & 2):
+            r = ray_plane(frm[1], frm[1] + delta[1])
+            if r is not None:
+                out.append((r[0], CODE_PLANE, RAY_GROUND, NO_ENTITY, r[1]))
+        out.sort(key=lambda hit: (hit[0], hit[1]))
+        return out
+
+    def clear(self, origin, direction, max_distance, mask, eps=1e-4):
+        """clear_decision() on this world."""
+        base = self.cast_all(origin, direction, max_distance, mask)
+        if len(base) > 1 and base[1][0] - base[0][0] <= eps:
+            return False
+        codes = [h[1] for h in base]
+        return all([h[1] for h in self.cast_all(origin, direction, max_distance, mask, grow=g)] == codes for g in (eps, -eps))
+
+
+def random_objects(rng, n, spread=6.0):
+    objs = []
+    for i in range(n):
+        capsule = bool(rng.integers(0, 2))
+        size = rng.uniform(0.1, 1.5, 3)
+        dims = capsule_dims(size) if capsule else box_half_extents(size)
+        q = rng.normal(size=4)
+        kind = RAY_BODY if i % 5 else RAY_TRIGGER
+        objs.append(Obj(kind, i, int(rng.choice([1, 2, 4, 5])), int(rng.choice([0xFFFFFFFF, 0xFFFFFFFF, 0])), capsule, dims,
+                        rng.uniform(-spread, spread, 3), q / np.linalg.norm(q)))
+    return objs
+
+
+# ------------------------------------------------------------------------------------------------ hand-worked cases
+
+IDQ = (0.0, 0.0, 0.0, 1.0)
+
+
+def test_reference_axis_aligned_box():
+    box = Obj(RAY_BODY, 3, 1, ~0 & 0xFFFFFFFF, False, (1.0, 2.0, 3.0), (10.0, 0.0, 0.0), IDQ)
+    # from (0, 0, 0) along +x over 20: enters the face x = 9 at f = 9 / 20, normal -x
+    h = cast_closest([box], (0, 0, 0), (1, 0, 0), 20.0, 1, False)
+    assert h[0] == pytest.approx(9 / 20) and h[3] == 3 and np.allclose(h[4], (-1, 0, 0))
+    # from above onto the top face y = 2
+    h = cast_closest([box], (10.5, 10, -2.5), (0, -1, 0), 100.0, 1, False)
+    assert h[0] == pytest.approx(8 / 100) and np.allclose(h[4], (0, 1, 0))
+    # too short, the wrong layer, an object mask of 0, beside the box
+    assert cast_closest([box], (0, 0, 0), (1, 0, 0), 8.9, 1, False) is None
+    assert cast_closest([box], (0, 0, 0), (1, 0, 0), 20.0, 2, False) is None
+    assert cast_closest([Obj(RAY_BODY, 3, 1, 0, False, (1, 2, 3), (10, 0, 0), IDQ)], (0, 0, 0), (1, 0, 0), 20.0, 1, False) is None
+    assert cast_closest([box], (0, 2.5, 0), (1, 0, 0), 20.0, 1, False) is None
+    # direction not normalised: the fraction is along direction * maxDistance
+    h = cast_closest([box], (0, 0, 0), (2, 0, 0), 10.0, 1, False)
+    assert h[0] == pytest.approx(9 / 20)
+
+
+def test_reference_rotated_box():
+    # 90 degrees about z: the local x half extent (1) lies along world y, the local y half extent (2) along world x
+    q = (0.0, 0.0, math.sin(math.pi / 4), math.cos(math.pi / 4))
+    box = Obj(RAY_BODY, 0, 1, 1, False, (1.0, 2.0, 3.0), (0.0, 0.0, 0.0), q)
+    h = cast_closest([box], (-10, 0, 0), (1, 0, 0), 20.0, 1, False)
+    assert h[0] == pytest.approx(8 / 20) and np.allclose(h[4], (-1, 0, 0), atol=1e-12)
+    h = cast_closest([box], (0, 10, 0), (0, -1, 0), 20.0, 1, False)
+    assert h[0] == pytest.approx(9 / 20) and np.allclose(h[4], (0, 1, 0), atol=1e-12)
+    # 45 degrees about y: a unit cube's corner edge points at a ray along x, at distance sqrt(2) from the centre
+    q45 = (0.0, math.sin(math.pi / 8), 0.0, math.cos(math.pi / 8))
+    cube = Obj(RAY_BODY, 0, 1, 1, False, (1.0, 1.0, 1.0), (0.0, 0.0, 0.0), q45)
+    h = cast_closest([cube], (-10, 0.5, 0.1), (1, 0, 0), 20.0, 1, False)
+    assert h[0] * 20 == pytest.approx(10 - math.sqrt(2) + 0.1) and abs(np.linalg.norm(h[4]) - 1) < 1e-12
+
+
+def test_reference_capsule_side_and_caps():
+    cap = Obj(RAY_BODY, 5, 1, 1, True, (0.5, 1.0, 0.5), (0.0, 0.0, 0.0), IDQ)
+    # side: x = -0.5 at f = 9.5 / 20
+    h = cast_closest([cap], (-10, 0.3, 0), (1, 0, 0), 20.0, 1, False)
+    assert h[0] == pytest.approx(9.5 / 20) and np.allclose(h[4], (-1, 0, 0))
+    # top cap from above: y = 1 + 0.5
+    h = cast_closest([cap], (0, 10, 0), (0, -1, 0), 20.0, 1, False)
+    assert h[0] == pytest.approx(8.5 / 20) and np.allclose(h[4], (0, 1, 0))
+    # bottom cap from below, off axis: the sphere at y = -1, x = 0.3 -> y = -1 - 0.4
+    h = cast_closest([cap], (0.3, -10, 0), (0, 1, 0), 20.0, 1, False)
+    assert h[0] * 20 == pytest.approx(10 - 1.4) and np.allclose(h[4], (0.6, -0.8, 0))
+    # rotated 90 degrees about x: the capsule's axis along z
+    q = (math.sin(math.pi / 4), 0.0, 0.0, math.cos(math.pi / 4))
+    capz = Obj(RAY_BODY, 5, 1, 1, True, (0.5, 1.0, 0.5), (0.0, 0.0, 0.0), q)
+    h = cast_closest([capz], (0, 0, -10), (0, 0, 1), 20.0, 1, False)
+    assert h[0] * 20 == pytest.approx(8.5) and np.allclose(h[4], (0, 0, -1), atol=1e-12)
+
+
+def test_reference_inside_start_rule():
+    box = Obj(RAY_BODY, 1, 1, 1, False, (1, 1, 1), (0, 0, 0), IDQ)
+    cap = Obj(RAY_BODY, 2, 1, 1, True, (0.5, 1.0, 0.5), (5, 0, 0), IDQ)
+    assert cast_closest([box], (0, 0, 0), (1, 0, 0), 20.0, 1, False) is None     # inside
+    assert cast_closest([box], (1, 0, 0), (-1, 0, 0), 20.0, 1, False) is None    # on the surface, going in
+    assert cast_closest([cap], (5, 1.2, 0), (0, 1, 0), 20.0, 1, False) is None   # inside the top cap
+    # starting inside the box, the ray still hits the capsule behind it
+    h = cast_closest([box, cap], (0, 0, 0), (1, 0, 0), 20.0, 1, False)
+    assert h[3] == 2 and h[0] == pytest.approx(4.5 / 20)
+
+
+def test_reference_plane_filter_and_ordering():
+    box = Obj(RAY_BODY, 7, 1, 0xFFFFFFFF, False, (50, 1, 50), (0, -0.01, 0), IDQ)
+    ghost = Obj(RAY_TRIGGER, 4, 4, 0xFFFFFFFF, False, (1.5, 1.5, 1.5), (5, 1, 5), IDQ)
+    objs = [box, ghost]
+    # plane group 2: a mask of 1 never sees it
+    hits = cast_all(objs, (5, 10, 5), (0, -1, 0), 200.0, 1, True)
+    assert [h[1] for h in hits] == [7]
+    hits = cast_all(objs, (5, 10, 5), (0, -1, 0), 200.0, 0xFFFFFFFF, True)
+    assert [h[2] for h in hits] == [RAY_TRIGGER, RAY_BODY, RAY_GROUND]
+    assert hits[0][0] * 200 == pytest.approx(7.5) and hits[1][0] * 200 == pytest.approx(9.01)
+    assert hits[2][0] * 200 == pytest.approx(10.0) and np.allclose(hits[2][4], (0, 1, 0))
+    # from below the plane: normal -y; parallel to it or ending on it: no hit
+    h = cast_closest([], (100, -3, 0), (0, 1, 0), 10.0, 2, True)
+    assert h[0] == pytest.approx(0.3) and np.allclose(h[4], (0, -1, 0))
+    assert cast_closest([], (0, 1, 0), (1, 0, 0), 10.0, 2, True) is None
+    assert cast_closest([], (0, 1, 0), (0, -1, 0), 1.0, 2, True) is None
+    # equal fractions: the lower object code first (bodies by entity, then ghosts, then the plane)
+    a = Obj(RAY_BODY, 9, 1, 1, False, (1, 1, 1), (0, 0, 0), IDQ)
+    b = Obj(RAY_BODY, 8, 1, 1, False, (1, 1, 1), (0, 0, 0), IDQ)
+    g = Obj(RAY_TRIGGER, 2, 1, 1, False, (1, 1, 1), (0, 0, 0), IDQ)
+    hits = cast_all([a, g, b], (0, 5, 0), (0, -1, 0), 10.0, 1, False)
+    assert [h[1] for h in hits] == [8, 9, CODE_GHOST | 2]
+
+
+def test_reference_no_hit_inputs():
+    box = Obj(RAY_BODY, 1, 1, 1, False, (1, 1, 1), (0, 0, 0), IDQ)
+    assert cast_all([box], (0, 5, 0), (0, -1, 0), 0.0, 1, True) == []
+    assert cast_all([box], (0, 5, 0), (0, -1, 0), -1.0, 1, True) == []
+    assert cast_all([box], (0, 5, 0), (0, -1, 0), 10.0, 0, True) == []
+    assert cast_all([box], (0, 5, 0), (0, 0, 0), 10.0, 1, True) == []
+    assert cast_all([box], (0, 5, float("nan")), (0, -1, 0), 10.0, 1, True) == []
+    assert cast_all([box], (0, 5, 0), (0, -1, 0), float("nan"), 1, True) == []
+    assert not clear_decision([box], (1.00005, 5, 0), (0, -1, 0), 10.0, 1, False)  # grazes an edge
+    assert clear_decision([box], (0.3, 5, 0), (0, -1, 0), 10.0, 1, False)
+
+
+def test_vectorised_reference_equals_scalar():
+    rng = np.random.default_rng(7)
+    objs = random_objects(rng, 60)
+    w64 = World64(objs, True)
+    n_hits = 0
+    for _ in range(300):
+        o = rng.uniform(-9, 9, 3)
+        d = rng.normal(size=3)
+        md = float(rng.uniform(1, 30))
+        mask = int(rng.choice([1, 2, 3, 4, 0xFFFFFFFF]))
+        a = cast_all(objs, o, d, md, mask, True)
+        b = w64.cast_all(o, d, md, mask)
+        assert [h[1] for h in a] == [h[1] for h in b]
+        for x, y in zip(a, b):
+            assert abs(x[0] - y[0]) < 1e-12 and np.allclose(x[4], y[4], atol=1e-9)
+        n_hits += len(a)
+        assert clear_decision(objs, o, d, md, mask, True) == w64.clear(o, d, md, mask)
+    assert n_hits > 100
+
+
+def test_box_half_extents_follow_the_library():
+    assert np.array_equal(box_half_extents((0.5, 0.5, 0.5)), np.float32([0.5, 0.5, 0.5]))
+    he = box_half_extents((50, 1, 50))
+    assert np.allclose(he, (50, 1, 50), rtol=1e-6)
+    assert np.allclose(box_half_extents((0.1, 2, 2)), (0.1, 2, 2), rtol=1e-6)
+
+
+# ------------------------------------------------------------------------------------------------ the ABI
+
+
+def test_raycast_symbols_exported():
+    from banggameengine_amd import _capi
+    lib = _capi.lib()
+    for name in ("bge_world_raycast", "bge_world_raycast_all", "bge_world_raycast_device"):
+        assert name in _capi.SYMBOLS
+        assert getattr(lib, name) is not None
+    from banggameengine_amd.world import RAY_DTYPE, RAY_HIT_DTYPE, make_rays
+    assert RAY_DTYPE.itemsize == 32 and RAY_HIT_DTYPE.itemsize == 40
+    r = make_rays([[0, 1, 0], [1, 2, 3]], [[0, -1, 0], [1, 0, 0]], [5.0, 6.0], 3)
+    assert r["max_distance"].tolist() == [5.0, 6.0] and r["layer_mask"].tolist() == [3, 3]
+
+
+def test_raycast_rejects_null_world_and_zero_rays():
+    from banggameengine_amd import _capi
+    lib = _capi.lib()
+    total = C.c_uint64(5)
+    assert lib.bge_world_raycast(None, 1, None, None) == -1
+    assert lib.bge_world_raycast_all(None, 0, None, None, 0, None, C.byref(total)) == -1
+    assert lib.bge_world_raycast_device(None, 0, None, None) == -1
+
+
+def test_abi_c99_raycast_records(tmp_path):
+    exe = str(tmp_path / "abi_check_raycast")
+    subprocess.check_call(["gcc", "-std=c99", "-pedantic", "-Wall", "-Wextra", "-Werror", "-o", exe, os.path.join(CPP, "abi_check_raycast.c"),
+                           f"-L{LIBDIR}", "-lbge_world", f"-Wl,-rpath,{LIBDIR}", "-Wl,-rpath,/opt/rocm/lib"])
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "raycast abi ok" in r.stdout
+
+
+def test_adapter_raycast_compiles_on_reference_shapes(tmp_path):
+    subprocess.check_call(["g++", "-std=c++20", "-O0", "-Wall", "-Wextra", "-Werror", "-Wno-unused-parameter", "-c",
+                           os.path.join(CPP, "raycast_reference_shapes.cpp"), "-o", str(tmp_path / "raycast_reference_shapes.o")])
