@@ -7,7 +7,7 @@ the benchmark configurations and the multi-GPU sharding helpers.  It never falls
 implementation: importing works without a GPU, creating a :class:`World` without one raises.
 """
 from ._capi import BgeError, lib, lib_path  # noqa: F401
-from .world import (BODY_DYNAMIC, BODY_KINEMATIC, BODY_NONE, BODY_STATIC, NO_PARENT, SHAPE_BOX, SHAPE_CAPSULE,  # noqa: F401
+from .world import (DEBUG_ALL, DEBUG_CONTACTS, DEBUG_SHAPES, BODY_DYNAMIC, BODY_KINEMATIC, BODY_NONE, BODY_STATIC, NO_PARENT, SHAPE_BOX, SHAPE_CAPSULE,  # noqa: F401
                     TICK_AABBS, TICK_ALL, TICK_BULLET_BASIS, TICK_BROADPHASE, TICK_GATHER_ROOTS, TICK_NORMAL_MATRICES, TICK_PHYSICS, TICK_TRANSFORMS, World, flatten_topology,
                     partition_subtrees)
 

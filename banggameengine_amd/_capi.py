@@ -20,6 +20,11 @@ class WorldDesc(C.Structure):
                 ("pair_capacity", C.c_uint64)]
 
 
+class DebugDesc(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("use_region", C.c_uint32),
+                ("region_min", C.c_float * 3), ("region_max", C.c_float * 3)]
+
+
 class WorldInfo(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ("n_entities", "n_transforms", "n_slots", "n_tiles", "n_passes", "n_roots",
                                           "n_limbo", "n_bodies", "max_depth")]
@@ -89,6 +94,8 @@ SYMBOLS = {
     "bge_world_raycast": (C.c_int, [_vp, _u64, _vp, _vp]),
     "bge_world_raycast_all": (C.c_int, [_vp, _u64, _vp, _vp, _u64, _vp, C.POINTER(_u64)]),
     "bge_world_raycast_device": (C.c_int, [_vp, _u64, _vp, _vp]),
+    "bge_world_debug_lines": (C.c_int, [_vp, _vp, _vp, _u64, C.POINTER(_u64)]),
+    "bge_world_debug_lines_device": (C.c_int, [_vp, _vp, _vp, _u64, _vp]),
     "bge_world_pack_roots": (C.c_int, [_vp, _vp]),
     "bge_world_device_array": (C.c_int, [_vp, C.c_int, C.POINTER(_vp), C.POINTER(_u64)]),
     "bge_world_get_info": (C.c_int, [_vp, C.POINTER(WorldInfo)]),

@@ -23,6 +23,7 @@
 #include "bge_broadphase.hpp"
 #include "bge_route.hpp"
 #include "bge_comm.hpp"
+#include "bge_debug.hpp"
 #include "bge_flatten.hpp"
 #include "bge_kernels.hpp"
 #include "bge_raycast.hpp"
@@ -290,6 +291,8 @@ struct bge_world {
     uint64_t ray_keys_n = 0;
     uint32_t ray_all_cap = 0;
     std::vector<bge::RayGhost> ray_ghosts_host, ray_ghosts_dev;
+    // debug overlay (bge_debug.hip): per-workgroup line counts and their offsets, the host entry point's line buffer and total
+    DevBuf dbg_block_sum, dbg_block_off, dbg_lines, dbg_total;
     uint32_t trigger_grid_min = 64;       // more ghosts than this: the broadphase grid answers for the small ones
     // Enter / Exit taken on the device (bge_kernels.hpp TriggerDiff): two key tables (this tick's, last tick's), header + deltas in
     // one device buffer with a page-locked copy.  The overlap sets above stay the truth; `trig_mirror_valid` says that last tick's
@@ -370,7 +373,8 @@ struct bge_world {
                           &angvel, &quat, &inv_mass, &half_extent, &group, &mask, &aabb, &root_worlds, &counter, &stage,
                           &stage2, &mass_palette, &normal, &deact, &filter_class, &filter_table, &grav_palette, &bp_partials, &cshape, &cmass, &cfriction, &cinfo, &manifold, &crestitution, &bmanifold, &obstacle_slots, &obstacle_gen, &obstacles, &obstacle_grid, &box_list, &box_count, &frozen, &rs_word, &trig_slot, &trig_entity, &trig_he, &trig_group,
                           &trig_mask, &trig_active, &trig_aabb, &trig_pairs, &trig_count, &trig_lists, &ground_list, &ground_count, &trig_tab[0], &trig_tab[1],
-                          &trig_delta_dev, &trig_keys_dev, &trig_pose, &ray_in, &ray_out, &ray_keys, &ray_all, &ray_all_count, &ray_ghosts}) {
+                          &trig_delta_dev, &trig_keys_dev, &trig_pose, &ray_in, &ray_out, &ray_keys, &ray_all, &ray_all_count, &ray_ghosts, &dbg_block_sum, &dbg_block_off,
+                          &dbg_lines, &dbg_total}) {
             b->release();
         }
         if (trig_delta_host) (void)hipHostFree(trig_delta_host);
@@ -2806,15 +2810,10 @@ static_assert(sizeof(bge_ray_hit) == 40, "bge_ray_hit is 40 bytes (include/bge_w
 
 namespace {
 
-// What every query needs: the ghosts the rays see (in the world, posed by a tick into the device arrays as they are indexed
-// now — uploaded only when the list changed), the per-ray keys, the body arrays.
-int ray_prepare(bge_world* w, uint64_t n_rays, bge::RayParams& p)
+// The trigger ghosts that are in the world for a query (ray queries, debug overlay): active, posed by a tick into the device
+// arrays as they are indexed now, in the order of the uploaded trigger array.  The device copy is sent only when the list changed.
+int sync_query_ghosts(bge_world* w)
 {
-    if (!w->has_topology) return fail(BGE_ERR_STATE, "bge_world_set_topology has not been called");
-    if (n_rays > 0x7fffffffull) return fail(BGE_ERR_INVALID, "n_rays = %llu: at most 2^31 - 1 rays per batch", (unsigned long long)n_rays);
-    if (w->flat.n_entities > bge::kRayEntityMask) {
-        return fail(BGE_ERR_UNSUPPORTED, "ray queries need entity indices below 2^30 (world has %llu)", (unsigned long long)w->flat.n_entities);
-    }
     std::vector<bge::RayGhost>& gh = w->ray_ghosts_host;
     gh.clear();
     if (w->trig_list_on_device && w->trig_pose.p) {
@@ -2848,6 +2847,18 @@ int ray_prepare(bge_world* w, uint64_t n_rays, bge::RayParams& p)
             HIP_TRY(hipStreamSynchronize(w->stream)); // (the list changes when the trigger set does, not per query)
         }
     }
+    return BGE_OK;
+}
+
+// What every ray query needs: the ghosts the rays see, the per-ray keys, the body arrays.
+int ray_prepare(bge_world* w, uint64_t n_rays, bge::RayParams& p)
+{
+    if (!w->has_topology) return fail(BGE_ERR_STATE, "bge_world_set_topology has not been called");
+    if (n_rays > 0x7fffffffull) return fail(BGE_ERR_INVALID, "n_rays = %llu: at most 2^31 - 1 rays per batch", (unsigned long long)n_rays);
+    if (w->flat.n_entities > bge::kRayEntityMask) {
+        return fail(BGE_ERR_UNSUPPORTED, "ray queries need entity indices below 2^30 (world has %llu)", (unsigned long long)w->flat.n_entities);
+    }
+    if (int rc = sync_query_ghosts(w)) return rc;
     if (n_rays > w->ray_keys_n) {
         HIP_TRY(w->ray_keys.ensure(n_rays * 8));
         HIP_TRY(hipMemsetAsync(w->ray_keys.p, 0xff, n_rays * 8, w->stream));
@@ -2990,6 +3001,120 @@ try {
     return BGE_OK;
 }
 BGE_CATCH_ALL("bge_world_raycast_all")
+
+// ---------------------------------------------------------------- debug overlay (bge_debug.hip)
+static_assert(sizeof(bge_debug_line) == 28, "bge_debug_line is 28 bytes (include/bge_world.h)");
+
+namespace {
+
+constexpr uint64_t kDebugMaxLines = 0xffffffffull;
+
+// Enqueues the whole query: *total_device = lines of the state as it is, lines_device[0 .. min(cap, total)) written.
+int debug_enqueue(bge_world* w, const bge_debug_desc* desc, void* lines_device, uint64_t cap, void* total_device)
+{
+    if (!w->has_topology) return fail(BGE_ERR_STATE, "bge_world_set_topology has not been called");
+    bge::DebugParams p{};
+    p.flags = BGE_DEBUG_ALL;
+    if (desc) {
+        if (desc->struct_size < sizeof(bge_debug_desc)) return fail(BGE_ERR_INVALID, "bge_debug_desc::struct_size = %u", desc->struct_size);
+        if (desc->flags & ~static_cast<uint32_t>(BGE_DEBUG_ALL)) return fail(BGE_ERR_INVALID, "bge_debug_desc::flags = 0x%x", desc->flags);
+        p.flags = desc->flags;
+        p.use_region = desc->use_region ? 1u : 0u;
+        for (int a = 0; a < 3; ++a) {
+            p.region_min[a] = desc->region_min[a];
+            p.region_max[a] = desc->region_max[a];
+        }
+    }
+    if (cap && !lines_device) return fail(BGE_ERR_INVALID, "lines is NULL");
+    if (reinterpret_cast<uintptr_t>(lines_device) & 3u) return fail(BGE_ERR_INVALID, "lines must be 4-byte aligned");
+    if (int rc = sync_query_ghosts(w)) return rc;
+    const bge::WorldView& v = w->view;
+    p.n_entities = w->flat.n_entities;
+    p.n_slots = w->flat.n_slots;
+    p.slot_of_entity = w->slot_of_entity.as<uint32_t>();
+    p.flag_words = v.flags;
+    p.pos = v.pos;
+    p.quat = v.quat;
+    p.cshape = v.cshape;
+    p.cinfo = v.cinfo;
+    p.ghosts = w->ray_ghosts.as<bge::RayGhost>();
+    p.n_ghosts = static_cast<uint32_t>(w->ray_ghosts_dev.size());
+    p.ghost_pose = w->trig_pose.as<float>();
+    p.plane = w->ground_plane ? 1u : 0u;
+    if (p.flags & BGE_DEBUG_SHAPES) {
+        const uint64_t items = bge::debug_items(p.n_entities, p.n_ghosts);
+        const uint64_t blocks = (items + bge::kDebugItemsPerBlock - 1) / bge::kDebugItemsPerBlock;
+        if (blocks > 0x7fffffffull) return fail(BGE_ERR_UNSUPPORTED, "debug overlay: %llu items", (unsigned long long)items);
+        p.n_blocks = static_cast<uint32_t>(blocks);
+        HIP_TRY(w->dbg_block_sum.ensure(blocks * 4));
+        HIP_TRY(w->dbg_block_off.ensure(blocks * 8));
+        p.block_sum = w->dbg_block_sum.as<uint32_t>();
+        p.block_off = w->dbg_block_off.as<uint64_t>();
+    }
+    if (p.flags & BGE_DEBUG_CONTACTS) {
+        // what bge_world_download_contacts / _box_contacts / _dynamic_pairs report while their switch is on
+        if (w->ground_plane && w->manifold.p) p.manifold = v.manifold;
+        if (w->static_contacts && w->bmanifold.p) p.bmanifold = v.bmanifold;
+        if (w->dynamic_contacts && w->isl_n_prev) {
+            const int at = w->isl_cur ^ 1; // (island_substep flipped the generations)
+            p.pair_keys = w->isl_keys[at].as<uint64_t>();
+            p.pair_man = w->isl_man[at].as<uint32_t>();
+            p.n_pairs = w->isl_n_prev;
+        }
+    }
+    p.lines = static_cast<float*>(lines_device);
+    p.cap = cap;
+    p.total = static_cast<unsigned long long*>(total_device);
+    HIP_TRY(bge::launch_debug_lines(w->stream, p));
+    return BGE_OK;
+}
+
+// the count alone (nothing is written anywhere but the world's own counter); synchronises
+int debug_count(bge_world* w, const bge_debug_desc* desc, uint64_t* total)
+{
+    HIP_TRY(w->dbg_total.ensure(8));
+    if (int rc = debug_enqueue(w, desc, nullptr, 0, w->dbg_total.p)) return rc;
+    HIP_TRY(hipMemcpyAsync(total, w->dbg_total.p, 8, hipMemcpyDeviceToHost, w->stream));
+    HIP_TRY(hipStreamSynchronize(w->stream));
+    return BGE_OK;
+}
+
+} // namespace
+
+int bge_world_debug_lines(bge_world* w, const bge_debug_desc* desc, bge_debug_line* lines, uint64_t cap, uint64_t* total)
+try {
+    if (!w || !total) return fail(BGE_ERR_INVALID, "NULL argument");
+    *total = 0;
+    DeviceGuard guard(w->device);
+    uint64_t n = 0;
+    if (int rc = debug_count(w, desc, &n)) return rc;
+    if (n > kDebugMaxLines) return fail(BGE_ERR_UNSUPPORTED, "debug overlay: %llu lines, at most 2^32 - 1", (unsigned long long)n);
+    *total = n;
+    if (!lines || n == 0) return BGE_OK;
+    if (cap < n) return fail(BGE_ERR_INVALID, "debug_lines: %llu lines, room for %llu", (unsigned long long)n, (unsigned long long)cap);
+    HIP_TRY(w->dbg_lines.ensure(n * sizeof(bge_debug_line)));
+    if (int rc = debug_enqueue(w, desc, w->dbg_lines.p, n, w->dbg_total.p)) return rc;
+    HIP_TRY(hipMemcpyAsync(lines, w->dbg_lines.p, n * sizeof(bge_debug_line), hipMemcpyDeviceToHost, w->stream));
+    HIP_TRY(hipStreamSynchronize(w->stream));
+    return BGE_OK;
+}
+BGE_CATCH_ALL("bge_world_debug_lines")
+
+int bge_world_debug_lines_device(bge_world* w, const bge_debug_desc* desc, void* lines_device, uint64_t cap, void* total_device)
+try {
+    if (!w || !total_device) return fail(BGE_ERR_INVALID, "NULL argument");
+    DeviceGuard guard(w->device);
+    // a world whose line count could pass 2^32 - 1 is counted first (one synchronisation), so that nothing is written when it does
+    const uint64_t most = bge::kDebugPlaneLines + (bge::kDebugCapsuleLines + 4ull + 4ull * bge::kBoxManifolds) * (w->flat.n_entities + w->triggers.size()) +
+                    4ull * w->isl_n_prev;
+    if (most > kDebugMaxLines) {
+        uint64_t n = 0;
+        if (int rc = debug_count(w, desc, &n)) return rc;
+        if (n > kDebugMaxLines) return fail(BGE_ERR_UNSUPPORTED, "debug overlay: %llu lines, at most 2^32 - 1", (unsigned long long)n);
+    }
+    return debug_enqueue(w, desc, lines_device, cap, total_device);
+}
+BGE_CATCH_ALL("bge_world_debug_lines_device")
 
 int bge_world_pack_roots(bge_world* w, void* dst_device)
 try {

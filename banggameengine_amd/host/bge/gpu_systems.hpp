@@ -62,6 +62,12 @@ struct GpuTriggerEvent {
     uint32_t other = 0;   // EntityId
 };
 
+// One line of the physics debug overlay: bge_debug_line has the members and layout of the reference's PhysicsDebugLine
+// (src/physics/PhysicsDebugDraw.h: float from[3], to[3]; uint32_t abgr), so the renderer's loop over the buffer compiles unchanged
+using DebugLine = ::bge_debug_line;
+static_assert(sizeof(DebugLine) == 28, "28-byte line record");
+using DebugLineBuffer = std::vector<DebugLine>;
+
 namespace detail {
 template <class S, class = void> struct has_trigger_volumes : std::false_type {};
 template <class S> struct has_trigger_volumes<S, std::void_t<decltype(std::declval<S&>().GetTriggerVolumes())>> : std::true_type {};
@@ -273,6 +279,24 @@ public:
         hits.resize(total);
         for (uint64_t i = 0; i < total; ++i) FillHit(ray_hits_[i], hits[i]);
         return hits;
+    }
+
+    // CollectDebugLines + debugDrawWorld(DBG_DrawContactPoints) (PhysicsSystem.cpp:857-873, 1148-1175) on the device world as
+    // the last Update left it: the count, then the lines (include/bge_world.h states what is drawn and in which order)
+    bool DebugLines(const bge_debug_desc& desc, DebugLineBuffer& out)
+    {
+        out.clear();
+        if (!ok()) return false;
+        uint64_t total = 0;
+        if (bge_world_debug_lines(world_, &desc, nullptr, 0, &total) != BGE_OK) return Log("bge_world_debug_lines");
+        out.resize(total);
+        if (total == 0) return true;
+        if (bge_world_debug_lines(world_, &desc, out.data(), total, &total) != BGE_OK) {
+            out.clear();
+            return Log("bge_world_debug_lines");
+        }
+        out.resize(total);
+        return true;
     }
 
 private:
@@ -820,6 +844,29 @@ public:
         return GpuMirrors<SceneT>::Of(*lastScene_).template RaycastAll<HitT>(origin, direction, maxDistance, layerMask);
     }
 
+    // The debug overlay (src/physics/PhysicsSystem.h:77-82, bound to a key at src/core/Application.cpp:173; the renderer gets
+    // GetDebugLines() every frame, :359).  While it is on, Update refills the buffer after the step (one bge_world_debug_lines
+    // query on the scene's mirror); while it is off GetDebugLines() is empty and Update does nothing for it.
+    void ToggleDebugOverlay() { SetDebugOverlayEnabled(!debugDrawEnabled_); }
+    void SetDebugOverlayEnabled(bool enabled)
+    {
+        if (debugDrawEnabled_ == enabled) return;
+        debugDrawEnabled_ = enabled;
+        if (!enabled) debugLines_.clear();
+        std::printf("[PhysicsDebug] overlay %s\n", enabled ? "ON" : "OFF");
+    }
+    bool IsDebugOverlayEnabled() const { return debugDrawEnabled_; }
+    const DebugLineBuffer& GetDebugLines() const { return debugDrawEnabled_ ? debugLines_ : emptyDebugLines_; }
+    // Not in the reference: draw only the bodies, ghosts and contact points inside the closed box [min, max] (the plane always) —
+    // what makes the overlay usable in a world of 10^6 bodies
+    template <class Vec3> void SetDebugRegion(const Vec3& mn, const Vec3& mx)
+    {
+        debugDesc_.use_region = 1u;
+        debugDesc_.region_min[0] = mn.x, debugDesc_.region_min[1] = mn.y, debugDesc_.region_min[2] = mn.z;
+        debugDesc_.region_max[0] = mx.x, debugDesc_.region_max[1] = mx.y, debugDesc_.region_max[2] = mx.z;
+    }
+    void ClearDebugRegion() { debugDesc_.use_region = 0u; }
+
     // PhysicsSystem::Config (src/physics/PhysicsSystem.h:85-95); the character fields are read and kept, nothing here uses them
     struct Config {
         float gravity = -9.81f;
@@ -889,6 +936,7 @@ private:
         lastStepDt_ = dt;
         lastStepSubsteps_ = m.last_sub_steps;
         lastBodies_ = m.CollisionObjectCount();
+        if (debugDrawEnabled_) m.DebugLines(debugDesc_, debugLines_); // debugDrawWorld + CollectDebugLines, PhysicsSystem.cpp:866-870
     }
 
     std::filesystem::path configPath_;
@@ -898,6 +946,10 @@ private:
     bool bulletBasis_ = false;
     bool groundPlane_ = true;
     SceneT* lastScene_ = nullptr; // the scene whose world the ray queries read
+    bool debugDrawEnabled_ = false;
+    bge_debug_desc debugDesc_{static_cast<uint32_t>(sizeof(bge_debug_desc)), BGE_DEBUG_ALL, 0u, {0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f}};
+    DebugLineBuffer debugLines_;
+    DebugLineBuffer emptyDebugLines_; // (stays empty)
     double lastStepDurationMs_ = 0.0, lastStepDt_ = 0.0;
     int lastStepSubsteps_ = 0, lastBodies_ = 0;
 };

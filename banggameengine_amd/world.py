@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import _capi
-from ._capi import WorldDesc, WorldInfo, check, lib
+from ._capi import DebugDesc, WorldDesc, WorldInfo, check, lib
 
 NO_PARENT = 0xFFFFFFFF
 BODY_STATIC, BODY_DYNAMIC, BODY_KINEMATIC, BODY_NONE = 0, 1, 2, 255
@@ -41,6 +41,22 @@ def make_rays(origins, directions, max_distance=200.0, layer_mask=0xFFFFFFFF):
 def _hit_fields(h):
     return {"kind": h["kind"].copy(), "entity": h["entity"].copy(), "fraction": h["fraction"].copy(),
             "distance": h["distance"].copy(), "point": h["point"].copy(), "normal": h["normal"].copy()}
+
+
+# debug overlay (bge_world_debug_lines*): bge_debug_flags and the 28-byte line record
+DEBUG_SHAPES, DEBUG_CONTACTS, DEBUG_ALL = 1, 2, 3
+DEBUG_LINE_DTYPE = np.dtype([("from", "<f4", (3,)), ("to", "<f4", (3,)), ("abgr", "<u4")])
+assert DEBUG_LINE_DTYPE.itemsize == 28
+
+
+def _debug_desc(flags, region):
+    """bge_debug_desc: region = None (the whole world) or (min xyz, max xyz)."""
+    d = DebugDesc(C.sizeof(DebugDesc), int(flags), 0 if region is None else 1)
+    if region is not None:
+        mn, mx = (np.asarray(r, np.float32).reshape(3) for r in region)
+        d.region_min = (C.c_float * 3)(*mn.tolist())
+        d.region_max = (C.c_float * 3)(*mx.tolist())
+    return d
 
 
 # fixed step and gravity of the reference (assets/config/physics.json:2-3)
@@ -373,6 +389,25 @@ class World:
         if not (rays.is_cuda and hits.is_cuda and rays.is_contiguous() and hits.is_contiguous()):
             raise ValueError("rays and hits must be contiguous device tensors")
         check(lib().bge_world_raycast_device(self._h, n, C.c_void_p(rays.data_ptr()), C.c_void_p(hits.data_ptr())))
+
+    # -- debug overlay (PhysicsSystem::GetDebugLines; include/bge_world.h states what is drawn and in which order)
+    def debug_lines(self, flags=DEBUG_ALL, region=None):
+        """The overlay's lines as a structured array (from, to: 3 x f4; abgr: u4): the shapes section in its fixed order, then
+        the contact lines.  region = (min xyz, max xyz) keeps the bodies / ghosts / contact points inside that closed box."""
+        desc = _debug_desc(flags, region)
+        total = C.c_uint64(0)
+        check(lib().bge_world_debug_lines(self._h, C.byref(desc), None, 0, C.byref(total)))
+        lines = np.zeros(int(total.value), DEBUG_LINE_DTYPE)
+        if len(lines):
+            check(lib().bge_world_debug_lines(self._h, C.byref(desc), _p(lines), len(lines), C.byref(total)))
+        return lines[:int(total.value)]
+
+    def debug_lines_device(self, lines_ptr, cap, total_ptr, flags=DEBUG_ALL, region=None):
+        """The same into device memory: lines_ptr = room for cap 28-byte records, total_ptr = one uint64 (device pointers, e.g.
+        tensor.data_ptr()).  Enqueued on the world's stream without synchronisation; lines beyond cap are counted, not written."""
+        desc = _debug_desc(flags, region)
+        check(lib().bge_world_debug_lines_device(self._h, C.byref(desc), C.c_void_p(lines_ptr) if lines_ptr else None, int(cap),
+                                                 C.c_void_p(total_ptr)))
 
     def pack_roots(self, dst_device_ptr: int | None = None):
         check(lib().bge_world_pack_roots(self._h, C.c_void_p(dst_device_ptr) if dst_device_ptr else None))

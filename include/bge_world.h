@@ -440,6 +440,69 @@ BGE_API int bge_world_raycast_all(bge_world* world, uint64_t n_rays, const bge_r
                                   uint64_t* offsets, uint64_t* total);
 BGE_API int bge_world_raycast_device(bge_world* world, uint64_t n_rays, const void* rays_device, void* hits_device);
 
+/*
+ * The physics debug overlay: what PhysicsSystem::GetDebugLines hands to the renderer while the overlay is on
+ * (src/physics/PhysicsSystem.cpp:857-873, 1148-1175; src/physics/BulletDebugDrawer.cpp) — every collision object's shape as
+ * wireframe lines in one colour, then one short red line per contact point — made on the device from the state the last tick
+ * left.  The query reads that state and changes nothing.  The rules below are the specification.
+ *   Shapes    (BGE_DEBUG_SHAPES) exactly the objects the ray queries see, at the same poses; the layer / mask play no part:
+ *             - every rigid body of any type, asleep or awake, that is in the world (not uploaded since the last physics tick,
+ *               not removed) at position + quaternion as held after the last physics tick, with the collider as Bullet holds it
+ *               (box: half extents with margin; capsule: radius, half height);
+ *             - every trigger ghost that is in the world and posed (as for rays);
+ *             - the ground plane when bge_world_set_ground_plane is on.
+ *   Lines     box      12: the corners (-x-y-z, +x-y-z, +x+y-z, -x+y-z, then the same four at +z) through the pose, edges
+ *                          0,1 1,2 2,3 3,0  4,5 5,6 6,7 7,4  0,4 1,5 2,6 3,7 (DrawBox).
+ *             capsule 120: up axis Y, the axes the NORMALISED columns of the basis; 24 segments x (top ring, bottom ring, side
+ *                          line) = 72 lines, then 12 hemisphere steps x (top, bottom in the plane of the basis' Z column, top,
+ *                          bottom in the plane of its X column) = 48 (DrawCapsule; ring angle i / 24 * 2 pi measured from the Z
+ *                          column towards the X column, as there).
+ *             plane    12: the square (-25,0,25) (-25,0,-25) (25,0,-25) (25,0,25) as 4 border lines, then for i = 1..4, t = i / 5
+ *                          the two grid lines lerp(c0,c3,t)-lerp(c1,c2,t) and lerp(c0,c1,t)-lerp(c3,c2,t) (DrawStaticPlane with
+ *                          btPlaneSpace1's u = (-1,0,0), v = (0,0,1)).
+ *   Colours   abgr: 0xffff00ff trigger ghosts; 0xff7f7f7f Static bodies and the plane; 0xff00ffff Dynamic AND Kinematic bodies (the
+ *             reference's Kinematic bodies end up without CF_STATIC_OBJECT, PhysicsSystem.cpp:443-465); 0xff0000ff contacts.
+ *   Order     of the shapes section — fixed, so that a caller finds an entity's lines from counts alone: (1) the plane's 12
+ *             lines, if on; (2) bodies in ascending ENTITY index, 12 lines per box, 120 per capsule; (3) ghosts in the order of
+ *             the uploaded trigger array.  (The reference's order is that of an unordered_map and of Bullet's object array: this
+ *             order is a specification choice.)
+ *   Contacts  (BGE_DEBUG_CONTACTS) behind the shapes: one line per contact point that bge_world_download_contacts (while the
+ *             plane is on), bge_world_download_box_contacts (while the static contacts are on) and
+ *             bge_world_download_dynamic_pairs (while the dynamic contacts are on) report at the time of the call:
+ *             from = body B's pose x localB, where B is the plane (its frame is the world's: (localB.x, 0, localB.z)), the
+ *             obstacle box, or the higher entity of a pair; to = from + 0.25 x normalise(normalWorldOnB), (0, 1, 0) for the plane
+ *             and for a normal of squared length below FLT_EPSILON.  (Bullet draws the m_positionWorldOnB cached by the last
+ *             narrowphase; for a Dynamic B that differs from "current pose x localB" by one integration step — a stated choice.)
+ *             The ORDER inside the contact section is unspecified: every point exactly once, the same multiset for the same state.
+ *   Region    with use_region a body or ghost is drawn when its origin lies in the closed box region_min <= origin <= region_max
+ *             (plain binary32 compares; all of its lines or none), a contact when its `from` point does, the plane always.  A
+ *             region with a NaN or with min > max on an axis draws only the plane.
+ *   Call order  as for rays: after a physics tick, before new poses are uploaded.
+ *   bge_world_debug_lines         the convention of bge_world_pairs: lines = NULL only counts; cap < *total is BGE_ERR_INVALID
+ *                                 with *total filled in and nothing written.  desc = NULL means BGE_DEBUG_ALL, whole world.
+ *                                 Synchronises the world's stream.
+ *   bge_world_debug_lines_device  device pointers: lines_device = bge_debug_line[cap] (4-byte aligned; may be NULL when cap = 0),
+ *                                 total_device = one uint64_t.  Enqueued on the world's stream, no synchronisation.  Lines beyond
+ *                                 cap are not written; *total_device still counts them (a renderer can draw from the buffer with
+ *                                 an indirect draw).
+ *   More than 2^32 - 1 lines is BGE_ERR_UNSUPPORTED, decided before anything is written.  No lines at all is not an error.
+ */
+typedef struct bge_debug_line {
+    float from[3];
+    float to[3];
+    uint32_t abgr;
+} bge_debug_line; /* 28 bytes: the reference's PhysicsDebugLine (src/physics/PhysicsDebugDraw.h) */
+enum bge_debug_flags { BGE_DEBUG_SHAPES = 1u, BGE_DEBUG_CONTACTS = 2u, BGE_DEBUG_ALL = 3u };
+typedef struct bge_debug_desc {
+    uint32_t struct_size; /* sizeof(bge_debug_desc) */
+    uint32_t flags;       /* bge_debug_flags; the reference's overlay is BGE_DEBUG_ALL */
+    uint32_t use_region;  /* 0: the whole world */
+    float region_min[3], region_max[3];
+} bge_debug_desc;
+BGE_API int bge_world_debug_lines(bge_world* world, const bge_debug_desc* desc, bge_debug_line* lines, uint64_t cap, uint64_t* total);
+BGE_API int bge_world_debug_lines_device(bge_world* world, const bge_debug_desc* desc, void* lines_device, uint64_t cap,
+                                         void* total_device);
+
 /* Multi-GPU support: compact the world matrices of all roots (entity order) into one buffer that the
  * caller all-gathers across ranks (one collective per frame).  dst = NULL packs into the world's own
  * BGE_ARRAY_ROOT_WORLDS buffer; otherwise dst is a device pointer with room for n_roots*16 floats. */
