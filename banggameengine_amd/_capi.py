@@ -94,6 +94,10 @@ SYMBOLS = {
     "bge_world_raycast": (C.c_int, [_vp, _u64, _vp, _vp]),
     "bge_world_raycast_all": (C.c_int, [_vp, _u64, _vp, _vp, _u64, _vp, C.POINTER(_u64)]),
     "bge_world_raycast_device": (C.c_int, [_vp, _u64, _vp, _vp]),
+    "bge_world_sphere_cast": (C.c_int, [_vp, _u64, _vp, _vp]),
+    "bge_world_sphere_cast_all": (C.c_int, [_vp, _u64, _vp, _vp, _u64, _vp, C.POINTER(_u64)]),
+    "bge_world_sphere_cast_device": (C.c_int, [_vp, _u64, _vp, _vp]),
+    "bge_world_overlap_sphere": (C.c_int, [_vp, _u64, _vp, _vp, _u64, _vp, C.POINTER(_u64)]),
     "bge_world_debug_lines": (C.c_int, [_vp, _vp, _vp, _u64, C.POINTER(_u64)]),
     "bge_world_debug_lines_device": (C.c_int, [_vp, _vp, _vp, _u64, _vp]),
     "bge_world_pack_roots": (C.c_int, [_vp, _vp]),

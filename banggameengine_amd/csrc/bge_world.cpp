@@ -27,6 +27,7 @@
 #include "bge_flatten.hpp"
 #include "bge_kernels.hpp"
 #include "bge_raycast.hpp"
+#include "bge_spherecast.hpp"
 
 namespace {
 
@@ -2884,11 +2885,60 @@ int ray_prepare(bge_world* w, uint64_t n_rays, bge::RayParams& p)
     return BGE_OK;
 }
 
-int ray_upload(bge_world* w, uint64_t n_rays, const bge_ray* rays)
+// the batch's query records (bge_ray, bge_sphere_cast, bge_sphere) into the staging buffer
+int ray_upload(bge_world* w, uint64_t bytes, const void* records)
 {
-    HIP_TRY(w->ray_in.ensure(n_rays * sizeof(bge_ray)));
-    HIP_TRY(hipMemcpyAsync(w->ray_in.p, rays, n_rays * sizeof(bge_ray), hipMemcpyHostToDevice, w->stream));
+    HIP_TRY(w->ray_in.ensure(bytes));
+    HIP_TRY(hipMemcpyAsync(w->ray_in.p, records, bytes, hipMemcpyHostToDevice, w->stream));
     return BGE_OK;
+}
+
+// Runs an all-hits launch (ray_all, sphere_cast_all, sphere_overlap) and brings its list back sorted by query, then by
+// (f, object code) or by object code alone: a total order, so the result does not depend on the order of the appends.  The list's
+// capacity grows to what a batch found: a second run of the same batch fits.
+int ray_collect(bge_world* w, bge::RayParams& p, hipError_t (*launch)(hipStream_t, const bge::RayParams&), bool by_fraction,
+                std::vector<bge::RayAllRec>& rec)
+{
+    HIP_TRY(w->ray_all_count.ensure(4));
+    p.all_count = w->ray_all_count.as<uint32_t>();
+    uint32_t found = 0;
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        const uint64_t want = std::max<uint64_t>({w->ray_all_cap, 4096u, 4ull * p.n_rays});
+        if (want > 0x7fffffffull) return fail(BGE_ERR_OOM, "ray hit list of %llu records", (unsigned long long)want);
+        HIP_TRY(w->ray_all.ensure(want * sizeof(bge::RayAllRec)));
+        w->ray_all_cap = static_cast<uint32_t>(want);
+        p.all = w->ray_all.as<bge::RayAllRec>();
+        p.all_cap = w->ray_all_cap;
+        HIP_TRY(hipMemsetAsync(w->ray_all_count.p, 0, 4, w->stream));
+        HIP_TRY(launch(w->stream, p));
+        HIP_TRY(hipMemcpyAsync(&found, w->ray_all_count.p, 4, hipMemcpyDeviceToHost, w->stream));
+        HIP_TRY(hipStreamSynchronize(w->stream));
+        if (found <= w->ray_all_cap) break;
+        w->ray_all_cap = found;
+    }
+    if (found > w->ray_all_cap) return fail(BGE_ERR_STATE, "ray hit list overflowed twice");
+    rec.resize(found);
+    if (found) {
+        HIP_TRY(hipMemcpyAsync(rec.data(), w->ray_all.p, found * sizeof(bge::RayAllRec), hipMemcpyDeviceToHost, w->stream));
+        HIP_TRY(hipStreamSynchronize(w->stream));
+    }
+    auto key = [by_fraction](const bge::RayAllRec& r) {
+        uint32_t fb = 0;
+        if (by_fraction) std::memcpy(&fb, &r.f, 4);
+        return std::make_pair(static_cast<uint64_t>(r.ray) << 32 | fb, r.code);
+    };
+    std::sort(rec.begin(), rec.end(), [&](const bge::RayAllRec& a, const bge::RayAllRec& b) { return key(a) < key(b); });
+    return BGE_OK;
+}
+
+// offsets[0 .. n] of a sorted list: the records of query i are [offsets[i], offsets[i + 1])
+void ray_offsets(const std::vector<bge::RayAllRec>& rec, uint64_t n, uint64_t* offsets)
+{
+    size_t at = 0;
+    for (uint64_t r = 0; r <= n; ++r) {
+        while (at < rec.size() && rec[at].ray < r) ++at;
+        offsets[r] = at;
+    }
 }
 
 } // namespace
@@ -2901,7 +2951,7 @@ try {
     DeviceGuard guard(w->device);
     bge::RayParams p;
     if (int rc = ray_prepare(w, n_rays, p)) return rc;
-    if (int rc = ray_upload(w, n_rays, rays)) return rc;
+    if (int rc = ray_upload(w, n_rays * sizeof(bge_ray), rays)) return rc;
     HIP_TRY(w->ray_out.ensure(n_rays * sizeof(bge_ray_hit)));
     p.rays = w->ray_in.p;
     p.hits = w->ray_out.p;
@@ -2940,47 +2990,13 @@ try {
     DeviceGuard guard(w->device);
     bge::RayParams p;
     if (int rc = ray_prepare(w, n_rays, p)) return rc;
-    if (int rc = ray_upload(w, n_rays, rays)) return rc;
-    HIP_TRY(w->ray_all_count.ensure(4));
+    if (int rc = ray_upload(w, n_rays * sizeof(bge_ray), rays)) return rc;
     p.rays = w->ray_in.p;
-    p.all_count = w->ray_all_count.as<uint32_t>();
-    uint32_t found = 0;
-    // the list's capacity grows to what a batch found: a second run of the same batch fits
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        const uint64_t want = std::max<uint64_t>({w->ray_all_cap, 4096u, 4 * n_rays});
-        if (want > 0x7fffffffull) return fail(BGE_ERR_OOM, "ray hit list of %llu records", (unsigned long long)want);
-        HIP_TRY(w->ray_all.ensure(want * sizeof(bge::RayAllRec)));
-        w->ray_all_cap = static_cast<uint32_t>(want);
-        p.all = w->ray_all.as<bge::RayAllRec>();
-        p.all_cap = w->ray_all_cap;
-        HIP_TRY(hipMemsetAsync(w->ray_all_count.p, 0, 4, w->stream));
-        HIP_TRY(bge::launch_ray_all(w->stream, p));
-        HIP_TRY(hipMemcpyAsync(&found, w->ray_all_count.p, 4, hipMemcpyDeviceToHost, w->stream));
-        HIP_TRY(hipStreamSynchronize(w->stream));
-        if (found <= w->ray_all_cap) break;
-        w->ray_all_cap = found;
-    }
-    if (found > w->ray_all_cap) return fail(BGE_ERR_STATE, "ray hit list overflowed twice");
-    std::vector<bge::RayAllRec> rec(found);
-    if (found) {
-        HIP_TRY(hipMemcpyAsync(rec.data(), w->ray_all.p, found * sizeof(bge::RayAllRec), hipMemcpyDeviceToHost, w->stream));
-        HIP_TRY(hipStreamSynchronize(w->stream));
-    }
-    // each ray's segment in (f, object code) order; the key is a total order, so the result does not depend on append order
-    auto key = [](const bge::RayAllRec& r) {
-        uint32_t fb;
-        std::memcpy(&fb, &r.f, 4);
-        return std::make_pair(static_cast<uint64_t>(r.ray) << 32 | fb, r.code);
-    };
-    std::sort(rec.begin(), rec.end(), [&](const bge::RayAllRec& a, const bge::RayAllRec& b) { return key(a) < key(b); });
+    std::vector<bge::RayAllRec> rec;
+    if (int rc = ray_collect(w, p, bge::launch_ray_all, true, rec)) return rc;
+    const uint32_t found = static_cast<uint32_t>(rec.size());
     *total = found;
-    if (offsets) {
-        size_t at = 0;
-        for (uint64_t r = 0; r <= n_rays; ++r) {
-            while (at < rec.size() && rec[at].ray < r) ++at;
-            offsets[r] = at;
-        }
-    }
+    if (offsets) ray_offsets(rec, n_rays, offsets);
     if (!hits) return BGE_OK;
     if (cap < found) return fail(BGE_ERR_INVALID, "raycast_all: %u hits, room for %llu", found, (unsigned long long)cap);
     for (size_t i = 0; i < rec.size(); ++i) {
@@ -3001,6 +3017,118 @@ try {
     return BGE_OK;
 }
 BGE_CATCH_ALL("bge_world_raycast_all")
+
+// ---------------------------------------------------------------- sphere queries (bge_spherecast.hip)
+static_assert(sizeof(bge_sphere_cast) == 40, "bge_sphere_cast is 40 bytes (include/bge_world.h)");
+static_assert(sizeof(bge_sphere) == 20, "bge_sphere is 20 bytes (include/bge_world.h)");
+static_assert(sizeof(bge_overlap_hit) == 12, "bge_overlap_hit is 12 bytes (include/bge_world.h)");
+
+int bge_world_sphere_cast(bge_world* w, uint64_t n, const bge_sphere_cast* casts, bge_ray_hit* hits)
+try {
+    if (!w) return fail(BGE_ERR_INVALID, "world is NULL");
+    if (n == 0) return BGE_OK;
+    if (!casts || !hits) return fail(BGE_ERR_INVALID, "NULL argument");
+    DeviceGuard guard(w->device);
+    bge::RayParams p;
+    if (int rc = ray_prepare(w, n, p)) return rc;
+    if (int rc = ray_upload(w, n * sizeof(bge_sphere_cast), casts)) return rc;
+    HIP_TRY(w->ray_out.ensure(n * sizeof(bge_ray_hit)));
+    p.rays = w->ray_in.p;
+    p.hits = w->ray_out.p;
+    HIP_TRY(bge::launch_sphere_cast_closest(w->stream, p));
+    HIP_TRY(hipMemcpyAsync(hits, w->ray_out.p, n * sizeof(bge_ray_hit), hipMemcpyDeviceToHost, w->stream));
+    HIP_TRY(hipStreamSynchronize(w->stream));
+    return BGE_OK;
+}
+BGE_CATCH_ALL("bge_world_sphere_cast")
+
+int bge_world_sphere_cast_device(bge_world* w, uint64_t n, const void* casts_device, void* hits_device)
+try {
+    if (!w) return fail(BGE_ERR_INVALID, "world is NULL");
+    if (n == 0) return BGE_OK;
+    if (!casts_device || !hits_device) return fail(BGE_ERR_INVALID, "NULL argument");
+    DeviceGuard guard(w->device);
+    bge::RayParams p;
+    if (int rc = ray_prepare(w, n, p)) return rc;
+    p.rays = casts_device;
+    p.hits = hits_device;
+    HIP_TRY(bge::launch_sphere_cast_closest(w->stream, p));
+    return BGE_OK;
+}
+BGE_CATCH_ALL("bge_world_sphere_cast_device")
+
+int bge_world_sphere_cast_all(bge_world* w, uint64_t n, const bge_sphere_cast* casts, bge_ray_hit* hits, uint64_t cap, uint64_t* offsets,
+                              uint64_t* total)
+try {
+    if (!w || !total) return fail(BGE_ERR_INVALID, "NULL argument");
+    *total = 0;
+    if (n == 0) {
+        if (offsets) offsets[0] = 0;
+        return BGE_OK;
+    }
+    if (!casts) return fail(BGE_ERR_INVALID, "casts is NULL");
+    DeviceGuard guard(w->device);
+    bge::RayParams p;
+    if (int rc = ray_prepare(w, n, p)) return rc;
+    if (int rc = ray_upload(w, n * sizeof(bge_sphere_cast), casts)) return rc;
+    p.rays = w->ray_in.p;
+    std::vector<bge::RayAllRec> rec;
+    if (int rc = ray_collect(w, p, bge::launch_sphere_cast_all, true, rec)) return rc;
+    *total = rec.size();
+    if (offsets) ray_offsets(rec, n, offsets);
+    if (!hits) return BGE_OK;
+    if (cap < rec.size()) return fail(BGE_ERR_INVALID, "sphere_cast_all: %zu hits, room for %llu", rec.size(), (unsigned long long)cap);
+    for (size_t i = 0; i < rec.size(); ++i) {
+        const bge::RayAllRec& r = rec[i];
+        const bge_sphere_cast& c = casts[r.ray];
+        bge_ray_hit& h = hits[i];
+        const uint32_t kind = r.code >> 30;
+        h.kind = kind == 0u ? BGE_RAY_BODY : (kind == 1u ? BGE_RAY_TRIGGER : BGE_RAY_GROUND);
+        h.entity = kind == 2u ? BGE_RAY_NO_ENTITY : (r.code & bge::kRayEntityMask);
+        h.fraction = r.f;
+        h.distance = r.f * c.max_distance;
+        for (int a = 0; a < 3; ++a) {
+            const float delta = c.direction[a] * c.max_distance; // the device's arithmetic (bge_spherecast.hip cast_prep, k_cast_finish)
+            const float centre = c.origin[a] + delta * r.f;
+            h.point[a] = centre - c.radius * r.n[a];
+            h.normal[a] = r.n[a];
+        }
+        if (kind == 2u) h.point[1] = 0.0f;
+    }
+    return BGE_OK;
+}
+BGE_CATCH_ALL("bge_world_sphere_cast_all")
+
+int bge_world_overlap_sphere(bge_world* w, uint64_t n, const bge_sphere* spheres, bge_overlap_hit* hits, uint64_t cap, uint64_t* offsets,
+                             uint64_t* total)
+try {
+    if (!w || !total) return fail(BGE_ERR_INVALID, "NULL argument");
+    *total = 0;
+    if (n == 0) {
+        if (offsets) offsets[0] = 0;
+        return BGE_OK;
+    }
+    if (!spheres) return fail(BGE_ERR_INVALID, "spheres is NULL");
+    DeviceGuard guard(w->device);
+    bge::RayParams p;
+    if (int rc = ray_prepare(w, n, p)) return rc;
+    if (int rc = ray_upload(w, n * sizeof(bge_sphere), spheres)) return rc;
+    p.rays = w->ray_in.p;
+    std::vector<bge::RayAllRec> rec;
+    if (int rc = ray_collect(w, p, bge::launch_sphere_overlap, false, rec)) return rc;
+    *total = rec.size();
+    if (offsets) ray_offsets(rec, n, offsets);
+    if (!hits) return BGE_OK;
+    if (cap < rec.size()) return fail(BGE_ERR_INVALID, "overlap_sphere: %zu hits, room for %llu", rec.size(), (unsigned long long)cap);
+    for (size_t i = 0; i < rec.size(); ++i) {
+        const uint32_t kind = rec[i].code >> 30;
+        hits[i].kind = kind == 0u ? BGE_RAY_BODY : (kind == 1u ? BGE_RAY_TRIGGER : BGE_RAY_GROUND);
+        hits[i].entity = kind == 2u ? BGE_RAY_NO_ENTITY : (rec[i].code & bge::kRayEntityMask);
+        hits[i].distance = rec[i].f;
+    }
+    return BGE_OK;
+}
+BGE_CATCH_ALL("bge_world_overlap_sphere")
 
 // ---------------------------------------------------------------- debug overlay (bge_debug.hip)
 static_assert(sizeof(bge_debug_line) == 28, "bge_debug_line is 28 bytes (include/bge_world.h)");

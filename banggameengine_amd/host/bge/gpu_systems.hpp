@@ -55,6 +55,13 @@
 namespace bge {
 
 // Trigger events as PhysicsSystem publishes them on its EventBus (src/physics/PhysicsSystem.h:50-62)
+// One object GpuPhysicsSystem::OverlapSphere found (an extension: the reference has no such query)
+struct GpuOverlapHit {
+    uint32_t entity = 0;   // EntityId of the body or trigger; kInvalidEntity (0) for the ground plane
+    bool trigger = false;  // a trigger ghost, not a rigid body
+    float distance = 0.0f; // from the sphere's centre to the shape, 0 when the centre is inside it
+};
+
 struct GpuTriggerEvent {
     enum class Type { Enter, Stay, Exit };
     Type type = Type::Enter;
@@ -279,6 +286,70 @@ public:
         hits.resize(total);
         for (uint64_t i = 0; i < total; ++i) FillHit(ray_hits_[i], hits[i]);
         return hits;
+    }
+
+    // EXTENSIONS without a reference counterpart: a sphere swept along origin + direction * maxDistance and a sphere at rest
+    // against the world the ray queries see (include/bge_world.h "Sphere queries") — the two primitives of a character
+    // controller.  HitT as for Raycast: point is the contact point on the shape, normal points from it to the sphere's centre.
+    template <class Vec3, class HitT>
+    bool SphereCast(const Vec3& origin, const Vec3& direction, float maxDistance, float radius, uint32_t layerMask, HitT& outHit)
+    {
+        if (!ok() || !(maxDistance > 0.0f) || !(radius >= 0.0f) || layerMask == 0u) return false;
+        const bge_sphere_cast cast = MakeCast(origin, direction, maxDistance, radius, layerMask);
+        bge_ray_hit h{};
+        if (bge_world_sphere_cast(world_, 1, &cast, &h) != BGE_OK) return Log("bge_world_sphere_cast");
+        if (h.kind == BGE_RAY_MISS) return false;
+        FillHit(h, outHit);
+        return true;
+    }
+    template <class HitT, class Vec3>
+    std::vector<HitT> SphereCastAll(const Vec3& origin, const Vec3& direction, float maxDistance, float radius, uint32_t layerMask)
+    {
+        std::vector<HitT> hits;
+        if (!ok() || !(maxDistance > 0.0f) || !(radius >= 0.0f) || layerMask == 0u) return hits;
+        const bge_sphere_cast cast = MakeCast(origin, direction, maxDistance, radius, layerMask);
+        uint64_t total = 0;
+        if (bge_world_sphere_cast_all(world_, 1, &cast, nullptr, 0, nullptr, &total) != BGE_OK) {
+            Log("bge_world_sphere_cast_all");
+            return hits;
+        }
+        ray_hits_.resize(total);
+        if (total && bge_world_sphere_cast_all(world_, 1, &cast, ray_hits_.data(), total, nullptr, &total) != BGE_OK) {
+            Log("bge_world_sphere_cast_all");
+            return hits;
+        }
+        hits.resize(total);
+        for (uint64_t i = 0; i < total; ++i) FillHit(ray_hits_[i], hits[i]);
+        return hits;
+    }
+    // every object within radius of center: bodies in ascending entity index, then trigger ghosts, then the plane
+    template <class Vec3> std::vector<GpuOverlapHit> OverlapSphere(const Vec3& center, float radius, uint32_t layerMask)
+    {
+        std::vector<GpuOverlapHit> out;
+        if (!ok() || !(radius >= 0.0f) || layerMask == 0u) return out;
+        bge_sphere s{};
+        s.center[0] = center.x, s.center[1] = center.y, s.center[2] = center.z;
+        s.radius = radius;
+        s.layer_mask = layerMask;
+        uint64_t total = 0;
+        if (bge_world_overlap_sphere(world_, 1, &s, nullptr, 0, nullptr, &total) != BGE_OK) {
+            Log("bge_world_overlap_sphere");
+            return out;
+        }
+        overlap_hits_.resize(total);
+        if (total && bge_world_overlap_sphere(world_, 1, &s, overlap_hits_.data(), total, nullptr, &total) != BGE_OK) {
+            Log("bge_world_overlap_sphere");
+            return out;
+        }
+        out.resize(total);
+        for (uint64_t i = 0; i < total; ++i) {
+            const bge_overlap_hit& h = overlap_hits_[i];
+            const bool has = h.entity != BGE_RAY_NO_ENTITY && h.entity < ids_.size();
+            out[i].entity = has ? ids_[h.entity] : Id{0};
+            out[i].trigger = h.kind == BGE_RAY_TRIGGER;
+            out[i].distance = h.distance;
+        }
+        return out;
     }
 
     // CollectDebugLines + debugDrawWorld(DBG_DrawContactPoints) (PhysicsSystem.cpp:857-873, 1148-1175) on the device world as
@@ -715,7 +786,18 @@ private:
     std::vector<bge_trigger_event> raw_events_;
     std::vector<GpuTriggerEvent> trigger_events_;
     std::vector<bge_ray_hit> ray_hits_;
+    std::vector<bge_overlap_hit> overlap_hits_;
 
+    template <class Vec3> static bge_sphere_cast MakeCast(const Vec3& o, const Vec3& d, float maxDistance, float radius, uint32_t layerMask)
+    {
+        bge_sphere_cast c{};
+        c.origin[0] = o.x, c.origin[1] = o.y, c.origin[2] = o.z;
+        c.direction[0] = d.x, c.direction[1] = d.y, c.direction[2] = d.z;
+        c.max_distance = maxDistance;
+        c.radius = radius;
+        c.layer_mask = layerMask;
+        return c;
+    }
     template <class Vec3> static bge_ray MakeRay(const Vec3& o, const Vec3& d, float maxDistance, uint32_t layerMask)
     {
         bge_ray r{};
@@ -842,6 +924,25 @@ public:
     {
         if (!lastScene_) return {};
         return GpuMirrors<SceneT>::Of(*lastScene_).template RaycastAll<HitT>(origin, direction, maxDistance, layerMask);
+    }
+
+    // EXTENSIONS, not in the reference's PhysicsSystem: sphere casts and a sphere overlap against the same world, under the same
+    // call order as Raycast (include/bge_world.h "Sphere queries"); false / empty before the first Update.
+    template <class Vec3, class HitT>
+    bool SphereCast(const Vec3& origin, const Vec3& direction, float maxDistance, float radius, uint32_t layerMask, HitT& outHit) const
+    {
+        return lastScene_ && GpuMirrors<SceneT>::Of(*lastScene_).SphereCast(origin, direction, maxDistance, radius, layerMask, outHit);
+    }
+    template <class HitT, class Vec3>
+    std::vector<HitT> SphereCastAll(const Vec3& origin, const Vec3& direction, float maxDistance, float radius, uint32_t layerMask) const
+    {
+        if (!lastScene_) return {};
+        return GpuMirrors<SceneT>::Of(*lastScene_).template SphereCastAll<HitT>(origin, direction, maxDistance, radius, layerMask);
+    }
+    template <class Vec3> std::vector<GpuOverlapHit> OverlapSphere(const Vec3& center, float radius, uint32_t layerMask) const
+    {
+        if (!lastScene_) return {};
+        return GpuMirrors<SceneT>::Of(*lastScene_).OverlapSphere(center, radius, layerMask);
     }
 
     // The debug overlay (src/physics/PhysicsSystem.h:77-82, bound to a key at src/core/Application.cpp:173; the renderer gets

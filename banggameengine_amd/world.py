@@ -43,6 +43,34 @@ def _hit_fields(h):
             "distance": h["distance"].copy(), "point": h["point"].copy(), "normal": h["normal"].copy()}
 
 
+# sphere queries (bge_world_sphere_cast*, bge_world_overlap_sphere): their records; a cast's hit is a RAY_HIT_DTYPE record
+SPHERE_CAST_DTYPE = np.dtype([("origin", "<f4", (3,)), ("direction", "<f4", (3,)), ("max_distance", "<f4"), ("radius", "<f4"),
+                              ("layer_mask", "<u4"), ("reserved", "<u4")])
+SPHERE_DTYPE = np.dtype([("center", "<f4", (3,)), ("radius", "<f4"), ("layer_mask", "<u4")])
+OVERLAP_HIT_DTYPE = np.dtype([("kind", "<u4"), ("entity", "<u4"), ("distance", "<f4")])
+assert SPHERE_CAST_DTYPE.itemsize == 40 and SPHERE_DTYPE.itemsize == 20 and OVERLAP_HIT_DTYPE.itemsize == 12
+
+
+def make_sphere_casts(origins, directions, max_distance=200.0, radius=0.5, layer_mask=0xFFFFFFFF):
+    """bge_sphere_cast records: make_rays() plus the radius, a scalar or one value per cast."""
+    rays = make_rays(origins, directions, max_distance, layer_mask)
+    casts = np.zeros(len(rays), SPHERE_CAST_DTYPE)
+    for k in ("origin", "direction", "max_distance", "layer_mask"):
+        casts[k] = rays[k]
+    casts["radius"] = np.broadcast_to(np.asarray(radius, np.float32), (len(rays),))
+    return casts
+
+
+def make_spheres(centers, radius, layer_mask=0xFFFFFFFF):
+    """bge_sphere records: centers (n, 3); radius and layer_mask a scalar or one value per sphere."""
+    c = np.ascontiguousarray(centers, np.float32).reshape(-1, 3)
+    spheres = np.zeros(len(c), SPHERE_DTYPE)
+    spheres["center"] = c
+    spheres["radius"] = np.broadcast_to(np.asarray(radius, np.float32), (len(c),))
+    spheres["layer_mask"] = np.broadcast_to(np.asarray(layer_mask, np.uint64).astype(np.uint32), (len(c),))
+    return spheres
+
+
 # debug overlay (bge_world_debug_lines*): bge_debug_flags and the 28-byte line record
 DEBUG_SHAPES, DEBUG_CONTACTS, DEBUG_ALL = 1, 2, 3
 DEBUG_LINE_DTYPE = np.dtype([("from", "<f4", (3,)), ("to", "<f4", (3,)), ("abgr", "<u4")])
@@ -389,6 +417,53 @@ class World:
         if not (rays.is_cuda and hits.is_cuda and rays.is_contiguous() and hits.is_contiguous()):
             raise ValueError("rays and hits must be contiguous device tensors")
         check(lib().bge_world_raycast_device(self._h, n, C.c_void_p(rays.data_ptr()), C.c_void_p(hits.data_ptr())))
+
+    # -- sphere queries (not in the reference; include/bge_world.h states what a sphere touches and where)
+    def sphere_cast(self, origins, directions, max_distance=200.0, radius=0.5, layer_mask=0xFFFFFFFF):
+        """Closest touch per sphere cast: the dict raycast() returns; point is the contact point on the shape, normal points
+        from it to the sphere's centre.  max_distance, radius and layer_mask take a scalar or one value per cast."""
+        casts = make_sphere_casts(origins, directions, max_distance, radius, layer_mask)
+        hits = np.zeros(len(casts), RAY_HIT_DTYPE)
+        check(lib().bge_world_sphere_cast(self._h, len(casts), _p(casts), _p(hits)))
+        return _hit_fields(hits)
+
+    def sphere_cast_all(self, origins, directions, max_distance=200.0, radius=0.5, layer_mask=0xFFFFFFFF):
+        """Every touch per cast: the arrays of sphere_cast() over all hits plus offsets (n + 1), as raycast_all()."""
+        casts = make_sphere_casts(origins, directions, max_distance, radius, layer_mask)
+        total = C.c_uint64(0)
+        offsets = np.zeros(len(casts) + 1, np.uint64)
+        check(lib().bge_world_sphere_cast_all(self._h, len(casts), _p(casts), None, 0, _p(offsets), C.byref(total)))
+        hits = np.zeros(max(int(total.value), 1), RAY_HIT_DTYPE)
+        check(lib().bge_world_sphere_cast_all(self._h, len(casts), _p(casts), _p(hits), len(hits), _p(offsets), C.byref(total)))
+        out = _hit_fields(hits[:int(total.value)])
+        out["offsets"] = offsets
+        return out
+
+    def sphere_cast_device(self, casts, hits):
+        """Closest touch per cast between device tensors: casts holds n bge_sphere_cast records (40 bytes each, e.g. a uint8
+        tensor made from make_sphere_casts()), hits room for n bge_ray_hit records (40 bytes each).  Enqueued on the world's
+        stream without synchronisation, as raycast_device()."""
+        nb = casts.numel() * casts.element_size()
+        if nb % 40:
+            raise ValueError(f"casts holds {nb} bytes, not a whole number of 40-byte records")
+        n = nb // 40
+        if hits.numel() * hits.element_size() < 40 * n:
+            raise ValueError(f"hits has room for {hits.numel() * hits.element_size()} bytes, {40 * n} needed")
+        if not (casts.is_cuda and hits.is_cuda and casts.is_contiguous() and hits.is_contiguous()):
+            raise ValueError("casts and hits must be contiguous device tensors")
+        check(lib().bge_world_sphere_cast_device(self._h, n, C.c_void_p(casts.data_ptr()), C.c_void_p(hits.data_ptr())))
+
+    def overlap_sphere(self, centers, radius, layer_mask=0xFFFFFFFF):
+        """Every object within radius of each centre: dict of kind, entity, distance (0 inside the shape) over all hits plus
+        offsets (n + 1); sphere i's objects are [offsets[i], offsets[i + 1]), bodies by entity, then ghosts, then the plane."""
+        spheres = make_spheres(centers, radius, layer_mask)
+        total = C.c_uint64(0)
+        offsets = np.zeros(len(spheres) + 1, np.uint64)
+        check(lib().bge_world_overlap_sphere(self._h, len(spheres), _p(spheres), None, 0, _p(offsets), C.byref(total)))
+        hits = np.zeros(max(int(total.value), 1), OVERLAP_HIT_DTYPE)
+        check(lib().bge_world_overlap_sphere(self._h, len(spheres), _p(spheres), _p(hits), len(hits), _p(offsets), C.byref(total)))
+        hits = hits[:int(total.value)]
+        return {"kind": hits["kind"].copy(), "entity": hits["entity"].copy(), "distance": hits["distance"].copy(), "offsets": offsets}
 
     # -- debug overlay (PhysicsSystem::GetDebugLines; include/bge_world.h states what is drawn and in which order)
     def debug_lines(self, flags=DEBUG_ALL, region=None):

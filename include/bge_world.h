@@ -441,6 +441,66 @@ BGE_API int bge_world_raycast_all(bge_world* world, uint64_t n_rays, const bge_r
 BGE_API int bge_world_raycast_device(bge_world* world, uint64_t n_rays, const void* rays_device, void* hits_device);
 
 /*
+ * Sphere queries: a sphere swept along a segment (cast) and a sphere at rest (overlap) against the world the ray queries see, for a
+ * batch at once.  NOT in the reference's PhysicsSystem: they are the two primitives its btKinematicCharacterController is made of
+ * (a convex sweep, an overlap test; src/physics/PhysicsSystem.cpp:762) for the one shape that is exact in closed form against
+ * every shape of the world.  The rules below are the specification.
+ *   Objects, poses, Filter, tie order, Call order   those of the ray queries above, word for word: every rigid body in the world
+ *             at the pose the last physics tick left, every live posed trigger ghost, the plane when it is on; an object is a
+ *             candidate when (objGroup & layer_mask) != 0 && objMask != 0; object code = bodies by entity index, then ghosts by
+ *             entity index, then the plane.
+ *   Distance  dist(c, S) is the Euclidean distance from the point c to the solid shape S, 0 inside it.  Box: the sharp box of its
+ *             half extents with margin (as for rays).  Capsule: the points within its radius R of its Y segment, so
+ *             dist = max(0, |c - closest point of the segment| - R).  Plane: |c.y|.
+ *   Cast      the centre moves along c(f) = origin + direction * max_distance * f, f in [0, 1] (direction is not normalised).
+ *             Object S is hit at the smallest f with dist(c(f), S) = radius, provided dist(c(0), S) > radius: a sphere that
+ *             STARTS TOUCHING OR OVERLAPPING a shape does not hit that shape (the ray rule "starts inside or on";
+ *             bge_world_overlap_sphere finds those).  Said otherwise, the ray of the centre against the shape grown by radius: a
+ *             capsule of radius R + radius; the ROUNDED box (sharp box + ball); the planes y = +-radius (from above: hit iff
+ *             origin.y > radius and end.y < radius, f = (origin.y - radius) / (origin.y - end.y); mirrored from below;
+ *             |origin.y| <= radius hits nothing).
+ *   Hit       the record is bge_ray_hit: fraction = f, distance = f * max_distance (the ray definition), point = the point of S
+ *             closest to c(f) (the contact point on the surface), normal = normalise(c(f) - point): on a box face the face
+ *             normal, on an edge or a corner the rounded direction; for the plane point = (c.x, 0, c.z), normal +-y.
+ *   No hit    the ray conditions (!(max_distance > 0), layer_mask == 0, direction == (0, 0, 0), any input not finite) and
+ *             !(radius >= 0).  radius == 0 is a legal cast; it agrees with the ray query to rounding (not bit for bit: on an exact
+ *             edge hit the box normal is defined differently).
+ *   Closest   smallest f, ties to the lowest object code.   All hits: one record per object, each cast's list in (f, object code) order.
+ *   Overlap   object S is reported iff dist(center, S) <= radius (plane: |center.y| <= radius), with that distance; each sphere's
+ *             list in ascending object code.  A sphere with a non-finite input, radius < 0 or layer_mask == 0 reports nothing.
+ *   bge_world_sphere_cast         hits[i] for casts[i]; a miss as for bge_world_raycast.  Synchronises the world's stream.
+ *   bge_world_sphere_cast_all     count / cap / offsets / hits = NULL / BGE_ERR_INVALID when cap < *total: as bge_world_raycast_all.
+ *   bge_world_sphere_cast_device  device pointers: casts_device = bge_sphere_cast[n], hits_device = bge_ray_hit[n]; enqueued on the
+ *                                 world's stream, no synchronisation.
+ *   bge_world_overlap_sphere      the list convention of bge_world_raycast_all with bge_overlap_hit records.
+ *   n = 0 is a no-op.  The entity indices of the world must stay below 2^30.
+ */
+typedef struct bge_sphere_cast {
+    float origin[3];
+    float direction[3];
+    float max_distance;
+    float radius;
+    uint32_t layer_mask;
+    uint32_t reserved; /* 0 */
+} bge_sphere_cast; /* 40 bytes */
+typedef struct bge_sphere {
+    float center[3];
+    float radius;
+    uint32_t layer_mask;
+} bge_sphere; /* 20 bytes */
+typedef struct bge_overlap_hit {
+    uint32_t kind;   /* bge_ray_kind: BGE_RAY_BODY, BGE_RAY_TRIGGER or BGE_RAY_GROUND */
+    uint32_t entity; /* entity index of the body or trigger; BGE_RAY_NO_ENTITY for the plane */
+    float distance;  /* from the centre to the shape, 0 when the centre is inside it */
+} bge_overlap_hit; /* 12 bytes */
+BGE_API int bge_world_sphere_cast(bge_world* world, uint64_t n, const bge_sphere_cast* casts, bge_ray_hit* hits);
+BGE_API int bge_world_sphere_cast_all(bge_world* world, uint64_t n, const bge_sphere_cast* casts, bge_ray_hit* hits, uint64_t cap,
+                                      uint64_t* offsets, uint64_t* total);
+BGE_API int bge_world_sphere_cast_device(bge_world* world, uint64_t n, const void* casts_device, void* hits_device);
+BGE_API int bge_world_overlap_sphere(bge_world* world, uint64_t n, const bge_sphere* spheres, bge_overlap_hit* hits, uint64_t cap,
+                                     uint64_t* offsets, uint64_t* total);
+
+/*
  * The physics debug overlay: what PhysicsSystem::GetDebugLines hands to the renderer while the overlay is on
  * (src/physics/PhysicsSystem.cpp:857-873, 1148-1175; src/physics/BulletDebugDrawer.cpp) — every collision object's shape as
  * wireframe lines in one colour, then one short red line per contact point — made on the device from the state the last tick
