@@ -95,7 +95,7 @@ __device__ __forceinline__ uint32_t load_item(const DebugParams& p, uint64_t it,
     }
     const uint64_t g = e - p.n_entities;
     if (g >= p.n_ghosts) return 0u;
-    const RayGhost gh = p.ghosts[g];
+    const QueryGhost gh = p.ghosts[g];
     const float* pose = p.ghost_pose + 8ull * gh.trigger;
     d.o = F3{pose[0], pose[1], pose[2]};
     if (!in_region(p, d.o)) return 0u;

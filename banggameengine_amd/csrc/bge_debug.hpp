@@ -6,7 +6,7 @@
 
 #include <cstdint>
 
-#include "bge_raycast.hpp"
+#include "bge_query.hpp"
 
 namespace bge {
 
@@ -25,8 +25,8 @@ struct DebugParams {
     const float* quat;
     const float4* cshape;
     const uint32_t* cinfo;
-    // ghosts (the list the ray queries see, in the order of the uploaded trigger array) and the plane
-    const RayGhost* ghosts;
+    // ghosts (the list the queries see, in the order of the uploaded trigger array) and the plane
+    const QueryGhost* ghosts;
     uint32_t n_ghosts;
     const float* ghost_pose;        // [triggers][8]
     uint32_t plane;

@@ -1,4 +1,4 @@
-// bge_ray_device.hpp — exact ray tests of the ray queries (bge_raycast.hip): ray / box by slabs in the box frame, ray / capsule,
+// bge_ray_device.hpp — exact ray tests of the ray queries (bge_query.hip): ray / box by slabs in the box frame, ray / capsule,
 // ray / plane.  A ray is the segment from + delta * f, f in [0, 1] (delta = direction * max_distance, include/bge_world.h).
 // Every function returns the fraction of the first entry into the shape, or -1 for no hit; a segment that starts inside or on
 // the shape does not hit it (the stated rule of include/bge_world.h).  Built with the library's -ffp-contract=off: the same

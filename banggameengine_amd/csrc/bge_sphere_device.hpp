@@ -1,4 +1,4 @@
-// bge_sphere_device.hpp — exact tests of the sphere queries (bge_spherecast.hip): closest points of a box and a capsule, and a
+// bge_sphere_device.hpp — exact tests of the sphere queries (bge_query.hip): closest points of a box and a capsule, and a
 // moving sphere against them.  A sphere of radius r whose centre moves along o + d * f, f in [0, 1], touches a shape where the
 // centre's ray enters the shape grown by r: a capsule of radius R + r, the ROUNDED box (sharp box + ball), the planes y = +-r.
 // Every cast returns the fraction of the first touch, or -1; a sphere that starts touching or overlapping the shape does not

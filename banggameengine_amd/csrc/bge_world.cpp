@@ -26,8 +26,7 @@
 #include "bge_debug.hpp"
 #include "bge_flatten.hpp"
 #include "bge_kernels.hpp"
-#include "bge_raycast.hpp"
-#include "bge_spherecast.hpp"
+#include "bge_query.hpp"
 
 namespace {
 
@@ -286,12 +285,12 @@ struct bge_world {
     bool trig_list_on_device = false; // the device arrays are indexed like `triggers` (false between an upload of the list and the next sync)
     DevBuf trig_slot, trig_entity, trig_he, trig_group, trig_mask, trig_active, trig_aabb, trig_pairs, trig_count, trig_lists;
     DevBuf trig_pose; // [triggers][8] ghost pose written beside the box by k_trigger_aabb (ray queries)
-    // ray queries (bge_raycast.hip): staging for the host entry points, the per-ray keys (all ones between calls), the all-hits
-    // list, and the ghosts the rays see (rebuilt from `triggers` per query, uploaded when it changed)
-    DevBuf ray_in, ray_out, ray_keys, ray_all, ray_all_count, ray_ghosts;
-    uint64_t ray_keys_n = 0;
-    uint32_t ray_all_cap = 0;
-    std::vector<bge::RayGhost> ray_ghosts_host, ray_ghosts_dev;
+    // queries (bge_query.hip): staging for the host entry points, the per-query keys (all ones between calls), the all-hits
+    // list, and the ghosts the queries see (rebuilt from `triggers` per query, uploaded when it changed)
+    DevBuf query_in, query_out, query_keys, query_all, query_all_count, query_ghosts;
+    uint64_t query_keys_n = 0;
+    uint32_t query_all_cap = 0;
+    std::vector<bge::QueryGhost> query_ghosts_host, query_ghosts_dev;
     // debug overlay (bge_debug.hip): per-workgroup line counts and their offsets, the host entry point's line buffer and total
     DevBuf dbg_block_sum, dbg_block_off, dbg_lines, dbg_total;
     uint32_t trigger_grid_min = 64;       // more ghosts than this: the broadphase grid answers for the small ones
@@ -374,7 +373,7 @@ struct bge_world {
                           &angvel, &quat, &inv_mass, &half_extent, &group, &mask, &aabb, &root_worlds, &counter, &stage,
                           &stage2, &mass_palette, &normal, &deact, &filter_class, &filter_table, &grav_palette, &bp_partials, &cshape, &cmass, &cfriction, &cinfo, &manifold, &crestitution, &bmanifold, &obstacle_slots, &obstacle_gen, &obstacles, &obstacle_grid, &box_list, &box_count, &frozen, &rs_word, &trig_slot, &trig_entity, &trig_he, &trig_group,
                           &trig_mask, &trig_active, &trig_aabb, &trig_pairs, &trig_count, &trig_lists, &ground_list, &ground_count, &trig_tab[0], &trig_tab[1],
-                          &trig_delta_dev, &trig_keys_dev, &trig_pose, &ray_in, &ray_out, &ray_keys, &ray_all, &ray_all_count, &ray_ghosts, &dbg_block_sum, &dbg_block_off,
+                          &trig_delta_dev, &trig_keys_dev, &trig_pose, &query_in, &query_out, &query_keys, &query_all, &query_all_count, &query_ghosts, &dbg_block_sum, &dbg_block_off,
                           &dbg_lines, &dbg_total}) {
             b->release();
         }
@@ -2805,23 +2804,27 @@ try {
 }
 BGE_CATCH_ALL("bge_world_trigger_query_stats")
 
-// ---------------------------------------------------------------- ray queries (bge_raycast.hip)
+// ---------------------------------------------------------------- queries: rays, sphere casts, sphere overlaps (bge_query.hip)
 static_assert(sizeof(bge_ray) == 32, "bge_ray is 32 bytes (include/bge_world.h)");
 static_assert(sizeof(bge_ray_hit) == 40, "bge_ray_hit is 40 bytes (include/bge_world.h)");
+static_assert(sizeof(bge_sphere_cast) == 40, "bge_sphere_cast is 40 bytes (include/bge_world.h)");
+static_assert(sizeof(bge_sphere) == 20, "bge_sphere is 20 bytes (include/bge_world.h)");
+static_assert(sizeof(bge_overlap_hit) == 12, "bge_overlap_hit is 12 bytes (include/bge_world.h)");
 
 namespace {
 
-// The trigger ghosts that are in the world for a query (ray queries, debug overlay): active, posed by a tick into the device
-// arrays as they are indexed now, in the order of the uploaded trigger array.  The device copy is sent only when the list changed.
+// The trigger ghosts that are in the world for a query (ray and sphere queries, debug overlay): active, posed by a tick into the
+// device arrays as they are indexed now, in the order of the uploaded trigger array.  The device copy is sent only when the list
+// changed.
 int sync_query_ghosts(bge_world* w)
 {
-    std::vector<bge::RayGhost>& gh = w->ray_ghosts_host;
+    std::vector<bge::QueryGhost>& gh = w->query_ghosts_host;
     gh.clear();
     if (w->trig_list_on_device && w->trig_pose.p) {
         for (size_t i = 0; i < w->triggers.size(); ++i) {
             const bge_world::Trigger& t = w->triggers[i];
             if (!t.runtime_active || !(t.posed || t.frozen)) continue;
-            bge::RayGhost g{};
+            bge::QueryGhost g{};
             if (t.shape == BGE_SHAPE_CAPSULE) {
                 g.capsule = 1u;
                 g.dims[0] = std::max(t.size[0], 0.01f); // btCapsuleShape(radius, 2 * halfHeight), as for bodies
@@ -2837,13 +2840,13 @@ int sync_query_ghosts(bge_world* w)
             gh.push_back(g);
         }
     }
-    const bool same = gh.size() == w->ray_ghosts_dev.size() &&
-                      (gh.empty() || std::memcmp(gh.data(), w->ray_ghosts_dev.data(), gh.size() * sizeof(bge::RayGhost)) == 0);
+    const bool same = gh.size() == w->query_ghosts_dev.size() &&
+                      (gh.empty() || std::memcmp(gh.data(), w->query_ghosts_dev.data(), gh.size() * sizeof(bge::QueryGhost)) == 0);
     if (!same) {
-        w->ray_ghosts_dev = gh;
+        w->query_ghosts_dev = gh;
         if (!gh.empty()) {
-            HIP_TRY(w->ray_ghosts.ensure(gh.size() * sizeof(bge::RayGhost)));
-            HIP_TRY(hipMemcpyAsync(w->ray_ghosts.p, w->ray_ghosts_dev.data(), gh.size() * sizeof(bge::RayGhost), hipMemcpyHostToDevice,
+            HIP_TRY(w->query_ghosts.ensure(gh.size() * sizeof(bge::QueryGhost)));
+            HIP_TRY(hipMemcpyAsync(w->query_ghosts.p, w->query_ghosts_dev.data(), gh.size() * sizeof(bge::QueryGhost), hipMemcpyHostToDevice,
                                    w->stream));
             HIP_TRY(hipStreamSynchronize(w->stream)); // (the list changes when the trigger set does, not per query)
         }
@@ -2851,22 +2854,22 @@ int sync_query_ghosts(bge_world* w)
     return BGE_OK;
 }
 
-// What every ray query needs: the ghosts the rays see, the per-ray keys, the body arrays.
-int ray_prepare(bge_world* w, uint64_t n_rays, bge::RayParams& p)
+// What every query needs: the ghosts the queries see, the per-query keys, the body arrays.
+int query_prepare(bge_world* w, uint64_t n, bge::QueryParams& p)
 {
     if (!w->has_topology) return fail(BGE_ERR_STATE, "bge_world_set_topology has not been called");
-    if (n_rays > 0x7fffffffull) return fail(BGE_ERR_INVALID, "n_rays = %llu: at most 2^31 - 1 rays per batch", (unsigned long long)n_rays);
-    if (w->flat.n_entities > bge::kRayEntityMask) {
+    if (n > 0x7fffffffull) return fail(BGE_ERR_INVALID, "n_rays = %llu: at most 2^31 - 1 rays per batch", (unsigned long long)n);
+    if (w->flat.n_entities > bge::kQueryEntityMask) {
         return fail(BGE_ERR_UNSUPPORTED, "ray queries need entity indices below 2^30 (world has %llu)", (unsigned long long)w->flat.n_entities);
     }
     if (int rc = sync_query_ghosts(w)) return rc;
-    if (n_rays > w->ray_keys_n) {
-        HIP_TRY(w->ray_keys.ensure(n_rays * 8));
-        HIP_TRY(hipMemsetAsync(w->ray_keys.p, 0xff, n_rays * 8, w->stream));
-        w->ray_keys_n = n_rays;
+    if (n > w->query_keys_n) {
+        HIP_TRY(w->query_keys.ensure(n * 8));
+        HIP_TRY(hipMemsetAsync(w->query_keys.p, 0xff, n * 8, w->stream));
+        w->query_keys_n = n;
     }
-    p = bge::RayParams{};
-    p.n_rays = static_cast<uint32_t>(n_rays);
+    p = bge::QueryParams{};
+    p.n_queries = static_cast<uint32_t>(n);
     p.n_slots = w->flat.n_slots;
     p.flags = w->view.flags;
     p.pos = w->view.pos;
@@ -2877,256 +2880,234 @@ int ray_prepare(bge_world* w, uint64_t n_rays, bge::RayParams& p)
     p.mask = w->view.mask;
     p.entity_of_slot = w->entity_of_slot.as<uint32_t>();
     p.slot_of_entity = w->slot_of_entity.as<uint32_t>();
-    p.ghosts = w->ray_ghosts.as<bge::RayGhost>();
-    p.n_ghosts = static_cast<uint32_t>(w->ray_ghosts_dev.size());
+    p.ghosts = w->query_ghosts.as<bge::QueryGhost>();
+    p.n_ghosts = static_cast<uint32_t>(w->query_ghosts_dev.size());
     p.ghost_pose = w->trig_pose.as<float>();
     p.plane = w->ground_plane ? 1u : 0u;
-    p.keys = w->ray_keys.as<unsigned long long>();
+    p.keys = w->query_keys.as<unsigned long long>();
     return BGE_OK;
 }
 
 // the batch's query records (bge_ray, bge_sphere_cast, bge_sphere) into the staging buffer
-int ray_upload(bge_world* w, uint64_t bytes, const void* records)
+int query_upload(bge_world* w, uint64_t bytes, const void* records, bge::QueryParams& p)
 {
-    HIP_TRY(w->ray_in.ensure(bytes));
-    HIP_TRY(hipMemcpyAsync(w->ray_in.p, records, bytes, hipMemcpyHostToDevice, w->stream));
+    HIP_TRY(w->query_in.ensure(bytes));
+    HIP_TRY(hipMemcpyAsync(w->query_in.p, records, bytes, hipMemcpyHostToDevice, w->stream));
+    p.records = w->query_in.p;
     return BGE_OK;
 }
 
-// Runs an all-hits launch (ray_all, sphere_cast_all, sphere_overlap) and brings its list back sorted by query, then by
-// (f, object code) or by object code alone: a total order, so the result does not depend on the order of the appends.  The list's
-// capacity grows to what a batch found: a second run of the same batch fits.
-int ray_collect(bge_world* w, bge::RayParams& p, hipError_t (*launch)(hipStream_t, const bge::RayParams&), bool by_fraction,
-                std::vector<bge::RayAllRec>& rec)
+// Runs an all-hits launch and brings its list back sorted by query, then by (f, object code) or, for the overlap, by object code
+// alone: a total order, so the result does not depend on the order of the appends.  The list's capacity grows to what a batch
+// found: a second run of the same batch fits.
+int query_collect(bge_world* w, bge::QueryKind kind, bge::QueryParams& p, std::vector<bge::QueryRec>& rec)
 {
-    HIP_TRY(w->ray_all_count.ensure(4));
-    p.all_count = w->ray_all_count.as<uint32_t>();
+    HIP_TRY(w->query_all_count.ensure(4));
+    p.all_count = w->query_all_count.as<uint32_t>();
     uint32_t found = 0;
     for (int attempt = 0; attempt < 2; ++attempt) {
-        const uint64_t want = std::max<uint64_t>({w->ray_all_cap, 4096u, 4ull * p.n_rays});
+        const uint64_t want = std::max<uint64_t>({w->query_all_cap, 4096u, 4ull * p.n_queries});
         if (want > 0x7fffffffull) return fail(BGE_ERR_OOM, "ray hit list of %llu records", (unsigned long long)want);
-        HIP_TRY(w->ray_all.ensure(want * sizeof(bge::RayAllRec)));
-        w->ray_all_cap = static_cast<uint32_t>(want);
-        p.all = w->ray_all.as<bge::RayAllRec>();
-        p.all_cap = w->ray_all_cap;
-        HIP_TRY(hipMemsetAsync(w->ray_all_count.p, 0, 4, w->stream));
-        HIP_TRY(launch(w->stream, p));
-        HIP_TRY(hipMemcpyAsync(&found, w->ray_all_count.p, 4, hipMemcpyDeviceToHost, w->stream));
+        HIP_TRY(w->query_all.ensure(want * sizeof(bge::QueryRec)));
+        w->query_all_cap = static_cast<uint32_t>(want);
+        p.all = w->query_all.as<bge::QueryRec>();
+        p.all_cap = w->query_all_cap;
+        HIP_TRY(hipMemsetAsync(w->query_all_count.p, 0, 4, w->stream));
+        HIP_TRY(bge::launch_query(w->stream, kind, p, true));
+        HIP_TRY(hipMemcpyAsync(&found, w->query_all_count.p, 4, hipMemcpyDeviceToHost, w->stream));
         HIP_TRY(hipStreamSynchronize(w->stream));
-        if (found <= w->ray_all_cap) break;
-        w->ray_all_cap = found;
+        if (found <= w->query_all_cap) break;
+        w->query_all_cap = found;
     }
-    if (found > w->ray_all_cap) return fail(BGE_ERR_STATE, "ray hit list overflowed twice");
+    if (found > w->query_all_cap) return fail(BGE_ERR_STATE, "ray hit list overflowed twice");
     rec.resize(found);
     if (found) {
-        HIP_TRY(hipMemcpyAsync(rec.data(), w->ray_all.p, found * sizeof(bge::RayAllRec), hipMemcpyDeviceToHost, w->stream));
+        HIP_TRY(hipMemcpyAsync(rec.data(), w->query_all.p, found * sizeof(bge::QueryRec), hipMemcpyDeviceToHost, w->stream));
         HIP_TRY(hipStreamSynchronize(w->stream));
     }
-    auto key = [by_fraction](const bge::RayAllRec& r) {
+    const bool by_fraction = kind != bge::QueryKind::SphereOverlap;
+    auto key = [by_fraction](const bge::QueryRec& r) {
         uint32_t fb = 0;
         if (by_fraction) std::memcpy(&fb, &r.f, 4);
-        return std::make_pair(static_cast<uint64_t>(r.ray) << 32 | fb, r.code);
+        return std::make_pair(static_cast<uint64_t>(r.query) << 32 | fb, r.code);
     };
-    std::sort(rec.begin(), rec.end(), [&](const bge::RayAllRec& a, const bge::RayAllRec& b) { return key(a) < key(b); });
+    std::sort(rec.begin(), rec.end(), [&](const bge::QueryRec& a, const bge::QueryRec& b) { return key(a) < key(b); });
     return BGE_OK;
 }
 
 // offsets[0 .. n] of a sorted list: the records of query i are [offsets[i], offsets[i + 1])
-void ray_offsets(const std::vector<bge::RayAllRec>& rec, uint64_t n, uint64_t* offsets)
+void query_offsets(const std::vector<bge::QueryRec>& rec, uint64_t n, uint64_t* offsets)
 {
     size_t at = 0;
     for (uint64_t r = 0; r <= n; ++r) {
-        while (at < rec.size() && rec[at].ray < r) ++at;
+        while (at < rec.size() && rec[at].query < r) ++at;
         offsets[r] = at;
     }
 }
+
+// An object code as the public records name it
+void decode_code(uint32_t code, uint32_t& kind, uint32_t& entity)
+{
+    const uint32_t k = code >> 30;
+    kind = k == 0u ? BGE_RAY_BODY : (k == 1u ? BGE_RAY_TRIGGER : BGE_RAY_GROUND);
+    entity = k == 2u ? BGE_RAY_NO_ENTITY : (code & bge::kQueryEntityMask);
+}
+
+// Closest hit per query (rays, sphere casts), host records to host hits
+int query_closest(bge_world* w, bge::QueryKind kind, uint64_t n, size_t record_bytes, const void* records, bge_ray_hit* hits)
+{
+    if (!w) return fail(BGE_ERR_INVALID, "world is NULL");
+    if (n == 0) return BGE_OK;
+    if (!records || !hits) return fail(BGE_ERR_INVALID, "NULL argument");
+    DeviceGuard guard(w->device);
+    bge::QueryParams p;
+    if (int rc = query_prepare(w, n, p)) return rc;
+    if (int rc = query_upload(w, n * record_bytes, records, p)) return rc;
+    HIP_TRY(w->query_out.ensure(n * sizeof(bge_ray_hit)));
+    p.hits = w->query_out.p;
+    HIP_TRY(bge::launch_query(w->stream, kind, p, false));
+    HIP_TRY(hipMemcpyAsync(hits, w->query_out.p, n * sizeof(bge_ray_hit), hipMemcpyDeviceToHost, w->stream));
+    HIP_TRY(hipStreamSynchronize(w->stream));
+    return BGE_OK;
+}
+
+// The same between device buffers, enqueued on the world's stream
+int query_closest_device(bge_world* w, bge::QueryKind kind, uint64_t n, const void* records_device, void* hits_device)
+{
+    if (!w) return fail(BGE_ERR_INVALID, "world is NULL");
+    if (n == 0) return BGE_OK;
+    if (!records_device || !hits_device) return fail(BGE_ERR_INVALID, "NULL argument");
+    DeviceGuard guard(w->device);
+    bge::QueryParams p;
+    if (int rc = query_prepare(w, n, p)) return rc;
+    p.records = records_device;
+    p.hits = hits_device;
+    HIP_TRY(bge::launch_query(w->stream, kind, p, false));
+    return BGE_OK;
+}
+
+// One list entry point: its names in the error texts, its record sizes, and fill(hit, sorted record, the caller's record of its query)
+struct QueryList {
+    bge::QueryKind kind;
+    const char* what;
+    const char* records_name;
+    size_t record_bytes, hit_bytes;
+    void (*fill)(void* hit, const bge::QueryRec& r, const void* record);
+};
+
+// Every hit per query: *total and offsets always, the hits when there is room for them
+int query_list(bge_world* w, const QueryList& q, uint64_t n, const void* records, void* hits, uint64_t cap, uint64_t* offsets, uint64_t* total)
+{
+    if (!w || !total) return fail(BGE_ERR_INVALID, "NULL argument");
+    *total = 0;
+    if (n == 0) {
+        if (offsets) offsets[0] = 0;
+        return BGE_OK;
+    }
+    if (!records) return fail(BGE_ERR_INVALID, "%s is NULL", q.records_name);
+    DeviceGuard guard(w->device);
+    bge::QueryParams p;
+    if (int rc = query_prepare(w, n, p)) return rc;
+    if (int rc = query_upload(w, n * q.record_bytes, records, p)) return rc;
+    std::vector<bge::QueryRec> rec;
+    if (int rc = query_collect(w, q.kind, p, rec)) return rc;
+    *total = rec.size();
+    if (offsets) query_offsets(rec, n, offsets);
+    if (!hits) return BGE_OK;
+    if (cap < rec.size()) return fail(BGE_ERR_INVALID, "%s: %zu hits, room for %llu", q.what, rec.size(), (unsigned long long)cap);
+    for (size_t i = 0; i < rec.size(); ++i) {
+        q.fill(static_cast<char*>(hits) + i * q.hit_bytes, rec[i], static_cast<const char*>(records) + rec[i].query * q.record_bytes);
+    }
+    return BGE_OK;
+}
+
+// The fills' point arithmetic is the device's (bge_query.hip: the descriptions' prep and point), operation for operation: the
+// first record of a query's list equals its closest hit bit for bit.
+void fill_ray_hit(void* hit, const bge::QueryRec& r, const void* record)
+{
+    bge_ray_hit& h = *static_cast<bge_ray_hit*>(hit);
+    const bge_ray& ray = *static_cast<const bge_ray*>(record);
+    decode_code(r.code, h.kind, h.entity);
+    h.fraction = r.f;
+    h.distance = r.f * ray.max_distance;
+    for (int a = 0; a < 3; ++a) {
+        const float delta = ray.direction[a] * ray.max_distance;
+        h.point[a] = ray.origin[a] + delta * r.f;
+        h.normal[a] = r.n[a];
+    }
+}
+
+void fill_sphere_cast_hit(void* hit, const bge::QueryRec& r, const void* record)
+{
+    bge_ray_hit& h = *static_cast<bge_ray_hit*>(hit);
+    const bge_sphere_cast& c = *static_cast<const bge_sphere_cast*>(record);
+    decode_code(r.code, h.kind, h.entity);
+    h.fraction = r.f;
+    h.distance = r.f * c.max_distance;
+    for (int a = 0; a < 3; ++a) {
+        const float delta = c.direction[a] * c.max_distance;
+        const float centre = c.origin[a] + delta * r.f;
+        h.point[a] = centre - c.radius * r.n[a];
+        h.normal[a] = r.n[a];
+    }
+    if (h.kind == BGE_RAY_GROUND) h.point[1] = 0.0f;
+}
+
+void fill_overlap_hit(void* hit, const bge::QueryRec& r, const void*)
+{
+    bge_overlap_hit& h = *static_cast<bge_overlap_hit*>(hit);
+    decode_code(r.code, h.kind, h.entity);
+    h.distance = r.f;
+}
+
+const QueryList kRaycastAll{bge::QueryKind::Ray, "raycast_all", "rays", sizeof(bge_ray), sizeof(bge_ray_hit), fill_ray_hit};
+const QueryList kSphereCastAll{bge::QueryKind::SphereCast, "sphere_cast_all", "casts", sizeof(bge_sphere_cast), sizeof(bge_ray_hit), fill_sphere_cast_hit};
+const QueryList kOverlapSphere{bge::QueryKind::SphereOverlap, "overlap_sphere", "spheres", sizeof(bge_sphere), sizeof(bge_overlap_hit), fill_overlap_hit};
 
 } // namespace
 
 int bge_world_raycast(bge_world* w, uint64_t n_rays, const bge_ray* rays, bge_ray_hit* hits)
 try {
-    if (!w) return fail(BGE_ERR_INVALID, "world is NULL");
-    if (n_rays == 0) return BGE_OK;
-    if (!rays || !hits) return fail(BGE_ERR_INVALID, "NULL argument");
-    DeviceGuard guard(w->device);
-    bge::RayParams p;
-    if (int rc = ray_prepare(w, n_rays, p)) return rc;
-    if (int rc = ray_upload(w, n_rays * sizeof(bge_ray), rays)) return rc;
-    HIP_TRY(w->ray_out.ensure(n_rays * sizeof(bge_ray_hit)));
-    p.rays = w->ray_in.p;
-    p.hits = w->ray_out.p;
-    HIP_TRY(bge::launch_ray_closest(w->stream, p));
-    HIP_TRY(hipMemcpyAsync(hits, w->ray_out.p, n_rays * sizeof(bge_ray_hit), hipMemcpyDeviceToHost, w->stream));
-    HIP_TRY(hipStreamSynchronize(w->stream));
-    return BGE_OK;
+    return query_closest(w, bge::QueryKind::Ray, n_rays, sizeof(bge_ray), rays, hits);
 }
 BGE_CATCH_ALL("bge_world_raycast")
 
 int bge_world_raycast_device(bge_world* w, uint64_t n_rays, const void* rays_device, void* hits_device)
 try {
-    if (!w) return fail(BGE_ERR_INVALID, "world is NULL");
-    if (n_rays == 0) return BGE_OK;
-    if (!rays_device || !hits_device) return fail(BGE_ERR_INVALID, "NULL argument");
-    DeviceGuard guard(w->device);
-    bge::RayParams p;
-    if (int rc = ray_prepare(w, n_rays, p)) return rc;
-    p.rays = rays_device;
-    p.hits = hits_device;
-    HIP_TRY(bge::launch_ray_closest(w->stream, p));
-    return BGE_OK;
+    return query_closest_device(w, bge::QueryKind::Ray, n_rays, rays_device, hits_device);
 }
 BGE_CATCH_ALL("bge_world_raycast_device")
 
 int bge_world_raycast_all(bge_world* w, uint64_t n_rays, const bge_ray* rays, bge_ray_hit* hits, uint64_t cap, uint64_t* offsets,
                           uint64_t* total)
 try {
-    if (!w || !total) return fail(BGE_ERR_INVALID, "NULL argument");
-    *total = 0;
-    if (n_rays == 0) {
-        if (offsets) offsets[0] = 0;
-        return BGE_OK;
-    }
-    if (!rays) return fail(BGE_ERR_INVALID, "rays is NULL");
-    DeviceGuard guard(w->device);
-    bge::RayParams p;
-    if (int rc = ray_prepare(w, n_rays, p)) return rc;
-    if (int rc = ray_upload(w, n_rays * sizeof(bge_ray), rays)) return rc;
-    p.rays = w->ray_in.p;
-    std::vector<bge::RayAllRec> rec;
-    if (int rc = ray_collect(w, p, bge::launch_ray_all, true, rec)) return rc;
-    const uint32_t found = static_cast<uint32_t>(rec.size());
-    *total = found;
-    if (offsets) ray_offsets(rec, n_rays, offsets);
-    if (!hits) return BGE_OK;
-    if (cap < found) return fail(BGE_ERR_INVALID, "raycast_all: %u hits, room for %llu", found, (unsigned long long)cap);
-    for (size_t i = 0; i < rec.size(); ++i) {
-        const bge::RayAllRec& r = rec[i];
-        const bge_ray& ray = rays[r.ray];
-        bge_ray_hit& h = hits[i];
-        const uint32_t kind = r.code >> 30;
-        h.kind = kind == 0u ? BGE_RAY_BODY : (kind == 1u ? BGE_RAY_TRIGGER : BGE_RAY_GROUND);
-        h.entity = kind == 2u ? BGE_RAY_NO_ENTITY : (r.code & bge::kRayEntityMask);
-        h.fraction = r.f;
-        h.distance = r.f * ray.max_distance;
-        for (int a = 0; a < 3; ++a) {
-            const float delta = ray.direction[a] * ray.max_distance; // the device's arithmetic (bge_raycast.hip ray_prep, k_ray_finish)
-            h.point[a] = ray.origin[a] + delta * r.f;
-            h.normal[a] = r.n[a];
-        }
-    }
-    return BGE_OK;
+    return query_list(w, kRaycastAll, n_rays, rays, hits, cap, offsets, total);
 }
 BGE_CATCH_ALL("bge_world_raycast_all")
 
-// ---------------------------------------------------------------- sphere queries (bge_spherecast.hip)
-static_assert(sizeof(bge_sphere_cast) == 40, "bge_sphere_cast is 40 bytes (include/bge_world.h)");
-static_assert(sizeof(bge_sphere) == 20, "bge_sphere is 20 bytes (include/bge_world.h)");
-static_assert(sizeof(bge_overlap_hit) == 12, "bge_overlap_hit is 12 bytes (include/bge_world.h)");
-
 int bge_world_sphere_cast(bge_world* w, uint64_t n, const bge_sphere_cast* casts, bge_ray_hit* hits)
 try {
-    if (!w) return fail(BGE_ERR_INVALID, "world is NULL");
-    if (n == 0) return BGE_OK;
-    if (!casts || !hits) return fail(BGE_ERR_INVALID, "NULL argument");
-    DeviceGuard guard(w->device);
-    bge::RayParams p;
-    if (int rc = ray_prepare(w, n, p)) return rc;
-    if (int rc = ray_upload(w, n * sizeof(bge_sphere_cast), casts)) return rc;
-    HIP_TRY(w->ray_out.ensure(n * sizeof(bge_ray_hit)));
-    p.rays = w->ray_in.p;
-    p.hits = w->ray_out.p;
-    HIP_TRY(bge::launch_sphere_cast_closest(w->stream, p));
-    HIP_TRY(hipMemcpyAsync(hits, w->ray_out.p, n * sizeof(bge_ray_hit), hipMemcpyDeviceToHost, w->stream));
-    HIP_TRY(hipStreamSynchronize(w->stream));
-    return BGE_OK;
+    return query_closest(w, bge::QueryKind::SphereCast, n, sizeof(bge_sphere_cast), casts, hits);
 }
 BGE_CATCH_ALL("bge_world_sphere_cast")
 
 int bge_world_sphere_cast_device(bge_world* w, uint64_t n, const void* casts_device, void* hits_device)
 try {
-    if (!w) return fail(BGE_ERR_INVALID, "world is NULL");
-    if (n == 0) return BGE_OK;
-    if (!casts_device || !hits_device) return fail(BGE_ERR_INVALID, "NULL argument");
-    DeviceGuard guard(w->device);
-    bge::RayParams p;
-    if (int rc = ray_prepare(w, n, p)) return rc;
-    p.rays = casts_device;
-    p.hits = hits_device;
-    HIP_TRY(bge::launch_sphere_cast_closest(w->stream, p));
-    return BGE_OK;
+    return query_closest_device(w, bge::QueryKind::SphereCast, n, casts_device, hits_device);
 }
 BGE_CATCH_ALL("bge_world_sphere_cast_device")
 
 int bge_world_sphere_cast_all(bge_world* w, uint64_t n, const bge_sphere_cast* casts, bge_ray_hit* hits, uint64_t cap, uint64_t* offsets,
                               uint64_t* total)
 try {
-    if (!w || !total) return fail(BGE_ERR_INVALID, "NULL argument");
-    *total = 0;
-    if (n == 0) {
-        if (offsets) offsets[0] = 0;
-        return BGE_OK;
-    }
-    if (!casts) return fail(BGE_ERR_INVALID, "casts is NULL");
-    DeviceGuard guard(w->device);
-    bge::RayParams p;
-    if (int rc = ray_prepare(w, n, p)) return rc;
-    if (int rc = ray_upload(w, n * sizeof(bge_sphere_cast), casts)) return rc;
-    p.rays = w->ray_in.p;
-    std::vector<bge::RayAllRec> rec;
-    if (int rc = ray_collect(w, p, bge::launch_sphere_cast_all, true, rec)) return rc;
-    *total = rec.size();
-    if (offsets) ray_offsets(rec, n, offsets);
-    if (!hits) return BGE_OK;
-    if (cap < rec.size()) return fail(BGE_ERR_INVALID, "sphere_cast_all: %zu hits, room for %llu", rec.size(), (unsigned long long)cap);
-    for (size_t i = 0; i < rec.size(); ++i) {
-        const bge::RayAllRec& r = rec[i];
-        const bge_sphere_cast& c = casts[r.ray];
-        bge_ray_hit& h = hits[i];
-        const uint32_t kind = r.code >> 30;
-        h.kind = kind == 0u ? BGE_RAY_BODY : (kind == 1u ? BGE_RAY_TRIGGER : BGE_RAY_GROUND);
-        h.entity = kind == 2u ? BGE_RAY_NO_ENTITY : (r.code & bge::kRayEntityMask);
-        h.fraction = r.f;
-        h.distance = r.f * c.max_distance;
-        for (int a = 0; a < 3; ++a) {
-            const float delta = c.direction[a] * c.max_distance; // the device's arithmetic (bge_spherecast.hip cast_prep, k_cast_finish)
-            const float centre = c.origin[a] + delta * r.f;
-            h.point[a] = centre - c.radius * r.n[a];
-            h.normal[a] = r.n[a];
-        }
-        if (kind == 2u) h.point[1] = 0.0f;
-    }
-    return BGE_OK;
+    return query_list(w, kSphereCastAll, n, casts, hits, cap, offsets, total);
 }
 BGE_CATCH_ALL("bge_world_sphere_cast_all")
 
 int bge_world_overlap_sphere(bge_world* w, uint64_t n, const bge_sphere* spheres, bge_overlap_hit* hits, uint64_t cap, uint64_t* offsets,
                              uint64_t* total)
 try {
-    if (!w || !total) return fail(BGE_ERR_INVALID, "NULL argument");
-    *total = 0;
-    if (n == 0) {
-        if (offsets) offsets[0] = 0;
-        return BGE_OK;
-    }
-    if (!spheres) return fail(BGE_ERR_INVALID, "spheres is NULL");
-    DeviceGuard guard(w->device);
-    bge::RayParams p;
-    if (int rc = ray_prepare(w, n, p)) return rc;
-    if (int rc = ray_upload(w, n * sizeof(bge_sphere), spheres)) return rc;
-    p.rays = w->ray_in.p;
-    std::vector<bge::RayAllRec> rec;
-    if (int rc = ray_collect(w, p, bge::launch_sphere_overlap, false, rec)) return rc;
-    *total = rec.size();
-    if (offsets) ray_offsets(rec, n, offsets);
-    if (!hits) return BGE_OK;
-    if (cap < rec.size()) return fail(BGE_ERR_INVALID, "overlap_sphere: %zu hits, room for %llu", rec.size(), (unsigned long long)cap);
-    for (size_t i = 0; i < rec.size(); ++i) {
-        const uint32_t kind = rec[i].code >> 30;
-        hits[i].kind = kind == 0u ? BGE_RAY_BODY : (kind == 1u ? BGE_RAY_TRIGGER : BGE_RAY_GROUND);
-        hits[i].entity = kind == 2u ? BGE_RAY_NO_ENTITY : (rec[i].code & bge::kRayEntityMask);
-        hits[i].distance = rec[i].f;
-    }
-    return BGE_OK;
+    return query_list(w, kOverlapSphere, n, spheres, hits, cap, offsets, total);
 }
 BGE_CATCH_ALL("bge_world_overlap_sphere")
 
@@ -3165,8 +3146,8 @@ int debug_enqueue(bge_world* w, const bge_debug_desc* desc, void* lines_device, 
     p.quat = v.quat;
     p.cshape = v.cshape;
     p.cinfo = v.cinfo;
-    p.ghosts = w->ray_ghosts.as<bge::RayGhost>();
-    p.n_ghosts = static_cast<uint32_t>(w->ray_ghosts_dev.size());
+    p.ghosts = w->query_ghosts.as<bge::QueryGhost>();
+    p.n_ghosts = static_cast<uint32_t>(w->query_ghosts_dev.size());
     p.ghost_pose = w->trig_pose.as<float>();
     p.plane = w->ground_plane ? 1u : 0u;
     if (p.flags & BGE_DEBUG_SHAPES) {
