@@ -25,6 +25,10 @@ class DebugDesc(C.Structure):
                 ("region_min", C.c_float * 3), ("region_max", C.c_float * 3)]
 
 
+class CullDesc(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("n_planes", C.c_uint32), ("planes", (C.c_float * 4) * 16)]
+
+
 class WorldInfo(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ("n_entities", "n_transforms", "n_slots", "n_tiles", "n_passes", "n_roots",
                                           "n_limbo", "n_bodies", "max_depth")]
@@ -100,6 +104,11 @@ SYMBOLS = {
     "bge_world_overlap_sphere": (C.c_int, [_vp, _u64, _vp, _vp, _u64, _vp, C.POINTER(_u64)]),
     "bge_world_debug_lines": (C.c_int, [_vp, _vp, _vp, _u64, C.POINTER(_u64)]),
     "bge_world_debug_lines_device": (C.c_int, [_vp, _vp, _vp, _u64, _vp]),
+    "bge_world_upload_bounds": (C.c_int, [_vp, _u64, _u64, _vp, _vp]),
+    "bge_world_upload_bounds_indexed": (C.c_int, [_vp, _u64, _vp, _vp, _vp]),
+    "bge_world_visible": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _u64, C.POINTER(_u64)]),
+    "bge_world_visible_device": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _u64, _vp]),
+    "bge_frustum_planes": (C.c_int, [_vp, C.c_int, _vp]),
     "bge_world_pack_roots": (C.c_int, [_vp, _vp]),
     "bge_world_device_array": (C.c_int, [_vp, C.c_int, C.POINTER(_vp), C.POINTER(_u64)]),
     "bge_world_get_info": (C.c_int, [_vp, C.POINTER(WorldInfo)]),

@@ -23,6 +23,7 @@
 #include "bge_broadphase.hpp"
 #include "bge_route.hpp"
 #include "bge_comm.hpp"
+#include "bge_cull.hpp"
 #include "bge_debug.hpp"
 #include "bge_flatten.hpp"
 #include "bge_kernels.hpp"
@@ -293,6 +294,10 @@ struct bge_world {
     std::vector<bge::QueryGhost> query_ghosts_host, query_ghosts_dev;
     // debug overlay (bge_debug.hip): per-workgroup line counts and their offsets, the host entry point's line buffer and total
     DevBuf dbg_block_sum, dbg_block_off, dbg_lines, dbg_total;
+    // frustum culling (bge_cull.hip): the model-space bounds per ENTITY (allocated with the first upload; a row of NaNs = no bounds;
+    // bounds_rows >= n_entities rows once it exists), the pass's ballots / counts / offsets, the host entry point's records and total
+    DevBuf bounds, cull_ballots, cull_block_sum, cull_block_off, cull_out, cull_total;
+    uint64_t bounds_rows = 0;
     uint32_t trigger_grid_min = 64;       // more ghosts than this: the broadphase grid answers for the small ones
     // Enter / Exit taken on the device (bge_kernels.hpp TriggerDiff): two key tables (this tick's, last tick's), header + deltas in
     // one device buffer with a page-locked copy.  The overlap sets above stay the truth; `trig_mirror_valid` says that last tick's
@@ -374,7 +379,7 @@ struct bge_world {
                           &stage2, &mass_palette, &normal, &deact, &filter_class, &filter_table, &grav_palette, &bp_partials, &cshape, &cmass, &cfriction, &cinfo, &manifold, &crestitution, &bmanifold, &obstacle_slots, &obstacle_gen, &obstacles, &obstacle_grid, &box_list, &box_count, &frozen, &rs_word, &trig_slot, &trig_entity, &trig_he, &trig_group,
                           &trig_mask, &trig_active, &trig_aabb, &trig_pairs, &trig_count, &trig_lists, &ground_list, &ground_count, &trig_tab[0], &trig_tab[1],
                           &trig_delta_dev, &trig_keys_dev, &trig_pose, &query_in, &query_out, &query_keys, &query_all, &query_all_count, &query_ghosts, &dbg_block_sum, &dbg_block_off,
-                          &dbg_lines, &dbg_total}) {
+                          &dbg_lines, &dbg_total, &bounds, &cull_ballots, &cull_block_sum, &cull_block_off, &cull_out, &cull_total}) {
             b->release();
         }
         if (trig_delta_host) (void)hipHostFree(trig_delta_host);
@@ -1439,6 +1444,23 @@ try {
         HIP_TRY(w->frozen.ensure(frozen_bits.size() * 4));
         HIP_TRY(hipMemcpy(w->frozen.p, frozen_bits.data(), frozen_bits.size() * 4, hipMemcpyHostToDevice));
         w->rebuild_view();
+    }
+    // bounds live in entity order: surviving indices keep theirs, indices that went or are new have none
+    if (w->bounds.p) {
+        const uint64_t old_n = w->flat.n_entities;
+        if (n > w->bounds_rows) {
+            TmpBuf grown;
+            HIP_TRY(grown.ensure(n * 24));
+            HIP_TRY(hipMemsetAsync(grown.p, 0xff, n * 24, w->stream));
+            const uint64_t keep = std::min(old_n, w->bounds_rows);
+            if (keep) HIP_TRY(hipMemcpyAsync(grown.p, w->bounds.p, keep * 24, hipMemcpyDeviceToDevice, w->stream));
+            HIP_TRY(hipStreamSynchronize(w->stream));
+            std::swap(w->bounds.p, grown.p);
+            std::swap(w->bounds.bytes, grown.bytes);
+            w->bounds_rows = n;
+        } else if (n < old_n) {
+            HIP_TRY(hipMemsetAsync(static_cast<char*>(w->bounds.p) + n * 24, 0xff, (std::min(old_n, w->bounds_rows) - n) * 24, w->stream));
+        }
     }
     w->any_frozen = any_frozen;
     w->flat = std::move(nf);
@@ -3224,6 +3246,157 @@ try {
     return debug_enqueue(w, desc, lines_device, cap, total_device);
 }
 BGE_CATCH_ALL("bge_world_debug_lines_device")
+
+// ---------------------------------------------------------------- frustum culling (bge_cull.hip)
+static_assert(sizeof(bge_cull_desc) == 8 + 4 * 4 * BGE_CULL_MAX_PLANES, "bge_cull_desc layout (include/bge_world.h)");
+static_assert(BGE_CULL_MAX_PLANES == bge::kCullMaxPlanes, "plane limit");
+
+namespace {
+
+int upload_bounds_impl(bge_world* w, uint64_t first, uint64_t count, const uint32_t* index, const float* center3, const float* half3)
+{
+    if (!center3 || !half3) return fail(BGE_ERR_INVALID, "center3 / half3 is NULL");
+    if (count == 0) return BGE_OK;
+    DeviceGuard guard(w->device);
+    if (!w->bounds.p) { // every entity starts without bounds: a row of NaNs
+        const uint64_t rows = std::max<uint64_t>(w->flat.n_entities, 1);
+        HIP_TRY(w->bounds.ensure(rows * 24));
+        HIP_TRY(hipMemsetAsync(w->bounds.p, 0xff, rows * 24, w->stream));
+        w->bounds_rows = rows;
+    }
+    const uint32_t* di = nullptr;
+    if (int rc = stage_index(w, count, index, &di)) return rc;
+    HIP_TRY(w->stage.ensure(count * 24));
+    float* sc = w->stage.as<float>();
+    HIP_TRY(hipMemcpyAsync(sc, center3, count * 12, hipMemcpyHostToDevice, w->stream));
+    HIP_TRY(hipMemcpyAsync(sc + 3 * count, half3, count * 12, hipMemcpyHostToDevice, w->stream));
+    HIP_TRY(bge::launch_cull_scatter_bounds(w->stream, di, first, count, sc, sc + 3 * count, w->bounds.as<float>()));
+    HIP_TRY(hipStreamSynchronize(w->stream)); // the staging buffers are reused by the next call
+    return BGE_OK;
+}
+
+// Everything of the pass but its outputs: the desc, the world's arrays, the scratch of the three kernels
+int cull_params(bge_world* w, const bge_cull_desc* desc, bool want_normal, bge::CullParams& p)
+{
+    if (!w->has_topology) return fail(BGE_ERR_STATE, "bge_world_set_topology has not been called");
+    if (desc) {
+        if (desc->struct_size < sizeof(bge_cull_desc)) return fail(BGE_ERR_INVALID, "bge_cull_desc::struct_size = %u", desc->struct_size);
+        if (desc->n_planes > BGE_CULL_MAX_PLANES) return fail(BGE_ERR_INVALID, "bge_cull_desc::n_planes = %u, at most %d", desc->n_planes, BGE_CULL_MAX_PLANES);
+        p.n_planes = desc->n_planes;
+        std::memcpy(p.planes, desc->planes, sizeof p.planes);
+    }
+    p.n_entities = w->flat.n_entities;
+    p.n_slots = w->flat.n_slots;
+    if (p.n_entities > 0xffffffffull) return fail(BGE_ERR_UNSUPPORTED, "visible: %llu entities, at most 2^32 - 1 records", (unsigned long long)p.n_entities);
+    if (want_normal) {
+        if (!w->normal.p) return fail(BGE_ERR_STATE, "no tick with BGE_TICK_NORMAL_MATRICES has run");
+        if (w->normal.bytes < p.n_slots * 64) return fail(BGE_ERR_STATE, "no tick with BGE_TICK_NORMAL_MATRICES has run since the world grew");
+        p.normal = w->normal.as<float>();
+    }
+    p.slot_of_entity = w->slot_of_entity.as<uint32_t>();
+    p.flag_words = w->view.flags;
+    p.bounds = w->bounds.as<float>();
+    p.world = w->view.world;
+    const uint64_t blocks = (p.n_entities + bge::kCullEntitiesPerBlock - 1) / bge::kCullEntitiesPerBlock;
+    p.n_blocks = static_cast<uint32_t>(blocks);
+    HIP_TRY(w->cull_ballots.ensure(std::max<uint64_t>(blocks, 1) * (bge::kCullEntitiesPerBlock / 64) * 8));
+    HIP_TRY(w->cull_block_sum.ensure(std::max<uint64_t>(blocks, 1) * 4));
+    HIP_TRY(w->cull_block_off.ensure(std::max<uint64_t>(blocks, 1) * 8));
+    p.ballots = w->cull_ballots.as<unsigned long long>();
+    p.block_sum = w->cull_block_sum.as<uint32_t>();
+    p.block_off = w->cull_block_off.as<uint64_t>();
+    return BGE_OK;
+}
+
+} // namespace
+
+int bge_world_upload_bounds(bge_world* w, uint64_t first, uint64_t count, const float* center3, const float* half3)
+try {
+    if (int rc = check_range(w, first, count)) return rc;
+    return upload_bounds_impl(w, first, count, nullptr, center3, half3);
+}
+BGE_CATCH_ALL("bge_world_upload_bounds")
+
+int bge_world_upload_bounds_indexed(bge_world* w, uint64_t count, const uint32_t* entity_index, const float* center3, const float* half3)
+try {
+    if (int rc = check_range(w, 0, 0)) return rc;
+    if (count && !entity_index) return fail(BGE_ERR_INVALID, "entity_index is NULL");
+    return upload_bounds_impl(w, 0, count, entity_index, center3, half3);
+}
+BGE_CATCH_ALL("bge_world_upload_bounds_indexed")
+
+int bge_world_visible(bge_world* w, const bge_cull_desc* desc, uint32_t* entities, float* world16, float* normal16, uint64_t cap,
+                      uint64_t* total)
+try {
+    if (!w || !total) return fail(BGE_ERR_INVALID, "NULL argument");
+    *total = 0;
+    DeviceGuard guard(w->device);
+    bge::CullParams p{};
+    if (int rc = cull_params(w, desc, normal16 != nullptr, p)) return rc;
+    HIP_TRY(w->cull_total.ensure(8));
+    p.total = w->cull_total.as<unsigned long long>();
+    HIP_TRY(bge::launch_cull_count(w->stream, p));
+    uint64_t n = 0;
+    HIP_TRY(hipMemcpyAsync(&n, w->cull_total.p, 8, hipMemcpyDeviceToHost, w->stream));
+    HIP_TRY(hipStreamSynchronize(w->stream));
+    *total = n;
+    if ((!entities && !world16 && !normal16) || n == 0) return BGE_OK;
+    if (cap < n) return fail(BGE_ERR_INVALID, "visible: %llu records, room for %llu", (unsigned long long)n, (unsigned long long)cap);
+    // the records are emitted from the ballots the count left (nothing ran in between) into one buffer: indices | world | normal
+    const uint64_t idx_bytes = (n * 4 + 15) & ~15ull;
+    HIP_TRY(w->cull_out.ensure(idx_bytes + n * 64 * ((world16 ? 1 : 0) + (normal16 ? 1 : 0))));
+    char* out = w->cull_out.as<char>();
+    p.out_entities = entities ? reinterpret_cast<uint32_t*>(out) : nullptr;
+    p.out_world = world16 ? reinterpret_cast<float*>(out + idx_bytes) : nullptr;
+    p.out_normal = normal16 ? reinterpret_cast<float*>(out + idx_bytes + (world16 ? n * 64 : 0)) : nullptr;
+    p.cap = n;
+    HIP_TRY(bge::launch_cull_emit(w->stream, p));
+    if (entities) HIP_TRY(hipMemcpyAsync(entities, p.out_entities, n * 4, hipMemcpyDeviceToHost, w->stream));
+    if (world16) HIP_TRY(hipMemcpyAsync(world16, p.out_world, n * 64, hipMemcpyDeviceToHost, w->stream));
+    if (normal16) HIP_TRY(hipMemcpyAsync(normal16, p.out_normal, n * 64, hipMemcpyDeviceToHost, w->stream));
+    HIP_TRY(hipStreamSynchronize(w->stream));
+    return BGE_OK;
+}
+BGE_CATCH_ALL("bge_world_visible")
+
+int bge_world_visible_device(bge_world* w, const bge_cull_desc* desc, void* entities_device, void* world16_device, void* normal16_device,
+                             uint64_t cap, void* total_device)
+try {
+    if (!w || !total_device) return fail(BGE_ERR_INVALID, "NULL argument");
+    if (reinterpret_cast<uintptr_t>(entities_device) & 3u) return fail(BGE_ERR_INVALID, "entities must be 4-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(world16_device) | reinterpret_cast<uintptr_t>(normal16_device)) & 15u) {
+        return fail(BGE_ERR_INVALID, "world16 / normal16 must be 16-byte aligned");
+    }
+    if (reinterpret_cast<uintptr_t>(total_device) & 7u) return fail(BGE_ERR_INVALID, "total must be 8-byte aligned");
+    DeviceGuard guard(w->device);
+    bge::CullParams p{};
+    if (int rc = cull_params(w, desc, normal16_device != nullptr, p)) return rc;
+    p.out_entities = static_cast<uint32_t*>(entities_device);
+    p.out_world = static_cast<float*>(world16_device);
+    p.out_normal = static_cast<float*>(normal16_device);
+    p.cap = cap;
+    p.total = static_cast<unsigned long long*>(total_device);
+    HIP_TRY(bge::launch_cull_count(w->stream, p));
+    HIP_TRY(bge::launch_cull_emit(w->stream, p));
+    return BGE_OK;
+}
+BGE_CATCH_ALL("bge_world_visible_device")
+
+int bge_frustum_planes(const float m[16], int homogeneous_depth, float planes24[24])
+try {
+    if (!m || !planes24) return fail(BGE_ERR_INVALID, "NULL argument");
+    for (int i = 0; i < 4; ++i) { // coefficient i of every plane comes from row i: clip_j = sum_i v_i * m[4i+j]
+        const float x = m[4 * i], y = m[4 * i + 1], z = m[4 * i + 2], ww = m[4 * i + 3];
+        planes24[0 + i] = ww + x;
+        planes24[4 + i] = ww - x;
+        planes24[8 + i] = ww + y;
+        planes24[12 + i] = ww - y;
+        planes24[16 + i] = homogeneous_depth ? ww + z : z;
+        planes24[20 + i] = ww - z;
+    }
+    return BGE_OK;
+}
+BGE_CATCH_ALL("bge_frustum_planes")
 
 int bge_world_pack_roots(bge_world* w, void* dst_device)
 try {

@@ -130,7 +130,7 @@ public:
     }
 
     // Resident mode: the world matrices stay on the device after TransformSystem::Update; only the host `dirty` flags
-    // are kept coherent and the caller fetches the matrices it needs (FetchWorld) — e.g. the visible set.  Coherent
+    // are kept coherent and the caller fetches the matrices it needs: the visible set (FetchVisible), or any list (FetchWorld).  Coherent
     // mode (default) copies every world matrix back each call, which is what makes the adapter a drop-in but also what
     // bounds it (64 B per entity over PCIe + a hash-map scatter).
     bool resident = false;
@@ -154,10 +154,60 @@ public:
         return true;
     }
 
+    // EXTENSION without a reference counterpart (its renderer submits every MeshRenderer, src/render/Renderer.cpp:606-665): the
+    // model-space box of an entity's mesh.  An entity with bounds is renderable; FetchVisible lists the renderable entities a view
+    // sees (include/bge_world.h "Frustum culling").  Sent lazily with the other dirty data, and again to the new index when a
+    // re-topology moves the entity.
+    void SetBounds(Id id, const float min[3], const float max[3])
+    {
+        Bounds b;
+        for (int a = 0; a < 3; ++a) {
+            b.v[a] = (min[a] + max[a]) * 0.5f;
+            b.v[3 + a] = (max[a] - min[a]) * 0.5f;
+        }
+        bounds_[id] = b;
+        bounds_stale_ = true;
+    }
+    void ClearBounds(Id id)
+    {
+        if (bounds_.erase(id)) bounds_stale_ = true;
+    }
+    // The six planes of a view-projection matrix (bx row-vector convention; homogeneousDepth as bgfx::getCaps()->homogeneousDepth)
+    static void FrustumPlanes(const float viewProj16[16], bool homogeneousDepth, float planes[6][4])
+    {
+        (void)bge_frustum_planes(viewProj16, homogeneousDepth ? 1 : 0, &planes[0][0]);
+    }
+    // The renderable entities inside the n planes (inward-pointing, n <= 16) after the last TransformSystem::Update, in ascending
+    // index order: one query on the device, one copy of the visible matrices into their Transform::world (as FetchWorld writes them)
+    bool FetchVisible(SceneT& scene, const float planes[][4], size_t n, std::vector<Id>& out)
+    {
+        out.clear();
+        if (!ok() || !UploadBounds()) return false;
+        bge_cull_desc desc{};
+        desc.struct_size = sizeof desc;
+        desc.n_planes = static_cast<uint32_t>(n);
+        if (n > BGE_CULL_MAX_PLANES) return Log("FetchVisible: more than 16 planes");
+        if (n) std::memcpy(desc.planes, planes, n * 16);
+        const size_t cap = ids_.size();
+        index_list_.resize(cap);
+        if (!down_.resize(cap * 16 + 1)) return Log("bge_host_alloc");
+        uint64_t total = 0;
+        if (bge_world_visible(world_, &desc, index_list_.data(), down_.data(), nullptr, cap, &total) != BGE_OK) return Log("bge_world_visible");
+        out.reserve(total);
+        for (uint64_t k = 0; k < total; ++k) {
+            const Id id = ids_[index_list_[k]];
+            auto* t = scene.GetTransform(id);
+            if (!t) continue;
+            std::memcpy(t->world, &down_[16 * k], 64);
+            out.push_back(id);
+        }
+        return true;
+    }
+
     // --- TransformSystem::Update(Scene&)
     bool UpdateTransforms(SceneT& scene)
     {
-        if (!ok() || !RefreshTopology(scene) || !UploadDirtyTransforms(scene)) return false;
+        if (!ok() || !RefreshTopology(scene) || !UploadDirtyTransforms(scene) || !UploadBounds()) return false;
         if (bge_world_tick(world_, 0.0f, gravity, BGE_TICK_TRANSFORMS) != BGE_OK) return Log("bge_world_tick");
         const size_t n = ids_.size();
         if (resident) {
@@ -465,6 +515,42 @@ private:
     struct BodyState {
         bool exists = false;
     };
+    struct Bounds {
+        float v[6]; // centre, half extents
+    };
+
+    // bounds the device should hold per index against what it was last sent: only the rows that differ travel
+    bool UploadBounds()
+    {
+        if (!bounds_stale_) return true;
+        static constexpr float kNoBounds[6] = {0.0f, 0.0f, 0.0f, -1.0f, -1.0f, -1.0f}; // a negative half extent: not renderable
+        const size_t n = ids_.size();
+        bounds_want_.resize(n * 6);
+        for (size_t i = 0; i < n; ++i) std::memcpy(&bounds_want_[6 * i], kNoBounds, 24);
+        for (const auto& kv : bounds_) {
+            auto it = index_of_.find(kv.first);
+            if (it != index_of_.end()) std::memcpy(&bounds_want_[6 * static_cast<size_t>(it->second)], kv.second.v, 24);
+        }
+        const size_t had = bounds_sent_.size() / 6;
+        bounds_sent_.resize(n * 6);
+        for (size_t i = had; i < n; ++i) std::memcpy(&bounds_sent_[6 * i], kNoBounds, 24); // (a new index has none on the device either)
+        index_list_.clear();
+        stage_.clear();
+        repack_.clear();
+        for (size_t i = 0; i < n; ++i) {
+            if (std::memcmp(&bounds_want_[6 * i], &bounds_sent_[6 * i], 24) == 0) continue;
+            index_list_.push_back(static_cast<uint32_t>(i));
+            stage_.insert(stage_.end(), &bounds_want_[6 * i], &bounds_want_[6 * i] + 3);
+            repack_.insert(repack_.end(), &bounds_want_[6 * i] + 3, &bounds_want_[6 * i] + 6);
+        }
+        if (!index_list_.empty() &&
+            bge_world_upload_bounds_indexed(world_, index_list_.size(), index_list_.data(), stage_.data(), repack_.data()) != BGE_OK) {
+            return Log("bge_world_upload_bounds_indexed");
+        }
+        bounds_sent_.swap(bounds_want_);
+        bounds_stale_ = false;
+        return true;
+    }
 
     bool Log(const char* what) const
     {
@@ -595,6 +681,7 @@ private:
         // (an index whose entity lost its Transform keeps the parent it had: to the device that entity's place in the
         //  hierarchy has not changed, so nothing below it is taken for re-parented)
         live_ = transforms.size();
+        bounds_stale_ = true; // an entity may sit on another index now
         if (bge_world_set_topology(world_, ids_.size(), parent_.data(), has_tf_.data()) != BGE_OK) return Log("bge_world_set_topology");
         // a reused index must not inherit the previous owner's device state: force a full upload
         for (uint32_t i : fresh_) {
@@ -745,6 +832,9 @@ private:
     std::unordered_map<Id, uint32_t> orphan_of_; // ids without a Transform whose body lives on, on the index they had
     bool topology_stale_ = false;               // an index was given up outside RefreshTopology
     std::vector<BodyState> body_;
+    std::unordered_map<Id, Bounds> bounds_;     // what SetBounds was given, per EntityId
+    std::vector<float> bounds_want_, bounds_sent_; // per dense index: the row the device should hold / was last sent
+    bool bounds_stale_ = false;
     std::vector<float> last_pose_;              // position + euler the physics write-back stored (6 floats per index)
     std::vector<float> last_scale_;             // scale as last uploaded (3 floats per index)
     std::vector<float> stage_, repack_;

@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import _capi
-from ._capi import DebugDesc, WorldDesc, WorldInfo, check, lib
+from ._capi import CullDesc, DebugDesc, WorldDesc, WorldInfo, check, lib
 
 NO_PARENT = 0xFFFFFFFF
 BODY_STATIC, BODY_DYNAMIC, BODY_KINEMATIC, BODY_NONE = 0, 1, 2, 255
@@ -85,6 +85,27 @@ def _debug_desc(flags, region):
         d.region_min = (C.c_float * 3)(*mn.tolist())
         d.region_max = (C.c_float * 3)(*mx.tolist())
     return d
+
+
+# frustum culling (bge_world_visible*): bge_cull_desc from an (n, 4) array of inward-pointing planes (a, b, c, d), n <= 16
+CULL_MAX_PLANES = 16
+
+
+def _cull_desc(planes):
+    pl = np.zeros((0, 4), np.float32) if planes is None else np.ascontiguousarray(planes, np.float32).reshape(-1, 4)
+    d = CullDesc(C.sizeof(CullDesc), len(pl))
+    n = min(len(pl), CULL_MAX_PLANES)  # (a longer list keeps its count: the library refuses it)
+    C.memmove(d.planes, pl.ctypes.data, 16 * n)
+    return d
+
+
+def frustum_planes(viewproj, homogeneous_depth=False):
+    """Host-only: the six planes (6, 4) of a view-projection matrix in the bx row-vector convention, in the order w+x, w-x, w+y,
+    w-y, near (z, or w+z with homogeneous_depth), w-z (bge_frustum_planes)."""
+    m = np.ascontiguousarray(viewproj, np.float32).reshape(16)
+    out = np.empty((6, 4), np.float32)
+    check(lib().bge_frustum_planes(_p(m), int(bool(homogeneous_depth)), _p(out)))
+    return out
 
 
 # fixed step and gravity of the reference (assets/config/physics.json:2-3)
@@ -483,6 +504,50 @@ class World:
         desc = _debug_desc(flags, region)
         check(lib().bge_world_debug_lines_device(self._h, C.byref(desc), C.c_void_p(lines_ptr) if lines_ptr else None, int(cap),
                                                  C.c_void_p(total_ptr)))
+
+    # -- frustum culling (include/bge_world.h states the rule and the order)
+    def upload_bounds(self, center, half, first=0, entity_index=None):
+        """Model-space bounds (centre, half extents; (n, 3) each) of a range of entities, or of entity_index[i] per row."""
+        c, h = _arr(center, np.float32, 3), _arr(half, np.float32, 3)
+        if len(c) != len(h):
+            raise ValueError(f"{len(c)} centres, {len(h)} half extents")
+        if entity_index is None:
+            check(lib().bge_world_upload_bounds(self._h, first, len(c), _p(c), _p(h)))
+        else:
+            idx = _arr(entity_index, np.uint32)
+            check(lib().bge_world_upload_bounds_indexed(self._h, len(idx), _p(idx), _p(c), _p(h)))
+
+    def visible_count(self, planes=None) -> int:
+        desc = _cull_desc(planes)
+        total = C.c_uint64(0)
+        check(lib().bge_world_visible(self._h, C.byref(desc), None, None, None, 0, C.byref(total)))
+        return int(total.value)
+
+    def visible(self, planes=None, want_world=True, want_normal=False):
+        """The visible entities in ascending entity index: dict of "entities" (n,) uint32 and, when asked for, "world" and
+        "normal" (n, 16) — row k of each belongs to entities[k]."""
+        desc = _cull_desc(planes)
+        n = self.visible_count(planes)
+        ent = np.empty(n, np.uint32)
+        wm = np.empty((n, 16), np.float32) if want_world else None
+        nm = np.empty((n, 16), np.float32) if want_normal else None
+        total = C.c_uint64(0)
+        if n or want_normal:  # (a missing normal-matrix tick is reported even when nothing is visible)
+            check(lib().bge_world_visible(self._h, C.byref(desc), _p(ent), _p(wm), _p(nm), n, C.byref(total)))
+        out = {"entities": ent}
+        if want_world:
+            out["world"] = wm
+        if want_normal:
+            out["normal"] = nm
+        return out
+
+    def visible_device(self, planes, entities_ptr, world_ptr, normal_ptr, cap, total_ptr):
+        """The same between device pointers (0 / None leaves an output out): room for cap records each, total_ptr one uint64.
+        Enqueued on the world's stream without synchronisation; records beyond cap are counted, not written."""
+        desc = _cull_desc(planes)
+        vp = lambda a: C.c_void_p(a) if a else None
+        check(lib().bge_world_visible_device(self._h, C.byref(desc), vp(entities_ptr), vp(world_ptr), vp(normal_ptr), int(cap),
+                                             C.c_void_p(total_ptr)))
 
     def pack_roots(self, dst_device_ptr: int | None = None):
         check(lib().bge_world_pack_roots(self._h, C.c_void_p(dst_device_ptr) if dst_device_ptr else None))

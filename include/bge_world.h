@@ -563,6 +563,60 @@ BGE_API int bge_world_debug_lines(bge_world* world, const bge_debug_desc* desc, 
 BGE_API int bge_world_debug_lines_device(bge_world* world, const bge_debug_desc* desc, void* lines_device, uint64_t cap,
                                          void* total_device);
 
+/*
+ * Frustum culling: which entities a view sees, with their matrices packed for an instanced or indirect draw.  An EXTENSION: the
+ * reference's renderer submits every MeshRenderer whose Transform is clean (src/render/Renderer.cpp:606-665).  The world and
+ * normal matrices are the render feed the tick ends in; this is its last step, made where they live.  The rules below are the
+ * specification.
+ *   Bounds    bge_world_upload_bounds / _indexed: the model-space box of the entity's mesh, a centre and half extents, three
+ *             floats each.  Stored per ENTITY (not per slot).  An entity is RENDERABLE once it has bounds whose three half extents
+ *             are finite and >= 0 and whose centre is finite; a negative, infinite or NaN half extent or a non-finite centre takes
+ *             it out again.  Bounds are component state: bge_world_set_topology keeps them for surviving indices, as it keeps
+ *             bodies (an index beyond the old entity count starts without bounds).  Uploading bounds marks nothing dirty.
+ *   Rule      binary32, each line evaluated left to right with one rounding per operation.  For entity e with slot s, world
+ *             matrix m = world[s] (translation in m[12..14]), centre c and half extents h:
+ *                 cw[j] = ((c.x*m[j] + c.y*m[4+j]) + c.z*m[8+j]) + m[12+j]                      j = 0, 1, 2
+ *             and for every plane (a, b, c4, d):
+ *                 e_i = (a*m[4i] + b*m[4i+1]) + c4*m[4i+2]                                      i = 0, 1, 2
+ *                 r   = (|e_0|*h.x + |e_1|*h.y) + |e_2|*h.z
+ *                 sd  = ((a*cw.x + b*cw.y) + c4*cw.z) + d
+ *             The entity is VISIBLE iff it is renderable, owns a Transform, is not dirty (bge_world_download_dirty reports 0:
+ *             it has been through a transforms tick since it was last marked; an entity inside a parent cycle stays dirty and is
+ *             never drawn, as the renderer skips transform->dirty) and sd >= -r is TRUE for every plane — so a NaN anywhere
+ *             culls.  Planes point inwards and need not be normalised.  n_planes = 0 lists every renderable, clean entity.
+ *             This is the usual oriented-box test: exact per plane, conservative at the corners of a frustum.
+ *   Order     ascending ENTITY index; record k of every output array belongs to the same entity.  world16[k] equals
+ *             bge_world_download_world_indexed of that entity bit for bit, normal16[k] bge_world_download_normal's.
+ *   bge_world_visible         the convention of bge_world_pairs / bge_world_debug_lines: with all three outputs NULL it only
+ *                             counts; cap < *total is BGE_ERR_INVALID with *total filled in and nothing written; any of the three
+ *                             outputs may be NULL.  Synchronises the world's stream.
+ *   bge_world_visible_device  device pointers (entities 4-byte, the matrices 16-byte aligned; any may be NULL) and one device
+ *                             uint64_t for the total.  Enqueued on the world's stream, no synchronisation.  Records beyond cap
+ *                             are not written and are still counted: a renderer can feed an indirect draw from the buffers.
+ *   normal16  before a BGE_TICK_NORMAL_MATRICES tick (or after a bge_world_set_topology that grew the world, before the next
+ *             one) asking for it is BGE_ERR_STATE, as bge_world_download_normal.
+ *   n_planes > 16 is BGE_ERR_INVALID.  More than 2^32 - 1 records is BGE_ERR_UNSUPPORTED (a world holds fewer entities than that).
+ *   The query changes no world state.
+ *   bge_frustum_planes   host only: the six planes of a view-projection matrix in the bx row-vector convention,
+ *             clip_j = sum_i v_i * m[4i+j], in the order w+x, w-x, w+y, w-y, near, w-z, where near is z (depth 0..1), or w+z with
+ *             homogeneous_depth (depth -1..1).  Plane k is planes24[4k..4k+3] = (a, b, c4, d); each coefficient is ONE binary32
+ *             add or subtract of two matrix elements (or the element itself).
+ */
+#define BGE_CULL_MAX_PLANES 16
+typedef struct bge_cull_desc {
+    uint32_t struct_size; /* sizeof(bge_cull_desc) */
+    uint32_t n_planes;    /* 0 .. BGE_CULL_MAX_PLANES */
+    float planes[BGE_CULL_MAX_PLANES][4];
+} bge_cull_desc;
+BGE_API int bge_world_upload_bounds(bge_world* world, uint64_t first, uint64_t count, const float* center3, const float* half3);
+BGE_API int bge_world_upload_bounds_indexed(bge_world* world, uint64_t count, const uint32_t* entity_index, const float* center3,
+                                            const float* half3);
+BGE_API int bge_world_visible(bge_world* world, const bge_cull_desc* desc, uint32_t* entities, float* world16, float* normal16,
+                              uint64_t cap, uint64_t* total);
+BGE_API int bge_world_visible_device(bge_world* world, const bge_cull_desc* desc, void* entities_device, void* world16_device,
+                                     void* normal16_device, uint64_t cap, void* total_device);
+BGE_API int bge_frustum_planes(const float viewproj16[16], int homogeneous_depth, float planes24[24]);
+
 /* Multi-GPU support: compact the world matrices of all roots (entity order) into one buffer that the
  * caller all-gathers across ranks (one collective per frame).  dst = NULL packs into the world's own
  * BGE_ARRAY_ROOT_WORLDS buffer; otherwise dst is a device pointer with room for n_roots*16 floats. */

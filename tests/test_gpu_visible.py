@@ -1,0 +1,349 @@
+"""Frustum culling on the device (include/bge_world.h bge_world_visible*) against the two references of test_visible_cpu.py.
+
+Exactness: the entity list equals the binary32 restatement of the rule fed the DEVICE's own downloaded world matrices — exactly,
+the rule fixes every rounding.  Against the float64 geometry it must agree for every entity that reference does not call
+ambiguous (within 1e-4 x (1 + |cw|_inf + |h * scale|_inf) of a plane); at most 2 % may be left out that way, which is a condition
+on the reference and never on the device's answer.  Matrices are compared byte for byte with the indexed downloads."""
+from __future__ import annotations
+
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import banggameengine_amd as B
+from banggameengine_amd import world as W
+from banggameengine_amd._capi import CullDesc, lib
+
+from test_visible_cpu import F, make_scene, narrow_view, renderable, visible_ref32, visible_ref64, wide_view
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+TICK = W.TICK_TRANSFORMS | W.TICK_NORMAL_MATRICES
+BEHIND_EVERYTHING = np.array([[0, 0, 1, -1.0e6]], F)  # z >= 1e6
+
+
+def _p(a):
+    return a.ctypes.data_as(C.c_void_p)
+
+
+def download_world_indexed(w, idx):
+    idx = np.ascontiguousarray(idx, np.uint32)
+    out = np.empty((len(idx), 16), F)
+    if len(idx):
+        B._capi.check(lib().bge_world_download_world_indexed(w._h, len(idx), _p(idx), _p(out)))
+    return out
+
+
+def flat_world(n, seed=7, tick=TICK):
+    sc = make_scene(seed, n)
+    w = B.World(device=0)
+    w.set_topology(np.full(n, W.NO_PARENT, np.uint32))
+    w.upload_trs(sc["pos"], sc["euler"], sc["scale"])
+    w.upload_bounds(sc["center"], sc["half"])
+    w.tick(flags=tick)
+    return w, sc
+
+
+def expected(w, center, half, planes, eligible=None):
+    """Entity list of the binary32 rule on the device's own matrices; entities without a slot download as zeros and are not eligible."""
+    mask = visible_ref32(w.download_world(), center, half, planes, eligible)
+    return np.nonzero(mask)[0].astype(np.uint32)
+
+
+def check_records(w, got, want, what, normal=True):
+    assert np.array_equal(got["entities"], want), f"{what}: {len(got['entities'])} entities, the rule gives {len(want)}"
+    assert got["world"].shape == (len(want), 16)
+    assert got["world"].tobytes() == download_world_indexed(w, want).tobytes(), f"{what}: world16 differs from the indexed download"
+    if normal:
+        assert got["normal"].tobytes() == w.download_normal()[want].tobytes(), f"{what}: normal16 differs from download_normal"
+
+
+@pytest.fixture(scope="module")
+def scene4000():
+    w, sc = flat_world(4000)
+    yield w, sc
+    w.close()
+
+
+# ---------------------------------------------------------------- exactness
+
+@pytest.mark.parametrize("view", ["wide", "narrow"])
+def test_seeded_scene_matches_both_references(scene4000, view):
+    w, sc = scene4000
+    planes = wide_view() if view == "wide" else narrow_view()
+    got = w.visible(planes, want_world=True, want_normal=True)
+    want = expected(w, sc["center"], sc["half"], planes)
+    print(f"{view}: {len(got['entities'])} visible of 4000")
+    assert 0 < len(want) < 4000
+    check_records(w, got, want, view)
+    vis64, amb = visible_ref64(w.download_world(), sc["center"], sc["half"], planes)
+    print(f"{view}: float64 reference {int(vis64.sum())} visible, {int(amb.sum())} ambiguous")
+    assert amb.sum() <= 0.02 * 4000  # (on the reference)
+    mask = np.zeros(4000, bool)
+    mask[got["entities"]] = True
+    assert np.array_equal(mask[~amb], vis64[~amb])
+
+
+# ---------------------------------------------------------------- sizes where the passes can break
+
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 255, 256, 257, 513, 262144 + 257])
+def test_sizes(n):
+    w, sc = flat_world(n, seed=11)
+    try:
+        everyone = np.arange(n, dtype=np.uint32)
+        # all visible
+        assert w.visible_count(None) == n
+        got = w.visible(None, want_world=True, want_normal=True)
+        check_records(w, got, everyone, f"n={n} all visible")
+        # none visible
+        assert w.visible_count(BEHIND_EVERYTHING) == 0
+        got = w.visible(BEHIND_EVERYTHING)
+        assert len(got["entities"]) == 0 and got["world"].shape == (0, 16)
+        # every third entity renderable: the others lose their bounds through a negative half extent
+        drop = everyone[everyone % 3 != 0]
+        if len(drop):
+            w.upload_bounds(np.zeros((len(drop), 3), F), np.full((len(drop), 3), -1, F), entity_index=drop)
+        half = sc["half"].copy()
+        half[drop] = -1
+        got = w.visible(None, want_world=True, want_normal=True)
+        check_records(w, got, everyone[::3], f"n={n} every third")
+        planes = wide_view()
+        got = w.visible(planes, want_world=True, want_normal=True)
+        check_records(w, got, expected(w, sc["center"], half, planes), f"n={n} every third, wide view")
+    finally:
+        w.close()
+
+
+# ---------------------------------------------------------------- order and gaps
+
+def _gappy_world():
+    """40 chains of depth 4 with the child listed BEFORE its parent (entity 4k+i hangs on 4k+i+1), then 20 free entities of which
+    some have no Transform and some no bounds, then a two-entity parent cycle."""
+    rng = np.random.default_rng(5)
+    n = 160 + 20 + 2
+    parent = np.full(n, W.NO_PARENT, np.uint32)
+    for k in range(40):
+        parent[4 * k:4 * k + 3] = np.arange(4 * k + 1, 4 * k + 4)
+    parent[180], parent[181] = 181, 180
+    has_tf = np.ones(n, np.uint8)
+    has_tf[[161, 165, 170]] = 0
+    pos = rng.uniform(-20, 20, (n, 3)).astype(F)
+    euler = rng.uniform(-3, 3, (n, 3)).astype(F)
+    scale = rng.uniform(0.5, 1.5, (n, 3)).astype(F)
+    center = rng.uniform(-1, 1, (n, 3)).astype(F)
+    half = rng.uniform(0.05, 2, (n, 3)).astype(F)
+    has_bounds = np.ones(n, bool)
+    has_bounds[[2, 7, 163, 172]] = False
+    w = B.World(device=0)
+    w.set_topology(parent, has_tf)
+    w.upload_trs(pos, euler, scale)
+    with_b = np.nonzero(has_bounds)[0].astype(np.uint32)
+    w.upload_bounds(center[with_b], half[with_b], entity_index=with_b)
+    w.tick(flags=TICK)
+    half_eff = np.where(has_bounds[:, None], half, F(-1))
+    return w, dict(n=n, parent=parent, has_tf=has_tf, center=center, half=half_eff, pos=pos, euler=euler, scale=scale)
+
+
+def _eligible(w, has_tf):
+    return has_tf.astype(bool) & ~w.download_dirty()
+
+
+def test_hierarchy_gaps_and_limbo():
+    w, s = _gappy_world()
+    try:
+        slot, _, _, info = W.flatten_topology(s["parent"], s["has_tf"])
+        live = slot[slot != W.NO_PARENT]
+        assert np.any(np.diff(live.astype(np.int64)) < 0), "slot order should differ from entity order here"
+        assert info["n_limbo"] == 2
+        dirty = w.download_dirty()
+        assert dirty[180] and dirty[181] and dirty.sum() == 2
+        elig = _eligible(w, s["has_tf"])
+        for planes, what in ((None, "no planes"), (wide_view(), "wide view"), (np.array([[1, 0, 0, 0.0]], F), "x >= 0")):
+            got = w.visible(planes, want_world=True, want_normal=True)
+            want = expected(w, s["center"], s["half"], planes, elig)
+            check_records(w, got, want, what)
+            assert np.all(np.diff(got["entities"].astype(np.int64)) > 0)
+            assert not np.isin([180, 181, 161, 165, 170, 2, 7, 163, 172], got["entities"]).any()
+        assert len(w.visible(None)["entities"]) == s["n"] - 2 - 3 - 4
+        # bounds removed by a negative half extent, and given back
+        w.upload_bounds(np.zeros((1, 3), F), np.array([[1, -0.5, 1]], F), first=10)
+        assert 10 not in w.visible(None)["entities"]
+        w.upload_bounds(np.zeros((1, 3), F), np.array([[1, 0, 1]], F), first=10)
+        assert 10 in w.visible(None)["entities"]
+        assert w.download_dirty().sum() == 2  # uploading bounds marks nothing dirty
+    finally:
+        w.close()
+
+
+def test_bounds_survive_set_topology():
+    w, s = _gappy_world()
+    try:
+        n0 = s["n"]
+        # grow to 200: entity 5 loses its Transform, 161 gains one, chains 0 and 1 are cut loose, the cycle is broken up
+        n1 = 200
+        parent = np.full(n1, W.NO_PARENT, np.uint32)
+        parent[:n0] = s["parent"]
+        parent[0:8] = W.NO_PARENT
+        parent[180] = W.NO_PARENT
+        has_tf = np.ones(n1, np.uint8)
+        has_tf[:n0] = s["has_tf"]
+        has_tf[5], has_tf[161] = 0, 1
+        w.set_topology(parent, has_tf)
+        rng = np.random.default_rng(6)
+        new = np.arange(n0, n1)
+        pos = np.concatenate([s["pos"], rng.uniform(-20, 20, (n1 - n0, 3)).astype(F)])
+        w.upload_trs(pos[new], first=n0)
+        w.upload_trs(pos[161:162], first=161)
+        w.tick(flags=TICK)
+        center = np.concatenate([s["center"], np.zeros((n1 - n0, 3), F)])
+        half = np.concatenate([s["half"], np.full((n1 - n0, 3), -1, F)])  # new indices start without bounds
+        elig = _eligible(w, has_tf)
+        assert elig[180] and elig[181] and elig[161] and not elig[5]
+        for planes in (None, wide_view()):
+            got = w.visible(planes, want_world=True, want_normal=True)
+            check_records(w, got, expected(w, center, half, planes, elig), "after growing")
+        ent = w.visible(None)["entities"]
+        assert not np.isin(new, ent).any() and 161 in ent and 180 in ent and 5 not in ent
+        # shrink to 150, then grow to 170: indices 150..169 come back without bounds, the survivors keep theirs
+        for n2 in (150, 170):
+            w.set_topology(np.full(n2, W.NO_PARENT, np.uint32))
+            w.upload_trs(np.zeros((n2, 3), F))
+            w.tick(flags=TICK)
+        want = np.nonzero(renderable(center[:150], half[:150]))[0].astype(np.uint32)
+        got = w.visible(None, want_world=True, want_normal=True)
+        check_records(w, got, want, "after shrinking and growing")
+    finally:
+        w.close()
+
+
+# ---------------------------------------------------------------- call forms
+
+def _desc(planes):
+    return W._cull_desc(planes)
+
+
+def test_call_forms(scene4000):
+    import torch
+
+    w, sc = scene4000
+    planes = wide_view()
+    full = w.visible(planes, want_world=True, want_normal=True)
+    n = len(full["entities"])
+    desc = _desc(planes)
+    total = C.c_uint64(0)
+    # count only
+    assert lib().bge_world_visible(w._h, C.byref(desc), None, None, None, 0, C.byref(total)) == 0 and total.value == n
+    assert w.visible_count(planes) == n
+    # cap < total: BGE_ERR_INVALID, *total filled in, nothing written
+    ent = np.full(n, 0xA5A5A5A5, np.uint32)
+    wm = np.full((n, 16), 7.25, F)
+    total = C.c_uint64(0)
+    rc = lib().bge_world_visible(w._h, C.byref(desc), _p(ent), _p(wm), None, n - 1, C.byref(total))
+    assert rc == -1 and total.value == n
+    assert np.all(ent == 0xA5A5A5A5) and np.all(wm == 7.25)
+    # any subset of the outputs
+    only_n = np.empty((n, 16), F)
+    assert lib().bge_world_visible(w._h, C.byref(desc), None, None, _p(only_n), n, C.byref(total)) == 0
+    assert only_n.tobytes() == full["normal"].tobytes()
+    # n_planes = 17
+    with pytest.raises(B.BgeError) as e:
+        w.visible(np.zeros((17, 4), F))
+    assert e.value.code == -1
+    # device form, room for half the records
+    cap = n // 2
+    pattern = 0x5A
+    d_ent = torch.full((4 * n,), pattern, dtype=torch.uint8, device="cuda:0")
+    d_world = torch.full((64 * n,), pattern, dtype=torch.uint8, device="cuda:0")
+    d_normal = torch.full((64 * n,), pattern, dtype=torch.uint8, device="cuda:0")
+    d_total = torch.zeros(1, dtype=torch.int64, device="cuda:0")
+    torch.cuda.synchronize()
+    w.visible_device(planes, d_ent.data_ptr(), d_world.data_ptr(), d_normal.data_ptr(), cap, d_total.data_ptr())
+    w.sync()
+    assert int(d_total.item()) == n
+    h_ent, h_world, h_normal = d_ent.cpu().numpy(), d_world.cpu().numpy(), d_normal.cpu().numpy()
+    assert h_ent[:4 * cap].tobytes() == full["entities"][:cap].tobytes()
+    assert h_world[:64 * cap].tobytes() == full["world"][:cap].tobytes()
+    assert h_normal[:64 * cap].tobytes() == full["normal"][:cap].tobytes()
+    assert np.all(h_ent[4 * cap:] == pattern) and np.all(h_world[64 * cap:] == pattern) and np.all(h_normal[64 * cap:] == pattern)
+    # device form that only counts
+    d_total.zero_()
+    torch.cuda.synchronize()
+    w.visible_device(planes, 0, 0, 0, 0, d_total.data_ptr())
+    w.sync()
+    assert int(d_total.item()) == n
+
+
+def test_normal_before_a_normal_matrices_tick_is_a_state_error():
+    w, sc = flat_world(100, tick=W.TICK_TRANSFORMS)
+    try:
+        with pytest.raises(B.BgeError) as e:
+            w.download_normal()
+        code = e.value.code
+        with pytest.raises(B.BgeError) as e:
+            w.visible(None, want_normal=True)
+        assert e.value.code == code == -4
+        assert len(w.visible(None)["entities"]) == 100  # the other outputs are not affected
+    finally:
+        w.close()
+
+
+# ---------------------------------------------------------------- the query changes nothing
+
+def test_query_changes_no_state(scene4000):
+    w, _ = scene4000
+    before = (w.download_world().tobytes(), w.download_pose()[0].tobytes(), w.download_pose()[1].tobytes(), w.download_dirty().tobytes(),
+              w.download_normal().tobytes())
+    w.visible(wide_view(), want_world=True, want_normal=True)
+    w.visible(None)
+    after = (w.download_world().tobytes(), w.download_pose()[0].tobytes(), w.download_pose()[1].tobytes(), w.download_dirty().tobytes(),
+             w.download_normal().tobytes())
+    assert before == after
+
+
+def test_ticks_with_queries_equal_ticks_without():
+    sc = make_scene(13, 3000)
+    rng = np.random.default_rng(14)
+    vel = rng.uniform(-3, 3, (3000, 3)).astype(F)
+    ang = rng.uniform(-2, 2, (3000, 3)).astype(F)
+    ang[::2] = 0
+    results = []
+    for query in (False, True):
+        w = B.World(device=0)
+        try:
+            w.set_topology(np.full(3000, W.NO_PARENT, np.uint32))
+            w.upload_trs(sc["pos"], sc["euler"], sc["scale"])
+            w.upload_bodies(np.full(3000, W.BODY_DYNAMIC, np.uint8))
+            w.upload_bounds(sc["center"], sc["half"])
+            w.tick(flags=W.TICK_ALL | W.TICK_NORMAL_MATRICES)
+            w.set_velocities(vel, ang)
+            seen = []
+            for _ in range(10):
+                w.tick(flags=W.TICK_ALL | W.TICK_NORMAL_MATRICES)
+                if query:
+                    seen.append(len(w.visible(wide_view(), want_world=True, want_normal=True)["entities"]))
+            bodies = w.download_bodies()
+            results.append((w.download_world().tobytes(), w.download_pose()[0].tobytes(), w.download_pose()[1].tobytes(),
+                            w.download_normal().tobytes(), bodies["linvel"].tobytes(), bodies["quat"].tobytes(), w.download_dirty().tobytes()))
+            if query:
+                assert min(seen) > 0
+        finally:
+            w.close()
+    assert results[0] == results[1]
+
+
+# ---------------------------------------------------------------- the C++ adapter
+
+def test_adapter_fetch_visible_in_resident_mode(tmp_path):
+    cpp = os.path.join(ROOT, "tests", "cpp")
+    libdir = os.path.join(ROOT, "banggameengine_amd")
+    exe = str(tmp_path / "visible_demo_scene")
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-Wall", "-Wextra", "-Wno-unused-parameter", "-o", exe,
+                           os.path.join(cpp, "visible_demo_scene.cpp"), f"-L{libdir}", "-lbge_world", f"-Wl,-rpath,{libdir}",
+                           "-Wl,-rpath,/opt/rocm/lib"])
+    r = subprocess.run([exe, os.path.join(ROOT, "tests", "golden", "demo_scene.json")], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
+    assert "all checks passed" in r.stdout
