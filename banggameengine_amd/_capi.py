@@ -109,6 +109,10 @@ SYMBOLS = {
     "bge_world_visible": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _u64, C.POINTER(_u64)]),
     "bge_world_visible_device": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _u64, _vp]),
     "bge_frustum_planes": (C.c_int, [_vp, C.c_int, _vp]),
+    "bge_world_upload_draw_keys": (C.c_int, [_vp, _u64, _u64, _vp]),
+    "bge_world_upload_draw_keys_indexed": (C.c_int, [_vp, _u64, _vp, _vp]),
+    "bge_world_draw_batches": (C.c_int, [_vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _u64, C.POINTER(_u64)]),
+    "bge_world_draw_batches_device": (C.c_int, [_vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _u64, _vp]),
     "bge_world_pack_roots": (C.c_int, [_vp, _vp]),
     "bge_world_device_array": (C.c_int, [_vp, C.c_int, C.POINTER(_vp), C.POINTER(_u64)]),
     "bge_world_get_info": (C.c_int, [_vp, C.POINTER(WorldInfo)]),

@@ -16,7 +16,7 @@
 #include <hip/hip_runtime.h>
 
 #include "bge_cull.hpp"
-#include "bge_flatten.hpp"
+#include "bge_cull_device.hpp"
 
 namespace bge {
 
@@ -24,38 +24,6 @@ namespace {
 
 constexpr uint32_t kThreads = kCullEntitiesPerBlock;
 constexpr uint32_t kWaves = kThreads / 64u;
-
-__device__ __forceinline__ bool finite_f(float v) { return __builtin_fabsf(v) < __builtin_inff(); } // false for NaN
-
-// the rule of include/bge_world.h, operation for operation (the file is built with -ffp-contract=off)
-__device__ __forceinline__ bool entity_visible(const CullParams& p, uint64_t e)
-{
-    if (!p.bounds) return false;
-    const uint32_t s = p.slot_of_entity[e];
-    if (s == kNone || s >= p.n_slots) return false;
-    const uint32_t f = p.flag_words[s];
-    if (!(f & kValid) || (f & kTDirty)) return false; // no Transform here (a body kept without one), or limbo / not ticked yet
-    const float* b = p.bounds + 6ull * e;
-    const float cx = b[0], cy = b[1], cz = b[2], hx = b[3], hy = b[4], hz = b[5];
-    if (!(hx >= 0.0f && hy >= 0.0f && hz >= 0.0f && finite_f(hx) && finite_f(hy) && finite_f(hz))) return false;
-    if (!(finite_f(cx) && finite_f(cy) && finite_f(cz))) return false;
-    const float4* m = reinterpret_cast<const float4*>(p.world) + 4ull * s;
-    const float4 r0 = m[0], r1 = m[1], r2 = m[2], r3 = m[3];
-    const float wx = ((cx * r0.x + cy * r1.x) + cz * r2.x) + r3.x;
-    const float wy = ((cx * r0.y + cy * r1.y) + cz * r2.y) + r3.y;
-    const float wz = ((cx * r0.z + cy * r1.z) + cz * r2.z) + r3.z;
-    bool vis = true;
-    for (uint32_t k = 0; k < p.n_planes; ++k) {
-        const float a = p.planes[k][0], bb = p.planes[k][1], c4 = p.planes[k][2], d = p.planes[k][3];
-        const float e0 = (a * r0.x + bb * r0.y) + c4 * r0.z;
-        const float e1 = (a * r1.x + bb * r1.y) + c4 * r1.z;
-        const float e2 = (a * r2.x + bb * r2.y) + c4 * r2.z;
-        const float r = (__builtin_fabsf(e0) * hx + __builtin_fabsf(e1) * hy) + __builtin_fabsf(e2) * hz;
-        const float sd = ((a * wx + bb * wy) + c4 * wz) + d;
-        vis = vis && (sd >= -r); // false for a NaN on either side
-    }
-    return vis;
-}
 
 __global__ void __launch_bounds__(kThreads) k_cull_test(CullParams p)
 {
@@ -158,6 +126,11 @@ __global__ void k_cull_scatter_bounds(const uint32_t* __restrict__ index, uint64
 hipError_t launch_cull_count(hipStream_t stream, const CullParams& p)
 {
     if (p.n_blocks) hipLaunchKernelGGL(k_cull_test, dim3(p.n_blocks), dim3(kThreads), 0, stream, p);
+    return launch_cull_scan(stream, p);
+}
+
+hipError_t launch_cull_scan(hipStream_t stream, const CullParams& p)
+{
     hipLaunchKernelGGL(k_cull_scan, dim3(1), dim3(1024), 0, stream, p);
     return hipGetLastError();
 }

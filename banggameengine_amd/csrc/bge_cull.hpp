@@ -35,6 +35,8 @@ struct CullParams {
 
 // k_cull_test + k_cull_scan: the ballots, the workgroups' offsets and *p.total
 hipError_t launch_cull_count(hipStream_t stream, const CullParams& p);
+// k_cull_scan alone, over block_sum written by another test kernel (bge_batch.hip): the workgroups' offsets and *p.total
+hipError_t launch_cull_scan(hipStream_t stream, const CullParams& p);
 // k_cull_emit from the ballots and offsets launch_cull_count left (same stream, same state): records [0, min(cap, total))
 hipError_t launch_cull_emit(hipStream_t stream, const CullParams& p);
 // bounds[entity] = (centre, half extents) for `count` rows: entity = index ? index[i] : first + i (entities already validated)

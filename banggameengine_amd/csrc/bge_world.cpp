@@ -23,6 +23,7 @@
 #include "bge_broadphase.hpp"
 #include "bge_route.hpp"
 #include "bge_comm.hpp"
+#include "bge_batch.hpp"
 #include "bge_cull.hpp"
 #include "bge_debug.hpp"
 #include "bge_flatten.hpp"
@@ -298,6 +299,10 @@ struct bge_world {
     // bounds_rows >= n_entities rows once it exists), the pass's ballots / counts / offsets, the host entry point's records and total
     DevBuf bounds, cull_ballots, cull_block_sum, cull_block_off, cull_out, cull_total;
     uint64_t bounds_rows = 0;
+    // draw batches (bge_batch.hip): the draw key per ENTITY (allocated with the first upload; all ones = no key; draw_key_rows >=
+    // n_entities rows once it exists), the sort's ping-pong records and digit tables, the host entry point's batches
+    DevBuf draw_keys, batch_sort, batch_hist, batch_out;
+    uint64_t draw_key_rows = 0;
     uint32_t trigger_grid_min = 64;       // more ghosts than this: the broadphase grid answers for the small ones
     // Enter / Exit taken on the device (bge_kernels.hpp TriggerDiff): two key tables (this tick's, last tick's), header + deltas in
     // one device buffer with a page-locked copy.  The overlap sets above stay the truth; `trig_mirror_valid` says that last tick's
@@ -379,7 +384,8 @@ struct bge_world {
                           &stage2, &mass_palette, &normal, &deact, &filter_class, &filter_table, &grav_palette, &bp_partials, &cshape, &cmass, &cfriction, &cinfo, &manifold, &crestitution, &bmanifold, &obstacle_slots, &obstacle_gen, &obstacles, &obstacle_grid, &box_list, &box_count, &frozen, &rs_word, &trig_slot, &trig_entity, &trig_he, &trig_group,
                           &trig_mask, &trig_active, &trig_aabb, &trig_pairs, &trig_count, &trig_lists, &ground_list, &ground_count, &trig_tab[0], &trig_tab[1],
                           &trig_delta_dev, &trig_keys_dev, &trig_pose, &query_in, &query_out, &query_keys, &query_all, &query_all_count, &query_ghosts, &dbg_block_sum, &dbg_block_off,
-                          &dbg_lines, &dbg_total, &bounds, &cull_ballots, &cull_block_sum, &cull_block_off, &cull_out, &cull_total}) {
+                          &dbg_lines, &dbg_total, &bounds, &cull_ballots, &cull_block_sum, &cull_block_off, &cull_out, &cull_total, &draw_keys,
+                          &batch_sort, &batch_hist, &batch_out}) {
             b->release();
         }
         if (trig_delta_host) (void)hipHostFree(trig_delta_host);
@@ -1460,6 +1466,23 @@ try {
             w->bounds_rows = n;
         } else if (n < old_n) {
             HIP_TRY(hipMemsetAsync(static_cast<char*>(w->bounds.p) + n * 24, 0xff, (std::min(old_n, w->bounds_rows) - n) * 24, w->stream));
+        }
+    }
+    // so do the draw keys
+    if (w->draw_keys.p) {
+        const uint64_t old_n = w->flat.n_entities;
+        if (n > w->draw_key_rows) {
+            TmpBuf grown;
+            HIP_TRY(grown.ensure(n * 4));
+            HIP_TRY(hipMemsetAsync(grown.p, 0xff, n * 4, w->stream));
+            const uint64_t keep = std::min(old_n, w->draw_key_rows);
+            if (keep) HIP_TRY(hipMemcpyAsync(grown.p, w->draw_keys.p, keep * 4, hipMemcpyDeviceToDevice, w->stream));
+            HIP_TRY(hipStreamSynchronize(w->stream));
+            std::swap(w->draw_keys.p, grown.p);
+            std::swap(w->draw_keys.bytes, grown.bytes);
+            w->draw_key_rows = n;
+        } else if (n < old_n) {
+            HIP_TRY(hipMemsetAsync(static_cast<char*>(w->draw_keys.p) + n * 4, 0xff, (std::min(old_n, w->draw_key_rows) - n) * 4, w->stream));
         }
     }
     w->any_frozen = any_frozen;
@@ -3381,6 +3404,142 @@ try {
     return BGE_OK;
 }
 BGE_CATCH_ALL("bge_world_visible_device")
+
+// ---------------------------------------------------------------- draw batches (bge_batch.hip)
+static_assert(sizeof(bge_draw_batch) == 8, "bge_draw_batch layout (include/bge_world.h)");
+static_assert(BGE_DRAW_MAX_KEYS == bge::kBatchMaxKeys, "key limit");
+
+namespace {
+
+int upload_draw_keys_impl(bge_world* w, uint64_t first, uint64_t count, const uint32_t* index, const uint32_t* key)
+{
+    if (!key) return fail(BGE_ERR_INVALID, "key is NULL");
+    if (count == 0) return BGE_OK;
+    DeviceGuard guard(w->device);
+    const uint32_t* di = nullptr;
+    if (int rc = stage_index(w, count, index, &di)) return rc;
+    if (!w->draw_keys.p) { // every entity starts without a key: all ones
+        const uint64_t rows = std::max<uint64_t>(w->flat.n_entities, 1);
+        HIP_TRY(w->draw_keys.ensure(rows * 4));
+        HIP_TRY(hipMemsetAsync(w->draw_keys.p, 0xff, rows * 4, w->stream));
+        w->draw_key_rows = rows;
+    }
+    HIP_TRY(w->stage.ensure(count * 4));
+    HIP_TRY(hipMemcpyAsync(w->stage.p, key, count * 4, hipMemcpyHostToDevice, w->stream));
+    HIP_TRY(bge::launch_batch_scatter_keys(w->stream, di, first, count, w->stage.as<uint32_t>(), w->draw_keys.as<uint32_t>()));
+    HIP_TRY(hipStreamSynchronize(w->stream)); // the staging buffers are reused by the next call
+    return BGE_OK;
+}
+
+// cull_params plus the keys and the sort's scratch
+int batch_params(bge_world* w, const bge_cull_desc* desc, uint32_t n_keys, bool want_normal, bge::BatchParams& p)
+{
+    if (n_keys == 0 || n_keys > BGE_DRAW_MAX_KEYS) return fail(BGE_ERR_INVALID, "n_keys = %u outside [1, %u]", n_keys, BGE_DRAW_MAX_KEYS);
+    if (int rc = cull_params(w, desc, want_normal, p.cull)) return rc;
+    p.key = w->draw_keys.as<uint32_t>();
+    p.n_keys = n_keys;
+    const uint64_t rows = std::max<uint64_t>(p.cull.n_entities, 1);
+    const uint64_t tiles = (rows + bge::kBatchTile - 1) / bge::kBatchTile;
+    HIP_TRY(w->batch_sort.ensure(rows * 16));
+    HIP_TRY(w->batch_hist.ensure(tiles * 256 * 4 * 2));
+    uint32_t* rec = w->batch_sort.as<uint32_t>();
+    p.sort_key[0] = rec;
+    p.sort_key[1] = rec + rows;
+    p.sort_entity[0] = rec + 2 * rows;
+    p.sort_entity[1] = rec + 3 * rows;
+    p.hist = w->batch_hist.as<uint32_t>();
+    p.hist_off = p.hist + tiles * 256;
+    return BGE_OK;
+}
+
+} // namespace
+
+int bge_world_upload_draw_keys(bge_world* w, uint64_t first, uint64_t count, const uint32_t* key)
+try {
+    if (int rc = check_range(w, first, count)) return rc;
+    return upload_draw_keys_impl(w, first, count, nullptr, key);
+}
+BGE_CATCH_ALL("bge_world_upload_draw_keys")
+
+int bge_world_upload_draw_keys_indexed(bge_world* w, uint64_t count, const uint32_t* entity_index, const uint32_t* key)
+try {
+    if (int rc = check_range(w, 0, 0)) return rc;
+    if (count && !entity_index) return fail(BGE_ERR_INVALID, "entity_index is NULL");
+    return upload_draw_keys_impl(w, 0, count, entity_index, key);
+}
+BGE_CATCH_ALL("bge_world_upload_draw_keys_indexed")
+
+int bge_world_draw_batches(bge_world* w, const bge_cull_desc* desc, uint32_t n_keys, bge_draw_batch* batches, uint32_t* entities,
+                           float* world16, float* normal16, uint64_t cap, uint64_t* total)
+try {
+    if (!w || !total) return fail(BGE_ERR_INVALID, "NULL argument");
+    *total = 0;
+    DeviceGuard guard(w->device);
+    bge::BatchParams p{};
+    if (int rc = batch_params(w, desc, n_keys, normal16 != nullptr, p)) return rc;
+    HIP_TRY(w->cull_total.ensure(8));
+    p.cull.total = w->cull_total.as<unsigned long long>();
+    HIP_TRY(bge::launch_batch_count(w->stream, p));
+    const bool records = entities || world16 || normal16;
+    if (batches || records) {
+        if (batches) {
+            HIP_TRY(w->batch_out.ensure(static_cast<size_t>(n_keys) * 8));
+            p.batches = w->batch_out.as<uint32_t>();
+        }
+        HIP_TRY(bge::launch_batch_sort(w->stream, p));
+        if (batches) HIP_TRY(hipMemcpyAsync(batches, p.batches, static_cast<size_t>(n_keys) * 8, hipMemcpyDeviceToHost, w->stream));
+    }
+    uint64_t n = 0;
+    HIP_TRY(hipMemcpyAsync(&n, w->cull_total.p, 8, hipMemcpyDeviceToHost, w->stream));
+    HIP_TRY(hipStreamSynchronize(w->stream));
+    *total = n;
+    if (!records || n == 0) return BGE_OK;
+    if (cap < n) return fail(BGE_ERR_INVALID, "draw batches: %llu records, room for %llu", (unsigned long long)n, (unsigned long long)cap);
+    // the records are gathered from the sorted list the sort left (nothing ran in between) into one buffer: indices | world | normal
+    const uint64_t idx_bytes = (n * 4 + 15) & ~15ull;
+    HIP_TRY(w->cull_out.ensure(idx_bytes + n * 64 * ((world16 ? 1 : 0) + (normal16 ? 1 : 0))));
+    char* out = w->cull_out.as<char>();
+    p.cull.out_entities = entities ? reinterpret_cast<uint32_t*>(out) : nullptr;
+    p.cull.out_world = world16 ? reinterpret_cast<float*>(out + idx_bytes) : nullptr;
+    p.cull.out_normal = normal16 ? reinterpret_cast<float*>(out + idx_bytes + (world16 ? n * 64 : 0)) : nullptr;
+    p.cull.cap = n;
+    HIP_TRY(bge::launch_batch_gather(w->stream, p));
+    if (entities) HIP_TRY(hipMemcpyAsync(entities, p.cull.out_entities, n * 4, hipMemcpyDeviceToHost, w->stream));
+    if (world16) HIP_TRY(hipMemcpyAsync(world16, p.cull.out_world, n * 64, hipMemcpyDeviceToHost, w->stream));
+    if (normal16) HIP_TRY(hipMemcpyAsync(normal16, p.cull.out_normal, n * 64, hipMemcpyDeviceToHost, w->stream));
+    HIP_TRY(hipStreamSynchronize(w->stream));
+    return BGE_OK;
+}
+BGE_CATCH_ALL("bge_world_draw_batches")
+
+int bge_world_draw_batches_device(bge_world* w, const bge_cull_desc* desc, uint32_t n_keys, void* batches_device, void* entities_device,
+                                  void* world16_device, void* normal16_device, uint64_t cap, void* total_device)
+try {
+    if (!w || !total_device) return fail(BGE_ERR_INVALID, "NULL argument");
+    if ((reinterpret_cast<uintptr_t>(batches_device) | reinterpret_cast<uintptr_t>(entities_device)) & 3u) {
+        return fail(BGE_ERR_INVALID, "batches / entities must be 4-byte aligned");
+    }
+    if ((reinterpret_cast<uintptr_t>(world16_device) | reinterpret_cast<uintptr_t>(normal16_device)) & 15u) {
+        return fail(BGE_ERR_INVALID, "world16 / normal16 must be 16-byte aligned");
+    }
+    if (reinterpret_cast<uintptr_t>(total_device) & 7u) return fail(BGE_ERR_INVALID, "total must be 8-byte aligned");
+    DeviceGuard guard(w->device);
+    bge::BatchParams p{};
+    if (int rc = batch_params(w, desc, n_keys, normal16_device != nullptr, p)) return rc;
+    p.batches = static_cast<uint32_t*>(batches_device);
+    p.cull.out_entities = static_cast<uint32_t*>(entities_device);
+    p.cull.out_world = static_cast<float*>(world16_device);
+    p.cull.out_normal = static_cast<float*>(normal16_device);
+    p.cull.cap = cap;
+    p.cull.total = static_cast<unsigned long long*>(total_device);
+    HIP_TRY(bge::launch_batch_count(w->stream, p));
+    if (p.batches || (cap && (p.cull.out_entities || p.cull.out_world || p.cull.out_normal))) {
+        HIP_TRY(bge::launch_batch_sort(w->stream, p));
+        HIP_TRY(bge::launch_batch_gather(w->stream, p));
+    }
+    return BGE_OK;
+}
+BGE_CATCH_ALL("bge_world_draw_batches_device")
 
 int bge_frustum_planes(const float m[16], int homogeneous_depth, float planes24[24])
 try {

@@ -204,10 +204,54 @@ public:
         return true;
     }
 
+    // EXTENSION: the draw key of an entity, the caller's id of its mesh + material (MeshRenderer { mesh, material },
+    // src/ecs/MeshRenderer.h).  FetchDrawBatches groups the visible entities by it (include/bge_world.h "Draw batches").  Kept per
+    // EntityId and sent lazily by dense index, as the bounds are.
+    void SetDrawKey(Id id, uint32_t key)
+    {
+        draw_keys_[id] = key;
+        draw_keys_stale_ = true;
+    }
+    void ClearDrawKey(Id id)
+    {
+        if (draw_keys_.erase(id)) draw_keys_stale_ = true;
+    }
+    // The visible entities (FetchVisible's rule) whose key is below n_keys, sorted by (key, index): batches[k] is the range of `out`
+    // that holds key k.  One query on the device, one copy of the listed matrices into their Transform::world.
+    bool FetchDrawBatches(SceneT& scene, const float planes[][4], size_t n, uint32_t n_keys, std::vector<bge_draw_batch>& batches,
+                          std::vector<Id>& out)
+    {
+        out.clear();
+        batches.clear();
+        if (!ok() || !UploadBounds() || !UploadDrawKeys()) return false;
+        bge_cull_desc desc{};
+        desc.struct_size = sizeof desc;
+        desc.n_planes = static_cast<uint32_t>(n);
+        if (n > BGE_CULL_MAX_PLANES) return Log("FetchDrawBatches: more than 16 planes");
+        if (n_keys == 0 || n_keys > BGE_DRAW_MAX_KEYS) return Log("FetchDrawBatches: n_keys outside [1, 65536]");
+        if (n) std::memcpy(desc.planes, planes, n * 16);
+        const size_t cap = ids_.size();
+        index_list_.resize(cap);
+        batches.resize(n_keys);
+        if (!down_.resize(cap * 16 + 1)) return Log("bge_host_alloc");
+        uint64_t total = 0;
+        if (bge_world_draw_batches(world_, &desc, n_keys, batches.data(), index_list_.data(), down_.data(), nullptr, cap, &total) != BGE_OK) {
+            batches.clear();
+            return Log("bge_world_draw_batches");
+        }
+        out.reserve(total);
+        for (uint64_t k = 0; k < total; ++k) { // (every listed entity owns a Transform: out[k] is record k)
+            const Id id = ids_[index_list_[k]];
+            if (auto* t = scene.GetTransform(id)) std::memcpy(t->world, &down_[16 * k], 64);
+            out.push_back(id);
+        }
+        return true;
+    }
+
     // --- TransformSystem::Update(Scene&)
     bool UpdateTransforms(SceneT& scene)
     {
-        if (!ok() || !RefreshTopology(scene) || !UploadDirtyTransforms(scene) || !UploadBounds()) return false;
+        if (!ok() || !RefreshTopology(scene) || !UploadDirtyTransforms(scene) || !UploadBounds() || !UploadDrawKeys()) return false;
         if (bge_world_tick(world_, 0.0f, gravity, BGE_TICK_TRANSFORMS) != BGE_OK) return Log("bge_world_tick");
         const size_t n = ids_.size();
         if (resident) {
@@ -552,6 +596,33 @@ private:
         return true;
     }
 
+    // the same for the draw keys
+    bool UploadDrawKeys()
+    {
+        if (!draw_keys_stale_) return true;
+        const size_t n = ids_.size();
+        draw_keys_want_.assign(n, BGE_NO_DRAW_KEY);
+        for (const auto& kv : draw_keys_) {
+            auto it = index_of_.find(kv.first);
+            if (it != index_of_.end()) draw_keys_want_[it->second] = kv.second;
+        }
+        draw_keys_sent_.resize(n, BGE_NO_DRAW_KEY); // (a new index has none on the device either)
+        index_list_.clear();
+        draw_keys_stage_.clear();
+        for (size_t i = 0; i < n; ++i) {
+            if (draw_keys_want_[i] == draw_keys_sent_[i]) continue;
+            index_list_.push_back(static_cast<uint32_t>(i));
+            draw_keys_stage_.push_back(draw_keys_want_[i]);
+        }
+        if (!index_list_.empty() &&
+            bge_world_upload_draw_keys_indexed(world_, index_list_.size(), index_list_.data(), draw_keys_stage_.data()) != BGE_OK) {
+            return Log("bge_world_upload_draw_keys_indexed");
+        }
+        draw_keys_sent_.swap(draw_keys_want_);
+        draw_keys_stale_ = false;
+        return true;
+    }
+
     bool Log(const char* what) const
     {
         std::fprintf(stderr, "[GPU] %s failed: %s\n", what, bge_last_error());
@@ -682,7 +753,12 @@ private:
         //  hierarchy has not changed, so nothing below it is taken for re-parented)
         live_ = transforms.size();
         bounds_stale_ = true; // an entity may sit on another index now
+        draw_keys_stale_ = true;
         if (bge_world_set_topology(world_, ids_.size(), parent_.data(), has_tf_.data()) != BGE_OK) return Log("bge_world_set_topology");
+        // the device has just cleared the per-index rows from ids_.size() on: what was "last sent" beyond it is gone as well, so a
+        // later regrowth sends those rows again even when no upload ran in between
+        if (bounds_sent_.size() > ids_.size() * 6) bounds_sent_.resize(ids_.size() * 6);
+        if (draw_keys_sent_.size() > ids_.size()) draw_keys_sent_.resize(ids_.size());
         // a reused index must not inherit the previous owner's device state: force a full upload
         for (uint32_t i : fresh_) {
             if (auto* t = scene.GetTransform(ids_[i])) t->dirty = true;
@@ -835,6 +911,9 @@ private:
     std::unordered_map<Id, Bounds> bounds_;     // what SetBounds was given, per EntityId
     std::vector<float> bounds_want_, bounds_sent_; // per dense index: the row the device should hold / was last sent
     bool bounds_stale_ = false;
+    std::unordered_map<Id, uint32_t> draw_keys_; // what SetDrawKey was given, per EntityId
+    std::vector<uint32_t> draw_keys_want_, draw_keys_sent_, draw_keys_stage_; // per dense index: wanted / last sent; the rows that travel
+    bool draw_keys_stale_ = false;
     std::vector<float> last_pose_;              // position + euler the physics write-back stored (6 floats per index)
     std::vector<float> last_scale_;             // scale as last uploaded (3 floats per index)
     std::vector<float> stage_, repack_;

@@ -89,6 +89,9 @@ def _debug_desc(flags, region):
 
 # frustum culling (bge_world_visible*): bge_cull_desc from an (n, 4) array of inward-pointing planes (a, b, c, d), n <= 16
 CULL_MAX_PLANES = 16
+# draw batches (bge_world_draw_batches*): the key of an entity that has none, and the largest n_keys
+NO_DRAW_KEY = 0xFFFFFFFF
+DRAW_MAX_KEYS = 65536
 
 
 def _cull_desc(planes):
@@ -548,6 +551,46 @@ class World:
         vp = lambda a: C.c_void_p(a) if a else None
         check(lib().bge_world_visible_device(self._h, C.byref(desc), vp(entities_ptr), vp(world_ptr), vp(normal_ptr), int(cap),
                                              C.c_void_p(total_ptr)))
+
+    # -- draw batches (include/bge_world.h states membership and order)
+    def upload_draw_keys(self, keys, first=0, entity_index=None):
+        """Draw key (uint32, the caller's id of a mesh + material) of a range of entities, or of entity_index[i] per row."""
+        k = _arr(keys, np.uint32).reshape(-1)
+        if entity_index is None:
+            check(lib().bge_world_upload_draw_keys(self._h, first, len(k), _p(k)))
+        else:
+            idx = _arr(entity_index, np.uint32).reshape(-1)
+            if len(idx) != len(k):
+                raise ValueError(f"{len(idx)} indices, {len(k)} keys")
+            check(lib().bge_world_upload_draw_keys_indexed(self._h, len(idx), _p(idx), _p(k)))
+
+    def draw_batches(self, planes, n_keys, want_world=True, want_normal=False):
+        """The visible entities whose key is below n_keys, sorted by (key, entity index): dict of "batches" (n_keys, 2) uint32
+        (first_instance, instance_count per key), "entities" (n,) uint32 and, when asked for, "world" and "normal" (n, 16)."""
+        desc = _cull_desc(planes)
+        n_keys = int(n_keys)
+        total = C.c_uint64(0)
+        check(lib().bge_world_draw_batches(self._h, C.byref(desc), n_keys, None, None, None, None, 0, C.byref(total)))
+        n = int(total.value)
+        batches = np.zeros((n_keys, 2), np.uint32)
+        ent = np.empty(n, np.uint32)
+        wm = np.empty((n, 16), np.float32) if want_world else None
+        nm = np.empty((n, 16), np.float32) if want_normal else None
+        check(lib().bge_world_draw_batches(self._h, C.byref(desc), n_keys, _p(batches), _p(ent), _p(wm), _p(nm), n, C.byref(total)))
+        out = {"batches": batches, "entities": ent}
+        if want_world:
+            out["world"] = wm
+        if want_normal:
+            out["normal"] = nm
+        return out
+
+    def draw_batches_device(self, planes, n_keys, batches_ptr, entities_ptr, world_ptr, normal_ptr, cap, total_ptr):
+        """The same between device pointers (0 / None leaves an output out): n_keys batches, room for cap records each, total_ptr
+        one uint64.  Enqueued on the world's stream without synchronisation; records beyond cap are counted, not written."""
+        desc = _cull_desc(planes)
+        vp = lambda a: C.c_void_p(a) if a else None
+        check(lib().bge_world_draw_batches_device(self._h, C.byref(desc), int(n_keys), vp(batches_ptr), vp(entities_ptr), vp(world_ptr),
+                                                  vp(normal_ptr), int(cap), C.c_void_p(total_ptr)))
 
     def pack_roots(self, dst_device_ptr: int | None = None):
         check(lib().bge_world_pack_roots(self._h, C.c_void_p(dst_device_ptr) if dst_device_ptr else None))

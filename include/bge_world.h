@@ -617,6 +617,50 @@ BGE_API int bge_world_visible_device(bge_world* world, const bge_cull_desc* desc
                                      void* normal16_device, uint64_t cap, void* total_device);
 BGE_API int bge_frustum_planes(const float viewproj16[16], int homogeneous_depth, float planes24[24]);
 
+/*
+ * Draw batches: the visible entities grouped by draw key, so that one instanced or indirect draw per key can be issued straight
+ * from the buffers.  An EXTENSION on top of the frustum culling above (the reference's renderer walks MeshRenderer { mesh,
+ * material } per entity, src/render/Renderer.cpp:606-700).  The rules below are the specification.
+ *   Keys      bge_world_upload_draw_keys / _indexed: one uint32_t per entity, the caller's id for a mesh + material combination.
+ *             Stored per ENTITY (not per slot), as the bounds are.  Every entity starts with BGE_NO_DRAW_KEY.  Any 32-bit value
+ *             may be uploaded.  bge_world_set_topology keeps the keys of surviving indices; an index beyond the old entity count
+ *             (also one that was removed and is reused after growth) starts without a key.  Uploading keys marks nothing dirty.
+ *   Members   entity e is in the result iff it is VISIBLE by the rule of bge_world_visible for the same desc (renderable, owns a
+ *             Transform, clean, sd >= -r on every plane) and key[e] < n_keys.  Entities whose key is >= n_keys, BGE_NO_DRAW_KEY
+ *             included, are left out and not counted.  With n_keys = 1 and every key 0 the result equals bge_world_visible's,
+ *             record for record.
+ *   Order     records are sorted by (key, entity index), both ascending.  batches[k].instance_count is the number of records
+ *             with key k; batches[k].first_instance is the sum of the counts of the keys below k, for empty batches too, so all
+ *             n_keys entries are defined.  *total is the sum of all counts.  Record i of entities, world16 and normal16 belongs to
+ *             the same entity; the matrices equal bge_world_download_world_indexed / bge_world_download_normal bit for bit.  The
+ *             same state gives the same bytes on every call.
+ *   bge_world_draw_batches         the convention of bge_world_visible; synchronises the world's stream.  batches, when not NULL,
+ *                                  has n_keys entries and is always filled, whatever cap is.  With the three record outputs NULL
+ *                                  the call only counts.  cap < *total is BGE_ERR_INVALID with *total and batches filled in and no
+ *                                  record written.
+ *   bge_world_draw_batches_device  device pointers (batches and entities 4-byte, the matrices 16-byte, total 8-byte aligned; all
+ *                                  but total may be NULL; a misaligned pointer is BGE_ERR_INVALID).  Enqueued on the world's
+ *                                  stream, no synchronisation.  Records at positions >= cap are not written and are still counted;
+ *                                  batches always holds the full counts.
+ *   n_keys == 0 or n_keys > BGE_DRAW_MAX_KEYS is BGE_ERR_INVALID; n_planes > 16 and a wrong struct_size as for bge_world_visible;
+ *   normal16 before a BGE_TICK_NORMAL_MATRICES tick is BGE_ERR_STATE; so is a call before bge_world_set_topology.  An indexed
+ *   upload with an index outside the world is BGE_ERR_INVALID and uploads nothing.
+ *   The query changes no world state, and does not change what the next bge_world_visible returns (nor the other way round).
+ */
+#define BGE_NO_DRAW_KEY 0xffffffffu
+#define BGE_DRAW_MAX_KEYS 65536u
+typedef struct bge_draw_batch {
+    uint32_t first_instance;
+    uint32_t instance_count;
+} bge_draw_batch; /* 8 bytes */
+BGE_API int bge_world_upload_draw_keys(bge_world* world, uint64_t first, uint64_t count, const uint32_t* key);
+BGE_API int bge_world_upload_draw_keys_indexed(bge_world* world, uint64_t count, const uint32_t* entity_index, const uint32_t* key);
+BGE_API int bge_world_draw_batches(bge_world* world, const bge_cull_desc* desc, uint32_t n_keys, bge_draw_batch* batches,
+                                   uint32_t* entities, float* world16, float* normal16, uint64_t cap, uint64_t* total);
+BGE_API int bge_world_draw_batches_device(bge_world* world, const bge_cull_desc* desc, uint32_t n_keys, void* batches_device,
+                                          void* entities_device, void* world16_device, void* normal16_device, uint64_t cap,
+                                          void* total_device);
+
 /* Multi-GPU support: compact the world matrices of all roots (entity order) into one buffer that the
  * caller all-gathers across ranks (one collective per frame).  dst = NULL packs into the world's own
  * BGE_ARRAY_ROOT_WORLDS buffer; otherwise dst is a device pointer with room for n_roots*16 floats. */

@@ -1,0 +1,444 @@
+"""Draw batches on the device (include/bge_world.h bge_world_draw_batches*) against draw_batches_ref() of test_draw_batches_cpu.py.
+
+Everything is integer work on top of the visibility rule, so every comparison is exact: the expected record order is
+draw_batches_ref() fed visible_ref32() of the DEVICE's own downloaded world matrices and the uploaded keys; batches, total,
+entities and the bytes of world16 / normal16 must be equal, for every entity.
+
+SORT_TILE = 2048 is the number of records one workgroup of a sort pass owns (kBatchTile in csrc/bge_batch.hpp); the sizes below
+include it - 1, it, it + 1 and two tiles + 1, next to the 64-lane and 256-thread edges of the visibility pass, and 262144 + 257
+entities (129 tiles x 256 digits = 33024 table entries: 36 per thread of the single-workgroup scan)."""
+from __future__ import annotations
+
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import banggameengine_amd as B
+from banggameengine_amd import world as W
+from banggameengine_amd._capi import lib
+
+from test_draw_batches_cpu import NO_KEY, draw_batches_ref
+from test_visible_cpu import F, make_scene, narrow_view, visible_ref32, wide_view
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+TICK = W.TICK_TRANSFORMS | W.TICK_NORMAL_MATRICES
+BEHIND_EVERYTHING = np.array([[0, 0, 1, -1.0e6]], F)  # z >= 1e6
+SORT_TILE = 2048
+INVALID, STATE = -1, -4
+
+
+def _p(a):
+    return a.ctypes.data_as(C.c_void_p)
+
+
+def download_world_indexed(w, idx):
+    idx = np.ascontiguousarray(idx, np.uint32)
+    out = np.empty((len(idx), 16), F)
+    if len(idx):
+        B._capi.check(lib().bge_world_download_world_indexed(w._h, len(idx), _p(idx), _p(out)))
+    return out
+
+
+def flat_world(n, seed=7, tick=TICK):
+    sc = make_scene(seed, n)
+    w = B.World(device=0)
+    w.set_topology(np.full(n, W.NO_PARENT, np.uint32))
+    w.upload_trs(sc["pos"], sc["euler"], sc["scale"])
+    w.upload_bounds(sc["center"], sc["half"])
+    w.tick(flags=tick)
+    return w, sc
+
+
+def count_only(w, planes, n_keys):
+    desc = W._cull_desc(planes)
+    total = C.c_uint64(0)
+    assert lib().bge_world_draw_batches(w._h, C.byref(desc), n_keys, None, None, None, None, 0, C.byref(total)) == 0
+    return int(total.value)
+
+
+def check(w, world, planes, n_keys, keys, center, half, what, eligible=None, normal=None):
+    """One query against the reference: world is w.download_world() (shared between the checks of one world state)."""
+    mask = visible_ref32(world, center, half, planes, eligible)
+    batches, entities = draw_batches_ref(mask, keys, n_keys)
+    got = w.draw_batches(planes, n_keys, want_world=True, want_normal=normal is not None)
+    assert got["batches"].shape == (n_keys, 2) and got["batches"].dtype == np.uint32
+    assert np.array_equal(got["entities"], entities), f"{what}: {len(got['entities'])} records, the reference gives {len(entities)}"
+    assert np.array_equal(got["batches"], batches), f"{what}: batches differ"
+    assert count_only(w, planes, n_keys) == len(entities)
+    assert got["world"].tobytes() == download_world_indexed(w, entities).tobytes(), f"{what}: world16 differs from the indexed download"
+    if normal is not None:
+        assert got["normal"].tobytes() == normal[entities].tobytes(), f"{what}: normal16 differs from download_normal"
+    return got
+
+
+@pytest.fixture(scope="module")
+def scene4000():
+    w, sc = flat_world(4000)
+    yield w, sc, w.download_world(), w.download_normal()
+    w.close()
+
+
+# ---------------------------------------------------------------- sizes where the passes can break
+
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 255, 256, 257, 513, SORT_TILE - 1, SORT_TILE, SORT_TILE + 1, 2 * SORT_TILE + 1, 262144 + 257])
+def test_sizes(n):
+    w, sc = flat_world(n, seed=11)
+    try:
+        rng = np.random.default_rng(n)
+        keys = rng.integers(0, 300, n).astype(np.uint32)
+        w.upload_draw_keys(keys)
+        world, normal = w.download_world(), w.download_normal()
+        everyone = np.arange(n, dtype=np.uint32)
+        half = sc["half"].copy()
+        for stage in ("all renderable", "every third renderable"):
+            if stage == "every third renderable":  # the others lose their bounds through a negative half extent
+                drop = everyone[everyone % 3 != 0]
+                if len(drop):
+                    w.upload_bounds(np.zeros((len(drop), 3), F), np.full((len(drop), 3), -1, F), entity_index=drop)
+                half[drop] = -1
+            for planes, view in ((None, "no planes"), (BEHIND_EVERYTHING, "none visible"), (wide_view(), "wide view")):
+                for n_keys in (300, 200) if view != "none visible" else (300,):  # two passes, every key inside; one pass, a third left out
+                    got = check(w, world, planes, n_keys, keys, sc["center"], half, f"n={n} {stage}, {view}, n_keys={n_keys}", normal=normal)
+                    if view == "none visible":
+                        assert len(got["entities"]) == 0 and not got["batches"].any()
+                    if view == "no planes" and stage == "all renderable" and n_keys == 300:
+                        assert len(got["entities"]) == n
+    finally:
+        w.close()
+
+
+# ---------------------------------------------------------------- n_keys: no pass, one pass, two passes, the digit boundary
+
+@pytest.mark.parametrize("n_keys", [1, 2, 255, 256, 257, 65536])
+def test_n_keys(scene4000, n_keys):
+    w, sc, world, normal = scene4000
+    rng = np.random.default_rng(n_keys)
+    keys = rng.integers(0, n_keys + 2, 4000).astype(np.uint32)  # n_keys and n_keys + 1 are left out
+    keys[rng.integers(0, 4000, 40)] = NO_KEY
+    w.upload_draw_keys(keys)
+    for planes, view in ((None, "no planes"), (wide_view(), "wide"), (narrow_view(), "narrow")):
+        got = check(w, world, planes, n_keys, keys, sc["center"], sc["half"], f"n_keys={n_keys}, {view}", normal=normal)
+        assert 0 < len(got["entities"]) < 4000
+
+
+# ---------------------------------------------------------------- key patterns
+
+def _patterns(n):
+    rng = np.random.default_rng(21)
+    e = np.arange(n, dtype=np.uint32)
+    skew = np.full(n, 5, np.uint32)
+    skew[rng.random(n) < 0.01] = 9
+    per_wave = np.zeros(n, np.uint32)
+    per_wave[(e % 64) == (e // 64) % 64] = 1 + (e[(e % 64) == (e // 64) % 64] // 64) % 200
+    mixed = rng.integers(0, 64, n).astype(np.uint32)
+    mixed[0::7] = 64           # = n_keys
+    mixed[1::11] = 65          # above it
+    mixed[2::13] = 70000
+    mixed[3::17] = NO_KEY
+    return {
+        "all equal": (np.full(n, 3, np.uint32), 4),
+        "all distinct, descending": ((n - 1 - e).astype(np.uint32), n),
+        "random over 64": (rng.integers(0, 64, n).astype(np.uint32), 64),
+        "99 % in one key": (skew, 16),
+        "one odd key per wave": (per_wave, 256),
+        "keys at and above n_keys, and none": (mixed, 64),
+    }
+
+
+@pytest.mark.parametrize("pattern", ["all equal", "all distinct, descending", "random over 64", "99 % in one key", "one odd key per wave",
+                                     "keys at and above n_keys, and none"])
+def test_key_patterns(scene4000, pattern):
+    w, sc, world, normal = scene4000
+    keys, n_keys = _patterns(4000)[pattern]
+    w.upload_draw_keys(keys)
+    for planes, view in ((None, "no planes"), (wide_view(), "wide")):
+        got = check(w, world, planes, n_keys, keys, sc["center"], sc["half"], f"{pattern}, {view}", normal=normal)
+        assert len(got["entities"]) > 0
+        if pattern == "all distinct, descending" and planes is None:
+            assert np.array_equal(got["entities"], np.arange(3999, -1, -1, dtype=np.uint32))
+
+
+# ---------------------------------------------------------------- against bge_world_visible
+
+def test_one_key_equals_visible_and_leaves_visible_alone(scene4000):
+    w, sc, world, normal = scene4000
+    w.upload_draw_keys(np.zeros(4000, np.uint32))
+    for planes in (None, wide_view(), narrow_view()):
+        vis = w.visible(planes, want_world=True, want_normal=True)
+        got = w.draw_batches(planes, 1, want_world=True, want_normal=True)
+        assert got["batches"].tolist() == [[0, len(vis["entities"])]]
+        for name in ("entities", "world", "normal"):
+            assert got[name].tobytes() == vis[name].tobytes(), name
+    # another key set in between: the next bge_world_visible returns what it returned before, and the other way round
+    keys = np.random.default_rng(3).integers(0, 500, 4000).astype(np.uint32)
+    w.upload_draw_keys(keys)
+    before = w.visible(wide_view(), want_world=True, want_normal=True)
+    first = w.draw_batches(wide_view(), 400, want_world=True, want_normal=True)
+    after = w.visible(wide_view(), want_world=True, want_normal=True)
+    second = w.draw_batches(wide_view(), 400, want_world=True, want_normal=True)
+    for name in ("entities", "world", "normal"):
+        assert before[name].tobytes() == after[name].tobytes(), name
+    for name in ("batches", "entities", "world", "normal"):
+        assert first[name].tobytes() == second[name].tobytes(), name
+    assert len(first["entities"]) < len(before["entities"])  # keys 400..499 are left out
+
+
+def test_determinism(scene4000):
+    w, sc, world, normal = scene4000
+    keys = np.random.default_rng(4).integers(0, 1000, 4000).astype(np.uint32)
+    w.upload_draw_keys(keys)
+    a = w.draw_batches(wide_view(), 1000, want_world=True, want_normal=True)
+    b = w.draw_batches(wide_view(), 1000, want_world=True, want_normal=True)
+    for name in ("batches", "entities", "world", "normal"):
+        assert a[name].tobytes() == b[name].tobytes(), name
+    before = (w.download_world().tobytes(), w.download_dirty().tobytes(), w.download_normal().tobytes())
+    assert before == (world.tobytes(), np.zeros(4000, np.uint8).tobytes(), normal.tobytes())  # the query changes no state
+
+
+# ---------------------------------------------------------------- entities that must be absent
+
+def _gappy_world():
+    """40 chains of depth 4 with the child listed BEFORE its parent (entity 4k+i hangs on 4k+i+1), then 20 free entities of which
+    some have no Transform and some no bounds, then a two-entity parent cycle.  Entity 175 is marked dirty after the tick."""
+    rng = np.random.default_rng(5)
+    n = 160 + 20 + 2
+    parent = np.full(n, W.NO_PARENT, np.uint32)
+    for k in range(40):
+        parent[4 * k:4 * k + 3] = np.arange(4 * k + 1, 4 * k + 4)
+    parent[180], parent[181] = 181, 180
+    has_tf = np.ones(n, np.uint8)
+    has_tf[[161, 165, 170]] = 0
+    center = rng.uniform(-1, 1, (n, 3)).astype(F)
+    half = rng.uniform(0.05, 2, (n, 3)).astype(F)
+    no_bounds = [2, 7, 163, 172]
+    half[no_bounds] = -1
+    w = B.World(device=0)
+    w.set_topology(parent, has_tf)
+    w.upload_trs(rng.uniform(-20, 20, (n, 3)).astype(F), rng.uniform(-3, 3, (n, 3)).astype(F), rng.uniform(0.5, 1.5, (n, 3)).astype(F))
+    with_b = np.setdiff1d(np.arange(n), no_bounds).astype(np.uint32)
+    w.upload_bounds(center[with_b], half[with_b], entity_index=with_b)
+    w.tick(flags=TICK)
+    w.mark_dirty(first=175, count=1)
+    return w, dict(n=n, parent=parent, has_tf=has_tf, center=center, half=half)
+
+
+def test_entities_that_must_be_absent():
+    w, s = _gappy_world()
+    try:
+        n = s["n"]
+        slot, _, _, info = W.flatten_topology(s["parent"], s["has_tf"])
+        live = slot[slot != W.NO_PARENT]
+        assert np.any(np.diff(live.astype(np.int64)) < 0), "slot order should differ from entity order here"
+        dirty = w.download_dirty().astype(bool)
+        assert dirty[180] and dirty[181] and dirty[175] and dirty.sum() == 3
+        keys = (np.arange(n, dtype=np.uint32) * 7) % 5
+        keys[[20, 21, 100]] = NO_KEY
+        w.upload_draw_keys(keys)
+        assert w.download_dirty().sum() == 3  # uploading keys marks nothing dirty
+        elig = s["has_tf"].astype(bool) & ~dirty
+        world, normal = w.download_world(), w.download_normal()
+        for planes, what in ((None, "no planes"), (wide_view(), "wide view"), (np.array([[1, 0, 0, 0.0]], F), "x >= 0")):
+            got = check(w, world, planes, 5, keys, s["center"], s["half"], what, eligible=elig, normal=normal)
+            assert not np.isin([180, 181, 175, 161, 165, 170, 2, 7, 163, 172, 20, 21, 100], got["entities"]).any()
+        assert len(w.draw_batches(None, 5)["entities"]) == n - 3 - 3 - 4 - 3
+    finally:
+        w.close()
+
+
+# ---------------------------------------------------------------- bge_world_set_topology
+
+def test_keys_through_shrink_and_growth():
+    n0, n1, n2 = 100, 60, 120
+    w, sc = flat_world(n0, seed=9)
+    try:
+        keys = (np.arange(n0, dtype=np.uint32) % 5)
+        w.upload_draw_keys(keys)
+        big = make_scene(9, n2)
+        for n in (n1, n2):
+            w.set_topology(np.full(n, W.NO_PARENT, np.uint32))
+            w.upload_trs(big["pos"][:n], big["euler"][:n], big["scale"][:n])
+            w.upload_bounds(big["center"][:n], big["half"][:n])  # everyone is renderable: only the key decides
+            w.tick(flags=TICK)
+        want = np.full(n2, NO_KEY, np.uint32)
+        want[:n1] = keys[:n1]  # survivors keep theirs; 60..99 were removed and are reused, 100..119 are new: none has a key
+        world, normal = w.download_world(), w.download_normal()
+        got = check(w, world, None, 5, want, big["center"], big["half"], "after shrinking and growing", normal=normal)
+        assert len(got["entities"]) == n1 and got["entities"].max() < n1
+        w.upload_draw_keys(np.array([4, 0], np.uint32), entity_index=np.array([70, 110], np.uint32))
+        want[70], want[110] = 4, 0
+        got = check(w, world, None, 5, want, big["center"], big["half"], "after giving two of them keys", normal=normal)
+        assert 70 in got["entities"] and 110 in got["entities"]
+        # growth beyond the allocated rows
+        w.set_topology(np.full(300, W.NO_PARENT, np.uint32))
+        sc3 = make_scene(10, 300)
+        w.upload_trs(sc3["pos"], sc3["euler"], sc3["scale"])
+        w.upload_bounds(sc3["center"], sc3["half"])
+        w.tick(flags=TICK)
+        want = np.concatenate([want, np.full(180, NO_KEY, np.uint32)])
+        check(w, w.download_world(), wide_view(), 5, want, sc3["center"], sc3["half"], "after growing past the allocation", normal=w.download_normal())
+        assert count_only(w, None, 5) == n1 + 2
+    finally:
+        w.close()
+
+
+# ---------------------------------------------------------------- call forms
+
+@pytest.fixture()
+def keyed4000(scene4000):
+    w, sc, world, normal = scene4000
+    keys = np.random.default_rng(8).integers(0, 310, 4000).astype(np.uint32)
+    w.upload_draw_keys(keys)
+    full = check(w, world, wide_view(), 300, keys, sc["center"], sc["half"], "full answer", normal=normal)
+    assert len(full["entities"]) > 100
+    return w, full
+
+
+def test_host_form_with_too_little_room(keyed4000):
+    w, full = keyed4000
+    n = len(full["entities"])
+    desc = W._cull_desc(wide_view())
+    batches = np.full((300, 2), 0xA5A5A5A5, np.uint32)
+    ent = np.full(n, 0xA5A5A5A5, np.uint32)
+    wm = np.full((n, 16), 7.25, F)
+    nm = np.full((n, 16), 7.25, F)
+    total = C.c_uint64(0)
+    rc = lib().bge_world_draw_batches(w._h, C.byref(desc), 300, _p(batches), _p(ent), _p(wm), _p(nm), n - 1, C.byref(total))
+    assert rc == INVALID and total.value == n
+    assert np.array_equal(batches, full["batches"])
+    assert np.all(ent == 0xA5A5A5A5) and np.all(wm == 7.25) and np.all(nm == 7.25)
+    # batches alone, and any single record output
+    batches[:] = 0
+    assert lib().bge_world_draw_batches(w._h, C.byref(desc), 300, _p(batches), None, None, None, 0, C.byref(total)) == 0
+    assert total.value == n and np.array_equal(batches, full["batches"])
+    assert lib().bge_world_draw_batches(w._h, C.byref(desc), 300, None, None, None, _p(nm), n, C.byref(total)) == 0
+    assert nm.tobytes() == full["normal"].tobytes()
+
+
+def test_device_form(keyed4000):
+    import torch
+
+    w, full = keyed4000
+    n = len(full["entities"])
+    planes = wide_view()
+    cap = n // 2
+    pattern = 0x5A
+
+    def buffers():
+        return (torch.full((8 * 300,), pattern, dtype=torch.uint8, device="cuda:0"), torch.full((4 * n,), pattern, dtype=torch.uint8, device="cuda:0"),
+                torch.full((64 * n,), pattern, dtype=torch.uint8, device="cuda:0"), torch.full((64 * n,), pattern, dtype=torch.uint8, device="cuda:0"))
+
+    d_total = torch.zeros(1, dtype=torch.int64, device="cuda:0")
+    want = (full["batches"].tobytes(), full["entities"].tobytes(), full["world"].tobytes(), full["normal"].tobytes())
+    width = (0, 4, 64, 64)
+    # room for half the records: the prefix of the full answer, the guard untouched, total and batches complete
+    bufs = buffers()
+    torch.cuda.synchronize()
+    w.draw_batches_device(planes, 300, *[b.data_ptr() for b in bufs], cap, d_total.data_ptr())
+    w.sync()
+    assert int(d_total.item()) == n
+    host = [b.cpu().numpy() for b in bufs]
+    assert host[0].tobytes() == want[0]
+    for k in (1, 2, 3):
+        assert host[k][:width[k] * cap].tobytes() == want[k][:width[k] * cap], k
+        assert np.all(host[k][width[k] * cap:] == pattern), k
+    # NULL outputs in every combination (cap = n)
+    for combo in range(16):
+        bufs = buffers()
+        d_total.zero_()
+        torch.cuda.synchronize()
+        ptrs = [b.data_ptr() if (combo >> k) & 1 else 0 for k, b in enumerate(bufs)]
+        w.draw_batches_device(planes, 300, *ptrs, n, d_total.data_ptr())
+        w.sync()
+        assert int(d_total.item()) == n, combo
+        for k, b in enumerate(bufs):
+            h = b.cpu().numpy()
+            if (combo >> k) & 1:
+                assert h.tobytes() == want[k], (combo, k)
+            else:
+                assert np.all(h == pattern), (combo, k)
+    # misaligned pointers
+    bufs = buffers()
+    base = [b.data_ptr() for b in bufs]
+    for k, off in ((0, 2), (1, 2), (2, 8), (3, 4)):
+        ptrs = list(base)
+        ptrs[k] += off
+        with pytest.raises(B.BgeError) as e:
+            w.draw_batches_device(planes, 300, *ptrs, n, d_total.data_ptr())
+        assert e.value.code == INVALID, k
+    with pytest.raises(B.BgeError) as e:
+        w.draw_batches_device(planes, 300, *base, n, d_total.data_ptr() + 4)
+    assert e.value.code == INVALID
+
+
+# ---------------------------------------------------------------- errors
+
+def test_errors(scene4000):
+    w, sc, world, normal = scene4000
+    for n_keys in (0, 65537):
+        with pytest.raises(B.BgeError) as e:
+            w.draw_batches(None, n_keys)
+        assert e.value.code == INVALID, n_keys
+    with pytest.raises(B.BgeError) as e:
+        w.draw_batches(np.zeros((17, 4), F), 4)
+    assert e.value.code == INVALID
+    # an indexed upload with an index out of range uploads nothing
+    keys = np.arange(4000, dtype=np.uint32) % 3
+    w.upload_draw_keys(keys)
+    with pytest.raises(B.BgeError) as e:
+        w.upload_draw_keys(np.array([0, 0], np.uint32), entity_index=np.array([5, 4000], np.uint32))
+    assert e.value.code == INVALID
+    with pytest.raises(B.BgeError) as e:
+        w.upload_draw_keys(np.zeros(2, np.uint32), first=3999)
+    assert e.value.code == INVALID
+    check(w, world, None, 3, keys, sc["center"], sc["half"], "after the refused uploads")
+
+
+def test_normal_before_a_normal_matrices_tick_and_calls_before_a_topology():
+    w, sc = flat_world(100, tick=W.TICK_TRANSFORMS)
+    try:
+        w.upload_draw_keys(np.zeros(100, np.uint32))
+        with pytest.raises(B.BgeError) as e:
+            w.draw_batches(None, 1, want_normal=True)
+        assert e.value.code == STATE
+        assert len(w.draw_batches(None, 1)["entities"]) == 100  # the other outputs are not affected
+    finally:
+        w.close()
+    w = B.World(device=0)
+    try:
+        with pytest.raises(B.BgeError) as e:
+            w.draw_batches(None, 1)
+        assert e.value.code == STATE
+        with pytest.raises(B.BgeError) as e:
+            w.upload_draw_keys(np.zeros(1, np.uint32))
+        assert e.value.code == STATE
+    finally:
+        w.close()
+
+
+def test_no_keys_uploaded_means_nobody_takes_part():
+    w, sc = flat_world(300)
+    try:
+        got = w.draw_batches(None, 4, want_world=True, want_normal=True)
+        assert len(got["entities"]) == 0 and not got["batches"].any() and got["world"].shape == (0, 16)
+        assert w.visible_count(None) == 300
+    finally:
+        w.close()
+
+
+# ---------------------------------------------------------------- the C++ adapter
+
+def test_adapter_fetch_draw_batches_in_resident_mode(tmp_path):
+    cpp = os.path.join(ROOT, "tests", "cpp")
+    libdir = os.path.join(ROOT, "banggameengine_amd")
+    exe = str(tmp_path / "batches_demo_scene")
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-Wall", "-Wextra", "-Wno-unused-parameter", "-o", exe,
+                           os.path.join(cpp, "batches_demo_scene.cpp"), f"-L{libdir}", "-lbge_world", f"-Wl,-rpath,{libdir}",
+                           "-Wl,-rpath,/opt/rocm/lib"])
+    r = subprocess.run([exe, os.path.join(ROOT, "tests", "golden", "demo_scene.json")], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
+    assert "all checks passed" in r.stdout
