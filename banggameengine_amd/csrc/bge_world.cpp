@@ -28,6 +28,7 @@
 #include "bge_debug.hpp"
 #include "bge_flatten.hpp"
 #include "bge_kernels.hpp"
+#include "bge_move.hpp"
 #include "bge_query.hpp"
 
 namespace {
@@ -293,6 +294,8 @@ struct bge_world {
     uint64_t query_keys_n = 0;
     uint32_t query_all_cap = 0;
     std::vector<bge::QueryGhost> query_ghosts_host, query_ghosts_dev;
+    // sphere moves (bge_move.hip): staging for the host entry point, the per-mover state, and the cast / hit records of the passes
+    DevBuf move_in, move_out, move_state, move_casts, move_hits;
     // debug overlay (bge_debug.hip): per-workgroup line counts and their offsets, the host entry point's line buffer and total
     DevBuf dbg_block_sum, dbg_block_off, dbg_lines, dbg_total;
     // frustum culling (bge_cull.hip): the model-space bounds per ENTITY (allocated with the first upload; a row of NaNs = no bounds;
@@ -383,7 +386,7 @@ struct bge_world {
                           &angvel, &quat, &inv_mass, &half_extent, &group, &mask, &aabb, &root_worlds, &counter, &stage,
                           &stage2, &mass_palette, &normal, &deact, &filter_class, &filter_table, &grav_palette, &bp_partials, &cshape, &cmass, &cfriction, &cinfo, &manifold, &crestitution, &bmanifold, &obstacle_slots, &obstacle_gen, &obstacles, &obstacle_grid, &box_list, &box_count, &frozen, &rs_word, &trig_slot, &trig_entity, &trig_he, &trig_group,
                           &trig_mask, &trig_active, &trig_aabb, &trig_pairs, &trig_count, &trig_lists, &ground_list, &ground_count, &trig_tab[0], &trig_tab[1],
-                          &trig_delta_dev, &trig_keys_dev, &trig_pose, &query_in, &query_out, &query_keys, &query_all, &query_all_count, &query_ghosts, &dbg_block_sum, &dbg_block_off,
+                          &trig_delta_dev, &trig_keys_dev, &trig_pose, &query_in, &query_out, &query_keys, &query_all, &query_all_count, &query_ghosts, &move_in, &move_out, &move_state, &move_casts, &move_hits, &dbg_block_sum, &dbg_block_off,
                           &dbg_lines, &dbg_total, &bounds, &cull_ballots, &cull_block_sum, &cull_block_off, &cull_out, &cull_total, &draw_keys,
                           &batch_sort, &batch_hist, &batch_out}) {
             b->release();
@@ -2855,6 +2858,8 @@ static_assert(sizeof(bge_ray_hit) == 40, "bge_ray_hit is 40 bytes (include/bge_w
 static_assert(sizeof(bge_sphere_cast) == 40, "bge_sphere_cast is 40 bytes (include/bge_world.h)");
 static_assert(sizeof(bge_sphere) == 20, "bge_sphere is 20 bytes (include/bge_world.h)");
 static_assert(sizeof(bge_overlap_hit) == 12, "bge_overlap_hit is 12 bytes (include/bge_world.h)");
+static_assert(sizeof(bge_sphere_move) == 48, "bge_sphere_move is 48 bytes (include/bge_world.h)");
+static_assert(sizeof(bge_sphere_move_result) == 80, "bge_sphere_move_result is 80 bytes (include/bge_world.h)");
 
 namespace {
 
@@ -3031,6 +3036,33 @@ int query_closest_device(bge_world* w, bge::QueryKind kind, uint64_t n, const vo
     return BGE_OK;
 }
 
+// A batch of sphere moves between device buffers (include/bge_world.h "Sphere moves"): begin, BGE_MOVE_SLIDES rounds of a
+// closest-hit sphere-cast pass and a step, the probe's pass, finish — all enqueued, nothing read in between.  q comes from
+// query_prepare(w, n, q), which holds the checks of the batch (topology, n, entity range) for both entry points.
+int move_enqueue(bge_world* w, bge::QueryParams q, uint64_t n, const void* moves_device, void* results_device)
+{
+    HIP_TRY(w->move_state.ensure(n * bge::kMoveStateBytes));
+    HIP_TRY(w->move_casts.ensure(n * sizeof(bge_sphere_cast)));
+    HIP_TRY(w->move_hits.ensure(n * sizeof(bge_ray_hit)));
+    q.records = w->move_casts.p;
+    q.hits = w->move_hits.p;
+    bge::MoveParams m{};
+    m.moves = moves_device;
+    m.results = results_device;
+    m.state = w->move_state.as<float4>();
+    m.casts = w->move_casts.p;
+    m.hits = w->move_hits.p;
+    m.n = static_cast<uint32_t>(n);
+    HIP_TRY(bge::launch_move_begin(w->stream, m));
+    for (uint32_t round = 0; round < BGE_MOVE_SLIDES; ++round) {
+        HIP_TRY(bge::launch_query(w->stream, bge::QueryKind::SphereCast, q, false));
+        HIP_TRY(bge::launch_move_step(w->stream, m, round));
+    }
+    HIP_TRY(bge::launch_query(w->stream, bge::QueryKind::SphereCast, q, false));
+    HIP_TRY(bge::launch_move_finish(w->stream, m));
+    return BGE_OK;
+}
+
 // One list entry point: its names in the error texts, its record sizes, and fill(hit, sorted record, the caller's record of its query)
 struct QueryList {
     bge::QueryKind kind;
@@ -3148,6 +3180,39 @@ try {
     return query_list(w, kSphereCastAll, n, casts, hits, cap, offsets, total);
 }
 BGE_CATCH_ALL("bge_world_sphere_cast_all")
+
+int bge_world_sphere_move(bge_world* w, uint64_t n, const bge_sphere_move* moves, bge_sphere_move_result* results)
+try {
+    if (!w) return fail(BGE_ERR_INVALID, "world is NULL");
+    if (n == 0) return BGE_OK;
+    if (!moves || !results) return fail(BGE_ERR_INVALID, "NULL argument");
+    DeviceGuard guard(w->device);
+    bge::QueryParams q;
+    if (int rc = query_prepare(w, n, q)) return rc; // (before the staging is sized: it refuses a batch that is too large)
+    HIP_TRY(w->move_in.ensure(n * sizeof(bge_sphere_move)));
+    HIP_TRY(w->move_out.ensure(n * sizeof(bge_sphere_move_result)));
+    HIP_TRY(hipMemcpyAsync(w->move_in.p, moves, n * sizeof(bge_sphere_move), hipMemcpyHostToDevice, w->stream));
+    if (int rc = move_enqueue(w, q, n, w->move_in.p, w->move_out.p)) return rc;
+    HIP_TRY(hipMemcpyAsync(results, w->move_out.p, n * sizeof(bge_sphere_move_result), hipMemcpyDeviceToHost, w->stream));
+    HIP_TRY(hipStreamSynchronize(w->stream));
+    return BGE_OK;
+}
+BGE_CATCH_ALL("bge_world_sphere_move")
+
+int bge_world_sphere_move_device(bge_world* w, uint64_t n, const void* moves_device, void* results_device)
+try {
+    if (!w) return fail(BGE_ERR_INVALID, "world is NULL");
+    if (n == 0) return BGE_OK;
+    if (!moves_device || !results_device) return fail(BGE_ERR_INVALID, "NULL argument");
+    if ((reinterpret_cast<uintptr_t>(moves_device) | reinterpret_cast<uintptr_t>(results_device)) & 3u) {
+        return fail(BGE_ERR_INVALID, "moves_device and results_device must be 4-byte aligned");
+    }
+    DeviceGuard guard(w->device);
+    bge::QueryParams q;
+    if (int rc = query_prepare(w, n, q)) return rc;
+    return move_enqueue(w, q, n, moves_device, results_device);
+}
+BGE_CATCH_ALL("bge_world_sphere_move_device")
 
 int bge_world_overlap_sphere(bge_world* w, uint64_t n, const bge_sphere* spheres, bge_overlap_hit* hits, uint64_t cap, uint64_t* offsets,
                              uint64_t* total)

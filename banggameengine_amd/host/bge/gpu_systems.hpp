@@ -36,6 +36,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -60,6 +61,34 @@ struct GpuOverlapHit {
     uint32_t entity = 0;   // EntityId of the body or trigger; kInvalidEntity (0) for the ground plane
     bool trigger = false;  // a trigger ghost, not a rigid body
     float distance = 0.0f; // from the sphere's centre to the shape, 0 when the centre is inside it
+};
+
+// One sphere of GpuPhysicsSystem::MoveSpheres and what a move returns (extensions: include/bge_world.h "Sphere moves").  Vec3 is
+// the engine's float3 (members x, y, z).
+template <class Vec3> struct GpuSphereMover {
+    Vec3 position{};         // centre before the move
+    Vec3 displacement{};     // asked motion of this call (walk direction, gravity and dt folded in by the caller)
+    float radius = 0.5f;
+    float skin = 0.01f;      // > 0: the gap kept to what was hit
+    float probeDistance = 0; // length of the ground probe straight down after the move; 0 = none
+    float maxSlopeRad = 0.7853982f; // grounded needs a ground normal within this angle of +y
+    uint32_t layerMask = 0xffffffffu;
+};
+template <class Vec3> struct GpuSphereMoveResult {
+    Vec3 position{};       // centre after the move
+    Vec3 remaining{};      // displacement left unspent (zero unless outOfSlides)
+    bool valid = false;    // false: an input was not finite or out of range, or there is no world; position is echoed
+    bool grounded = false; // the probe found ground no steeper than maxSlopeRad
+    bool probeHit = false;
+    bool outOfSlides = false;
+    uint32_t hits = 0;           // rounds that hit something, 0 .. BGE_MOVE_SLIDES
+    uint32_t hitEntity = 0;      // EntityId of the last thing hit; kInvalidEntity (0) for the ground plane or none
+    bool hitTrigger = false;
+    Vec3 hitNormal{};
+    uint32_t groundEntity = 0;   // the probe's hit, same convention
+    bool groundTrigger = false;
+    float groundDistance = 0.0f;
+    Vec3 groundNormal{};
 };
 
 struct GpuTriggerEvent {
@@ -444,6 +473,70 @@ public:
             out[i].distance = h.distance;
         }
         return out;
+    }
+
+    // EXTENSION: collide-and-slide moves of a batch of spheres (include/bge_world.h "Sphere moves"): each is moved by its
+    // displacement, stopped at what it hits, slid along it, and probed for ground.  One call, no round trip per sphere or per
+    // slide.  Nothing is written into a Transform: the caller applies result.position where it wants it.  false when there is
+    // no world or the call failed; results[i].valid tells an invalid mover.
+    template <class Vec3> bool MoveSpheres(const std::vector<GpuSphereMover<Vec3>>& movers, std::vector<GpuSphereMoveResult<Vec3>>& results)
+    {
+        results.assign(movers.size(), GpuSphereMoveResult<Vec3>{});
+        for (size_t i = 0; i < movers.size(); ++i) results[i].position = movers[i].position;
+        if (!ok()) return false;
+        if (movers.empty()) return true;
+        moves_.resize(movers.size());
+        move_results_.resize(movers.size());
+        for (size_t i = 0; i < movers.size(); ++i) {
+            const GpuSphereMover<Vec3>& m = movers[i];
+            bge_sphere_move& o = moves_[i];
+            o = bge_sphere_move{};
+            o.position[0] = m.position.x, o.position[1] = m.position.y, o.position[2] = m.position.z;
+            o.displacement[0] = m.displacement.x, o.displacement[1] = m.displacement.y, o.displacement[2] = m.displacement.z;
+            o.radius = m.radius;
+            o.skin = m.skin;
+            o.probe_distance = m.probeDistance;
+            o.min_ground_ny = std::cos(m.maxSlopeRad);
+            o.layer_mask = m.layerMask;
+        }
+        if (bge_world_sphere_move(world_, moves_.size(), moves_.data(), move_results_.data()) != BGE_OK) return Log("bge_world_sphere_move");
+        for (size_t i = 0; i < movers.size(); ++i) {
+            const bge_sphere_move_result& r = move_results_[i];
+            GpuSphereMoveResult<Vec3>& o = results[i];
+            o.position.x = r.position[0], o.position.y = r.position[1], o.position.z = r.position[2];
+            o.remaining.x = r.remaining[0], o.remaining.y = r.remaining[1], o.remaining.z = r.remaining[2];
+            o.valid = (r.flags & BGE_MOVE_INVALID) == 0u;
+            o.grounded = (r.flags & BGE_MOVE_GROUNDED) != 0u;
+            o.probeHit = (r.flags & BGE_MOVE_PROBE_HIT) != 0u;
+            o.outOfSlides = (r.flags & BGE_MOVE_OUT_OF_SLIDES) != 0u;
+            o.hits = r.n_hits;
+            o.hitEntity = r.hit_entity != BGE_RAY_NO_ENTITY && r.hit_entity < ids_.size() ? ids_[r.hit_entity] : Id{0};
+            o.hitTrigger = r.hit_kind == BGE_RAY_TRIGGER;
+            o.hitNormal.x = r.hit_normal[0], o.hitNormal.y = r.hit_normal[1], o.hitNormal.z = r.hit_normal[2];
+            o.groundEntity = r.ground_entity != BGE_RAY_NO_ENTITY && r.ground_entity < ids_.size() ? ids_[r.ground_entity] : Id{0};
+            o.groundTrigger = r.ground_kind == BGE_RAY_TRIGGER;
+            o.groundDistance = r.ground_distance;
+            o.groundNormal.x = r.ground_normal[0], o.groundNormal.y = r.ground_normal[1], o.groundNormal.z = r.ground_normal[2];
+        }
+        return true;
+    }
+    // one sphere: true when it was moved (a valid mover on a world)
+    template <class Vec3>
+    bool MoveSphere(const Vec3& position, const Vec3& displacement, float radius, float skin, float probeDistance, float maxSlopeRad,
+                    uint32_t layerMask, GpuSphereMoveResult<Vec3>& result)
+    {
+        std::vector<GpuSphereMover<Vec3>> one(1);
+        one[0].position = position;
+        one[0].displacement = displacement;
+        one[0].radius = radius;
+        one[0].skin = skin;
+        one[0].probeDistance = probeDistance;
+        one[0].maxSlopeRad = maxSlopeRad;
+        one[0].layerMask = layerMask;
+        std::vector<GpuSphereMoveResult<Vec3>> out;
+        const bool done = MoveSpheres(one, out);
+        result = out[0];
+        return done && result.valid;
     }
 
     // CollectDebugLines + debugDrawWorld(DBG_DrawContactPoints) (PhysicsSystem.cpp:857-873, 1148-1175) on the device world as
@@ -956,6 +1049,8 @@ private:
     std::vector<GpuTriggerEvent> trigger_events_;
     std::vector<bge_ray_hit> ray_hits_;
     std::vector<bge_overlap_hit> overlap_hits_;
+    std::vector<bge_sphere_move> moves_;
+    std::vector<bge_sphere_move_result> move_results_;
 
     template <class Vec3> static bge_sphere_cast MakeCast(const Vec3& o, const Vec3& d, float maxDistance, float radius, uint32_t layerMask)
     {
@@ -1112,6 +1207,29 @@ public:
     {
         if (!lastScene_) return {};
         return GpuMirrors<SceneT>::Of(*lastScene_).OverlapSphere(center, radius, layerMask);
+    }
+
+    // EXTENSION: collide-and-slide moves of spheres against the same world, under the same call order as Raycast
+    // (include/bge_world.h "Sphere moves"); false before the first Update, with every position echoed.
+    template <class Vec3>
+    bool MoveSphere(const Vec3& position, const Vec3& displacement, float radius, float skin, float probeDistance, float maxSlopeRad,
+                    uint32_t layerMask, GpuSphereMoveResult<Vec3>& result) const
+    {
+        if (!lastScene_) {
+            result = GpuSphereMoveResult<Vec3>{};
+            result.position = position;
+            return false;
+        }
+        return GpuMirrors<SceneT>::Of(*lastScene_).MoveSphere(position, displacement, radius, skin, probeDistance, maxSlopeRad, layerMask, result);
+    }
+    template <class Vec3> bool MoveSpheres(const std::vector<GpuSphereMover<Vec3>>& movers, std::vector<GpuSphereMoveResult<Vec3>>& results) const
+    {
+        if (!lastScene_) {
+            results.assign(movers.size(), GpuSphereMoveResult<Vec3>{});
+            for (size_t i = 0; i < movers.size(); ++i) results[i].position = movers[i].position;
+            return false;
+        }
+        return GpuMirrors<SceneT>::Of(*lastScene_).MoveSpheres(movers, results);
     }
 
     // The debug overlay (src/physics/PhysicsSystem.h:77-82, bound to a key at src/core/Application.cpp:173; the renderer gets

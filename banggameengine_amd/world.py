@@ -71,6 +71,33 @@ def make_spheres(centers, radius, layer_mask=0xFFFFFFFF):
     return spheres
 
 
+# sphere moves (bge_world_sphere_move*): bge_move_flags and the two records
+MOVE_SLIDES = 4
+MOVE_INVALID, MOVE_GROUNDED, MOVE_OUT_OF_SLIDES, MOVE_PROBE_HIT = 1, 2, 4, 8
+SPHERE_MOVE_DTYPE = np.dtype([("position", "<f4", (3,)), ("displacement", "<f4", (3,)), ("radius", "<f4"), ("skin", "<f4"),
+                              ("probe_distance", "<f4"), ("min_ground_ny", "<f4"), ("layer_mask", "<u4"), ("reserved", "<u4")])
+SPHERE_MOVE_RESULT_DTYPE = np.dtype([("position", "<f4", (3,)), ("remaining", "<f4", (3,)), ("flags", "<u4"), ("n_hits", "<u4"),
+                                     ("hit_kind", "<u4"), ("hit_entity", "<u4"), ("hit_normal", "<f4", (3,)), ("ground_kind", "<u4"),
+                                     ("ground_entity", "<u4"), ("ground_distance", "<f4"), ("ground_normal", "<f4", (3,)),
+                                     ("reserved", "<u4")])
+assert SPHERE_MOVE_DTYPE.itemsize == 48 and SPHERE_MOVE_RESULT_DTYPE.itemsize == 80
+
+
+def make_sphere_moves(positions, displacements, radius=0.5, skin=0.01, probe_distance=0.0, min_ground_ny=0.7071068, layer_mask=0xFFFFFFFF):
+    """bge_sphere_move records: positions / displacements (n, 3); every other argument a scalar or one value per mover."""
+    p = np.ascontiguousarray(positions, np.float32).reshape(-1, 3)
+    d = np.ascontiguousarray(displacements, np.float32).reshape(-1, 3)
+    if len(p) != len(d):
+        raise ValueError(f"{len(p)} positions, {len(d)} displacements")
+    moves = np.zeros(len(p), SPHERE_MOVE_DTYPE)
+    moves["position"] = p
+    moves["displacement"] = d
+    for k, v in (("radius", radius), ("skin", skin), ("probe_distance", probe_distance), ("min_ground_ny", min_ground_ny)):
+        moves[k] = np.broadcast_to(np.asarray(v, np.float32), (len(p),))
+    moves["layer_mask"] = np.broadcast_to(np.asarray(layer_mask, np.uint64).astype(np.uint32), (len(p),))
+    return moves
+
+
 # debug overlay (bge_world_debug_lines*): bge_debug_flags and the 28-byte line record
 DEBUG_SHAPES, DEBUG_CONTACTS, DEBUG_ALL = 1, 2, 3
 DEBUG_LINE_DTYPE = np.dtype([("from", "<f4", (3,)), ("to", "<f4", (3,)), ("abgr", "<u4")])
@@ -488,6 +515,30 @@ class World:
         check(lib().bge_world_overlap_sphere(self._h, len(spheres), _p(spheres), _p(hits), len(hits), _p(offsets), C.byref(total)))
         hits = hits[:int(total.value)]
         return {"kind": hits["kind"].copy(), "entity": hits["entity"].copy(), "distance": hits["distance"].copy(), "offsets": offsets}
+
+    # -- sphere moves (not in the reference; include/bge_world.h states the rule: collide, slide, probe for ground)
+    def sphere_move(self, positions, displacements, radius=0.5, skin=0.01, probe_distance=0.0, min_ground_ny=0.7071068,
+                    layer_mask=0xFFFFFFFF):
+        """One collide-and-slide move per sphere: a SPHERE_MOVE_RESULT_DTYPE array (position, remaining, flags, n_hits, the last
+        hit of the slides, the ground probe's hit).  Every argument but the first two takes a scalar or one value per mover."""
+        moves = make_sphere_moves(positions, displacements, radius, skin, probe_distance, min_ground_ny, layer_mask)
+        results = np.zeros(len(moves), SPHERE_MOVE_RESULT_DTYPE)
+        check(lib().bge_world_sphere_move(self._h, len(moves), _p(moves), _p(results)))
+        return results
+
+    def sphere_move_device(self, moves, results):
+        """The same between device tensors: moves holds n bge_sphere_move records (48 bytes each, e.g. a uint8 tensor made from
+        make_sphere_moves()), results room for n bge_sphere_move_result records (80 bytes each).  Enqueued on the world's stream
+        without synchronisation, as raycast_device()."""
+        nb = moves.numel() * moves.element_size()
+        if nb % 48:
+            raise ValueError(f"moves holds {nb} bytes, not a whole number of 48-byte records")
+        n = nb // 48
+        if results.numel() * results.element_size() < 80 * n:
+            raise ValueError(f"results has room for {results.numel() * results.element_size()} bytes, {80 * n} needed")
+        if not (moves.is_cuda and results.is_cuda and moves.is_contiguous() and results.is_contiguous()):
+            raise ValueError("moves and results must be contiguous device tensors")
+        check(lib().bge_world_sphere_move_device(self._h, n, C.c_void_p(moves.data_ptr()), C.c_void_p(results.data_ptr())))
 
     # -- debug overlay (PhysicsSystem::GetDebugLines; include/bge_world.h states what is drawn and in which order)
     def debug_lines(self, flags=DEBUG_ALL, region=None):

@@ -501,6 +501,84 @@ BGE_API int bge_world_overlap_sphere(bge_world* world, uint64_t n, const bge_sph
                                      uint64_t* offsets, uint64_t* total);
 
 /*
+ * Sphere moves: the core of a kinematic controller for a batch of spheres at once — move the sphere by a displacement, stop at
+ * what it hits, slide what is left along the surface, probe for ground.  NOT in the reference's PhysicsSystem (its character is
+ * Bullet's btKinematicCharacterController on a capsule, src/physics/PhysicsSystem.cpp:709-846).  A move is BGE_MOVE_SLIDES
+ * rounds of bge_world_sphere_cast plus one probe cast, all on the device with no host round trip in between.  The rule below is
+ * the specification.  All arithmetic is binary32, each line evaluated left to right with one rounding per
+ * operation; j runs over x, y, z.
+ *   Sees      Objects, poses, Filter, tie order and Call order are those of bge_world_sphere_cast, word for word: the mover sees
+ *             the world only through that cast.
+ *   Valid     a mover is valid iff every float of it is finite, radius >= 0, skin > 0, probe_distance >= 0 and layer_mask != 0.
+ *             An invalid mover returns flags = BGE_MOVE_INVALID, position echoed, the kinds BGE_RAY_MISS, the entities
+ *             BGE_RAY_NO_ENTITY, everything else 0.
+ *   State     p = position, r = displacement, d0 = displacement, no previous normal, not finished.
+ *   Rounds    for each of the BGE_MOVE_SLIDES rounds, unless finished:
+ *             1. L2 = (r.x*r.x + r.y*r.y) + r.z*r.z.  If !(L2 > 1e-12f): r = 0, finished.
+ *             2. Take the closest hit of the cast {origin p, direction r, max_distance 1, radius, layer_mask}.  On a miss:
+ *                p_j = p_j + r_j, r = 0, finished.
+ *             3. On a hit with fraction f and normal n:
+ *                  L = sqrtf(L2)
+ *                  a = -(((r.x*n.x + r.y*n.y) + r.z*n.z) / L);   if !(a >= 0.0625f) then a = 0.0625f
+ *                  g = f - skin / (a * L);                       if !(g > 0) then g = 0
+ *                  p_j = p_j + r_j * g
+ *                n_hits += 1; hit_kind, hit_entity and hit_normal take the hit's kind, entity and normal.
+ *             4. Leftover:  w = 1 - f;  l_j = r_j * w;  dn = (l.x*n.x + l.y*n.y) + l.z*n.z;  s_j = l_j - n_j * dn.
+ *             5. Crease.  If there is a previous normal m and ((s.x*m.x + s.y*m.y) + s.z*m.z) < 0:
+ *                  c = (m.y*n.z - m.z*n.y, m.z*n.x - m.x*n.z, m.x*n.y - m.y*n.x);  cc = (c.x*c.x + c.y*c.y) + c.z*c.z
+ *                  if !(cc > 1e-12f): s = 0;  otherwise t = ((l.x*c.x + l.y*c.y) + l.z*c.z) / cc and s_j = c_j * t.
+ *             6. A slide never turns against the asked direction: if !(((s.x*d0.x + s.y*d0.y) + s.z*d0.z) > 0): s = 0.
+ *             7. r = s; the previous normal becomes n.
+ *   After     if (r.x*r.x + r.y*r.y) + r.z*r.z > 1e-12f, BGE_MOVE_OUT_OF_SLIDES is set and remaining = r; otherwise remaining = 0.
+ *             position = p.
+ *   Probe     if probe_distance > 0, the cast {origin p, direction (0, -1, 0), max_distance probe_distance, radius, layer_mask}.
+ *             On a hit BGE_MOVE_PROBE_HIT is set, ground_kind, ground_entity and ground_normal take the hit and ground_distance
+ *             is the hit's distance; BGE_MOVE_GROUNDED is set iff additionally ground_normal[1] >= min_ground_ny.
+ *   Skin      the cast ignores a shape the sphere starts touching, so a mover must never come to rest at distance radius from
+ *             anything: it would fall through it in the next call.  The back-off by skin / a along the path keeps a gap of skin
+ *             to a flat surface (a is the cosine of the approach).  The clamp at a = 1/16 bounds the back-off at grazing angles to
+ *             16 skins of path, where the gap kept is then smaller than skin, never negative.  Choose skin well above the
+ *             binary32 spacing at the scene's extent (1e-3 .. 1e-2 for a scene of a few hundred units).
+ *   Not done  capsule or box movers; stepping up (composed by the caller from an up move, a forward move and a down move);
+ *             recovery of a sphere that starts in penetration (the cast does not see what it starts in: bge_world_overlap_sphere
+ *             finds those); moving platforms; the result is not written into any Transform.
+ *   The query changes no world state.  n = 0 is a no-op.  A NULL argument with n > 0 is BGE_ERR_INVALID.  Before
+ *   bge_world_set_topology it returns what bge_world_sphere_cast returns there.
+ *   bge_world_sphere_move         results[i] for moves[i].  Synchronises the world's stream.
+ *   bge_world_sphere_move_device  device pointers: moves_device = bge_sphere_move[n], results_device = bge_sphere_move_result[n],
+ *                                 both 4-byte aligned (a misaligned pointer is BGE_ERR_INVALID); enqueued on the world's stream,
+ *                                 no synchronisation.
+ */
+#define BGE_MOVE_SLIDES 4
+typedef struct bge_sphere_move {
+    float position[3];     /* centre before the move */
+    float displacement[3]; /* asked motion of this call (the caller folds in walk direction, gravity, dt) */
+    float radius;
+    float skin;            /* > 0: the gap kept to what was hit */
+    float probe_distance;  /* >= 0: length of the ground probe straight down after the move; 0 = no probe */
+    float min_ground_ny;   /* GROUNDED needs ground normal.y >= this (cos of the max slope) */
+    uint32_t layer_mask;
+    uint32_t reserved;     /* 0 */
+} bge_sphere_move; /* 48 bytes */
+enum bge_move_flags { BGE_MOVE_INVALID = 1u, BGE_MOVE_GROUNDED = 2u, BGE_MOVE_OUT_OF_SLIDES = 4u, BGE_MOVE_PROBE_HIT = 8u };
+typedef struct bge_sphere_move_result {
+    float position[3];  /* centre after the move */
+    float remaining[3]; /* displacement left unspent (zero unless OUT_OF_SLIDES) */
+    uint32_t flags;     /* bge_move_flags */
+    uint32_t n_hits;    /* rounds that hit something, 0 .. BGE_MOVE_SLIDES */
+    uint32_t hit_kind;  /* last hit of the slides: bge_ray_kind; BGE_RAY_MISS / BGE_RAY_NO_ENTITY / 0 if none */
+    uint32_t hit_entity;
+    float hit_normal[3];
+    uint32_t ground_kind; /* the probe's hit, same convention */
+    uint32_t ground_entity;
+    float ground_distance;
+    float ground_normal[3];
+    uint32_t reserved; /* 0 */
+} bge_sphere_move_result; /* 80 bytes */
+BGE_API int bge_world_sphere_move(bge_world* world, uint64_t n, const bge_sphere_move* moves, bge_sphere_move_result* results);
+BGE_API int bge_world_sphere_move_device(bge_world* world, uint64_t n, const void* moves_device, void* results_device);
+
+/*
  * The physics debug overlay: what PhysicsSystem::GetDebugLines hands to the renderer while the overlay is on
  * (src/physics/PhysicsSystem.cpp:857-873, 1148-1175; src/physics/BulletDebugDrawer.cpp) — every collision object's shape as
  * wireframe lines in one colour, then one short red line per contact point — made on the device from the state the last tick
