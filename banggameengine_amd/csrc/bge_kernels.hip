@@ -20,6 +20,8 @@
 //   writes  pos 12 B + vel 12 B (Dynamic only), world 64 B; flags only when a bit changed
 //   Waves whose rotation rows are current (WorldView::rs_word) read neither euler nor scale and write only world row 3:
 //   68 B per flat body instead of 140 B.
+//   Waves whose bodies are all asleep (rest word, WorldView::rs_word word 1) read flags, the deactivation record and the contact
+//   word, 8..12 B per body, and store nothing.
 //   The world matrices leave through LDS so that every wave-level store instruction writes 1 KiB of
 //   contiguous memory (16 B per lane), whatever the per-node compute layout was.
 //   The kernel is HBM-bound (~250 flop against >= 113 B per entity): no MFMA.
@@ -200,12 +202,45 @@ __global__ void __launch_bounds__(kTile, NORMAL ? 4 : (AABB ? BGE_AABB_MIN_WAVES
     // §4.1: 68 instead of 140 B per flat body).  The word is loaded as a scalar next to the tile header.
     constexpr bool kRowsPath = XFORM && !AABB && !NORMAL && !BASIS;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const uint32_t rs_old = (kRowsPath && p.rs_epoch != 0u) ? w.rs_word[tile * 4u + wave] : 0u;
+    const uint32_t rs_old = (kRowsPath && p.rs_epoch != 0u) ? w.rs_word[2u * (tile * 4u + wave)] : 0u;
     // (header: wave-local, max level 0, no frozen root, no external parent)
-    const bool rs_tile = kRowsPath && p.rs_epoch != 0u && (hdr & (kHdrWaveLocal | kHdrFrozen | kHdrExt | kHdrLevelMask)) == kHdrWaveLocal;
+    const bool flat_tile = kRowsPath && (hdr & (kHdrWaveLocal | kHdrFrozen | kHdrExt | kHdrLevelMask)) == kHdrWaveLocal;
+    const bool rs_tile = flat_tile && p.rs_epoch != 0u;
     const bool rs_hint = rs_tile && rs_old == p.rs_epoch;
 
-    const uint32_t f0 = w.flags[slot];
+    // Rest path (WorldView::rs_word, word 1): a wave whose rest word equals p.rest_epoch ended its last full tick with every lane at
+    // rest — no dirty bit, no spin, a Dynamic body ISLAND_SLEEPING with zero velocities stored, or no Dynamic body at all — and with
+    // all four world rows = bx_mtx_srt(scale, euler, pos) of what is in memory; the host has not touched the world since (it bumps the
+    // epoch on every call that could).  Only a kernel of this tick's contact stage can have changed that, and whichever does leaves a
+    // mark in the flags, the deactivation record or the contact word (the audit table).  So the wave reads those 12 B per
+    // body and, when one ballot finds no mark, returns: a sleeping body is not integrated, its zero velocity and its matrix would be
+    // stored over the same bits, and its flags end the tick as they started (kTDirty is set and cleared within it).  Otherwise the
+    // lanes go on into the ordinary path below.  Wave-local tiles of these variants have no workgroup barrier to miss.
+    const uint32_t rest_old = (kRowsPath && p.rest_epoch != 0u) ? w.rs_word[2u * (tile * 4u + wave) + 1u] : 0u;
+    const bool rest_tile = flat_tile && p.rest_epoch != 0u;
+    uint32_t f0;
+    if (rest_tile && rest_old == p.rest_epoch) { // (wave-uniform)
+        f0 = w.flags[slot];
+        // (both read whether or not the flags say they matter: one round trip instead of two; the arrays cover whole tiles)
+        const uint32_t dz_r = PHYS ? w.deact[slot] : 0u;
+        const uint32_t ci_r = (PHYS && p.cinfo_in) ? p.cinfo_in[slot] : 0u;
+        const uint32_t type_r = f0 & kTypeMask;
+        bool moved;
+        if (f0 & kValid) {
+            moved = (f0 & (kTDirty | kSpin | kExtParent | kLevelMask)) != 0;
+            if (PHYS) {
+                moved = moved || (f0 & kBDirty) || type_r == 3u;
+                // (the bits of the contact word this kernel obeys or consumes; kCiNoGravity, which k_island_begin sets on every sleeper,
+                //  is read by the island kernels alone and stays)
+                if (type_r == 2u) moved = moved || !(f0 & kDrowsy) || dz_r != kDeactSleeping || (ci_r & (kCiSolved | kCiMoved | kCiIsland));
+            }
+        } else {
+            moved = PHYS && type_r != 0u; // an orphaned body is stepped: never on this path
+        }
+        if (__ballot(moved) == 0ull) return;
+    } else {
+        f0 = w.flags[slot];
+    }
     // The component loads do not wait for the flag word: every array is allocated for whole tiles, so the loads of a slot
     // that turns out to be empty (or of a velocity nobody integrates) are harmless, and issuing them together with the flags
     // takes one memory round trip instead of two out of a workgroup's life.  Measured at
@@ -267,6 +302,7 @@ __global__ void __launch_bounds__(kTile, NORMAL ? 4 : (AABB ? BGE_AABB_MIN_WAVES
     // (AABB variants) this lane's fed box for the wave's broadphase partial: identity when the slot carries no body
     float box_mn[3] = {INFINITY, INFINITY, INFINITY}, box_mx[3] = {-INFINITY, -INFINITY, -INFINITY};
     bool has_box = false;
+    bool asleep = false; // a Dynamic body that ends this tick ISLAND_SLEEPING with zero velocities stored (the rest word)
     if (PHYS) {
         const uint32_t type = f & kTypeMask;
         if (type != 0) { // (type bits exist only on slots that carry a body: with a Transform, or orphaned)
@@ -374,6 +410,7 @@ __global__ void __launch_bounds__(kTile, NORMAL ? 4 : (AABB ? BGE_AABB_MIN_WAVES
                     // asleep: no gravity, not solved, not integrated; updateActivationState zeroes the velocities
                     v = F3{0.0f, 0.0f, 0.0f};
                     st3(w.vel, slot, v);
+                    asleep = true;
                     if (spin) {
                         st3(w.angvel, slot, v);
                         spin = false;
@@ -528,6 +565,13 @@ __global__ void __launch_bounds__(kTile, NORMAL ? 4 : (AABB ? BGE_AABB_MIN_WAVES
         // the path off where the working set outgrows the Infinity Cache (16 M slots: partially written lines cost 2.7x whole ones)
         if (valid) reinterpret_cast<float4*>(w.world)[4ull * slot + 3u] = make_float4(pos.x, pos.y, pos.z, 1.0f);
         f &= ~kTDirty; // transform->dirty = false
+        if (kRowsPath && PHYS && p.rest_epoch != 0u) {
+            // rows 0..2 were current and row 3 is stored: the rest word says so when every lane ends the tick at rest (written only when it changes)
+            const uint32_t type = f & kTypeMask;
+            const bool rests = valid ? (!(f & (kTDirty | kBDirty | kSpin | kExtParent | kLevelMask)) && type != 3u && (type != 2u || asleep)) : !orphan_body;
+            const uint32_t rest_new = (rest_tile && __ballot(!rests) == 0ull) ? p.rest_epoch : 0u;
+            if (rest_new != rest_old && (tid & 63u) == 0u) w.rs_word[2u * (tile * 4u + wave) + 1u] = rest_new;
+        }
     } else if (XFORM) {
         float local[16];
         bx_mtx_srt(local, scl, eul, pos);
@@ -577,7 +621,14 @@ __global__ void __launch_bounds__(kTile, NORMAL ? 4 : (AABB ? BGE_AABB_MIN_WAVES
                 // it: every valid lane ends the tick without spin in a tile of the fast path's shape (written only when it changes)
                 const bool keeps = rs_tile && __ballot(valid && (f & (kSpin | kExtParent | kLevelMask))) == 0ull;
                 const uint32_t rs_new = keeps ? p.rs_epoch : 0u;
-                if (rs_new != rs_old && (tid & 63u) == 0u) w.rs_word[tile * 4u + wave] = rs_new;
+                if (rs_new != rs_old && (tid & 63u) == 0u) w.rs_word[2u * (tile * 4u + wave)] = rs_new;
+            }
+            if (kRowsPath && PHYS && p.rest_epoch != 0u) {
+                // all four rows just stored are bx_mtx_srt of what is in memory; kTDirty ends the tick cleared (below)
+                const uint32_t type = f & kTypeMask;
+                const bool rests = valid ? (!(f & (kBDirty | kSpin | kExtParent | kLevelMask)) && type != 3u && (type != 2u || asleep)) : !orphan_body;
+                const uint32_t rest_new = (rest_tile && __ballot(!rests) == 0ull) ? p.rest_epoch : 0u;
+                if (rest_new != rest_old && (tid & 63u) == 0u) w.rs_word[2u * (tile * 4u + wave) + 1u] = rest_new;
             }
             if (NORMAL) {
                 // render feed: normalMtx = transpose(inverse(world)) (Renderer.cpp:633-636), same LDS round trip

@@ -47,9 +47,13 @@ struct WorldView {
     uint32_t* bmanifold;      // [slots][kBoxManifolds][kBoxManifoldWords] a Dynamic box's manifolds with boxes, in no particular order:
                               //             words 0..3 = other entity, points, the other body's generation, 0; then four points x 12 floats
                               //             (localA.xyz, localB.xyz, normalWorldOnB.xyz, distance, appliedImpulse, appliedImpulseLateral1)
-    uint32_t* rs_word;        // [tiles * 4] one word per wave64, kept by k_tick: equal to TickParams::rs_epoch only while world rows 0..2
-                              //             of every valid slot of the wave are bx_mtx_srt(scale, euler) of the scale and euler in memory
-                              //             (wave-local tile, max level 0, no frozen root, no external parent); zeroed with every layout
+    uint32_t* rs_word;        // [tiles * 4][2] two words per wave64, kept by k_tick, zeroed with every layout.  Word 0 equals
+                              //             TickParams::rs_epoch only while world rows 0..2 of every valid slot of the wave are
+                              //             bx_mtx_srt(scale, euler) of the scale and euler in memory (wave-local tile, max level 0, no
+                              //             frozen root, no external parent).  Word 1 (the rest word) equals TickParams::rest_epoch only
+                              //             while, in a tile of the same shape, all four world rows of every valid slot are bx_mtx_srt of
+                              //             the scale, euler and pos in memory and every lane is at rest: no dirty bit, no spin, and
+                              //             either a Dynamic body that is ISLAND_SLEEPING with zero velocities or no body / a Static one
     uint32_t* frozen;         // [slots / 32] bit per slot, or null: a root whose parent entity lost its Transform keeps the world matrix it had
                               //             (parent * local) until something marks it dirty — TransformSystem::Update recomputes a node only when
                               //             it or an ancestor is dirty, and Scene::RemoveTransform marks nobody (tiles with kHdrFrozen look here)
@@ -202,6 +206,9 @@ struct TickParams {
     const uint32_t* cinfo_in; // ground plane on: k_ground ran before this kernel; bodies it solved carry kCiSolved (null: no ground)
     uint32_t rs_epoch;  // non-zero: waves whose rs_word holds this value store only the translation row of the world matrices and
                         // keep the word; 0: the fast path is off and no word is written (the host bumps its epoch instead)
+    uint32_t rest_epoch; // non-zero: waves whose rest word (WorldView::rs_word, word 1) holds this value read flags, the deactivation
+                         // record and the contact word, and return without a store when those confirm that every lane still rests;
+                         // 0: the rest path is off and no rest word is written (the host bumps its epoch instead)
     uint32_t no_repose; // this tick is the 2nd..nth sub-step of ONE stepSimulation call (bge_world_step_simulation): dirty flags
                         // do not re-pose bodies — SyncKinematicBodiesToPhysics ran once, before the first sub-step
 };

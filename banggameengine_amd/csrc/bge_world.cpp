@@ -27,6 +27,7 @@
 #include "bge_cull.hpp"
 #include "bge_debug.hpp"
 #include "bge_flatten.hpp"
+#include "bge_epochs.hpp"
 #include "bge_kernels.hpp"
 #include "bge_move.hpp"
 #include "bge_query.hpp"
@@ -160,17 +161,20 @@ struct bge_world {
     DevBuf root_worlds, counter, stage, stage2, mass_palette, normal, deact, filter_class, filter_table, grav_palette;
     DevBuf cshape, cmass, cfriction, cinfo, manifold; // ground contact (bge_contact.hip); manifold allocated when the plane is switched on
     DevBuf ground_list, ground_count;                 // slots k_ground_select hands to the solver; count + ticket words
-    // "rotation rows current" words of the tick kernel (WorldView::rs_word, one per wave64, zeroed with every layout) and the
-    // epoch they are compared with.  Every call that can write euler, scale, world, quat, angular velocity, body types or flags —
-    // and every tick whose launches include another kernel that writes them — moves the epoch on, which invalidates all words.
+    // The tick kernel's per-wave words (WorldView::rs_word: "rotation rows current" and "at rest", two per wave64, zeroed with every
+    // layout) and the epochs they are compared with (bge_epochs.hpp).  Every call that can write pos, euler, scale, world, quat,
+    // velocities, deactivation records, contact words, body types or flags moves BOTH epochs on (epochs_edit), which invalidates all
+    // words.  A tick whose launches include another kernel that writes euler, scale, world or quat moves the rows epoch alone; a tick
+    // of a variant without the rest path moves the rest epoch alone.
     DevBuf rs_word;
-    uint32_t rs_epoch = 1;
-    void rs_bump()
+    bge::PathEpochs epochs;
+    void words_clear()
     {
-        if (++rs_epoch == 0) { // (after 2^32 - 1 bumps: a word may still hold the new value)
-            rs_epoch = 1;
-            if (rs_word.p) (void)hipMemsetAsync(rs_word.p, 0, rs_word.bytes, stream);
-        }
+        if (rs_word.p) (void)hipMemsetAsync(rs_word.p, 0, rs_word.bytes, stream);
+    }
+    void epochs_edit()
+    {
+        if (epochs.host_edit()) words_clear();
     }
     // Dynamic boxes on the Static / Kinematic box colliders of the scene (round 3, bge_contact.hip): off by default, like the plane
     bool static_contacts = false;
@@ -1351,9 +1355,9 @@ try {
     HIP_TRY(w->flags.ensure(S * 4));
     HIP_TRY(w->parent.ensure(S * 4));
     HIP_TRY(w->tile_hdr.ensure(T * 4));
-    HIP_TRY(w->rs_word.ensure(T * 16));
-    HIP_TRY(hipMemsetAsync(w->rs_word.p, 0, T * 16, w->stream));
-    w->rs_bump();
+    HIP_TRY(w->rs_word.ensure(T * 32));
+    HIP_TRY(hipMemsetAsync(w->rs_word.p, 0, T * 32, w->stream));
+    w->epochs_edit();
     HIP_TRY(w->slot_of_entity.ensure(std::max<uint64_t>(n, 1) * 4));
     HIP_TRY(w->entity_of_slot.ensure(S * 4));
     HIP_TRY(w->root_index.ensure(S * 4));
@@ -1524,7 +1528,7 @@ static int upload_trs_impl(bge_world* w, uint64_t first, uint64_t count, const u
                                      w->flags.as<uint32_t>(), bge::kTDirty, di, bge::kValid));
     HIP_TRY(hipStreamSynchronize(w->stream));
     w->maybe_dirty = true;
-    w->rs_bump();
+    w->epochs_edit();
     return BGE_OK;
 }
 
@@ -1553,7 +1557,7 @@ try {
     HIP_TRY(bge::launch_scatter_rows(w->stream, w->slot_of_entity.as<uint32_t>(), first, count, 0, nullptr, nullptr,
                                      w->flags.as<uint32_t>(), bge::kTDirty, nullptr, bge::kValid));
     w->maybe_dirty = true;
-    w->rs_bump();
+    w->epochs_edit();
     return BGE_OK;
 }
 BGE_CATCH_ALL("bge_world_mark_dirty")
@@ -1698,7 +1702,7 @@ static int upload_bodies_impl(bge_world* w, uint64_t first, uint64_t count, cons
                                        d + 12 * count));
     HIP_TRY(hipStreamSynchronize(w->stream));
     w->maybe_dirty = true;
-    w->rs_bump();
+    w->epochs_edit();
     return BGE_OK;
 }
 
@@ -1716,7 +1720,7 @@ try {
     HIP_TRY(bge::launch_scatter_velocities(w->stream, w->slot_of_entity.as<uint32_t>(), first, count, linvel3 ? dl : nullptr,
                                            angvel3 ? da : nullptr, w->view));
     HIP_TRY(hipStreamSynchronize(w->stream));
-    w->rs_bump();
+    w->epochs_edit();
     return BGE_OK;
 }
 BGE_CATCH_ALL("bge_world_set_velocities")
@@ -1917,6 +1921,13 @@ int tick_impl(bge_world* w, uint32_t ticks, float dt, const float gravity[3], ui
     bool rows_path = xform && !contacts && !nt_out &&
                      !(flags & (BGE_TICK_AABBS | BGE_TICK_BROADPHASE | BGE_TICK_NORMAL_MATRICES | BGE_TICK_BULLET_BASIS | BGE_TICK_GATHER_ROOTS));
     if (const char* e = std::getenv("BGE_WORLD_ROWS")) rows_path = rows_path && std::atoi(e) != 0;
+    // Rest path of the tick kernel (WorldView::rs_word, word 1): waves whose bodies are all asleep read 12 B per body and store
+    // nothing.  In the same variants as the translation-row path — but ON with the ground plane, obstacles and Dynamic contacts,
+    // where a scene at rest spends its life: every kernel of the contact stage either leaves a sleeping body alone or marks its
+    // flags, deactivation record or contact word.  It stores nothing, so the non-temporal regime needs no
+    // exclusion.  BGE_REST_PATH=0 turns it off (A/B runs); a tick without it moves its epoch on.
+    bool rest_path = xform && !(flags & (BGE_TICK_AABBS | BGE_TICK_BROADPHASE | BGE_TICK_NORMAL_MATRICES | BGE_TICK_BULLET_BASIS | BGE_TICK_GATHER_ROOTS));
+    if (const char* e = std::getenv("BGE_REST_PATH")) rest_path = rest_path && std::atoi(e) != 0;
     for (uint32_t t = 0; t < ticks; ++t) {
         if (!phys && !w->maybe_dirty && !(flags & BGE_TICK_NORMAL_MATRICES)) {
             // TransformSystem::Update with nothing dirty: a no-op scan — only the kernel launches are skipped.  The
@@ -1935,8 +1946,10 @@ int tick_impl(bge_world* w, uint32_t ticks, float dt, const float gravity[3], ui
         p.gz = gravity ? gravity[2] : 0.0f;
         p.nt_out = nt_out ? 1u : 0u;
         p.no_repose = sub.no_repose ? 1u : 0u;
-        if (rows_path) p.rs_epoch = w->rs_epoch;
-        else w->rs_bump();
+        if (rows_path) p.rs_epoch = w->epochs.rows;
+        else if (w->epochs.tick_without_rows()) w->words_clear();
+        if (rest_path) p.rest_epoch = w->epochs.rest;
+        else if (w->epochs.tick_without_rest()) w->words_clear();
         w->fill_sleep(p);
         const bool with_triggers = (flags & BGE_TICK_BROADPHASE) && !w->triggers.empty();
         if (with_triggers && !sub.ghosts_posed) {
@@ -2058,7 +2071,7 @@ try {
         DeviceGuard guard(w->device);
         HIP_TRY(bge::launch_pose_only(w->stream, w->view, ticked_slots(w), (flags & BGE_TICK_BULLET_BASIS) != 0));
         w->maybe_dirty = true;
-        w->rs_bump(); // (k_pose_only re-poses: it writes quat, euler, velocities)
+        w->epochs_edit(); // (k_pose_only re-poses: it writes quat, euler, velocities, and marks every Dynamic Transform dirty)
         if (triggers) {
             process_triggers_without_a_step(w);
         }
@@ -2104,7 +2117,7 @@ try {
         w->rebuild_view();
     }
     w->ground_plane = on;
-    w->rs_bump();
+    w->epochs_edit();
     return BGE_OK;
 }
 BGE_CATCH_ALL("bge_world_set_ground_plane")
@@ -2124,7 +2137,7 @@ try {
     w->static_contacts = on;
     w->static_contacts_ever = w->static_contacts_ever || on;
     w->obstacles_stale = true;
-    w->rs_bump();
+    w->epochs_edit();
     return BGE_OK;
 }
 BGE_CATCH_ALL("bge_world_set_static_contacts")
@@ -2146,7 +2159,7 @@ try {
     w->dynamic_contacts = enabled != 0;
     w->isl_n_prev = 0; // (off and on again: the pair cache starts empty)
     w->isl_gen_stale = true;
-    w->rs_bump();
+    w->epochs_edit();
     return BGE_OK;
 }
 BGE_CATCH_ALL("bge_world_set_dynamic_contacts")
@@ -2475,6 +2488,7 @@ try {
     w->sleep_lin = linear_threshold;
     w->sleep_ang = angular_threshold;
     w->sleep_time = seconds;
+    w->epochs_edit(); // (what decides a body's deactivation state changed)
     return BGE_OK;
 }
 BGE_CATCH_ALL("bge_world_set_sleeping")
