@@ -173,7 +173,7 @@ __global__ void __launch_bounds__(256) k_ground_select(WorldView w, GroundParams
         st4(w.quat, slot, q);
         f &= ~kSettled;
         const F3 zero{0.0f, 0.0f, 0.0f};
-        if (type == 2u) st3(w.vel, slot, zero);
+        if (type == 2u) st_vel(w.vel, slot, zero);
         if (f & kSpin) {
             st3(w.angvel, slot, zero);
             f &= ~kSpin;
@@ -194,7 +194,7 @@ __global__ void __launch_bounds__(256) k_ground_select(WorldView w, GroundParams
             if (!boxes) {
                 const float4 cs = w.cshape[slot];
                 const F3 pos = ld3(w.pos, slot);
-                const F3 v = ld3(w.vel, slot);
+                const F3 v = ld_vel(w.vel, slot);
                 const float reach = (__builtin_fabsf(cs.x) + __builtin_fabsf(cs.y) + __builtin_fabsf(cs.z)) * 1.01f + 0.05f;
                 const float rx = reach + __builtin_fabsf(v.x) * g.dt * 1.01f, ry = reach + __builtin_fabsf(v.y) * g.dt * 1.01f,
                             rz = reach + __builtin_fabsf(v.z) * g.dt * 1.01f;

@@ -676,7 +676,7 @@ __device__ void ground_body(const WorldView& w, const GroundParams& g, uint32_t 
         if (ci != ci0) w.cinfo[slot] = ci;
         return; // k_tick's plain update
     }
-    F3 v = ld3(w.vel, slot);
+    F3 v = ld_vel(w.vel, slot);
     F3 av = spin ? ld3(w.angvel, slot) : F3{0.0f, 0.0f, 0.0f};
     if (g.want_aabb) {
         // the AABB Bullet feeds its broadphase is taken BEFORE the solver runs (predictUnconstraintMotion / updateAabbs):
@@ -705,7 +705,7 @@ __device__ void ground_body(const WorldView& w, const GroundParams& g, uint32_t 
     const F3 invInertiaLocal = ct_inv_inertia_local(localInertia);
     Q4 orn = BASIS ? bt_quat_from_mat(basis) : q;
     const bool moved = ct_solve(pos, v, av, orn, basis, p, n, inv_mass, invInertiaLocal, w.cfriction[slot], force, g.dt);
-    st3(w.vel, slot, v);
+    st_vel(w.vel, slot, v);
     st3(w.angvel, slot, av);
     if (moved) {
         st3(w.pos, slot, pos);
@@ -1053,7 +1053,7 @@ __device__ void contact_body(const WorldView& w, const GroundParams& g, uint32_t
     const float breaking = ct_breaking_threshold(shape);
     Q4 q = ld4(w.quat, slot);
     M3 basis = bt_mat_from_quat(q);
-    F3 v = ld3(w.vel, slot);
+    F3 v = ld_vel(w.vel, slot);
     F3 av = spin ? ld3(w.angvel, slot) : F3{0.0f, 0.0f, 0.0f};
     // the AABB Bullet feeds its broadphase (predictUnconstraintMotion / updateAabbs: pose and velocity as the sub-step starts)
     float fed_mn[3], fed_mx[3];
@@ -1281,7 +1281,7 @@ __device__ void contact_body(const WorldView& w, const GroundParams& g, uint32_t
     }
     v = add3(sb.linVel, sb.extForce);
     av = add3(sb.angVel, sb.extTorque);
-    st3(w.vel, slot, v);
+    st_vel(w.vel, slot, v);
     st3(w.angvel, slot, av);
     if (moved) {
         st3(w.pos, slot, pos);

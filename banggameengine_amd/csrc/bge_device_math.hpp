@@ -36,6 +36,43 @@ __device__ __forceinline__ void st3(float* __restrict__ base, uint32_t slot, con
     p[1] = v.y;
     p[2] = v.z;
 }
+// Linear velocities live in per-wave component blocks: each 64-slot group owns 192 floats, float2 xz[64] (four 128-B
+// lines) and then float y[64] (two lines).  A wave's y store is 256 contiguous bytes, and under a y-only gravity the xz
+// lines of a falling body are never written.  (Slot counts are multiples of 256, so the blocks cover the array exactly.)
+template <typename T> __device__ __forceinline__ T* vel_block(T* base, uint32_t slot) { return base + 192ull * (slot >> 6); }
+// index of component c (0 x, 1 y, 2 z) of a slot's velocity, for code that moves rows a word at a time
+__device__ __forceinline__ uint64_t vel_word(uint32_t slot, uint32_t c)
+{
+    const uint32_t l = slot & 63u;
+    return 192ull * (slot >> 6) + (c == 1u ? 128u + l : 2u * l + (c >> 1));
+}
+__device__ __forceinline__ F3 ld_vel(const float* __restrict__ base, uint32_t slot)
+{
+    const float* blk = vel_block(base, slot);
+    const uint32_t l = slot & 63u;
+    const float2 xz = reinterpret_cast<const float2*>(blk)[l];
+    return F3{xz.x, blk[128u + l], xz.y};
+}
+// Stores the parts of `v` the caller names.  With xz / y = "the bits differ from the value loaded from this slot"
+// (vel_xz_changed / vel_y_changed) memory ends up byte for byte what an unconditional store would leave; -0.0f and 0.0f
+// differ, so the compares are on the bits and not on the floats.
+__device__ __forceinline__ void st_vel_if(float* __restrict__ base, uint32_t slot, const F3& v, bool xz, bool y)
+{
+    float* blk = vel_block(base, slot);
+    const uint32_t l = slot & 63u;
+    if (xz) reinterpret_cast<float2*>(blk)[l] = make_float2(v.x, v.z);
+    if (y) blk[128u + l] = v.y;
+}
+__device__ __forceinline__ bool vel_xz_changed(const F3& v, const F3& old)
+{
+    return __float_as_uint(v.x) != __float_as_uint(old.x) || __float_as_uint(v.z) != __float_as_uint(old.z);
+}
+__device__ __forceinline__ bool vel_y_changed(const F3& v, const F3& old) { return __float_as_uint(v.y) != __float_as_uint(old.y); }
+__device__ __forceinline__ void st_vel(float* __restrict__ base, uint32_t slot, const F3& v) { st_vel_if(base, slot, v, true, true); }
+__device__ __forceinline__ void st_vel_changed(float* __restrict__ base, uint32_t slot, const F3& v, const F3& old)
+{
+    st_vel_if(base, slot, v, vel_xz_changed(v, old), vel_y_changed(v, old));
+}
 __device__ __forceinline__ Q4 ld4(const float* __restrict__ base, uint32_t slot)
 {
     const float4 v = reinterpret_cast<const float4*>(base)[slot];

@@ -83,7 +83,7 @@ __global__ void __launch_bounds__(256) k_island_begin(WorldView w, GroundParams 
         st4(w.quat, slot, q);
         f &= ~kSettled;
         const F3 zero{0.0f, 0.0f, 0.0f};
-        if (type == 2u) st3(w.vel, slot, zero);
+        if (type == 2u) st_vel(w.vel, slot, zero);
         if (f & kSpin) {
             st3(w.angvel, slot, zero);
             f &= ~kSpin;
@@ -108,7 +108,7 @@ __global__ void __launch_bounds__(256) k_island_begin(WorldView w, GroundParams 
     bt_aabb_of_pose(pos, basis, he, mn, mx);
     if (type == 2u) {
         const bool spin = (f & kSpin) != 0;
-        const F3 v = ld3(w.vel, slot);
+        const F3 v = ld_vel(w.vel, slot);
         const F3 av = spin ? ld3(w.angvel, slot) : F3{0.0f, 0.0f, 0.0f};
         const F3 pp{pos.x + v.x * g.dt, pos.y + v.y * g.dt, pos.z + v.z * g.dt};
         float mn2[3], mx2[3];
@@ -689,7 +689,7 @@ __device__ uint32_t isl_prepare_body(const WorldView& w, const GroundParams& g, 
         const M3 invI = ct_inv_inertia_world(basis, invInertiaLocal);
         IslBody b;
         b.dLin = b.dAng = b.push = b.turn = F3{0.0f, 0.0f, 0.0f};
-        b.linVel = ld3(w.vel, slot);
+        b.linVel = ld_vel(w.vel, slot);
         b.angVel = spin ? ld3(w.angvel, slot) : F3{0.0f, 0.0f, 0.0f};
         b.invMass = inv_mass;
         b.extForce = scale3(scale3(force, inv_mass), g.dt);
@@ -848,7 +848,7 @@ __device__ void isl_finish_body(const WorldView& w, const GroundParams& g, IslBo
             ci |= kCiMoved;
         }
         const F3 v = add3(s.linVel, s.extForce), av = add3(s.angVel, s.extTorque);
-        st3(w.vel, slot, v);
+        st_vel(w.vel, slot, v);
         st3(w.angvel, slot, av);
         uint32_t f0 = w.flags[slot];
         uint32_t f = (av.x != 0.0f || av.y != 0.0f || av.z != 0.0f) ? (f0 | kSpin) : (f0 & ~kSpin);

@@ -17,9 +17,12 @@
 // Memory plan (all streams indexed by slot, 256 consecutive slots per workgroup):
 //   reads   flags 4 B (body type, dirty bits, level, in-tile parent index, mass class), pos/euler/scale 12 B
 //           each, vel 12 B (Dynamic bodies only); parent slot 4 B only for nodes whose parent is in an earlier pass
-//   writes  pos 12 B + vel 12 B (Dynamic only), world 64 B; flags only when a bit changed
+//   writes  pos 12 B (Dynamic only), world 64 B; flags only when a bit changed; of vel only the components whose bits the
+//           tick changed: 4 B (y) per body falling under a y-only gravity, 12 B under a gravity with x and z components
+//   vel is stored in per-wave component blocks (bge_device_math.hpp: per 64 slots float2 xz[64], float y[64]), so that the y
+//   store of a wave is 256 contiguous bytes and the xz lines stay clean; pos, euler, scale are rows of three floats.
 //   Waves whose rotation rows are current (WorldView::rs_word) read neither euler nor scale and write only world row 3:
-//   68 B per flat body instead of 140 B.
+//   60 B per flat body instead of 132 B.
 //   Waves whose bodies are all asleep (rest word, WorldView::rs_word word 1) read flags, the deactivation record and the contact
 //   word, 8..12 B per body, and store nothing.
 //   The world matrices leave through LDS so that every wave-level store instruction writes 1 KiB of
@@ -251,7 +254,7 @@ __global__ void __launch_bounds__(kTile, NORMAL ? 4 : (AABB ? BGE_AABB_MIN_WAVES
         eul = ld3(w.euler, slot);
         if (XFORM) scl = ld3(w.scale, slot);
     }
-    if (PHYS && (hdr & kHdrAllDynamic)) vel_early = ld3(w.vel, slot); // (elsewhere most slots have no velocity to read)
+    if (PHYS && (hdr & kHdrAllDynamic)) vel_early = ld_vel(w.vel, slot); // (elsewhere most slots have no velocity to read)
     // The mass palette entry (gravity force, inverse mass) is one more dependent round trip behind the flag word.  In tiles whose
     // slots all carry a Dynamic body every lane fetches palette entry (lane) with the loads above and takes its class's entry
     // from lane (class) once the flags are there (classes are < 64; outside any divergent branch: a permute reads active lanes).
@@ -337,7 +340,7 @@ __global__ void __launch_bounds__(kTile, NORMAL ? 4 : (AABB ? BGE_AABB_MIN_WAVES
                     if (!BASIS) turn = false; // its angular velocity is zero now: the default scheme leaves the re-posed quaternion alone
                 }
             } else {
-                if (dynamic) v = (hdr & kHdrAllDynamic) ? vel_early : ld3(w.vel, slot);
+                if (dynamic) v = (hdr & kHdrAllDynamic) ? vel_early : ld_vel(w.vel, slot);
                 if (spin) av = ld3(w.angvel, slot);
                 if (turn || AABB) q = ld4(w.quat, slot);
             }
@@ -409,7 +412,7 @@ __global__ void __launch_bounds__(kTile, NORMAL ? 4 : (AABB ? BGE_AABB_MIN_WAVES
                 if (inv_mass != 0.0f && dz == kDeactSleeping) {
                     // asleep: no gravity, not solved, not integrated; updateActivationState zeroes the velocities
                     v = F3{0.0f, 0.0f, 0.0f};
-                    st3(w.vel, slot, v);
+                    st_vel(w.vel, slot, v);
                     asleep = true;
                     if (spin) {
                         st3(w.angvel, slot, v);
@@ -418,10 +421,16 @@ __global__ void __launch_bounds__(kTile, NORMAL ? 4 : (AABB ? BGE_AABB_MIN_WAVES
                     }
                 } else if (inv_mass != 0.0f) {
                     // applyGravity (F = g * (1/invMass)) + solver write-back of the external force impulse
+                    // Of the velocity only the components whose bits the impulse changed are stored: a y-only gravity leaves the xz
+                    // lines of the velocity blocks clean (8 B per falling body less to write back).  A solved body's velocity is
+                    // what k_ground stored; a re-posed body's zero was not loaded, so it is stored whole.  Stored here and not next
+                    // to the position below: neither the loaded components nor the compares then stay live across the turn.
                     if (!solved) {
-                        v.x = v.x + (force.x * inv_mass) * p.dt;
-                        v.y = v.y + (force.y * inv_mass) * p.dt;
-                        v.z = v.z + (force.z * inv_mass) * p.dt;
+                        const F3 v1{v.x + (force.x * inv_mass) * p.dt, v.y + (force.y * inv_mass) * p.dt, v.z + (force.z * inv_mass) * p.dt};
+                        st_vel_if(w.vel, slot, v1, repose || vel_xz_changed(v1, v), repose || vel_y_changed(v1, v));
+                        v = v1;
+                    } else if (repose) {
+                        st_vel(w.vel, slot, v);
                     }
                     // integrateTransforms
                     pos.x = pos.x + v.x * p.dt;
@@ -446,7 +455,6 @@ __global__ void __launch_bounds__(kTile, NORMAL ? 4 : (AABB ? BGE_AABB_MIN_WAVES
                             f |= kSettled;
                         }
                     }
-                    st3(w.vel, slot, v);
                     st3(w.pos, slot, pos);
                     // updateActivationState: updateDeactivation + wantsSleeping.  The kernel is close to VALU-bound, so the
                     // common case is decided by one compare: |v.y| >= threshold implies |v|^2 >= threshold^2 in float
@@ -472,7 +480,7 @@ __global__ void __launch_bounds__(kTile, NORMAL ? 4 : (AABB ? BGE_AABB_MIN_WAVES
                     f = dz ? (f | kDrowsy) : (f & ~kDrowsy);
                 }
                 if (inv_mass == 0.0f && repose) {
-                    st3(w.vel, slot, v);
+                    st_vel(w.vel, slot, v);
                 }
                 // SyncRigidBodiesFromPhysics: rotationEuler <- getEulerZYX(basis) whenever the orientation was
                 // (re)posed or advanced; a non-spinning body keeps its euler triple bit for bit
@@ -729,7 +737,7 @@ __global__ void __launch_bounds__(256) k_pose_only(WorldView w, uint64_t n_slots
         st4(w.quat, slot, q);
         f &= ~kSettled;
         const F3 zero{0.0f, 0.0f, 0.0f};
-        if (dynamic) st3(w.vel, slot, zero);
+        if (dynamic) st_vel(w.vel, slot, zero);
         if (f & kSpin) {
             st3(w.angvel, slot, zero);
             f &= ~kSpin;
@@ -749,10 +757,12 @@ __global__ void __launch_bounds__(256) k_pose_only(WorldView w, uint64_t n_slots
 // ------------------------------------------------------------------ component scatter / gather (entity order <-> slots)
 // stage holds `count` rows of `width` 32-bit words for entities [first, first+count).
 // `index` (nullable) selects entities explicitly: row i belongs to entity index[i] instead of first + i.
+// `vel_blocks`: the device array is WorldView::vel — rows of three words on the host side, per-wave component blocks on the device
+// (bge_device_math.hpp, vel_word).
 __global__ void k_scatter_rows(const uint32_t* __restrict__ slot_of_entity, const uint32_t* __restrict__ index,
                                uint64_t first, uint64_t count,
                                uint32_t width, const uint32_t* __restrict__ stage, uint32_t* __restrict__ dst,
-                               uint32_t* __restrict__ flags, uint32_t or_bits, uint32_t need_bits)
+                               uint32_t* __restrict__ flags, uint32_t or_bits, uint32_t need_bits, bool vel_blocks)
 {
     const uint64_t i = blockIdx.x * static_cast<uint64_t>(blockDim.x) + threadIdx.x;
     if (i >= count) return;
@@ -762,20 +772,20 @@ __global__ void k_scatter_rows(const uint32_t* __restrict__ slot_of_entity, cons
     // Transform (there the position array is the body's origin, and nothing marks what does not exist)
     if (need_bits && (flags[slot] & need_bits) != need_bits) return;
     if (dst) {
-        for (uint32_t k = 0; k < width; ++k) dst[static_cast<uint64_t>(slot) * width + k] = stage[i * width + k];
+        for (uint32_t k = 0; k < width; ++k) dst[vel_blocks ? vel_word(slot, k) : static_cast<uint64_t>(slot) * width + k] = stage[i * width + k];
     }
     if (flags && or_bits) flags[slot] |= or_bits;
 }
 
 __global__ void k_gather_rows(const uint32_t* __restrict__ slot_of_entity, const uint32_t* __restrict__ index,
                               uint64_t first, uint64_t count,
-                              uint32_t width, const uint32_t* __restrict__ src, uint32_t* __restrict__ stage)
+                              uint32_t width, const uint32_t* __restrict__ src, uint32_t* __restrict__ stage, bool vel_blocks)
 {
     const uint64_t i = blockIdx.x * static_cast<uint64_t>(blockDim.x) + threadIdx.x;
     if (i >= count) return;
     const uint32_t slot = slot_of_entity[index ? index[i] : first + i];
     for (uint32_t k = 0; k < width; ++k) {
-        stage[i * width + k] = slot == kNone ? 0u : src[static_cast<uint64_t>(slot) * width + k];
+        stage[i * width + k] = slot == kNone ? 0u : src[vel_blocks ? vel_word(slot, k) : static_cast<uint64_t>(slot) * width + k];
     }
 }
 
@@ -815,7 +825,7 @@ __global__ void k_scatter_bodies(const uint32_t* __restrict__ slot_of_entity, co
     w.mask[slot] = mask[i];
     if ((f & kTypeMask) == 0) {
         // body removed: forget its state
-        w.vel[3ull * slot] = w.vel[3ull * slot + 1] = w.vel[3ull * slot + 2] = 0.0f;
+        st_vel(w.vel, slot, F3{0.0f, 0.0f, 0.0f});
         w.angvel[3ull * slot] = w.angvel[3ull * slot + 1] = w.angvel[3ull * slot + 2] = 0.0f;
     }
 }
@@ -830,9 +840,7 @@ __global__ void k_scatter_velocities(const uint32_t* __restrict__ slot_of_entity
     uint32_t f = w.flags[slot];
     if ((f & kTypeMask) != 2u) return; // only Dynamic bodies carry velocity
     if (lin) {
-        w.vel[3ull * slot + 0] = lin[3 * i + 0];
-        w.vel[3ull * slot + 1] = lin[3 * i + 1];
-        w.vel[3ull * slot + 2] = lin[3 * i + 2];
+        st_vel(w.vel, slot, F3{lin[3 * i + 0], lin[3 * i + 1], lin[3 * i + 2]});
     }
     if (ang) {
         const float ax = ang[3 * i + 0], ay = ang[3 * i + 1], az = ang[3 * i + 2];
@@ -853,7 +861,7 @@ __global__ void k_init_slots(uint64_t n_slots, const uint32_t* __restrict__ stru
     w.pos[3 * s] = w.pos[3 * s + 1] = w.pos[3 * s + 2] = 0.0f;
     w.euler[3 * s] = w.euler[3 * s + 1] = w.euler[3 * s + 2] = 0.0f;
     w.scale[3 * s] = w.scale[3 * s + 1] = w.scale[3 * s + 2] = 1.0f;
-    w.vel[3 * s] = w.vel[3 * s + 1] = w.vel[3 * s + 2] = 0.0f;
+    st_vel(w.vel, static_cast<uint32_t>(s), F3{0.0f, 0.0f, 0.0f});
     w.angvel[3 * s] = w.angvel[3 * s + 1] = w.angvel[3 * s + 2] = 0.0f;
     w.quat[4 * s] = w.quat[4 * s + 1] = w.quat[4 * s + 2] = 0.0f;
     w.quat[4 * s + 3] = 1.0f;
@@ -1109,20 +1117,22 @@ hipError_t launch_pose_only(hipStream_t stream, const WorldView& w, uint64_t n_s
 
 hipError_t launch_scatter_rows(hipStream_t stream, const uint32_t* slot_of_entity, uint64_t first, uint64_t count,
                                uint32_t width, const void* stage, void* dst, uint32_t* flags, uint32_t or_bits,
-                               const uint32_t* index, uint32_t need_bits)
+                               const uint32_t* index, uint32_t need_bits, bool vel_blocks)
 {
     if (count == 0) return hipSuccess;
+    if (vel_blocks && width != 3) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_scatter_rows, grid_for(count, 256), dim3(256), 0, stream, slot_of_entity, index, first, count, width,
-                       static_cast<const uint32_t*>(stage), static_cast<uint32_t*>(dst), flags, or_bits, need_bits);
+                       static_cast<const uint32_t*>(stage), static_cast<uint32_t*>(dst), flags, or_bits, need_bits, vel_blocks);
     return hipGetLastError();
 }
 
 hipError_t launch_gather_rows(hipStream_t stream, const uint32_t* slot_of_entity, uint64_t first, uint64_t count,
-                              uint32_t width, const void* src, void* stage, const uint32_t* index)
+                              uint32_t width, const void* src, void* stage, const uint32_t* index, bool vel_blocks)
 {
     if (count == 0) return hipSuccess;
+    if (vel_blocks && width != 3) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_gather_rows, grid_for(count, 256), dim3(256), 0, stream, slot_of_entity, index, first, count, width,
-                       static_cast<const uint32_t*>(src), static_cast<uint32_t*>(stage));
+                       static_cast<const uint32_t*>(src), static_cast<uint32_t*>(stage), vel_blocks);
     return hipGetLastError();
 }
 

@@ -21,7 +21,7 @@ struct WorldView {
     // world matrices (Transform::world); `local` is never materialised
     float* world;             // [slots][16]
     // rigid body state (Bullet's btRigidBody) and parameters
-    float* vel;               // [slots][3]
+    float* vel;               // [slots / 64] blocks of {float2 xz[64]; float y[64]} (ld_vel / st_vel)
     float* angvel;            // [slots][3]
     float* quat;              // [slots][4]
     float* inv_mass;          // [slots]     only read for mass class 63 (more than 62 distinct masses)
@@ -235,9 +235,9 @@ hipError_t launch_ground(hipStream_t stream, const WorldView& w, const GroundPar
 
 hipError_t launch_scatter_rows(hipStream_t stream, const uint32_t* slot_of_entity, uint64_t first, uint64_t count,
                                uint32_t width, const void* stage, void* dst, uint32_t* flags, uint32_t or_bits,
-                               const uint32_t* index = nullptr, uint32_t need_bits = 0);
+                               const uint32_t* index = nullptr, uint32_t need_bits = 0, bool vel_blocks = false);
 hipError_t launch_gather_rows(hipStream_t stream, const uint32_t* slot_of_entity, uint64_t first, uint64_t count,
-                              uint32_t width, const void* src, void* stage, const uint32_t* index = nullptr);
+                              uint32_t width, const void* src, void* stage, const uint32_t* index = nullptr, bool vel_blocks = false);
 hipError_t launch_scatter_bodies(hipStream_t stream, const uint32_t* slot_of_entity, uint64_t first, uint64_t count,
                                  const uint32_t* type_bits, const float* inv_mass, const float* half_extent3,
                                  const uint32_t* group, const uint32_t* mask, const uint32_t* filter_class, const WorldView& w,

@@ -486,18 +486,19 @@ int upload_rows(bge_world* w, uint64_t first, uint64_t count, uint32_t width, co
     return BGE_OK;
 }
 
+// (vel_blocks: `src` is the velocity array, which is not rows of `width` words — always through the gather kernel)
 int download_rows(bge_world* w, uint64_t first, uint64_t count, uint32_t width, const void* src, void* host,
-                  const uint32_t* dev_index = nullptr)
+                  const uint32_t* dev_index = nullptr, bool vel_blocks = false)
 {
     const size_t bytes = static_cast<size_t>(count) * width * 4;
-    if (w->flat.identity && !dev_index) {
+    if (w->flat.identity && !dev_index && !vel_blocks) {
         // flat scene: slot == entity index, the rows are already contiguous in entity order
         HIP_TRY(hipMemcpyAsync(host, static_cast<const char*>(src) + first * width * 4, bytes, hipMemcpyDeviceToHost, w->stream));
         HIP_TRY(hipStreamSynchronize(w->stream));
         return BGE_OK;
     }
     HIP_TRY(w->stage.ensure(bytes));
-    HIP_TRY(bge::launch_gather_rows(w->stream, w->slot_of_entity.as<uint32_t>(), first, count, width, src, w->stage.p, dev_index));
+    HIP_TRY(bge::launch_gather_rows(w->stream, w->slot_of_entity.as<uint32_t>(), first, count, width, src, w->stage.p, dev_index, vel_blocks));
     HIP_TRY(hipMemcpyAsync(host, w->stage.p, bytes, hipMemcpyDeviceToHost, w->stream));
     HIP_TRY(hipStreamSynchronize(w->stream));
     return BGE_OK;
@@ -1266,7 +1267,7 @@ try {
         }
         for (Carry& c : carries) {
             HIP_TRY(c.tmp.ensure(n_keep * c.width * 4));
-            HIP_TRY(bge::launch_gather_rows(w->stream, w->slot_of_entity.as<uint32_t>(), 0, n_keep, c.width, c.buf->p, c.tmp.p));
+            HIP_TRY(bge::launch_gather_rows(w->stream, w->slot_of_entity.as<uint32_t>(), 0, n_keep, c.width, c.buf->p, c.tmp.p, nullptr, c.buf == &w->vel));
         }
         HIP_TRY(old_flags_tmp.ensure(n_keep * 4));
         HIP_TRY(bge::launch_gather_rows(w->stream, w->slot_of_entity.as<uint32_t>(), 0, n_keep, 1, w->flags.p, old_flags_tmp.p));
@@ -1430,7 +1431,8 @@ try {
         HIP_TRY(map_dev.ensure(n_keep * 4));
         HIP_TRY(hipMemcpyAsync(map_dev.p, carry_map.data(), n_keep * 4, hipMemcpyHostToDevice, w->stream));
         for (Carry& c : carries) {
-            HIP_TRY(bge::launch_scatter_rows(w->stream, map_dev.as<uint32_t>(), 0, n_keep, c.width, c.tmp.p, c.buf->p, nullptr, 0));
+            HIP_TRY(bge::launch_scatter_rows(w->stream, map_dev.as<uint32_t>(), 0, n_keep, c.width, c.tmp.p, c.buf->p, nullptr, 0, nullptr, 0,
+                                             c.buf == &w->vel));
         }
         // flags: keep body type / dirty / spin / shape bits of the old word, structure from the new one
         std::vector<uint32_t> merged(nf.flags);
@@ -2435,7 +2437,7 @@ try {
     if (count == 0) return BGE_OK;
     DeviceGuard guard(w->device);
     if (linvel3) {
-        if (int rc = download_rows(w, first, count, 3, w->vel.p, linvel3)) return rc;
+        if (int rc = download_rows(w, first, count, 3, w->vel.p, linvel3, nullptr, true)) return rc;
     }
     if (angvel3) {
         if (int rc = download_rows(w, first, count, 3, w->angvel.p, angvel3)) return rc;

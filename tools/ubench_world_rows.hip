@@ -9,6 +9,8 @@
 //   d  fast path    read flags, pos, vel; write pos, vel and row 3
 //   b2 rows 2-3     32 B per slot at a 64-B stride (two 16-B stores per lane: whole 32-B sectors)
 //   e  fast path, whole sectors: read flags, pos, vel and row 2; write pos, vel and rows 2-3
+//   f  fast path, vel in per-wave component blocks (ld_vel / st_vel_changed): only vel.y changes, only vel.y is stored
+//   g  as f with all three components stored (st_vel): the layout alone, without the skipped stores
 // Each kernel runs `reps` times back to back between two events after a warm-up; one JSON line per (kernel, store
 // policy, size).  Built by tools/ubench_world_rows.sh; no part of the product library.
 #include <hip/hip_runtime.h>
@@ -150,6 +152,45 @@ template <bool NT> __global__ void __launch_bounds__(kBlock, 8) k_flat_rows23(So
     }
 }
 
+// (f) as (d) with vel in per-wave component blocks; a y-only gravity leaves x and z as loaded, so their lines stay clean
+template <bool NT> __global__ void __launch_bounds__(kBlock, 8) k_flat_row3_vy(Soa s, uint32_t n_slots, float dt)
+{
+    const uint32_t slot = blockIdx.x * kBlock + threadIdx.x;
+    const uint32_t f = s.flags[slot];
+    F3 pos = ld3(s.pos, slot), vel = ld_vel(s.vel, slot);
+    if (f & 1u) {
+        const F3 old = vel;
+        vel.y = vel.y + -9.81f * dt;
+        const bool cxz = vel_xz_changed(vel, old), cy = vel_y_changed(vel, old);
+        pos.x = pos.x + vel.x * dt;
+        pos.y = pos.y + vel.y * dt;
+        pos.z = pos.z + vel.z * dt;
+        st_vel_if(s.vel, slot, vel, cxz, cy);
+        st3(s.pos, slot, pos);
+        put4<NT>(s.world + 4ull * slot + 3, make_float4(pos.x, pos.y, pos.z, 1.0f));
+    }
+}
+
+// (g) as (f), every component stored.  The x and z impulses are run-time zeros: a store of the very value just loaded is one
+// the compiler may drop, and then (g) would be (f).
+template <bool NT> __global__ void __launch_bounds__(kBlock, 8) k_flat_row3_vblk(Soa s, uint32_t n_slots, float dt, float gx, float gz)
+{
+    const uint32_t slot = blockIdx.x * kBlock + threadIdx.x;
+    const uint32_t f = s.flags[slot];
+    F3 pos = ld3(s.pos, slot), vel = ld_vel(s.vel, slot);
+    if (f & 1u) {
+        vel.x = vel.x + gx * dt;
+        vel.y = vel.y + -9.81f * dt;
+        vel.z = vel.z + gz * dt;
+        pos.x = pos.x + vel.x * dt;
+        pos.y = pos.y + vel.y * dt;
+        pos.z = pos.z + vel.z * dt;
+        st_vel(s.vel, slot, vel);
+        st3(s.pos, slot, pos);
+        put4<NT>(s.world + 4ull * slot + 3, make_float4(pos.x, pos.y, pos.z, 1.0f));
+    }
+}
+
 template <typename F> float time_us(F launch, int warm, int reps)
 {
     hipEvent_t a, b;
@@ -176,7 +217,7 @@ void report(const char* kernel, bool nt, uint32_t n, float us, double bytes_per_
     std::fflush(stdout);
 }
 
-template <bool NT> void run_size(uint32_t n, int reps, Soa s)
+template <bool NT> void run_size(uint32_t n, int reps, Soa s, float zero)
 {
     const int warm = 20;
     const dim3 blk(kBlock);
@@ -187,6 +228,12 @@ template <bool NT> void run_size(uint32_t n, int reps, Soa s)
     report("c_flat_full", NT, n, time_us([&] { k_flat_full<NT><<<g_slot, blk>>>(s, n, 1.0f / 60.0f); }, warm, reps), 140.0);
     report("d_flat_row3", NT, n, time_us([&] { k_flat_row3<NT><<<g_slot, blk>>>(s, n, 1.0f / 60.0f); }, warm, reps), 68.0);
     report("e_flat_rows23", NT, n, time_us([&] { k_flat_rows23<NT><<<g_slot, blk>>>(s, n, 1.0f / 60.0f); }, warm, reps), 100.0);
+    // (d) again on either side of (f) and (g): the spread of the three (d) lines is the yardstick for the other two
+    report("f_flat_row3_vy", NT, n, time_us([&] { k_flat_row3_vy<NT><<<g_slot, blk>>>(s, n, 1.0f / 60.0f); }, warm, reps), 60.0);
+    report("d_flat_row3", NT, n, time_us([&] { k_flat_row3<NT><<<g_slot, blk>>>(s, n, 1.0f / 60.0f); }, warm, reps), 68.0);
+    report("g_flat_row3_vblk", NT, n, time_us([&] { k_flat_row3_vblk<NT><<<g_slot, blk>>>(s, n, 1.0f / 60.0f, zero, zero); }, warm, reps), 68.0);
+    report("d_flat_row3", NT, n, time_us([&] { k_flat_row3<NT><<<g_slot, blk>>>(s, n, 1.0f / 60.0f); }, warm, reps), 68.0);
+    report("f_flat_row3_vy", NT, n, time_us([&] { k_flat_row3_vy<NT><<<g_slot, blk>>>(s, n, 1.0f / 60.0f); }, warm, reps), 60.0);
     CK(hipGetLastError());
     CK(hipDeviceSynchronize());
 }
@@ -194,12 +241,13 @@ template <bool NT> void run_size(uint32_t n, int reps, Soa s)
 } // namespace
 
 // usage: ubench_world_rows [slots ...]   (default 1048576 16777216; rounded up to whole 256-slot blocks)
-//        env UBENCH_REPS: timed launches per kernel (default 200)
+//        env UBENCH_REPS: timed launches per kernel (default 200); UBENCH_GXZ: x and z gravity of kernel (g) (default 0)
 int main(int argc, char** argv)
 {
     std::vector<uint32_t> sizes;
     for (int i = 1; i < argc; ++i) sizes.push_back(static_cast<uint32_t>(std::strtoul(argv[i], nullptr, 10)));
     if (sizes.empty()) sizes = {1u << 20, 1u << 24};
+    const float zero = std::getenv("UBENCH_GXZ") ? static_cast<float>(std::atof(std::getenv("UBENCH_GXZ"))) : 0.0f; // (g)'s x / z gravity
     const int reps = std::getenv("UBENCH_REPS") ? std::atoi(std::getenv("UBENCH_REPS")) : 200;
     for (uint32_t n0 : sizes) {
         const uint32_t n = (n0 + kBlock - 1) / kBlock * kBlock;
@@ -220,8 +268,8 @@ int main(int argc, char** argv)
         CK(hipMemcpy(s.scale, v3.data(), 12ull * n, hipMemcpyHostToDevice));
         CK(hipMemset(s.vel, 0, 12ull * n));
         CK(hipMemset(s.world, 0, 64ull * n));
-        run_size<false>(n, reps, s);
-        run_size<true>(n, reps, s);
+        run_size<false>(n, reps, s, zero);
+        run_size<true>(n, reps, s, zero);
         CK(hipFree(s.flags));
         CK(hipFree(s.pos));
         CK(hipFree(s.vel));

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Store-shape microbenchmark of the world matrices (tools/ubench_world_rows.hip), run on the GPU box:
 #   bash tools/ubench_world_rows.sh [OUT_DIR]
-# 1. event timing of the four kernels, plain and non-temporal stores, 1 M and 16 M slots  -> times.jsonl
+# 1. event timing of every kernel, plain and non-temporal stores, 1 M and 16 M slots  -> times.jsonl
 # 2. rocprofv3 --kernel-trace --stats                                                      -> stats/
 # 3. rocprofv3 --pmc FETCH_SIZE, then --pmc WRITE_SIZE, each a run of its own              -> pmc_FETCH_SIZE/, pmc_WRITE_SIZE/
 # then a per-kernel digest of all three (tools/ubench_world_rows_digest.py).
