@@ -100,6 +100,58 @@ struct TmpBuf : DevBuf {
     ~TmpBuf() { release(); }
 };
 
+// A per-slot device array and its format, set once where the member is declared: upload, download, allocation and the carry of
+// bge_world_set_topology read it from here.
+struct SlotBuf : DevBuf {
+    static constexpr int kNoFill = -1;
+    const uint32_t words;        // 32-bit words per slot
+    const bool vel_blocks;       // per-wave velocity blocks (bge_device_math.hpp vel_word) instead of rows of `words`
+    const int fill;              // the byte a fresh store is filled with; kNoFill: k_init_slots and the uploads write every row
+    const bool* const feature[2]; // optional store: made when one of these is first switched on, then kept; none = always there
+    explicit SlotBuf(uint32_t words, bool vel_blocks = false, int fill = kNoFill, const bool* f0 = nullptr, const bool* f1 = nullptr)
+        : words(words), vel_blocks(vel_blocks), fill(fill), feature{f0, f1} {}
+    size_t bytes_for(uint64_t slots) const { return slots * words * 4; }
+    // has a store in every layout: always, or exists already, or its feature is on
+    bool wanted() const { return !feature[0] || p || *feature[0] || (feature[1] && *feature[1]); }
+};
+
+// A device array in ENTITY order (a re-flattening moves slots, not entities): allocated with the first upload, a row of all ones
+// (NaNs) = nothing uploaded, rows >= n_entities once it exists.
+struct EntityBuf : DevBuf {
+    const uint32_t words; // per entity
+    uint64_t rows = 0;
+    explicit EntityBuf(uint32_t words) : words(words) {}
+    int first_use(uint64_t n_entities, hipStream_t stream)
+    {
+        if (p) return BGE_OK;
+        const uint64_t n = std::max<uint64_t>(n_entities, 1);
+        HIP_TRY(ensure(n * words * 4));
+        HIP_TRY(hipMemsetAsync(p, 0xff, n * words * 4, stream));
+        rows = n;
+        return BGE_OK;
+    }
+    // a topology of n entities after one of old_n: surviving indices keep their row, indices that went or are new have none
+    int follow_topology(uint64_t n, uint64_t old_n, hipStream_t stream)
+    {
+        if (!p) return BGE_OK;
+        const size_t row = words * 4;
+        if (n > rows) {
+            TmpBuf grown;
+            HIP_TRY(grown.ensure(n * row));
+            HIP_TRY(hipMemsetAsync(grown.p, 0xff, n * row, stream));
+            const uint64_t keep = std::min(old_n, rows);
+            if (keep) HIP_TRY(hipMemcpyAsync(grown.p, p, keep * row, hipMemcpyDeviceToDevice, stream));
+            HIP_TRY(hipStreamSynchronize(stream));
+            std::swap(p, grown.p);
+            std::swap(bytes, grown.bytes);
+            rows = n;
+        } else if (n < old_n) {
+            HIP_TRY(hipMemsetAsync(static_cast<char*>(p) + n * row, 0xff, (std::min(old_n, rows) - n) * row, stream));
+        }
+        return BGE_OK;
+    }
+};
+
 // Collider size -> AABB half extents in the collider's frame.
 // Box: btBoxShape ctor (implicit = he - 0.04), setSafeMargin (margin = min(0.04, 0.1*min he) through
 // btBoxShape::setMargin), btTransformAabb adds the margin back.  Capsule (up axis Y): (r, r+h/2, r).
@@ -156,10 +208,27 @@ struct bge_world {
     float local_time = 0.0f; // btDiscreteDynamicsWorld::m_localTime (bge_world_step_simulation)
 
     // device arrays
-    DevBuf flags, parent, tile_hdr, slot_of_entity, entity_of_slot, root_slots, root_index;
-    DevBuf pos, euler, scale, world, vel, angvel, quat, inv_mass, half_extent, group, mask, aabb;
-    DevBuf root_worlds, counter, stage, stage2, mass_palette, normal, deact, filter_class, filter_table, grav_palette;
-    DevBuf cshape, cmass, cfriction, cinfo, manifold; // ground contact (bge_contact.hip); manifold allocated when the plane is switched on
+    DevBuf parent, tile_hdr, slot_of_entity, entity_of_slot, root_slots, root_index;
+    DevBuf root_worlds, counter, stage, stage2, mass_palette, filter_table, grav_palette;
+    // Per-slot arrays that are not carried as rows: flags are merged on the host; normal is allocated by the first tick that asks
+    // for it and not carried (cull_params relies on its size staying stale after growth).
+    SlotBuf flags{1}, normal{16};
+    // Per-slot component state.  `carried` below is the one place that enumerates these.
+    SlotBuf pos{3}, euler{3}, scale{3}, world{16}, vel{3, true}, angvel{3}, quat{4}, inv_mass{1}, deact{1}, filter_class{1};
+    SlotBuf half_extent{3}, group{1}, mask{1}, aabb{6};
+    SlotBuf cshape{4}, cmass{1}, cfriction{1}, cinfo{1}; // ground contact (bge_contact.hip)
+    SlotBuf manifold{32, false, 0x00, &ground_plane};    // ... its four points per slot, from the first time the plane is switched on
+    SlotBuf crestitution{1};                             // RigidBody::restitution per slot (k_init_slots writes the component default, 0)
+    // kBoxManifolds manifold rows per slot, every row free (bge::kBoxNone) until a contact takes it.  A body of an island collides
+    // its own pairs through contact_body, which keeps the obstacle manifold rows of its slot tidy whether or not there are
+    // obstacles: the store exists from the first bge_world_set_static_contacts(1) or bge_world_set_dynamic_contacts(1) on.
+    SlotBuf bmanifold{bge::kBoxManifolds * bge::kBoxManifoldWords, false, 0xff, &static_contacts, &dynamic_contacts};
+    // What bge_world_set_topology carries over to the new layout, allocates for it and (the optional stores) fills, in this order.
+    // An optional store follows every layout from its first use on, feature on or off: the carry scatters its rows to the NEW slot
+    // indices, and the kernels index it by slot as soon as the feature is back.
+    SlotBuf* const carried[21] = {&pos,   &euler, &scale, &world,  &vel,   &angvel,    &quat,  &inv_mass, &deact,        &filter_class, &half_extent,
+                                  &group, &mask,  &aabb,  &cshape, &cmass, &cfriction, &cinfo, &manifold, &crestitution, &bmanifold};
+    uint64_t slot_rows() const { return std::max<uint64_t>(flat.n_slots, bge::kTile); } // arrays are allocated for whole tiles
     DevBuf ground_list, ground_count;                 // slots k_ground_select hands to the solver; count + ticket words
     // The tick kernel's per-wave words (WorldView::rs_word: "rotation rows current" and "at rest", two per wave64, zeroed with every
     // layout) and the epochs they are compared with (bge_epochs.hpp).  Every call that can write pos, euler, scale, world, quat,
@@ -178,8 +247,6 @@ struct bge_world {
     }
     // Dynamic boxes on the Static / Kinematic box colliders of the scene (round 3, bge_contact.hip): off by default, like the plane
     bool static_contacts = false;
-    DevBuf crestitution;                              // RigidBody::restitution per slot (allocated with the layout, zero = the component default)
-    DevBuf bmanifold;                                 // kBoxManifolds manifold rows per slot (allocated when the feature is switched on)
     DevBuf obstacle_slots, obstacle_gen, obstacles, obstacle_grid, box_list, box_count;
     bool obstacle_grid_on = true; // BGE_OBSTACLE_GRID=0: every body tests every obstacle (measurements)
     uint32_t n_obstacles = 0;
@@ -302,14 +369,14 @@ struct bge_world {
     DevBuf move_in, move_out, move_state, move_casts, move_hits;
     // debug overlay (bge_debug.hip): per-workgroup line counts and their offsets, the host entry point's line buffer and total
     DevBuf dbg_block_sum, dbg_block_off, dbg_lines, dbg_total;
-    // frustum culling (bge_cull.hip): the model-space bounds per ENTITY (allocated with the first upload; a row of NaNs = no bounds;
-    // bounds_rows >= n_entities rows once it exists), the pass's ballots / counts / offsets, the host entry point's records and total
-    DevBuf bounds, cull_ballots, cull_block_sum, cull_block_off, cull_out, cull_total;
-    uint64_t bounds_rows = 0;
-    // draw batches (bge_batch.hip): the draw key per ENTITY (allocated with the first upload; all ones = no key; draw_key_rows >=
-    // n_entities rows once it exists), the sort's ping-pong records and digit tables, the host entry point's batches
-    DevBuf draw_keys, batch_sort, batch_hist, batch_out;
-    uint64_t draw_key_rows = 0;
+    // frustum culling (bge_cull.hip): the model-space bounds per ENTITY (a row of NaNs = no bounds), the pass's ballots / counts /
+    // offsets, the host entry point's records and total
+    EntityBuf bounds{6};
+    DevBuf cull_ballots, cull_block_sum, cull_block_off, cull_out, cull_total;
+    // draw batches (bge_batch.hip): the draw key per ENTITY (all ones = no key), the sort's ping-pong records and digit tables, the
+    // host entry point's batches
+    EntityBuf draw_keys{1};
+    DevBuf batch_sort, batch_hist, batch_out;
     uint32_t trigger_grid_min = 64;       // more ghosts than this: the broadphase grid answers for the small ones
     // Enter / Exit taken on the device (bge_kernels.hpp TriggerDiff): two key tables (this tick's, last tick's), header + deltas in
     // one device buffer with a page-locked copy.  The overlap sets above stay the truth; `trig_mirror_valid` says that last tick's
@@ -386,9 +453,9 @@ struct bge_world {
     }
     void release_all()
     {
-        for (DevBuf* b : {&flags, &parent, &tile_hdr, &slot_of_entity, &entity_of_slot, &root_slots, &root_index, &pos, &euler, &scale, &world, &vel,
-                          &angvel, &quat, &inv_mass, &half_extent, &group, &mask, &aabb, &root_worlds, &counter, &stage,
-                          &stage2, &mass_palette, &normal, &deact, &filter_class, &filter_table, &grav_palette, &bp_partials, &cshape, &cmass, &cfriction, &cinfo, &manifold, &crestitution, &bmanifold, &obstacle_slots, &obstacle_gen, &obstacles, &obstacle_grid, &box_list, &box_count, &frozen, &rs_word, &trig_slot, &trig_entity, &trig_he, &trig_group,
+        for (SlotBuf* a : carried) a->release();
+        for (DevBuf* b : std::initializer_list<DevBuf*>{&flags, &parent, &tile_hdr, &slot_of_entity, &entity_of_slot, &root_slots, &root_index, &root_worlds, &counter, &stage,
+                          &stage2, &mass_palette, &normal, &filter_table, &grav_palette, &bp_partials, &obstacle_slots, &obstacle_gen, &obstacles, &obstacle_grid, &box_list, &box_count, &frozen, &rs_word, &trig_slot, &trig_entity, &trig_he, &trig_group,
                           &trig_mask, &trig_active, &trig_aabb, &trig_pairs, &trig_count, &trig_lists, &ground_list, &ground_count, &trig_tab[0], &trig_tab[1],
                           &trig_delta_dev, &trig_keys_dev, &trig_pose, &query_in, &query_out, &query_keys, &query_all, &query_all_count, &query_ghosts, &move_in, &move_out, &move_state, &move_casts, &move_hits, &dbg_block_sum, &dbg_block_off,
                           &dbg_lines, &dbg_total, &bounds, &cull_ballots, &cull_block_sum, &cull_block_off, &cull_out, &cull_total, &draw_keys,
@@ -455,7 +522,6 @@ int check_range(const bge_world* w, uint64_t first, uint64_t count)
     return BGE_OK;
 }
 
-// upload one host array of `count` rows x `width` words into a per-slot device array
 // device copy of an explicit entity-index list (validated against n_entities), or null for a range call
 int stage_index(bge_world* w, uint64_t count, const uint32_t* index, const uint32_t** dev)
 {
@@ -473,34 +539,72 @@ int stage_index(bge_world* w, uint64_t count, const uint32_t* index, const uint3
     return BGE_OK;
 }
 
-int upload_rows(bge_world* w, uint64_t first, uint64_t count, uint32_t width, const void* host, void* dst,
-                uint32_t or_bits, const uint32_t* dev_index = nullptr, uint32_t need_bits = 0)
+// What an X(first, count, ...) / X_indexed(count, entity_index, ...) pair of entry points was called with
+struct Entities {
+    uint64_t first, count;
+    const uint32_t* index; // the host's list (X_indexed)
+    bool indexed;
+    static Entities range(uint64_t first, uint64_t count) { return {first, count, nullptr, false}; }
+    static Entities list(uint64_t count, const uint32_t* index) { return {0, count, index, true}; }
+};
+constexpr int kNothingToDo = 1; // what `pre` answers for count == 0: BGE_OK, and nothing more happens
+
+// The prologue those entry points share.  `pre()` holds what differs before the list is staged: the payload's NULL tests and the
+// count == 0 exit, in the entry point's own order; then `body(device index list or null)` runs.
+template <class Pre, class Body>
+int with_entities(bge_world* w, const Entities& e, Pre pre, Body body, const char* null_index = "entity_index is NULL")
 {
-    const size_t bytes = static_cast<size_t>(count) * width * 4;
+    if (int rc = e.indexed ? check_range(w, 0, 0) : check_range(w, e.first, e.count)) return rc;
+    if (e.indexed && e.count && !e.index) return fail(BGE_ERR_INVALID, "%s", null_index);
+    DeviceGuard guard(w->device);
+    if (int rc = pre()) return rc == kNothingToDo ? BGE_OK : rc;
+    const uint32_t* di = nullptr;
+    if (int rc = stage_index(w, e.count, e.index, &di)) return rc;
+    return body(di);
+}
+
+// upload one host array of `count` rows into a per-slot device array
+int upload_rows(bge_world* w, uint64_t first, uint64_t count, const void* host, SlotBuf& dst, uint32_t or_bits,
+                const uint32_t* dev_index = nullptr, uint32_t need_bits = 0)
+{
+    const size_t bytes = dst.bytes_for(count);
     HIP_TRY(w->stage.ensure(bytes));
     HIP_TRY(hipMemcpyAsync(w->stage.p, host, bytes, hipMemcpyHostToDevice, w->stream));
-    HIP_TRY(bge::launch_scatter_rows(w->stream, w->slot_of_entity.as<uint32_t>(), first, count, width, w->stage.p, dst,
-                                     w->flags.as<uint32_t>(), or_bits, dev_index, need_bits));
+    HIP_TRY(bge::launch_scatter_rows(w->stream, w->slot_of_entity.as<uint32_t>(), first, count, dst.words, w->stage.p, dst.p,
+                                     w->flags.as<uint32_t>(), or_bits, dev_index, need_bits, dst.vel_blocks));
     // the staging buffer is reused by the next call
     HIP_TRY(hipStreamSynchronize(w->stream));
     return BGE_OK;
 }
 
-// (vel_blocks: `src` is the velocity array, which is not rows of `width` words — always through the gather kernel)
-int download_rows(bge_world* w, uint64_t first, uint64_t count, uint32_t width, const void* src, void* host,
-                  const uint32_t* dev_index = nullptr, bool vel_blocks = false)
+// (the velocity blocks are not rows of `words` words: always through the gather kernel)
+int download_rows(bge_world* w, uint64_t first, uint64_t count, const SlotBuf& src, void* host, const uint32_t* dev_index = nullptr)
 {
-    const size_t bytes = static_cast<size_t>(count) * width * 4;
-    if (w->flat.identity && !dev_index && !vel_blocks) {
+    const size_t bytes = src.bytes_for(count);
+    if (w->flat.identity && !dev_index && !src.vel_blocks) {
         // flat scene: slot == entity index, the rows are already contiguous in entity order
-        HIP_TRY(hipMemcpyAsync(host, static_cast<const char*>(src) + first * width * 4, bytes, hipMemcpyDeviceToHost, w->stream));
+        HIP_TRY(hipMemcpyAsync(host, src.as<char>() + src.bytes_for(first), bytes, hipMemcpyDeviceToHost, w->stream));
         HIP_TRY(hipStreamSynchronize(w->stream));
         return BGE_OK;
     }
     HIP_TRY(w->stage.ensure(bytes));
-    HIP_TRY(bge::launch_gather_rows(w->stream, w->slot_of_entity.as<uint32_t>(), first, count, width, src, w->stage.p, dev_index, vel_blocks));
+    HIP_TRY(bge::launch_gather_rows(w->stream, w->slot_of_entity.as<uint32_t>(), first, count, src.words, src.p, w->stage.p, dev_index,
+                                    src.vel_blocks));
     HIP_TRY(hipMemcpyAsync(host, w->stage.p, bytes, hipMemcpyDeviceToHost, w->stream));
     HIP_TRY(hipStreamSynchronize(w->stream));
+    return BGE_OK;
+}
+
+// Make an optional store exist for the current layout when its feature is switched on.  bge_world_set_topology keeps an existing
+// store sized for the layout, so a smaller one cannot survive — checked by size all the same: the kernels load and store
+// a[words * slot ..] for every slot of the layout.  (synced: the caller has just waited for the stream)
+int make_store(bge_world* w, SlotBuf& a, bool synced = false)
+{
+    if (!w->has_topology || a.bytes >= a.bytes_for(w->slot_rows())) return BGE_OK;
+    if (!synced) HIP_TRY(hipStreamSynchronize(w->stream));
+    HIP_TRY(a.ensure(a.bytes_for(w->slot_rows())));
+    HIP_TRY(hipMemsetAsync(a.p, a.fill, a.bytes, w->stream));
+    w->rebuild_view();
     return BGE_OK;
 }
 
@@ -1251,23 +1355,19 @@ try {
     const bool carry = w->has_topology && w->flat.n_slots > 0;
     const uint64_t n_keep = carry ? std::min<uint64_t>(n, w->flat.n_entities) : 0;
     struct Carry {
-        DevBuf* buf;
-        uint32_t width;
+        SlotBuf* buf;
         TmpBuf tmp;
     };
     std::vector<Carry> carries;
     TmpBuf old_flags_tmp;
     if (n_keep) {
-        for (auto [buf, width] : std::initializer_list<std::pair<DevBuf*, uint32_t>>{
-                 {&w->pos, 3}, {&w->euler, 3}, {&w->scale, 3}, {&w->world, 16}, {&w->vel, 3}, {&w->angvel, 3},
-                 {&w->quat, 4}, {&w->inv_mass, 1}, {&w->deact, 1}, {&w->filter_class, 1}, {&w->half_extent, 3}, {&w->group, 1}, {&w->mask, 1}, {&w->aabb, 6},
-                 {&w->cshape, 4}, {&w->cmass, 1}, {&w->cfriction, 1}, {&w->cinfo, 1}, {&w->manifold, 32}, {&w->crestitution, 1},
-                 {&w->bmanifold, bge::kBoxManifolds * bge::kBoxManifoldWords}}) {
-            if (buf->p) carries.push_back(Carry{buf, width, TmpBuf{}}); // (the manifold store exists only with the ground plane on)
+        for (SlotBuf* a : w->carried) {
+            if (a->p) carries.push_back(Carry{a, TmpBuf{}}); // (an optional store that was never made has nothing to carry)
         }
         for (Carry& c : carries) {
-            HIP_TRY(c.tmp.ensure(n_keep * c.width * 4));
-            HIP_TRY(bge::launch_gather_rows(w->stream, w->slot_of_entity.as<uint32_t>(), 0, n_keep, c.width, c.buf->p, c.tmp.p, nullptr, c.buf == &w->vel));
+            HIP_TRY(c.tmp.ensure(c.buf->bytes_for(n_keep)));
+            HIP_TRY(bge::launch_gather_rows(w->stream, w->slot_of_entity.as<uint32_t>(), 0, n_keep, c.buf->words, c.buf->p, c.tmp.p, nullptr,
+                                            c.buf->vel_blocks));
         }
         HIP_TRY(old_flags_tmp.ensure(n_keep * 4));
         HIP_TRY(bge::launch_gather_rows(w->stream, w->slot_of_entity.as<uint32_t>(), 0, n_keep, 1, w->flags.p, old_flags_tmp.p));
@@ -1363,35 +1463,11 @@ try {
     HIP_TRY(w->entity_of_slot.ensure(S * 4));
     HIP_TRY(w->root_index.ensure(S * 4));
     HIP_TRY(w->root_slots.ensure(std::max<size_t>(nf.root_slots.size(), 1) * 4));
-    HIP_TRY(w->pos.ensure(S * 12));
-    HIP_TRY(w->euler.ensure(S * 12));
-    HIP_TRY(w->scale.ensure(S * 12));
-    HIP_TRY(w->world.ensure(S * 64));
-    HIP_TRY(w->vel.ensure(S * 12));
-    HIP_TRY(w->angvel.ensure(S * 12));
-    HIP_TRY(w->quat.ensure(S * 16));
-    HIP_TRY(w->inv_mass.ensure(S * 4));
-    HIP_TRY(w->deact.ensure(S * 4));
-    HIP_TRY(w->filter_class.ensure(S * 4));
-    HIP_TRY(w->filter_table.ensure(256 * 16));
-    HIP_TRY(w->half_extent.ensure(S * 12));
-    HIP_TRY(w->group.ensure(S * 4));
-    HIP_TRY(w->mask.ensure(S * 4));
-    HIP_TRY(w->aabb.ensure(S * 24));
-    HIP_TRY(w->cshape.ensure(S * 16));
-    HIP_TRY(w->cmass.ensure(S * 4));
-    HIP_TRY(w->cfriction.ensure(S * 4));
-    HIP_TRY(w->cinfo.ensure(S * 4));
-    // (the manifold store exists from the first time the plane is switched on and then follows every layout, plane on or off:
-    //  the carry above scatters its rows to the NEW slot indices, and k_ground indexes it by slot as soon as the plane is back)
-    if (w->ground_plane || w->manifold.p) {
-        HIP_TRY(w->manifold.ensure(S * 128));
-        HIP_TRY(hipMemsetAsync(w->manifold.p, 0, w->manifold.bytes, w->stream));
-    }
-    HIP_TRY(w->crestitution.ensure(S * 4)); // (k_init_slots writes the default, the carry below the surviving values)
-    if (w->static_contacts || w->dynamic_contacts || w->bmanifold.p) { // (exists from the first bge_world_set_static_contacts(1) on and follows every layout, like the plane's store)
-        HIP_TRY(w->bmanifold.ensure(S * bge::kBoxManifolds * bge::kBoxManifoldWords * 4));
-        HIP_TRY(hipMemsetAsync(w->bmanifold.p, 0xff, w->bmanifold.bytes, w->stream));
+    for (SlotBuf* a : w->carried) { // (k_init_slots writes the defaults, the carry below the surviving values)
+        if (a == &w->half_extent) HIP_TRY(w->filter_table.ensure(256 * 16)); // (its place in the order of first allocations)
+        if (!a->wanted()) continue;
+        HIP_TRY(a->ensure(a->bytes_for(S)));
+        if (a->fill != SlotBuf::kNoFill) HIP_TRY(hipMemsetAsync(a->p, a->fill, a->bytes, w->stream));
     }
     w->obstacles_stale = true; // slots moved
     HIP_TRY(w->root_worlds.ensure(std::max<size_t>(nf.root_slots.size(), 1) * 64));
@@ -1431,8 +1507,8 @@ try {
         HIP_TRY(map_dev.ensure(n_keep * 4));
         HIP_TRY(hipMemcpyAsync(map_dev.p, carry_map.data(), n_keep * 4, hipMemcpyHostToDevice, w->stream));
         for (Carry& c : carries) {
-            HIP_TRY(bge::launch_scatter_rows(w->stream, map_dev.as<uint32_t>(), 0, n_keep, c.width, c.tmp.p, c.buf->p, nullptr, 0, nullptr, 0,
-                                             c.buf == &w->vel));
+            HIP_TRY(bge::launch_scatter_rows(w->stream, map_dev.as<uint32_t>(), 0, n_keep, c.buf->words, c.tmp.p, c.buf->p, nullptr, 0, nullptr, 0,
+                                             c.buf->vel_blocks));
         }
         // flags: keep body type / dirty / spin / shape bits of the old word, structure from the new one
         std::vector<uint32_t> merged(nf.flags);
@@ -1460,40 +1536,8 @@ try {
         HIP_TRY(hipMemcpy(w->frozen.p, frozen_bits.data(), frozen_bits.size() * 4, hipMemcpyHostToDevice));
         w->rebuild_view();
     }
-    // bounds live in entity order: surviving indices keep theirs, indices that went or are new have none
-    if (w->bounds.p) {
-        const uint64_t old_n = w->flat.n_entities;
-        if (n > w->bounds_rows) {
-            TmpBuf grown;
-            HIP_TRY(grown.ensure(n * 24));
-            HIP_TRY(hipMemsetAsync(grown.p, 0xff, n * 24, w->stream));
-            const uint64_t keep = std::min(old_n, w->bounds_rows);
-            if (keep) HIP_TRY(hipMemcpyAsync(grown.p, w->bounds.p, keep * 24, hipMemcpyDeviceToDevice, w->stream));
-            HIP_TRY(hipStreamSynchronize(w->stream));
-            std::swap(w->bounds.p, grown.p);
-            std::swap(w->bounds.bytes, grown.bytes);
-            w->bounds_rows = n;
-        } else if (n < old_n) {
-            HIP_TRY(hipMemsetAsync(static_cast<char*>(w->bounds.p) + n * 24, 0xff, (std::min(old_n, w->bounds_rows) - n) * 24, w->stream));
-        }
-    }
-    // so do the draw keys
-    if (w->draw_keys.p) {
-        const uint64_t old_n = w->flat.n_entities;
-        if (n > w->draw_key_rows) {
-            TmpBuf grown;
-            HIP_TRY(grown.ensure(n * 4));
-            HIP_TRY(hipMemsetAsync(grown.p, 0xff, n * 4, w->stream));
-            const uint64_t keep = std::min(old_n, w->draw_key_rows);
-            if (keep) HIP_TRY(hipMemcpyAsync(grown.p, w->draw_keys.p, keep * 4, hipMemcpyDeviceToDevice, w->stream));
-            HIP_TRY(hipStreamSynchronize(w->stream));
-            std::swap(w->draw_keys.p, grown.p);
-            std::swap(w->draw_keys.bytes, grown.bytes);
-            w->draw_key_rows = n;
-        } else if (n < old_n) {
-            HIP_TRY(hipMemsetAsync(static_cast<char*>(w->draw_keys.p) + n * 4, 0xff, (std::min(old_n, w->draw_key_rows) - n) * 4, w->stream));
-        }
-    }
+    if (int rc = w->bounds.follow_topology(n, w->flat.n_entities, w->stream)) return rc;
+    if (int rc = w->draw_keys.follow_topology(n, w->flat.n_entities, w->stream)) return rc;
     w->any_frozen = any_frozen;
     w->flat = std::move(nf);
     w->orphan_host.swap(orphan);
@@ -1510,44 +1554,35 @@ try {
 }
 BGE_CATCH_ALL("bge_world_set_topology")
 
-static int upload_trs_impl(bge_world* w, uint64_t first, uint64_t count, const uint32_t* index, const float* pos3,
-                           const float* euler3, const float* scale3)
+static int upload_trs(bge_world* w, const Entities& e, const float* pos3, const float* euler3, const float* scale3)
 {
-    if (count == 0) return BGE_OK;
-    DeviceGuard guard(w->device);
-    const uint32_t* di = nullptr;
-    if (int rc = stage_index(w, count, index, &di)) return rc;
-    if (pos3) {
-        if (int rc = upload_rows(w, first, count, 3, pos3, w->pos.p, 0, di, bge::kValid)) return rc;
-    }
-    if (euler3) {
-        if (int rc = upload_rows(w, first, count, 3, euler3, w->euler.p, 0, di, bge::kValid)) return rc;
-    }
-    if (scale3) {
-        if (int rc = upload_rows(w, first, count, 3, scale3, w->scale.p, 0, di, bge::kValid)) return rc;
-    }
-    HIP_TRY(bge::launch_scatter_rows(w->stream, w->slot_of_entity.as<uint32_t>(), first, count, 0, nullptr, nullptr,
-                                     w->flags.as<uint32_t>(), bge::kTDirty, di, bge::kValid));
-    HIP_TRY(hipStreamSynchronize(w->stream));
-    w->maybe_dirty = true;
-    w->epochs_edit();
-    return BGE_OK;
+    return with_entities(
+        w, e, [&] { return e.count ? BGE_OK : kNothingToDo; },
+        [&](const uint32_t* di) -> int {
+            for (auto [host, dst] : {std::pair{pos3, &w->pos}, {euler3, &w->euler}, {scale3, &w->scale}}) {
+                if (!host) continue;
+                if (int rc = upload_rows(w, e.first, e.count, host, *dst, 0, di, bge::kValid)) return rc;
+            }
+            HIP_TRY(bge::launch_scatter_rows(w->stream, w->slot_of_entity.as<uint32_t>(), e.first, e.count, 0, nullptr, nullptr,
+                                             w->flags.as<uint32_t>(), bge::kTDirty, di, bge::kValid));
+            HIP_TRY(hipStreamSynchronize(w->stream));
+            w->maybe_dirty = true;
+            w->epochs_edit();
+            return BGE_OK;
+        });
 }
 
 int bge_world_upload_trs(bge_world* w, uint64_t first, uint64_t count, const float* pos3, const float* euler3,
                          const float* scale3)
 try {
-    if (int rc = check_range(w, first, count)) return rc;
-    return upload_trs_impl(w, first, count, nullptr, pos3, euler3, scale3);
+    return upload_trs(w, Entities::range(first, count), pos3, euler3, scale3);
 }
 BGE_CATCH_ALL("bge_world_upload_trs")
 
 int bge_world_upload_trs_indexed(bge_world* w, uint64_t count, const uint32_t* entity_index, const float* pos3,
                                  const float* euler3, const float* scale3)
 try {
-    if (int rc = check_range(w, 0, 0)) return rc;
-    if (count && !entity_index) return fail(BGE_ERR_INVALID, "entity_index is NULL");
-    return upload_trs_impl(w, 0, count, entity_index, pos3, euler3, scale3);
+    return upload_trs(w, Entities::list(count, entity_index), pos3, euler3, scale3);
 }
 BGE_CATCH_ALL("bge_world_upload_trs_indexed")
 
@@ -1564,38 +1599,10 @@ try {
 }
 BGE_CATCH_ALL("bge_world_mark_dirty")
 
-static int upload_bodies_impl(bge_world* w, uint64_t first, uint64_t count, const uint32_t* index, const uint8_t* type,
-                              const float* mass, const uint8_t* shape, const float* size3, const uint32_t* layer,
-                              const uint32_t* mask);
-
-int bge_world_upload_bodies(bge_world* w, uint64_t first, uint64_t count, const uint8_t* type, const float* mass,
-                            const uint8_t* shape, const float* size3, const uint32_t* layer, const uint32_t* mask)
-try {
-    if (int rc = check_range(w, first, count)) return rc;
-    return upload_bodies_impl(w, first, count, nullptr, type, mass, shape, size3, layer, mask);
-}
-BGE_CATCH_ALL("bge_world_upload_bodies")
-
-int bge_world_upload_bodies_indexed(bge_world* w, uint64_t count, const uint32_t* entity_index, const uint8_t* type,
-                                    const float* mass, const uint8_t* shape, const float* size3, const uint32_t* layer,
-                                    const uint32_t* mask)
-try {
-    if (int rc = check_range(w, 0, 0)) return rc;
-    if (count && !entity_index) return fail(BGE_ERR_INVALID, "entity_index is NULL");
-    return upload_bodies_impl(w, 0, count, entity_index, type, mass, shape, size3, layer, mask);
-}
-BGE_CATCH_ALL("bge_world_upload_bodies_indexed")
-
-static int upload_bodies_impl(bge_world* w, uint64_t first, uint64_t count, const uint32_t* index, const uint8_t* type,
-                              const float* mass, const uint8_t* shape, const float* size3, const uint32_t* layer,
-                              const uint32_t* mask)
+// (the body of bge_world_upload_bodies / _indexed once with_entities has staged the list: di)
+static int upload_bodies(bge_world* w, uint64_t first, uint64_t count, const uint32_t* index, const uint32_t* di, const uint8_t* type,
+                         const float* mass, const uint8_t* shape, const float* size3, const uint32_t* layer, const uint32_t* mask)
 {
-    if (!type) return fail(BGE_ERR_INVALID, "type is NULL");
-    if (count == 0) return BGE_OK;
-    DeviceGuard guard(w->device);
-    const uint32_t* di = nullptr;
-    if (int rc = stage_index(w, count, index, &di)) return rc;
-
     // host: component values -> device parameters (PhysicsSystem.cpp:398-477, 686-707)
     bool palette_changed = w->palette_inv_mass.empty();
     if (palette_changed) {
@@ -1707,6 +1714,33 @@ static int upload_bodies_impl(bge_world* w, uint64_t first, uint64_t count, cons
     w->epochs_edit();
     return BGE_OK;
 }
+
+static int upload_bodies(bge_world* w, const Entities& e, const uint8_t* type, const float* mass, const uint8_t* shape, const float* size3,
+                         const uint32_t* layer, const uint32_t* mask)
+{
+    return with_entities(
+        w, e,
+        [&]() -> int {
+            if (!type) return fail(BGE_ERR_INVALID, "type is NULL");
+            return e.count ? BGE_OK : kNothingToDo;
+        },
+        [&](const uint32_t* di) -> int { return upload_bodies(w, e.first, e.count, e.index, di, type, mass, shape, size3, layer, mask); });
+}
+
+int bge_world_upload_bodies(bge_world* w, uint64_t first, uint64_t count, const uint8_t* type, const float* mass,
+                            const uint8_t* shape, const float* size3, const uint32_t* layer, const uint32_t* mask)
+try {
+    return upload_bodies(w, Entities::range(first, count), type, mass, shape, size3, layer, mask);
+}
+BGE_CATCH_ALL("bge_world_upload_bodies")
+
+int bge_world_upload_bodies_indexed(bge_world* w, uint64_t count, const uint32_t* entity_index, const uint8_t* type,
+                                    const float* mass, const uint8_t* shape, const float* size3, const uint32_t* layer,
+                                    const uint32_t* mask)
+try {
+    return upload_bodies(w, Entities::list(count, entity_index), type, mass, shape, size3, layer, mask);
+}
+BGE_CATCH_ALL("bge_world_upload_bodies_indexed")
 
 int bge_world_set_velocities(bge_world* w, uint64_t first, uint64_t count, const float* linvel3, const float* angvel3)
 try {
@@ -1873,9 +1907,9 @@ int tick_impl(bge_world* w, uint32_t ticks, float dt, const float gravity[3], ui
         return fail(BGE_ERR_INVALID, "BGE_TICK_NORMAL_MATRICES needs BGE_TICK_TRANSFORMS (they are derived from the new world matrices)");
     }
     DeviceGuard guard(w->device);
-    if ((flags & BGE_TICK_NORMAL_MATRICES) && w->normal.bytes < std::max<uint64_t>(w->flat.n_slots, bge::kTile) * 64) {
+    if ((flags & BGE_TICK_NORMAL_MATRICES) && w->normal.bytes < w->normal.bytes_for(w->slot_rows())) {
         HIP_TRY(hipStreamSynchronize(w->stream));
-        HIP_TRY(w->normal.ensure(std::max<uint64_t>(w->flat.n_slots, bge::kTile) * 64));
+        HIP_TRY(w->normal.ensure(w->normal.bytes_for(w->slot_rows())));
         HIP_TRY(hipMemsetAsync(w->normal.p, 0, w->normal.bytes, w->stream));
         w->rebuild_view();
     }
@@ -2109,15 +2143,7 @@ try {
     if (!w) return fail(BGE_ERR_INVALID, "world is NULL");
     DeviceGuard guard(w->device);
     const bool on = enabled != 0;
-    const uint64_t manifold_bytes = std::max<uint64_t>(w->flat.n_slots, bge::kTile) * 128;
-    if (on && w->has_topology && w->manifold.bytes < manifold_bytes) {
-        // (first use; bge_world_set_topology keeps an existing store sized for the layout, so a smaller one cannot survive —
-        //  checked by size all the same: k_ground loads and stores manifold[32 * slot ..] for every slot of the layout)
-        HIP_TRY(hipStreamSynchronize(w->stream));
-        HIP_TRY(w->manifold.ensure(manifold_bytes));
-        HIP_TRY(hipMemsetAsync(w->manifold.p, 0, w->manifold.bytes, w->stream));
-        w->rebuild_view();
-    }
+    if (int rc = on ? make_store(w, w->manifold) : BGE_OK) return rc;
     w->ground_plane = on;
     w->epochs_edit();
     return BGE_OK;
@@ -2129,13 +2155,7 @@ try {
     if (!w) return fail(BGE_ERR_INVALID, "world is NULL");
     DeviceGuard guard(w->device);
     const bool on = enabled != 0;
-    const uint64_t bytes = std::max<uint64_t>(w->flat.n_slots, bge::kTile) * bge::kBoxManifolds * bge::kBoxManifoldWords * 4;
-    if (on && w->has_topology && w->bmanifold.bytes < bytes) {
-        HIP_TRY(hipStreamSynchronize(w->stream));
-        HIP_TRY(w->bmanifold.ensure(bytes));
-        HIP_TRY(hipMemsetAsync(w->bmanifold.p, 0xff, w->bmanifold.bytes, w->stream)); // every row free (bge::kBoxNone)
-        w->rebuild_view();
-    }
+    if (int rc = on ? make_store(w, w->bmanifold) : BGE_OK) return rc;
     w->static_contacts = on;
     w->static_contacts_ever = w->static_contacts_ever || on;
     w->obstacles_stale = true;
@@ -2149,14 +2169,7 @@ try {
     if (!w) return fail(BGE_ERR_INVALID, "world is NULL");
     DeviceGuard guard(w->device);
     HIP_TRY(hipStreamSynchronize(w->stream));
-    // (a body of an island collides its own pairs through contact_body, which keeps the obstacle manifold rows of its slot tidy
-    //  whether or not there are obstacles: the store exists from here on, as after bge_world_set_static_contacts(1))
-    const uint64_t bytes = std::max<uint64_t>(w->flat.n_slots, bge::kTile) * bge::kBoxManifolds * bge::kBoxManifoldWords * 4;
-    if (enabled && w->has_topology && w->bmanifold.bytes < bytes) {
-        HIP_TRY(w->bmanifold.ensure(bytes));
-        HIP_TRY(hipMemsetAsync(w->bmanifold.p, 0xff, w->bmanifold.bytes, w->stream)); // every row free (bge::kBoxNone)
-        w->rebuild_view();
-    }
+    if (int rc = enabled ? make_store(w, w->bmanifold, true) : BGE_OK) return rc;
     if (const char* e = std::getenv("BGE_ISLAND_BIG_POINTS")) w->isl_big_points = static_cast<uint32_t>(std::strtoul(e, nullptr, 10));
     w->dynamic_contacts = enabled != 0;
     w->isl_n_prev = 0; // (off and on again: the pair cache starts empty)
@@ -2199,28 +2212,27 @@ try {
 }
 BGE_CATCH_ALL("bge_world_download_dynamic_pairs")
 
-static int upload_restitution_impl(bge_world* w, uint64_t first, uint64_t count, const uint32_t* index, const float* restitution)
+// RigidBody::restitution / ::friction: one float per entity into its per-slot array
+static int upload_scalar(bge_world* w, const Entities& e, const float* value, const char* name, SlotBuf* dst)
 {
-    if (count == 0) return BGE_OK;
-    if (!restitution) return fail(BGE_ERR_INVALID, "restitution is NULL");
-    DeviceGuard guard(w->device);
-    const uint32_t* di = nullptr;
-    if (int rc = stage_index(w, count, index, &di)) return rc;
-    return upload_rows(w, first, count, 1, restitution, w->crestitution.p, 0, di);
+    return with_entities(
+        w, e,
+        [&]() -> int {
+            if (e.count == 0) return kNothingToDo;
+            return value ? BGE_OK : fail(BGE_ERR_INVALID, "%s is NULL", name);
+        },
+        [&](const uint32_t* di) -> int { return upload_rows(w, e.first, e.count, value, *dst, 0, di); });
 }
 
 int bge_world_upload_restitution(bge_world* w, uint64_t first, uint64_t count, const float* restitution)
 try {
-    if (int rc = check_range(w, first, count)) return rc;
-    return upload_restitution_impl(w, first, count, nullptr, restitution);
+    return upload_scalar(w, Entities::range(first, count), restitution, "restitution", w ? &w->crestitution : nullptr);
 }
 BGE_CATCH_ALL("bge_world_upload_restitution")
 
 int bge_world_upload_restitution_indexed(bge_world* w, uint64_t count, const uint32_t* entity_index, const float* restitution)
 try {
-    if (int rc = check_range(w, 0, 0)) return rc;
-    if (count && !entity_index) return fail(BGE_ERR_INVALID, "entity_index is NULL");
-    return upload_restitution_impl(w, 0, count, entity_index, restitution);
+    return upload_scalar(w, Entities::list(count, entity_index), restitution, "restitution", w ? &w->crestitution : nullptr);
 }
 BGE_CATCH_ALL("bge_world_upload_restitution_indexed")
 
@@ -2230,12 +2242,12 @@ try {
     if (count == 0) return BGE_OK;
     DeviceGuard guard(w->device);
     std::vector<uint32_t> ci(count);
-    if (int rc = download_rows(w, first, count, 1, w->cinfo.p, ci.data())) return rc;
-    constexpr uint32_t kWords = bge::kBoxManifolds * bge::kBoxManifoldWords;
+    if (int rc = download_rows(w, first, count, w->cinfo, ci.data())) return rc;
+    const uint32_t kWords = w->bmanifold.words;
     std::vector<uint32_t> rows;
     if (w->bmanifold.p) {
         rows.resize(count * kWords);
-        if (int rc = download_rows(w, first, count, kWords, w->bmanifold.p, rows.data())) return rc;
+        if (int rc = download_rows(w, first, count, w->bmanifold, rows.data())) return rc;
     }
     for (uint64_t i = 0; i < count; ++i) {
         // the device keeps a body's rows in no particular order: ascending entity of the other box here
@@ -2271,28 +2283,15 @@ try {
 }
 BGE_CATCH_ALL("bge_world_download_box_contacts")
 
-static int upload_friction_impl(bge_world* w, uint64_t first, uint64_t count, const uint32_t* index, const float* friction)
-{
-    if (count == 0) return BGE_OK;
-    if (!friction) return fail(BGE_ERR_INVALID, "friction is NULL");
-    DeviceGuard guard(w->device);
-    const uint32_t* di = nullptr;
-    if (int rc = stage_index(w, count, index, &di)) return rc;
-    return upload_rows(w, first, count, 1, friction, w->cfriction.p, 0, di);
-}
-
 int bge_world_upload_friction(bge_world* w, uint64_t first, uint64_t count, const float* friction)
 try {
-    if (int rc = check_range(w, first, count)) return rc;
-    return upload_friction_impl(w, first, count, nullptr, friction);
+    return upload_scalar(w, Entities::range(first, count), friction, "friction", w ? &w->cfriction : nullptr);
 }
 BGE_CATCH_ALL("bge_world_upload_friction")
 
 int bge_world_upload_friction_indexed(bge_world* w, uint64_t count, const uint32_t* entity_index, const float* friction)
 try {
-    if (int rc = check_range(w, 0, 0)) return rc;
-    if (count && !entity_index) return fail(BGE_ERR_INVALID, "entity_index is NULL");
-    return upload_friction_impl(w, 0, count, entity_index, friction);
+    return upload_scalar(w, Entities::list(count, entity_index), friction, "friction", w ? &w->cfriction : nullptr);
 }
 BGE_CATCH_ALL("bge_world_upload_friction_indexed")
 
@@ -2302,14 +2301,14 @@ try {
     if (count == 0) return BGE_OK;
     DeviceGuard guard(w->device);
     std::vector<uint32_t> ci(count);
-    if (int rc = download_rows(w, first, count, 1, w->cinfo.p, ci.data())) return rc;
+    if (int rc = download_rows(w, first, count, w->cinfo, ci.data())) return rc;
     if (n_points) {
         for (uint64_t i = 0; i < count; ++i) n_points[i] = w->manifold.p ? static_cast<uint8_t>((ci[i] >> bge::kCiCountShift) & 7u) : 0;
     }
     if (points32) {
         if (!w->manifold.p) {
-            std::memset(points32, 0, count * 128);
-        } else if (int rc = download_rows(w, first, count, 32, w->manifold.p, points32)) {
+            std::memset(points32, 0, w->manifold.bytes_for(count));
+        } else if (int rc = download_rows(w, first, count, w->manifold, points32)) {
             return rc;
         }
     }
@@ -2370,37 +2369,38 @@ try {
     if (!out16) return fail(BGE_ERR_INVALID, "out16 is NULL");
     if (count == 0) return BGE_OK;
     DeviceGuard guard(w->device);
-    return download_rows(w, first, count, 16, w->world.p, out16);
+    return download_rows(w, first, count, w->world, out16);
 }
 BGE_CATCH_ALL("bge_world_download_world")
 
 int bge_world_download_world_indexed(bge_world* w, uint64_t count, const uint32_t* entity_index, float* out16)
 try {
-    if (int rc = check_range(w, 0, 0)) return rc;
-    if (count == 0) return BGE_OK;
-    if (!entity_index || !out16) return fail(BGE_ERR_INVALID, "NULL argument");
-    DeviceGuard guard(w->device);
-    const uint32_t* di = nullptr;
-    if (int rc = stage_index(w, count, entity_index, &di)) return rc;
-    return download_rows(w, 0, count, 16, w->world.p, out16, di);
+    return with_entities(
+        w, Entities::list(count, entity_index),
+        [&]() -> int {
+            if (count == 0) return kNothingToDo;
+            return out16 ? BGE_OK : fail(BGE_ERR_INVALID, "NULL argument");
+        },
+        [&](const uint32_t* di) -> int { return download_rows(w, 0, count, w->world, out16, di); }, "NULL argument");
 }
 BGE_CATCH_ALL("bge_world_download_world_indexed")
 
+static int download_pose(bge_world* w, const Entities& e, float* pos3, float* euler3)
+{
+    return with_entities(
+        w, e, [&] { return e.count ? BGE_OK : kNothingToDo; },
+        [&](const uint32_t* di) -> int {
+            for (auto [src, host] : {std::pair{&w->pos, pos3}, {&w->euler, euler3}}) {
+                if (!host) continue;
+                if (int rc = download_rows(w, e.first, e.count, *src, host, di)) return rc;
+            }
+            return BGE_OK;
+        });
+}
+
 int bge_world_download_pose_indexed(bge_world* w, uint64_t count, const uint32_t* entity_index, float* pos3, float* euler3)
 try {
-    if (int rc = check_range(w, 0, 0)) return rc;
-    if (count == 0) return BGE_OK;
-    if (!entity_index) return fail(BGE_ERR_INVALID, "entity_index is NULL");
-    DeviceGuard guard(w->device);
-    const uint32_t* di = nullptr;
-    if (int rc = stage_index(w, count, entity_index, &di)) return rc;
-    if (pos3) {
-        if (int rc = download_rows(w, 0, count, 3, w->pos.p, pos3, di)) return rc;
-    }
-    if (euler3) {
-        if (int rc = download_rows(w, 0, count, 3, w->euler.p, euler3, di)) return rc;
-    }
-    return BGE_OK;
+    return download_pose(w, Entities::list(count, entity_index), pos3, euler3);
 }
 BGE_CATCH_ALL("bge_world_download_pose_indexed")
 
@@ -2411,22 +2411,13 @@ try {
     if (!w->normal.p) return fail(BGE_ERR_STATE, "no tick with BGE_TICK_NORMAL_MATRICES has run");
     if (count == 0) return BGE_OK;
     DeviceGuard guard(w->device);
-    return download_rows(w, first, count, 16, w->normal.p, out16);
+    return download_rows(w, first, count, w->normal, out16);
 }
 BGE_CATCH_ALL("bge_world_download_normal")
 
 int bge_world_download_pose(bge_world* w, uint64_t first, uint64_t count, float* pos3, float* euler3)
 try {
-    if (int rc = check_range(w, first, count)) return rc;
-    if (count == 0) return BGE_OK;
-    DeviceGuard guard(w->device);
-    if (pos3) {
-        if (int rc = download_rows(w, first, count, 3, w->pos.p, pos3)) return rc;
-    }
-    if (euler3) {
-        if (int rc = download_rows(w, first, count, 3, w->euler.p, euler3)) return rc;
-    }
-    return BGE_OK;
+    return download_pose(w, Entities::range(first, count), pos3, euler3);
 }
 BGE_CATCH_ALL("bge_world_download_pose")
 
@@ -2437,16 +2428,16 @@ try {
     if (count == 0) return BGE_OK;
     DeviceGuard guard(w->device);
     if (linvel3) {
-        if (int rc = download_rows(w, first, count, 3, w->vel.p, linvel3, nullptr, true)) return rc;
+        if (int rc = download_rows(w, first, count, w->vel, linvel3)) return rc;
     }
     if (angvel3) {
-        if (int rc = download_rows(w, first, count, 3, w->angvel.p, angvel3)) return rc;
+        if (int rc = download_rows(w, first, count, w->angvel, angvel3)) return rc;
     }
     if (quat4) {
-        if (int rc = download_rows(w, first, count, 4, w->quat.p, quat4)) return rc;
+        if (int rc = download_rows(w, first, count, w->quat, quat4)) return rc;
     }
     if (aabb6) {
-        if (int rc = download_rows(w, first, count, 6, w->aabb.p, aabb6)) return rc;
+        if (int rc = download_rows(w, first, count, w->aabb, aabb6)) return rc;
     }
     return BGE_OK;
 }
@@ -2458,8 +2449,8 @@ try {
     if (count == 0) return BGE_OK;
     DeviceGuard guard(w->device);
     std::vector<uint32_t> rec(count), fl(count);
-    if (int rc = download_rows(w, first, count, 1, w->deact.p, rec.data())) return rc;
-    if (int rc = download_rows(w, first, count, 1, w->flags.p, fl.data())) return rc;
+    if (int rc = download_rows(w, first, count, w->deact, rec.data())) return rc;
+    if (int rc = download_rows(w, first, count, w->flags, fl.data())) return rc;
     for (uint64_t i = 0; i < count; ++i) {
         const uint32_t type = fl[i] & bge::kTypeMask; // download_rows zero-fills entities without a slot
         const uint32_t r = (fl[i] & bge::kDrowsy) ? rec[i] : 0u;
@@ -3357,26 +3348,25 @@ static_assert(BGE_CULL_MAX_PLANES == bge::kCullMaxPlanes, "plane limit");
 
 namespace {
 
-int upload_bounds_impl(bge_world* w, uint64_t first, uint64_t count, const uint32_t* index, const float* center3, const float* half3)
+int upload_bounds(bge_world* w, const Entities& e, const float* center3, const float* half3)
 {
-    if (!center3 || !half3) return fail(BGE_ERR_INVALID, "center3 / half3 is NULL");
-    if (count == 0) return BGE_OK;
-    DeviceGuard guard(w->device);
-    if (!w->bounds.p) { // every entity starts without bounds: a row of NaNs
-        const uint64_t rows = std::max<uint64_t>(w->flat.n_entities, 1);
-        HIP_TRY(w->bounds.ensure(rows * 24));
-        HIP_TRY(hipMemsetAsync(w->bounds.p, 0xff, rows * 24, w->stream));
-        w->bounds_rows = rows;
-    }
-    const uint32_t* di = nullptr;
-    if (int rc = stage_index(w, count, index, &di)) return rc;
-    HIP_TRY(w->stage.ensure(count * 24));
-    float* sc = w->stage.as<float>();
-    HIP_TRY(hipMemcpyAsync(sc, center3, count * 12, hipMemcpyHostToDevice, w->stream));
-    HIP_TRY(hipMemcpyAsync(sc + 3 * count, half3, count * 12, hipMemcpyHostToDevice, w->stream));
-    HIP_TRY(bge::launch_cull_scatter_bounds(w->stream, di, first, count, sc, sc + 3 * count, w->bounds.as<float>()));
-    HIP_TRY(hipStreamSynchronize(w->stream)); // the staging buffers are reused by the next call
-    return BGE_OK;
+    const uint64_t count = e.count;
+    return with_entities(
+        w, e,
+        [&]() -> int {
+            if (!center3 || !half3) return fail(BGE_ERR_INVALID, "center3 / half3 is NULL");
+            if (count == 0) return kNothingToDo;
+            return w->bounds.first_use(w->flat.n_entities, w->stream); // (before the list is staged)
+        },
+        [&](const uint32_t* di) -> int {
+            HIP_TRY(w->stage.ensure(count * 24));
+            float* sc = w->stage.as<float>();
+            HIP_TRY(hipMemcpyAsync(sc, center3, count * 12, hipMemcpyHostToDevice, w->stream));
+            HIP_TRY(hipMemcpyAsync(sc + 3 * count, half3, count * 12, hipMemcpyHostToDevice, w->stream));
+            HIP_TRY(bge::launch_cull_scatter_bounds(w->stream, di, e.first, count, sc, sc + 3 * count, w->bounds.as<float>()));
+            HIP_TRY(hipStreamSynchronize(w->stream)); // the staging buffers are reused by the next call
+            return BGE_OK;
+        });
 }
 
 // Everything of the pass but its outputs: the desc, the world's arrays, the scratch of the three kernels
@@ -3416,16 +3406,13 @@ int cull_params(bge_world* w, const bge_cull_desc* desc, bool want_normal, bge::
 
 int bge_world_upload_bounds(bge_world* w, uint64_t first, uint64_t count, const float* center3, const float* half3)
 try {
-    if (int rc = check_range(w, first, count)) return rc;
-    return upload_bounds_impl(w, first, count, nullptr, center3, half3);
+    return upload_bounds(w, Entities::range(first, count), center3, half3);
 }
 BGE_CATCH_ALL("bge_world_upload_bounds")
 
 int bge_world_upload_bounds_indexed(bge_world* w, uint64_t count, const uint32_t* entity_index, const float* center3, const float* half3)
 try {
-    if (int rc = check_range(w, 0, 0)) return rc;
-    if (count && !entity_index) return fail(BGE_ERR_INVALID, "entity_index is NULL");
-    return upload_bounds_impl(w, 0, count, entity_index, center3, half3);
+    return upload_bounds(w, Entities::list(count, entity_index), center3, half3);
 }
 BGE_CATCH_ALL("bge_world_upload_bounds_indexed")
 
@@ -3492,24 +3479,22 @@ static_assert(BGE_DRAW_MAX_KEYS == bge::kBatchMaxKeys, "key limit");
 
 namespace {
 
-int upload_draw_keys_impl(bge_world* w, uint64_t first, uint64_t count, const uint32_t* index, const uint32_t* key)
+int upload_draw_keys(bge_world* w, const Entities& e, const uint32_t* key)
 {
-    if (!key) return fail(BGE_ERR_INVALID, "key is NULL");
-    if (count == 0) return BGE_OK;
-    DeviceGuard guard(w->device);
-    const uint32_t* di = nullptr;
-    if (int rc = stage_index(w, count, index, &di)) return rc;
-    if (!w->draw_keys.p) { // every entity starts without a key: all ones
-        const uint64_t rows = std::max<uint64_t>(w->flat.n_entities, 1);
-        HIP_TRY(w->draw_keys.ensure(rows * 4));
-        HIP_TRY(hipMemsetAsync(w->draw_keys.p, 0xff, rows * 4, w->stream));
-        w->draw_key_rows = rows;
-    }
-    HIP_TRY(w->stage.ensure(count * 4));
-    HIP_TRY(hipMemcpyAsync(w->stage.p, key, count * 4, hipMemcpyHostToDevice, w->stream));
-    HIP_TRY(bge::launch_batch_scatter_keys(w->stream, di, first, count, w->stage.as<uint32_t>(), w->draw_keys.as<uint32_t>()));
-    HIP_TRY(hipStreamSynchronize(w->stream)); // the staging buffers are reused by the next call
-    return BGE_OK;
+    return with_entities(
+        w, e,
+        [&]() -> int {
+            if (!key) return fail(BGE_ERR_INVALID, "key is NULL");
+            return e.count ? BGE_OK : kNothingToDo;
+        },
+        [&](const uint32_t* di) -> int {
+            if (int rc = w->draw_keys.first_use(w->flat.n_entities, w->stream)) return rc; // (after the list is staged)
+            HIP_TRY(w->stage.ensure(e.count * 4));
+            HIP_TRY(hipMemcpyAsync(w->stage.p, key, e.count * 4, hipMemcpyHostToDevice, w->stream));
+            HIP_TRY(bge::launch_batch_scatter_keys(w->stream, di, e.first, e.count, w->stage.as<uint32_t>(), w->draw_keys.as<uint32_t>()));
+            HIP_TRY(hipStreamSynchronize(w->stream)); // the staging buffers are reused by the next call
+            return BGE_OK;
+        });
 }
 
 // cull_params plus the keys and the sort's scratch
@@ -3537,16 +3522,13 @@ int batch_params(bge_world* w, const bge_cull_desc* desc, uint32_t n_keys, bool 
 
 int bge_world_upload_draw_keys(bge_world* w, uint64_t first, uint64_t count, const uint32_t* key)
 try {
-    if (int rc = check_range(w, first, count)) return rc;
-    return upload_draw_keys_impl(w, first, count, nullptr, key);
+    return upload_draw_keys(w, Entities::range(first, count), key);
 }
 BGE_CATCH_ALL("bge_world_upload_draw_keys")
 
 int bge_world_upload_draw_keys_indexed(bge_world* w, uint64_t count, const uint32_t* entity_index, const uint32_t* key)
 try {
-    if (int rc = check_range(w, 0, 0)) return rc;
-    if (count && !entity_index) return fail(BGE_ERR_INVALID, "entity_index is NULL");
-    return upload_draw_keys_impl(w, 0, count, entity_index, key);
+    return upload_draw_keys(w, Entities::list(count, entity_index), key);
 }
 BGE_CATCH_ALL("bge_world_upload_draw_keys_indexed")
 

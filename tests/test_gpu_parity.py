@@ -1574,6 +1574,180 @@ def test_ground_plane_switched_off_then_scene_grows_then_on_again():
         assert_bits_equal(w.download_world(), ref.bulk_world()[0], "world matrices at the end")
 
 
+def _relayout_scene():
+    """70 entities without Transform or body, 6 Static platforms, 300 Dynamic boxes (some above a platform), then the 230 Dynamic
+    boxes the edit appends.  Everything per entity index; the oracle's entity id is index + 1."""
+    lead, n_plat, n_dyn, n_new = 70, 6, 300, 230
+    n0 = lead + n_plat + n_dyn
+    n1 = n0 + n_new
+    rng = np.random.default_rng(70)
+    wl = synth.Workload("re-layout", synth.FLAT, n1, 4321)
+    wl.scale[:] = 1.0
+    wl.euler[:] = rng.uniform(-0.6, 0.6, (n1, 3)).astype(np.float32)
+    wl.pos[:, 0] = rng.uniform(-30, 30, n1).astype(np.float32)
+    wl.pos[:, 2] = rng.uniform(-30, 30, n1).astype(np.float32)
+    wl.pos[:, 1] = rng.uniform(0.3, 1.2, n1).astype(np.float32)
+    body_type = np.full(n1, B.BODY_NONE, np.uint8)
+    body_type[lead:lead + n_plat] = B.BODY_STATIC
+    body_type[lead + n_plat:] = B.BODY_DYNAMIC
+    size = (0.2 + 0.4 * rng.permutation(3 * n1).reshape(n1, 3) / (3 * n1)).astype(np.float32)   # no two boxes alike
+    for k in range(n_plat):
+        e = lead + k
+        wl.pos[e] = (20.0 * (k % 3) - 20.0, 0.3, 20.0 * (k // 3) - 10.0)
+        wl.euler[e] = (0.4 * k, 0.0, 0.0)
+        size[e] = (3.0, 0.3, 3.0)
+        above = lead + n_plat + 8 * k + np.arange(8)              # eight boxes over each platform
+        wl.pos[above, 0] = wl.pos[e, 0] + rng.uniform(-2.0, 2.0, 8).astype(np.float32)
+        wl.pos[above, 2] = wl.pos[e, 2] + rng.uniform(-2.0, 2.0, 8).astype(np.float32)
+        wl.pos[above, 1] += np.float32(0.8)
+    mass = rng.choice([0.5, 1.0, 3.0], n1).astype(np.float32)
+    friction = rng.choice([0.05, 0.3, 1.0, 2.0], n1).astype(np.float32)      # (the component defaults are 0.5 and 0)
+    restitution = rng.choice([0.2, 0.4, 0.7], n1).astype(np.float32)
+    has_tf = np.ones(n1, np.uint8)
+    has_tf[:lead] = 0
+    wl.body_type = body_type
+    return dict(lead=lead, n0=n0, n1=n1, wl=wl, size=size, mass=mass, friction=friction, restitution=restitution, has_tf=has_tf,
+                dyn0=np.arange(lead + n_plat, n0))
+
+
+def _relayout_oracle(sc):
+    wl, n0 = sc["wl"], sc["n0"]
+    ref = po.RefScene()
+    ref.SetPhysicsOptions(-9.81, po.ORIENT_IDEAL, False)
+    ref.bulk_build(parent_i32(wl.parent[:n0]), wl.pos[:n0], wl.euler[:n0], wl.scale[:n0], has_transform=sc["has_tf"][:n0],
+                   body_type=wl.body_type[:n0], size=sc["size"][:n0], mass=sc["mass"][:n0])
+    for e in range(sc["lead"], n0):
+        ref.SetFriction(e + 1, float(sc["friction"][e]))
+        ref.SetRestitution(e + 1, float(sc["restitution"][e]))
+    ref.SetGroundPlane(True)
+    ref.SetStaticContacts(True)
+    return ref
+
+
+def _relayout_oracle_edit(ref, sc):
+    wl, lead, n0, n1 = sc["wl"], sc["lead"], sc["n0"], sc["n1"]
+    for e in range(lead):
+        ref.AddTransform(e + 1, wl.pos[e], wl.euler[e], wl.scale[e])
+    for e in range(n0, n1):
+        eid = ref.CreateEntity()
+        ref.AddTransform(eid, wl.pos[e], wl.euler[e], wl.scale[e])
+        ref.AddCollider(eid, 0, sc["size"][e])
+        ref.AddRigidBody(eid, po.BODY_DYNAMIC, float(sc["mass"][e]))
+        ref.SetFriction(eid, float(sc["friction"][e]))
+        ref.SetRestitution(eid, float(sc["restitution"][e]))
+    ref.n = n1
+
+
+def test_every_carried_array_survives_a_re_layout_that_moves_slots():
+    """bge_world_set_topology carries every per-slot array to the new layout with that array's own width and layout, the optional
+    stores (plane manifolds, box manifolds) included.  300 Dynamic boxes of distinct sizes, three masses, friction and restitution
+    off their defaults (uploaded half through the range form, half through the indexed form) come to rest on the plane and on six
+    Static platforms; then ONE edit gives the 70 leading entities a Transform and appends 230 bodies: every surviving slot moves by
+    70 — not a multiple of the 64-slot velocity block, across the 256-slot tile boundary — and the layout grows from 2 tiles to 3.
+    Right after the edit and 40 ticks later: pose, both velocities, activation, plane contacts, box manifolds and world matrices
+    against the oracle, bit for bit.  Friction and restitution have no download: a body that fell back to the defaults (0.5, 0)
+    leaves the oracle's trajectory within a few ticks of contact.  (With the seed above the oracle alone has, before the edit, 297
+    of 300 bodies on a contact, 59 of them on a box manifold.)"""
+    import ctypes as C
+    from banggameengine_amd._capi import check, lib
+    from banggameengine_amd.world import ARRAY_SLOT_OF_ENTITY
+
+    sc = _relayout_scene()
+    wl, lead, n0, n1, dyn0 = sc["wl"], sc["lead"], sc["n0"], sc["n1"], sc["dyn0"]
+    size, mass, friction, restitution = sc["size"], sc["mass"], sc["friction"], sc["restitution"]
+    ref = _relayout_oracle(sc)
+    for name in ("libamdhip64.so", "libamdhip64.so.7", "libamdhip64.so.6", "/opt/rocm/lib/libamdhip64.so"):
+        try:
+            hip = C.CDLL(name)
+            break
+        except OSError:
+            continue
+    else:
+        pytest.fail("HIP runtime library not found")
+    hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+
+    def slots(w, n):
+        w.sync()
+        ptr, count = w.device_array(ARRAY_SLOT_OF_ENTITY)
+        assert count == n
+        out = np.zeros(n, np.uint32)
+        assert hip.hipMemcpy(out.ctypes.data, ptr, 4 * n, 2) == 0  # device -> host
+        return out
+
+    def upload_material(w, first, last):
+        # the lower half through the range form, the upper half through the indexed form in descending order
+        mid = (first + last) // 2
+        w.upload_friction(friction[first:mid], first=first)
+        w.upload_restitution(restitution[first:mid], first=first)
+        idx = np.arange(last - 1, mid - 1, -1, dtype=np.uint32)
+        fr, re = np.ascontiguousarray(friction[idx]), np.ascontiguousarray(restitution[idx])
+        check(lib().bge_world_upload_friction_indexed(w._h, len(idx), idx.ctypes.data_as(C.c_void_p), fr.ctypes.data_as(C.c_void_p)))
+        check(lib().bge_world_upload_restitution_indexed(w._h, len(idx), idx.ctypes.data_as(C.c_void_p), re.ctypes.data_as(C.c_void_p)))
+
+    def compare(w, n, bodies, what):
+        pos, euler = w.download_pose()
+        rpos, reuler = ref.bulk_pose()
+        assert_bits_equal(pos, rpos, f"{what}: position")
+        assert_bits_equal(euler, reuler, f"{what}: rotationEuler")
+        rb, gb = ref.bulk_bodies(), w.download_bodies()
+        assert_bits_equal(gb["linvel"][bodies], rb["linvel"][bodies], f"{what}: linear velocity")
+        assert_bits_equal(gb["angvel"][bodies], rb["angvel"][bodies], f"{what}: angular velocity")
+        assert_bits_equal(gb["quat"][rb["exists"]], rb["quat"][rb["exists"]], f"{what}: quaternion")
+        st, tm = w.download_activation()
+        rst, rtm = ref.bulk_activation()
+        ex = rb["exists"]
+        assert np.array_equal(st[ex], rst[ex].astype(np.uint8)), f"{what}: activation states"
+        assert_bits_equal(tm[ex & (rst == 1)], rtm[ex & (rst == 1)], f"{what}: deactivation timers")
+        cn, cpts = w.download_contacts()
+        nb, hdr, pts = w.download_box_contacts()
+        for e in bodies:
+            rn, rpts = ref.GroundContacts(int(e) + 1)
+            assert cn[e] == rn, f"{what}: body {e} has {cn[e]} plane contacts, oracle {rn}"
+            assert_bits_equal(cpts[e, :rn], rpts, f"{what}: plane contact points of body {e}")
+            want = ref.BoxContacts(int(e) + 1)
+            assert nb[e] == len(want), f"{what}: body {e} has {nb[e]} box manifolds, oracle {len(want)}"
+            for k, (other, rows) in enumerate(want):
+                assert hdr[e, k, 0] == other - 1 and hdr[e, k, 1] == len(rows), f"{what}: body {e} manifold {k}: {hdr[e, k]} vs ({other - 1}, {len(rows)})"
+                assert_bits_equal(pts[e, k, :len(rows)], rows, f"{what}: body {e} manifold {k} points")
+        assert_bits_equal(w.download_world(), ref.bulk_world()[0], f"{what}: world matrices")
+        return cn, nb, hdr
+
+    with B.World() as w:
+        w.set_topology(wl.parent[:n0], sc["has_tf"][:n0])
+        w.upload_trs(wl.pos[:n0], wl.euler[:n0], wl.scale[:n0])
+        w.upload_bodies(wl.body_type[:n0], mass=mass[:n0], size=size[:n0])
+        upload_material(w, lead, n0)
+        w.set_ground_plane(True)
+        w.set_static_contacts(True)
+        for tick in range(90):
+            ref.PhysicsSystemUpdate(DT)
+            ref.TransformSystemUpdate()
+            w.tick(dt=DT)
+        cn, nb, hdr = compare(w, n0, dyn0, "at rest before the edit")
+        on_boxes = (hdr[dyn0, :, 1] > 0).any(axis=1)
+        assert ((cn[dyn0] > 0) | on_boxes).sum() >= 0.8 * len(dyn0) and on_boxes.any()
+        before = slots(w, n0)
+
+        _relayout_oracle_edit(ref, sc)
+        w.set_topology(wl.parent)
+        after = slots(w, n1)
+        assert (before[:lead] == 0xFFFFFFFF).all() and (after[lead:n0] == before[lead:n0] + lead).all()   # every surviving slot moved
+        assert (int(before[lead:].max()) // 256 + 1, int(after.max()) // 256 + 1) == (2, 3)               # 2 tiles -> 3 tiles
+        w.upload_trs(wl.pos[:lead], wl.euler[:lead], wl.scale[:lead])
+        w.upload_trs(wl.pos[n0:], wl.euler[n0:], wl.scale[n0:], first=n0)
+        w.upload_bodies(wl.body_type[n0:], mass=mass[n0:], size=size[n0:], first=n0)
+        upload_material(w, n0, n1)
+        compare(w, n1, dyn0, "right after the edit")
+        bodies = np.arange(lead + 6, n1)
+        for tick in range(40):
+            ref.PhysicsSystemUpdate(DT)
+            ref.TransformSystemUpdate()
+            w.tick(dt=DT)
+            if tick in (0, 3):
+                compare(w, n1, bodies[::3], f"tick {tick} after the edit")
+        compare(w, n1, bodies, "40 ticks after the edit")
+
+
 def test_transform_fixtures_incl_multi_pass_layouts():
     """tests/golden/transform_cases.npz on the GPU: flat, chains, subtrees, a forest with Transform-less parents, a
     600-deep chain (three dependent passes) and a 700-wide root (children in a later pass read the parent from memory)."""

@@ -47,7 +47,7 @@ def test_every_entry_point_that_bumps_the_rows_epoch_bumps_the_rest_epoch():
         if "epochs_edit()" in body:
             editors.add(name)
     # everything that can change what a sleeping body's wave vouched for
-    want = {"bge_world_set_topology", "upload_trs_impl", "bge_world_mark_dirty", "upload_bodies_impl", "bge_world_set_velocities",
+    want = {"bge_world_set_topology", "upload_trs", "bge_world_mark_dirty", "upload_bodies", "bge_world_set_velocities",
             "bge_world_step_simulation", "bge_world_set_ground_plane", "bge_world_set_static_contacts", "bge_world_set_dynamic_contacts",
             "bge_world_set_sleeping"}
     assert want <= editors, sorted(want - editors)
