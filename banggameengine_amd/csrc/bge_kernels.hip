@@ -23,6 +23,9 @@
 //   store of a wave is 256 contiguous bytes and the xz lines stay clean; pos, euler, scale are rows of three floats.
 //   Waves whose rotation rows are current (WorldView::rs_word) read neither euler nor scale and write only world row 3:
 //   60 B per flat body instead of 132 B.
+//   Of those, waves whose 64 flag words are vouched for (WorldView::rs_word words 2 and 3: one clean value, nothing has stored to
+//   flags since) do not read flags either: the wave's 16-B record and one palette entry through wave-uniform addresses stand in
+//   for 64 x 4 B, 56 B per flat body.  k_tick<PHYS, XFORM> only; BGE_FLAG_WORD=0 turns it off.
 //   Waves whose bodies are all asleep (rest word, WorldView::rs_word word 1) read flags, the deactivation record and the contact
 //   word, 8..12 B per body, and store nothing.
 //   The world matrices leave through LDS so that every wave-level store instruction writes 1 KiB of
@@ -205,7 +208,9 @@ __global__ void __launch_bounds__(kTile, NORMAL ? 4 : (AABB ? BGE_AABB_MIN_WAVES
     // §4.1: 68 instead of 140 B per flat body).  The word is loaded as a scalar next to the tile header.
     constexpr bool kRowsPath = XFORM && !AABB && !NORMAL && !BASIS;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const uint32_t rs_old = (kRowsPath && p.rs_epoch != 0u) ? w.rs_word[2u * (tile * 4u + wave)] : 0u;
+    // The wave's record {rows word, rest word, flag value, flag epoch} (WorldView::rs_word) in one wave-uniform 16-B load.
+    const uint4 rec = (kRowsPath && (p.rs_epoch | p.rest_epoch) != 0u) ? reinterpret_cast<const uint4*>(w.rs_word)[tile * 4u + wave] : make_uint4(0u, 0u, 0u, 0u);
+    const uint32_t rs_old = p.rs_epoch != 0u ? rec.x : 0u;
     // (header: wave-local, max level 0, no frozen root, no external parent)
     const bool flat_tile = kRowsPath && (hdr & (kHdrWaveLocal | kHdrFrozen | kHdrExt | kHdrLevelMask)) == kHdrWaveLocal;
     const bool rs_tile = flat_tile && p.rs_epoch != 0u;
@@ -219,7 +224,7 @@ __global__ void __launch_bounds__(kTile, NORMAL ? 4 : (AABB ? BGE_AABB_MIN_WAVES
     // body and, when one ballot finds no mark, returns: a sleeping body is not integrated, its zero velocity and its matrix would be
     // stored over the same bits, and its flags end the tick as they started (kTDirty is set and cleared within it).  Otherwise the
     // lanes go on into the ordinary path below.  Wave-local tiles of these variants have no workgroup barrier to miss.
-    const uint32_t rest_old = (kRowsPath && p.rest_epoch != 0u) ? w.rs_word[2u * (tile * 4u + wave) + 1u] : 0u;
+    const uint32_t rest_old = p.rest_epoch != 0u ? rec.y : 0u;
     const bool rest_tile = flat_tile && p.rest_epoch != 0u;
     uint32_t f0;
     if (rest_tile && rest_old == p.rest_epoch) { // (wave-uniform)
@@ -242,6 +247,33 @@ __global__ void __launch_bounds__(kTile, NORMAL ? 4 : (AABB ? BGE_AABB_MIN_WAVES
         }
         if (__ballot(moved) == 0ull) return;
     } else {
+        // Vouched wave (WorldView::rs_word words 2 and 3, DESIGN.md §4.1 "flag word"): flag epoch == p.rs_epoch means that every one
+        // of the wave's 64 flag words in memory is the record's flag value F, and F is kValid | Dynamic | mass class with no other bit:
+        // awake with no deactivation record, not spinning, not dirty, no parent.  With the rows word current as well, all the ordinary
+        // path would take from the 64 flag loads is F.  So the wave integrates with the palette entry of F's class (a uniform address)
+        // and, unless a lane is slow enough to look at its deactivation record, stores what the ordinary path would store — velocity,
+        // position, row 3; the flags end the tick as they are, kTDirty set and cleared — and returns.  It writes neither flags nor
+        // words and touches neither the deactivation records nor the contact words; a wave that declines has stored nothing and goes
+        // on into the ordinary path.  Every condition is wave-uniform.
+        if (PHYS && kRowsPath && rs_hint && p.flag_word != 0u && rec.w == p.rs_epoch && (hdr & kHdrAllDynamic) && p.cinfo_in == nullptr) {
+            const float4 gf = w.grav_palette[rec.z >> kMassShift];
+            if (gf.w != 0.0f) {
+                F3 x0 = ld3(w.pos, slot);
+                const F3 v = ld_vel(w.vel, slot);
+                // (pins the position load here, next to the velocity loads: the compiler otherwise sinks it behind the ballot below,
+                //  a second memory round trip in the wave's life)
+                asm volatile("" : "+v"(x0.x), "+v"(x0.y), "+v"(x0.z));
+                // (the expressions of applyGravity and integrateTransforms below, in their order)
+                const F3 v1{v.x + (gf.x * gf.w) * p.dt, v.y + (gf.y * gf.w) * p.dt, v.z + (gf.z * gf.w) * p.dt};
+                if (__ballot(!(fabsf(v1.y) >= p.sleep_lin)) == 0ull) {
+                    st_vel_if(w.vel, slot, v1, vel_xz_changed(v1, v), vel_y_changed(v1, v));
+                    const F3 x1{x0.x + v1.x * p.dt, x0.y + v1.y * p.dt, x0.z + v1.z * p.dt};
+                    st3(w.pos, slot, x1);
+                    reinterpret_cast<float4*>(w.world)[4ull * slot + 3u] = make_float4(x1.x, x1.y, x1.z, 1.0f);
+                    return;
+                }
+            }
+        }
         f0 = w.flags[slot];
     }
     // The component loads do not wait for the flag word: every array is allocated for whole tiles, so the loads of a slot
@@ -578,7 +610,17 @@ __global__ void __launch_bounds__(kTile, NORMAL ? 4 : (AABB ? BGE_AABB_MIN_WAVES
             const uint32_t type = f & kTypeMask;
             const bool rests = valid ? (!(f & (kTDirty | kBDirty | kSpin | kExtParent | kLevelMask)) && type != 3u && (type != 2u || asleep)) : !orphan_body;
             const uint32_t rest_new = (rest_tile && __ballot(!rests) == 0ull) ? p.rest_epoch : 0u;
-            if (rest_new != rest_old && (tid & 63u) == 0u) w.rs_word[2u * (tile * 4u + wave) + 1u] = rest_new;
+            if (rest_new != rest_old && (tid & 63u) == 0u) w.rs_word[4u * (tile * 4u + wave) + 1u] = rest_new;
+        }
+        if (PHYS && kRowsPath && p.rs_epoch != 0u) {
+            // flag word (words 2 and 3): the wave's 64 flag words end the tick equal and of the vouched form, or the flag epoch is 0
+            const uint32_t f_end = f;
+            const uint32_t f_first = __builtin_amdgcn_readfirstlane(f_end);
+            const bool vouch = rs_tile && (hdr & kHdrAllDynamic) && __ballot(f_end != f_first) == 0ull &&
+                               (f_first & ~kMassMask) == (kValid | 2u) && (f_first >> kMassShift) != kMassClassArray;
+            const uint32_t fe_new = vouch ? p.rs_epoch : 0u;
+            if ((fe_new != rec.w || (vouch && f_first != rec.z)) && (tid & 63u) == 0u)
+                reinterpret_cast<uint2*>(w.rs_word)[2u * (tile * 4u + wave) + 1u] = make_uint2(f_first, fe_new);
         }
     } else if (XFORM) {
         float local[16];
@@ -629,14 +671,24 @@ __global__ void __launch_bounds__(kTile, NORMAL ? 4 : (AABB ? BGE_AABB_MIN_WAVES
                 // it: every valid lane ends the tick without spin in a tile of the fast path's shape (written only when it changes)
                 const bool keeps = rs_tile && __ballot(valid && (f & (kSpin | kExtParent | kLevelMask))) == 0ull;
                 const uint32_t rs_new = keeps ? p.rs_epoch : 0u;
-                if (rs_new != rs_old && (tid & 63u) == 0u) w.rs_word[2u * (tile * 4u + wave)] = rs_new;
+                if (rs_new != rs_old && (tid & 63u) == 0u) w.rs_word[4u * (tile * 4u + wave)] = rs_new;
             }
             if (kRowsPath && PHYS && p.rest_epoch != 0u) {
                 // all four rows just stored are bx_mtx_srt of what is in memory; kTDirty ends the tick cleared (below)
                 const uint32_t type = f & kTypeMask;
                 const bool rests = valid ? (!(f & (kBDirty | kSpin | kExtParent | kLevelMask)) && type != 3u && (type != 2u || asleep)) : !orphan_body;
                 const uint32_t rest_new = (rest_tile && __ballot(!rests) == 0ull) ? p.rest_epoch : 0u;
-                if (rest_new != rest_old && (tid & 63u) == 0u) w.rs_word[2u * (tile * 4u + wave) + 1u] = rest_new;
+                if (rest_new != rest_old && (tid & 63u) == 0u) w.rs_word[4u * (tile * 4u + wave) + 1u] = rest_new;
+            }
+            if (PHYS && kRowsPath && p.rs_epoch != 0u) {
+                // flag word (words 2 and 3): the wave's 64 flag words end the tick equal and of the vouched form, or the flag epoch is 0
+                const uint32_t f_end = f & ~kTDirty /* (cleared below) */;
+                const uint32_t f_first = __builtin_amdgcn_readfirstlane(f_end);
+                const bool vouch = rs_tile && (hdr & kHdrAllDynamic) && __ballot(f_end != f_first) == 0ull &&
+                                   (f_first & ~kMassMask) == (kValid | 2u) && (f_first >> kMassShift) != kMassClassArray;
+                const uint32_t fe_new = vouch ? p.rs_epoch : 0u;
+                if ((fe_new != rec.w || (vouch && f_first != rec.z)) && (tid & 63u) == 0u)
+                    reinterpret_cast<uint2*>(w.rs_word)[2u * (tile * 4u + wave) + 1u] = make_uint2(f_first, fe_new);
             }
             if (NORMAL) {
                 // render feed: normalMtx = transpose(inverse(world)) (Renderer.cpp:633-636), same LDS round trip

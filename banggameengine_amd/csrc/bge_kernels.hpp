@@ -47,13 +47,18 @@ struct WorldView {
     uint32_t* bmanifold;      // [slots][kBoxManifolds][kBoxManifoldWords] a Dynamic box's manifolds with boxes, in no particular order:
                               //             words 0..3 = other entity, points, the other body's generation, 0; then four points x 12 floats
                               //             (localA.xyz, localB.xyz, normalWorldOnB.xyz, distance, appliedImpulse, appliedImpulseLateral1)
-    uint32_t* rs_word;        // [tiles * 4][2] two words per wave64, kept by k_tick, zeroed with every layout.  Word 0 equals
+    uint32_t* rs_word;        // [tiles * 4][4] one 16-B record per wave64 {rows word, rest word, flag value F, flag epoch}, 16-B aligned,
+                              //             kept by k_tick, zeroed with every layout.  Word 0 equals
                               //             TickParams::rs_epoch only while world rows 0..2 of every valid slot of the wave are
                               //             bx_mtx_srt(scale, euler) of the scale and euler in memory (wave-local tile, max level 0, no
                               //             frozen root, no external parent).  Word 1 (the rest word) equals TickParams::rest_epoch only
                               //             while, in a tile of the same shape, all four world rows of every valid slot are bx_mtx_srt of
                               //             the scale, euler and pos in memory and every lane is at rest: no dirty bit, no spin, and
-                              //             either a Dynamic body that is ISLAND_SLEEPING with zero velocities or no body / a Static one
+                              //             either a Dynamic body that is ISLAND_SLEEPING with zero velocities or no body / a Static one.
+                              //             Words 2 and 3 (kept by k_tick<PHYS, XFORM> alone): word 3 == TickParams::rs_epoch  =>  for all 64
+                              //             slots of the wave, flags[slot] == F (word 2) bit for bit in memory at kernel start; F is
+                              //             kValid | Dynamic | mass class (not kMassClassArray) and no other bit.  Every store to flags
+                              //             outside a translation-row tick moves the rows epoch (the audit table)
     uint32_t* frozen;         // [slots / 32] bit per slot, or null: a root whose parent entity lost its Transform keeps the world matrix it had
                               //             (parent * local) until something marks it dirty — TransformSystem::Update recomputes a node only when
                               //             it or an ancestor is dirty, and Scene::RemoveTransform marks nobody (tiles with kHdrFrozen look here)
@@ -209,6 +214,9 @@ struct TickParams {
     uint32_t rest_epoch; // non-zero: waves whose rest word (WorldView::rs_word, word 1) holds this value read flags, the deactivation
                          // record and the contact word, and return without a store when those confirm that every lane still rests;
                          // 0: the rest path is off and no rest word is written (the host bumps its epoch instead)
+    uint32_t flag_word; // non-zero: a translation-row wave whose flag epoch (WorldView::rs_word word 3) equals rs_epoch takes its flag
+                        // word from the record and does not read flags; 0: every wave reads them (BGE_FLAG_WORD=0).  Words 2 and 3
+                        // are kept either way
     uint32_t no_repose; // this tick is the 2nd..nth sub-step of ONE stepSimulation call (bge_world_step_simulation): dirty flags
                         // do not re-pose bodies — SyncKinematicBodiesToPhysics ran once, before the first sub-step
 };

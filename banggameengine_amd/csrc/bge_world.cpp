@@ -230,9 +230,9 @@ struct bge_world {
                                   &group, &mask,  &aabb,  &cshape, &cmass, &cfriction, &cinfo, &manifold, &crestitution, &bmanifold};
     uint64_t slot_rows() const { return std::max<uint64_t>(flat.n_slots, bge::kTile); } // arrays are allocated for whole tiles
     DevBuf ground_list, ground_count;                 // slots k_ground_select hands to the solver; count + ticket words
-    // The tick kernel's per-wave words (WorldView::rs_word: "rotation rows current" and "at rest", two per wave64, zeroed with every
-    // layout) and the epochs they are compared with (bge_epochs.hpp).  Every call that can write pos, euler, scale, world, quat,
-    // velocities, deactivation records, contact words, body types or flags moves BOTH epochs on (epochs_edit), which invalidates all
+    // The tick kernel's per-wave words (WorldView::rs_word: "rotation rows current", "at rest", and the flag value with its epoch: four
+    // per wave64, zeroed with every layout) and the epochs they are compared with (bge_epochs.hpp).  Every call that can write pos,
+    // euler, scale, world, quat, velocities, deactivation records, contact words, body types or flags moves BOTH epochs on (epochs_edit), which invalidates all
     // words.  A tick whose launches include another kernel that writes euler, scale, world or quat moves the rows epoch alone; a tick
     // of a variant without the rest path moves the rest epoch alone.
     DevBuf rs_word;
@@ -1456,8 +1456,8 @@ try {
     HIP_TRY(w->flags.ensure(S * 4));
     HIP_TRY(w->parent.ensure(S * 4));
     HIP_TRY(w->tile_hdr.ensure(T * 4));
-    HIP_TRY(w->rs_word.ensure(T * 32));
-    HIP_TRY(hipMemsetAsync(w->rs_word.p, 0, T * 32, w->stream));
+    HIP_TRY(w->rs_word.ensure(T * 64));
+    HIP_TRY(hipMemsetAsync(w->rs_word.p, 0, T * 64, w->stream));
     w->epochs_edit();
     HIP_TRY(w->slot_of_entity.ensure(std::max<uint64_t>(n, 1) * 4));
     HIP_TRY(w->entity_of_slot.ensure(S * 4));
@@ -1957,6 +1957,10 @@ int tick_impl(bge_world* w, uint32_t ticks, float dt, const float gravity[3], ui
     bool rows_path = xform && !contacts && !nt_out &&
                      !(flags & (BGE_TICK_AABBS | BGE_TICK_BROADPHASE | BGE_TICK_NORMAL_MATRICES | BGE_TICK_BULLET_BASIS | BGE_TICK_GATHER_ROOTS));
     if (const char* e = std::getenv("BGE_WORLD_ROWS")) rows_path = rows_path && std::atoi(e) != 0;
+    // Vouched waves of the translation-row path (WorldView::rs_word, words 2 and 3): a wave whose 64 flag words are known to be one
+    // clean value skips the flags read.  The words are kept whether or not the block runs; BGE_FLAG_WORD=0 turns the block off (A/B runs).
+    bool flag_word = rows_path;
+    if (const char* e = std::getenv("BGE_FLAG_WORD")) flag_word = flag_word && std::atoi(e) != 0;
     // Rest path of the tick kernel (WorldView::rs_word, word 1): waves whose bodies are all asleep read 12 B per body and store
     // nothing.  In the same variants as the translation-row path — but ON with the ground plane, obstacles and Dynamic contacts,
     // where a scene at rest spends its life: every kernel of the contact stage either leaves a sleeping body alone or marks its
@@ -1982,6 +1986,7 @@ int tick_impl(bge_world* w, uint32_t ticks, float dt, const float gravity[3], ui
         p.gz = gravity ? gravity[2] : 0.0f;
         p.nt_out = nt_out ? 1u : 0u;
         p.no_repose = sub.no_repose ? 1u : 0u;
+        p.flag_word = flag_word ? 1u : 0u;
         if (rows_path) p.rs_epoch = w->epochs.rows;
         else if (w->epochs.tick_without_rows()) w->words_clear();
         if (rest_path) p.rest_epoch = w->epochs.rest;

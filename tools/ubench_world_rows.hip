@@ -11,6 +11,7 @@
 //   e  fast path, whole sectors: read flags, pos, vel and row 2; write pos, vel and rows 2-3
 //   f  fast path, vel in per-wave component blocks (ld_vel / st_vel_changed): only vel.y changes, only vel.y is stored
 //   g  as f with all three components stored (st_vel): the layout alone, without the skipped stores
+//   h  as f without the per-lane flags load: one 16-B per-wave record through a wave-uniform address stands in for it
 // Each kernel runs `reps` times back to back between two events after a warm-up; one JSON line per (kernel, store
 // policy, size).  Built by tools/ubench_world_rows.sh; no part of the product library.
 #include <hip/hip_runtime.h>
@@ -191,6 +192,30 @@ template <bool NT> __global__ void __launch_bounds__(kBlock, 8) k_flat_row3_vblk
     }
 }
 
+// (h) as (f), but no lane loads its flag word: the wave reads one 16-B record {rows epoch, -, flag word, flag epoch} through a
+// wave-uniform address (one scalar load), proceeds when both epochs equal the launch's, and takes the flag word from the record
+template <bool NT>
+__global__ void __launch_bounds__(kBlock, 8) k_flat_row3_wave(Soa s, const uint4* __restrict__ words, uint32_t epoch, uint32_t n_slots, float dt)
+{
+    const uint32_t slot = blockIdx.x * kBlock + threadIdx.x;
+    const uint32_t wave = blockIdx.x * 4u + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint4 w = words[wave];
+    if (((w.x ^ epoch) | (w.w ^ epoch)) != 0u) return;
+    const uint32_t f = w.z;
+    F3 pos = ld3(s.pos, slot), vel = ld_vel(s.vel, slot);
+    if (f & 1u) {
+        const F3 old = vel;
+        vel.y = vel.y + -9.81f * dt;
+        const bool cxz = vel_xz_changed(vel, old), cy = vel_y_changed(vel, old);
+        pos.x = pos.x + vel.x * dt;
+        pos.y = pos.y + vel.y * dt;
+        pos.z = pos.z + vel.z * dt;
+        st_vel_if(s.vel, slot, vel, cxz, cy);
+        st3(s.pos, slot, pos);
+        put4<NT>(s.world + 4ull * slot + 3, make_float4(pos.x, pos.y, pos.z, 1.0f));
+    }
+}
+
 template <typename F> float time_us(F launch, int warm, int reps)
 {
     hipEvent_t a, b;
@@ -217,7 +242,9 @@ void report(const char* kernel, bool nt, uint32_t n, float us, double bytes_per_
     std::fflush(stdout);
 }
 
-template <bool NT> void run_size(uint32_t n, int reps, Soa s, float zero)
+constexpr uint32_t kEpoch = 7; // what words 0 and 3 of every record of (h) hold, and what its launches pass
+
+template <bool NT> void run_size(uint32_t n, int reps, Soa s, const uint4* words, float zero)
 {
     const int warm = 20;
     const dim3 blk(kBlock);
@@ -233,6 +260,11 @@ template <bool NT> void run_size(uint32_t n, int reps, Soa s, float zero)
     report("d_flat_row3", NT, n, time_us([&] { k_flat_row3<NT><<<g_slot, blk>>>(s, n, 1.0f / 60.0f); }, warm, reps), 68.0);
     report("g_flat_row3_vblk", NT, n, time_us([&] { k_flat_row3_vblk<NT><<<g_slot, blk>>>(s, n, 1.0f / 60.0f, zero, zero); }, warm, reps), 68.0);
     report("d_flat_row3", NT, n, time_us([&] { k_flat_row3<NT><<<g_slot, blk>>>(s, n, 1.0f / 60.0f); }, warm, reps), 68.0);
+    report("f_flat_row3_vy", NT, n, time_us([&] { k_flat_row3_vy<NT><<<g_slot, blk>>>(s, n, 1.0f / 60.0f); }, warm, reps), 60.0);
+    // (h) between (f)s, the same way: with the (f) line above, three (f) lines around two (h) lines
+    report("h_flat_row3_wave", NT, n, time_us([&] { k_flat_row3_wave<NT><<<g_slot, blk>>>(s, words, kEpoch, n, 1.0f / 60.0f); }, warm, reps), 56.25);
+    report("f_flat_row3_vy", NT, n, time_us([&] { k_flat_row3_vy<NT><<<g_slot, blk>>>(s, n, 1.0f / 60.0f); }, warm, reps), 60.0);
+    report("h_flat_row3_wave", NT, n, time_us([&] { k_flat_row3_wave<NT><<<g_slot, blk>>>(s, words, kEpoch, n, 1.0f / 60.0f); }, warm, reps), 56.25);
     report("f_flat_row3_vy", NT, n, time_us([&] { k_flat_row3_vy<NT><<<g_slot, blk>>>(s, n, 1.0f / 60.0f); }, warm, reps), 60.0);
     CK(hipGetLastError());
     CK(hipDeviceSynchronize());
@@ -268,8 +300,13 @@ int main(int argc, char** argv)
         CK(hipMemcpy(s.scale, v3.data(), 12ull * n, hipMemcpyHostToDevice));
         CK(hipMemset(s.vel, 0, 12ull * n));
         CK(hipMemset(s.world, 0, 64ull * n));
-        run_size<false>(n, reps, s, zero);
-        run_size<true>(n, reps, s, zero);
+        uint4* words = nullptr; // one record per wave of 64 slots
+        std::vector<uint4> wr(n / 64u, uint4{kEpoch, 0u, 1u, kEpoch});
+        CK(hipMalloc(&words, 16ull * wr.size()));
+        CK(hipMemcpy(words, wr.data(), 16ull * wr.size(), hipMemcpyHostToDevice));
+        run_size<false>(n, reps, s, words, zero);
+        run_size<true>(n, reps, s, words, zero);
+        CK(hipFree(words));
         CK(hipFree(s.flags));
         CK(hipFree(s.pos));
         CK(hipFree(s.vel));

@@ -31,10 +31,10 @@ def main():
     times = {}
     names = {"a_full_rows": "k_full_rows", "b_row3": "k_row3", "c_flat_full": "k_flat_full", "d_flat_row3": "k_flat_row3",
              "b2_rows23": "k_rows23", "e_flat_rows23": "k_flat_rows23", "f_flat_row3_vy": "k_flat_row3_vy",
-             "g_flat_row3_vblk": "k_flat_row3_vblk"}
+             "g_flat_row3_vblk": "k_flat_row3_vblk", "h_flat_row3_wave": "k_flat_row3_wave"}
     for line in open(os.path.join(out, "times.jsonl")):
         d = json.loads(line)
-        times.setdefault((names[d["kernel"]], bool(d["nt"]), d["slots"]), []).append(d["us"])  # (d) and (f) run more than once
+        times.setdefault((names[d["kernel"]], bool(d["nt"]), d["slots"]), []).append(d["us"])  # (d), (f) and (h) run more than once
     traced = defaultdict(list)
     for path in glob.glob(os.path.join(out, "stats", "**", "*kernel_trace.csv"), recursive=True):
         for row in csv.DictReader(open(path)):
@@ -58,6 +58,13 @@ def main():
                          read_B_per_slot=round(rd, 2), write_B_per_slot=round(wr, 2)))
         print(f"{base:12s} {int(nt):2d} {slots:9d} {ev:9.2f} {tr:9.2f} {rd:7.2f} {wr:7.2f}")
     json.dump(rows, open(os.path.join(out, "digest.json"), "w"), indent=1)
+    # the gate of (h): its slower run against the fastest of the last three (f) runs, the ones around it, at 1 M slots
+    f = times.get(("k_flat_row3_vy", False, 1 << 20), [])[-3:]
+    h = times.get(("k_flat_row3_wave", False, 1 << 20), [])
+    if len(f) == 3 and h:
+        gain, spread = min(f) - max(h), max(f) - min(f)
+        print(f"gate (h): f {f} h {h}: min f - max h = {gain:.3f} us, 2 x (max f - min f) = {2 * spread:.3f} us: "
+              f"{'PASS' if gain >= 2 * spread else 'FAIL'}")
 
 
 if __name__ == "__main__":
