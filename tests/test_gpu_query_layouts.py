@@ -1,0 +1,408 @@
+"""Ray queries, sphere casts, sphere overlaps and sphere moves on worlds whose slot order differs from their entity order.
+
+Every other query test builds a flat world, where slot_of_entity and entity_of_slot are the identity: a library that reported a
+slot for an entity, read the winner's pose at the entity's index, or scanned n_entities slots would pass them all.  Here the
+layout scene of test_query_layouts_cpu.py (1900 Transforms in 2048 slots, nearly every entity off its index, slots beyond the
+entity count, padding slots) is asked the same questions, then re-laid out, edited, grown and shrunk.
+
+What is in the world (include/bge_world.h, "Ray queries" and bge_world_set_topology):
+  * a body: its entity owns a Transform (or lost it while the body was in the world), its type is not BODY_NONE, and it has not
+    been uploaded since the last physics tick;
+  * a ghost: its trigger is active (component and World.trigger_active, which a fired one-shot clears) and a tick has posed it
+    since the last upload_triggers; it stands where the Transform was before that tick.
+LayoutScene.objects() builds the float64 World64 from exactly that set, at the poses download_pose / download_bodies report.
+
+Every expected answer is one of: the float64 references of test_raycast_cpu.py / test_sphere_queries_cpu.py fed the device's own
+poses, through the existing checkers at their existing tolerances (F_REL, F_ABS, P_REL, N_ABS, N_SCALE as imported; none is
+introduced here); an invariant (a re-layout without a tick changes no byte; the device form equals the host form; every entity
+reported is in the world); or a pose fixed by construction (Static boxes of size 1 and 0.5 at chosen places, 1e-5 as
+check_hand_case and check_hand_move).  test_query_layouts_cpu.py asserts that the reference alone clears the checkers' floors for
+each batch used here."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import banggameengine_amd as B
+from banggameengine_amd import world as W
+
+from test_gpu_raycast import FLAGS, Scene, check_against_reference, check_all_hits
+from test_gpu_sphere_move import device_caster, move
+from test_gpu_sphere_queries import check_all_casts, check_casts, check_overlaps
+from test_query_layouts_cpu import (N, N_GROWN, N_SHRUNK, PHASES, SCENE_SEED, N_TRIGGERS, Edits, layout_topology, movers, query_batches,
+                                    relayout_topology, scene_reference)
+from test_raycast_cpu import NO_ENTITY, RAY_BODY, RAY_GROUND, RAY_MISS, RAY_TRIGGER
+from test_sphere_move_cpu import check_hand_move, move_ref
+from test_sphere_queries_cpu import SphereRef, check_hand_case
+
+pytestmark = pytest.mark.gpu
+
+ALL = 0xFFFFFFFF
+N_ALL = 256  # the all-hits lists are compared for the first 256 queries of a batch, as the flat-scene tests do
+
+
+class LayoutScene(Scene):
+    """The ray tests' scene under the layout topology, with the book-keeping of what is in the world."""
+
+    def __init__(self):
+        _, _, trig = scene_reference()
+        self.parent, self.ht = layout_topology(N, trig)
+        super().__init__(N, np.random.default_rng(SCENE_SEED), n_triggers=N_TRIGGERS, parent=self.parent, has_transform=self.ht)
+        assert np.array_equal(np.sort(self.trig), trig), "the scene's draws are no longer those scene_world64 repeats"
+        self.fresh = np.zeros(N, bool)  # body uploaded since the last physics tick
+        self.posed = False              # a tick has posed the ghosts since the last upload_triggers
+        info = self.w.info()
+        slot, _, _, flat = W.flatten_topology(self.parent, self.ht)
+        has = self.ht.astype(bool)
+        print(f"layout: {flat['n_transforms']} transforms in {flat['n_slots']} slots, {int((slot[has] != np.arange(N)[has]).sum())} entities "
+              f"off their index, largest slot {int(slot[has].max())}, depth {flat['max_depth']}")
+        assert info["n_slots"] == flat["n_slots"] > info["n_transforms"] and slot[has].max() >= N
+
+    def upload_triggers(self):
+        super().upload_triggers()
+        self.posed = False
+
+    def tick(self, k=1):
+        super().tick(k)
+        self.fresh[:] = False
+        self.posed = True
+
+    def set_topology(self, parent, ht):
+        self.w.set_topology(parent, ht)
+        self.parent, self.ht = parent, ht
+
+    def bodies_in_world(self):
+        return np.nonzero(self.ht.astype(bool) & (self.type != W.BODY_NONE) & ~self.fresh)[0]
+
+    def ghosts_in_world(self):
+        if not self.posed:
+            return self.trig[:0]
+        return self.trig[self.t_active.astype(bool) & self.w.trigger_active(self.trig)]
+
+    def members(self):
+        return np.sort(np.concatenate([self.bodies_in_world(), self.ghosts_in_world()]))
+
+    def batches(self, phase):
+        pos, _ = self.w.download_pose()
+        return query_batches(phase, pos[self.members()])
+
+    def remove(self, ents):
+        """BODY_NONE for the listed entities: they leave the world at once."""
+        idx, none = np.ascontiguousarray(ents, np.uint32), np.full(len(ents), W.BODY_NONE, np.uint8)
+        rc = B.lib().bge_world_upload_bodies_indexed(self.w._h, len(idx), idx.ctypes.data_as(C.c_void_p), none.ctypes.data_as(C.c_void_p),
+                                                     None, None, None, None, None)
+        assert rc == 0
+        self.type[idx] = W.BODY_NONE
+
+    def grow(self, ed):
+        """Entities N .. N_GROWN - 1 with TRS and bodies: in the world after the next tick."""
+        self.set_topology(ed.parent_grown, ed.has_transform_grown)
+        self.w.upload_trs(ed.pos, ed.euler, np.ones((len(ed.pos), 3)), first=N)
+        self.w.upload_bodies(ed.type, None, ed.shape, ed.size, ed.layer, ed.mask, first=N)
+        for k in ("type", "shape", "size", "layer", "mask"):
+            setattr(self, k, np.concatenate([getattr(self, k), getattr(ed, k)]))
+        self.fresh = np.concatenate([self.fresh, np.ones(len(ed.pos), bool)])
+        self.n = N_GROWN
+
+    def drop_above(self, n):
+        """What the header asks of a caller that drops entities: their triggers leave the uploaded set and their bodies are removed
+        before the call."""
+        keep = self.trig < n
+        self.trig, self.t_active, self.t_oneshot = self.trig[keep], self.t_active[keep], self.t_oneshot[keep]
+        self.upload_triggers()
+        self.w.upload_bodies(np.full(self.n - n, W.BODY_NONE, np.uint8), first=n)
+        self.type[n:] = W.BODY_NONE
+
+    def shrink(self, n, ed):
+        self.set_topology(ed.parent_shrunk, ed.has_transform_shrunk)
+        for k in ("type", "shape", "size", "layer", "mask", "fresh"):
+            setattr(self, k, getattr(self, k)[:n])
+        self.n = n
+
+
+# ------------------------------------------------------------------------------------------------ asking and checking
+
+
+def _bytes(answer):
+    return {k: np.ascontiguousarray(v).tobytes() for k, v in answer.items()}
+
+
+def ask(w, batches):
+    """The five answers to a phase's batches; the device forms of the two closest-hit queries must equal the host forms."""
+    import torch
+    (o, d, md, mask), (co, cd, cmd, crad, cmask), spheres = batches
+    ans = dict(ray=w.raycast(o, d, md, mask), ray_all=w.raycast_all(o, d, md, mask), cast=w.sphere_cast(co, cd, cmd, crad, cmask),
+               cast_all=w.sphere_cast_all(co, cd, cmd, crad, cmask), overlap=w.overlap_sphere(*spheres))
+    for name, records, fn in (("ray", W.make_rays(o, d, md, mask), w.raycast_device),
+                              ("cast", W.make_sphere_casts(co, cd, cmd, crad, cmask), w.sphere_cast_device)):
+        rt = torch.from_numpy(records.view(np.uint8)).to("cuda:0")
+        ht = torch.zeros(len(records) * 40, dtype=torch.uint8, device="cuda:0")
+        torch.cuda.synchronize()
+        fn(rt, ht)
+        w.sync()
+        hd = ht.cpu().numpy().view(W.RAY_HIT_DTYPE)
+        for k, v in ans[name].items():
+            assert np.ascontiguousarray(hd[k]).tobytes() == v.tobytes(), (name, k)
+    return ans
+
+
+def check_members(sc, ans):
+    """Every entity of every answer is in the world: a body's among the bodies, a trigger's among the posed live ghosts, nothing
+    at or above the entity count; the plane and a miss carry no entity."""
+    bodies, ghosts = sc.bodies_in_world(), sc.ghosts_in_world()
+    assert sc.n == sc.w.n and (len(bodies) == 0 or bodies.max() < sc.n)
+    seen = 0
+    for name, a in ans.items():
+        kind, ent = a["kind"], a["entity"]
+        assert np.isin(kind, (RAY_MISS, RAY_BODY, RAY_TRIGGER, RAY_GROUND)).all(), name
+        is_b, is_t = kind == RAY_BODY, kind == RAY_TRIGGER
+        stray = ent[is_b][~np.isin(ent[is_b], bodies)]
+        assert len(stray) == 0, f"{name}: bodies {np.unique(stray)[:8]} are not in the world (entity count {sc.n})"
+        stray = ent[is_t][~np.isin(ent[is_t], ghosts)]
+        assert len(stray) == 0, f"{name}: triggers {np.unique(stray)[:8]} are not in the world"
+        assert (ent[~is_b & ~is_t] == NO_ENTITY).all() and (ent[is_b | is_t] < sc.n).all(), name
+        seen += int(is_b.sum())
+    assert seen >= 100, "the batches met hardly any body"
+
+
+def head(allh, k):
+    """The all-hits answer of the first k queries of a batch."""
+    end = int(allh["offsets"][k])
+    out = {key: v[:end] for key, v in allh.items() if key != "offsets"}
+    out["offsets"] = allh["offsets"][:k + 1]
+    return out
+
+
+def compare(sc, batches, kind, ans=None):
+    """The answers to a phase's batches against the float64 references on what is in the world."""
+    ans = ask(sc.w, batches) if ans is None else ans
+    check_members(sc, ans)
+    ref = sc.objects()
+    rays, casts, spheres = batches
+    if kind == "rays":
+        check_against_reference(ref, *rays, ans["ray"])
+        assert (ans["ray"]["kind"] == RAY_BODY).any() and (ans["ray"]["kind"] == RAY_MISS).any()
+        check_all_hits(ref, *(a[:N_ALL] for a in rays), ans["ray"], head(ans["ray_all"], N_ALL))
+    else:
+        sref = SphereRef(ref)
+        check_casts(sref, casts, ans["cast"])
+        assert (ans["cast"]["kind"] == RAY_BODY).any() and (ans["cast"]["kind"] == RAY_MISS).any()
+        check_all_casts(sref, tuple(a[:N_ALL] for a in casts), ans["cast"], head(ans["cast_all"], N_ALL))
+        check_overlaps(sref, spheres, ans["overlap"])
+    return ans
+
+
+KINDS = ("rays", "spheres")
+
+# ------------------------------------------------------------------------------------------------ 1, 2: the layout and a re-layout
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_random_comparisons_on_the_layout_scene(kind):
+    sc = LayoutScene()
+    try:
+        sc.tick(6)
+        ans = compare(sc, sc.batches("layout"), kind)
+        assert any((a["kind"] == RAY_TRIGGER).any() for a in ans.values()) and (ans["ray"]["kind"] == RAY_GROUND).any()
+        # slots beyond the entity count hold bodies, and the queries report some of them by their entity
+        slot = W.flatten_topology(sc.parent, sc.ht)[0]
+        far = np.nonzero(sc.ht.astype(bool) & (slot >= N))[0]
+        assert np.isin(far, ans["overlap"]["entity"]).any() or np.isin(far, ans["ray_all"]["entity"]).any()
+    finally:
+        sc.close()
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_a_relayout_changes_no_answer(kind):
+    """bge_world_set_topology "keeps all component state of surviving indices", ghosts keep the pose the last tick gave them, the
+    closest hit is an atomicMin on a total order and the lists are sorted: without a tick no byte of any answer may change."""
+    sc = LayoutScene()
+    try:
+        sc.tick(6)
+        batches = sc.batches("layout")
+        before = ask(sc.w, batches)
+        slots_before, old = sc.w.info()["n_slots"], W.flatten_topology(sc.parent, sc.ht)[0]
+        sc.set_topology(relayout_topology(sc.parent), sc.ht)
+        new, has = W.flatten_topology(sc.parent, sc.ht)[0], sc.ht.astype(bool)
+        print(f"re-layout: {int((new[has] != old[has]).sum())} of {int(has.sum())} slots moved, n_slots {slots_before} -> {sc.w.info()['n_slots']}")
+        assert sc.w.info()["n_slots"] != slots_before and (new[has] != old[has]).sum() >= 0.5 * has.sum()
+        after = ask(sc.w, batches)
+        for name in before:
+            for k, v in _bytes(before[name]).items():
+                assert _bytes(after[name])[k] == v, f"{name}.{k} changed with the layout"
+        check_members(sc, after)
+        # ghosts are posed from the new slots now
+        sc.tick(2)
+        compare(sc, batches, kind)
+    finally:
+        sc.close()
+
+
+# ------------------------------------------------------------------------------------------------ 3: edits between ticks
+
+
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("upto", PHASES[1:])
+def test_edits_between_ticks(upto, kind):
+    """The history runs to the phase `upto`; every phase passed is asked its batches and every entity reported must be in the
+    world, and the last phase's answers are compared with the float64 references."""
+    sc = LayoutScene()
+    try:
+        ed = Edits(sc.parent, sc.ht, np.sort(sc.trig))
+        sc.tick(6)
+
+        def phase(name):
+            batches = sc.batches(name)
+            if name == upto:
+                compare(sc, batches, kind)
+            else:
+                check_members(sc, ask(sc.w, batches))
+            return name == upto
+
+        # BODY_NONE for a tenth of the bodies: absent at once
+        n_before = len(sc.bodies_in_world())
+        sc.remove(ed.removed)
+        assert len(sc.bodies_in_world()) == n_before - len(ed.removed)
+        if phase("removed"):
+            return
+        # 300 new entities, a third of them children of old ones: their bodies are absent before the next tick ...
+        sc.grow(ed)
+        assert sc.w.n == N_GROWN and not np.isin(np.arange(N, N_GROWN), sc.bodies_in_world()).any()
+        if phase("grown, before the tick"):
+            return
+        # ... and present after it
+        sc.tick(1)
+        assert np.isin(np.arange(N, N_GROWN), sc.bodies_in_world()).all()
+        if phase("grown"):
+            return
+        # shrink to 1600: triggers and bodies of the dropped entities go first; the re-uploaded ghosts wait for the next tick
+        batches = sc.batches("grown")
+        sc.drop_above(N_SHRUNK)
+        assert len(sc.trig) == len(ed.trig_shrunk) and len(sc.ghosts_in_world()) == 0
+        ans = ask(sc.w, batches)
+        check_members(sc, ans)
+        assert not any((a["kind"] == RAY_TRIGGER).any() for a in ans.values())
+        sc.shrink(N_SHRUNK, ed)
+        check_members(sc, ask(sc.w, batches))
+        sc.tick(1)
+        assert len(sc.ghosts_in_world()) == len(ed.trig_shrunk)
+        assert phase("shrunk")
+    finally:
+        sc.close()
+
+
+# ------------------------------------------------------------------------------------------------ 4: Transform loss, hand-worked
+
+NP = W.NO_PARENT
+# entity 0: a Static box on its own          1: Static box, child of 7 (loses its Transform)   2: trigger volume, child of 7 (loses it
+# and gets it back elsewhere)   3: never owns a Transform, yet a body is uploaded   4: a root   5: Static box, child of 6 (its parent
+# loses its Transform)   6, 7: parents listed after their children
+HAND_PARENT = np.array([NP, 7, 7, NP, NP, 6, NP, NP], np.uint32)
+HAND_POS = np.float32([[-20, 2, 0], [0, 2, 0], [5, 2, 0], [10, 2, 0], [0, 0, 30], [20, 2, 0], [3, 1, -7], [1, 4, 9]])
+DOWN = (0.0, -1.0, 0.0)
+
+
+def _column(w, x, z, want, name):
+    """A ray and a sphere of radius 0.25 straight down from (x, 10, z) over 20: want = (kind, entity, y of the surface) or None."""
+    r = w.raycast([[x, 10, z]], [DOWN], 20.0, ALL)
+    c = w.sphere_cast([[x, 10, z]], [DOWN], 20.0, 0.25, ALL)
+    for h, rad, what in ((r, 0.0, "ray"), (c, 0.25, "cast")):
+        got = None if h["kind"][0] == RAY_MISS else (int(h["entity"][0]), float(h["fraction"][0]), h["point"][0], h["normal"][0])
+        exp = None if want is None else (want[1], (10.0 - want[2] - rad) / 20.0, (x, want[2], z), (0, 1, 0))
+        check_hand_case(f"{name}, {what}", got, exp, tol=1e-5)
+        if want is not None:
+            assert h["kind"][0] == want[0], f"{name}, {what}: kind {h['kind'][0]}"
+    return r["fraction"][0].tobytes() + c["fraction"][0].tobytes()
+
+
+def test_transform_loss_hand_worked():
+    w = B.World(device=0)
+    try:
+        ht = np.array([1, 1, 1, 0, 1, 1, 1, 1], np.uint8)
+        slot = W.flatten_topology(HAND_PARENT, ht)[0]
+        print("hand-worked layout: slots", slot.tolist())
+        assert all(slot[e] != e and slot[e] >= len(ht) for e in (1, 2, 5)), "slot order equals entity order: the scene tests nothing"
+        w.set_topology(HAND_PARENT, ht)
+        w.upload_trs(HAND_POS, np.zeros((8, 3)), np.ones((8, 3)))
+        types = np.uint8([W.BODY_STATIC, W.BODY_STATIC, W.BODY_NONE, W.BODY_STATIC, W.BODY_NONE, W.BODY_STATIC, W.BODY_NONE, W.BODY_NONE])
+        w.upload_bodies(types, None, np.zeros(8, np.uint8), np.full((8, 3), 0.5, np.float32), np.full(8, 1, np.uint32), np.full(8, ALL, np.uint32))
+        w.upload_triggers(np.uint32([2]), None, np.float32([[1, 1, 1]]), np.uint32([4]), None, np.uint8([0]), np.uint8([1]))
+        w.set_ground_plane(False)
+        w.tick(flags=FLAGS)
+
+        def everything(trigger_z, box1):
+            """All columns; a sphere around everything lists exactly what is in the world."""
+            f = _column(w, -20, 0, (RAY_BODY, 0, 2.5), "the box on its own")
+            f += _column(w, 0, 0, (RAY_BODY, 1, 2.5) if box1 else None, "box 1")
+            f += _column(w, 5, trigger_z, (RAY_TRIGGER, 2, 3.0), "trigger 2")
+            _column(w, 5, 20 - trigger_z, None, "where trigger 2 is not")
+            _column(w, 10, 0, None, "the body of an entity that never owned a Transform")
+            f += _column(w, 20, 0, (RAY_BODY, 5, 2.5), "box 5")
+            for x, z in ((3, -7), (1, 9), (0, 30)):
+                _column(w, x, z, None, "a parent without a body")
+            ov = w.overlap_sphere([[0, 2, 0]], 100.0, ALL)
+            want = [(RAY_BODY, 0)] + ([(RAY_BODY, 1)] if box1 else []) + [(RAY_BODY, 5), (RAY_TRIGGER, 2)]
+            assert list(zip(ov["kind"].tolist(), ov["entity"].tolist())) == want
+            return f
+
+        first = everything(0, True)
+        # entity 1 (a body in the world), entity 2 (a posed trigger) and entity 6 (the parent of box 5) lose their Transforms
+        ht = np.array([1, 0, 0, 0, 1, 1, 0, 1], np.uint8)
+        w.set_topology(HAND_PARENT, ht)
+        assert everything(0, True) == first, "a fraction changed when Transforms were lost"
+        w.tick(flags=FLAGS)
+        assert everything(0, True) == first, "a fraction changed in the tick after Transforms were lost"
+        # a sphere move lands on the body whose entity lost its Transform: the centre meets the top y = 2.5 at 3.0 (f = 0.5);
+        # a = 1, L = 4: g = 0.5 - 0.01 / 4, y = 5 - 4 g = 3.01; nothing is left to slide
+        moves = W.make_sphere_moves([[0, 5, 0]], [[0, -4, 0]], 0.5, 0.01, 0.0, 0.7071068, ALL)
+        got = move(w, moves)
+        check_hand_move("onto box 1", got[0], dict(position=(0, 3.01, 0), remaining=(0, 0, 0), flags=0, n_hits=1, hit_kind=RAY_BODY, hit_entity=1,
+                                                   hit_normal=(0, 1, 0)))
+        assert got[0].tobytes() == move_ref(device_caster(w), moves)[0].tobytes()
+        # uploads to entity 1 are ignored, except BODY_NONE, which removes the body at once
+        w.upload_trs(np.float32([[0, 2, 50]]), first=1)
+        w.upload_bodies(np.uint8([W.BODY_STATIC]), None, np.uint8([0]), np.float32([[1, 1, 1]]), first=1)
+        assert everything(0, True) == first
+        w.upload_bodies(np.uint8([W.BODY_NONE]), first=1)
+        everything(0, False)
+        w.tick(flags=FLAGS)
+        everything(0, False)
+        # the trigger's Transform comes back at z = 20: after one tick the ghost stands there and not at the old place
+        ht = np.array([1, 0, 1, 0, 1, 1, 0, 1], np.uint8)
+        w.set_topology(HAND_PARENT, ht)
+        slot = W.flatten_topology(HAND_PARENT, ht)[0]
+        assert slot[2] != 2 and slot[5] != 5
+        w.upload_trs(np.float32([[5, 2, 20]]), np.zeros((1, 3)), np.ones((1, 3)), first=2)
+        w.tick(flags=FLAGS)
+        everything(20, False)
+    finally:
+        w.close()
+
+
+# ------------------------------------------------------------------------------------------------ 5: sphere moves
+
+
+def test_sphere_moves_before_and_after_a_relayout():
+    sc = LayoutScene()
+    try:
+        sc.tick(1)
+        moves = movers()
+        want = move_ref(device_caster(sc.w), moves)
+        kinds = {k: int((want["hit_kind"] == k).sum()) for k in (RAY_BODY, RAY_GROUND, RAY_TRIGGER)}
+        print(f"movers: last hit on a body {kinds[RAY_BODY]}, the ground {kinds[RAY_GROUND]}, a trigger {kinds[RAY_TRIGGER]}")
+        assert all(v > 0 for v in kinds.values()), kinds
+        bodies, ghosts = sc.bodies_in_world(), sc.ghosts_in_world()
+        for field_kind, field_ent in (("hit_kind", "hit_entity"), ("ground_kind", "ground_entity")):
+            assert np.isin(want[field_ent][want[field_kind] == RAY_BODY], bodies).all()
+            assert np.isin(want[field_ent][want[field_kind] == RAY_TRIGGER], ghosts).all()
+        before = move(sc.w, moves)
+        bad = [i for i in range(len(moves)) if before[i].tobytes() != want[i].tobytes()]
+        assert not bad, f"{len(bad)} of {len(moves)} differ, first {bad[0]}: {before[bad[0]]} vs {want[bad[0]]}"
+        sc.set_topology(relayout_topology(sc.parent), sc.ht)
+        after = move(sc.w, moves)
+        assert after.tobytes() == before.tobytes(), "a move changed with the layout"
+        assert move_ref(device_caster(sc.w), moves).tobytes() == want.tobytes()
+    finally:
+        sc.close()

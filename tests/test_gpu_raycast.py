@@ -18,7 +18,7 @@ import pytest
 import banggameengine_amd as B
 from banggameengine_amd import world as W
 
-from test_raycast_cpu import RAY_BODY, RAY_GROUND, RAY_MISS, RAY_TRIGGER, NO_ENTITY, Obj, World64, quat_from_euler
+from test_raycast_cpu import RAY_BODY, RAY_GROUND, RAY_MISS, RAY_TRIGGER, NO_ENTITY, Obj, World64, quat_from_euler, random_rays
 
 pytestmark = pytest.mark.gpu
 
@@ -30,10 +30,10 @@ FLAGS = W.TICK_ALL | W.TICK_BROADPHASE
 class Scene:
     """A world plus what the reference needs to rebuild its objects."""
 
-    def __init__(self, n, rng, n_triggers=0, spread=30.0, plane=True):
+    def __init__(self, n, rng, n_triggers=0, spread=30.0, plane=True, parent=None, has_transform=None):
         self.n = n
         self.w = B.World(device=0)
-        self.w.set_topology(np.full(n, W.NO_PARENT, np.uint32))
+        self.w.set_topology(np.full(n, W.NO_PARENT, np.uint32) if parent is None else parent, has_transform)
         pos = np.stack([rng.uniform(-spread, spread, n), rng.uniform(0.3, 6.0, n), rng.uniform(-spread, spread, n)], 1)
         self.w.upload_trs(pos, rng.uniform(-math.pi, math.pi, (n, 3)), np.ones((n, 3)))
         self.type = rng.choice([W.BODY_STATIC, W.BODY_DYNAMIC, W.BODY_KINEMATIC], n, p=[0.3, 0.5, 0.2]).astype(np.uint8)
@@ -72,14 +72,19 @@ class Scene:
         cap = np.stack([h[:, 0], np.maximum(self.size[:, 1], np.float32(0)), h[:, 0]], 1)
         return np.where(self.shape[:, None] == 1, cap, box)
 
+    def bodies_in_world(self):
+        return np.nonzero(self.type != W.BODY_NONE)[0]
+
+    def ghosts_in_world(self):
+        return self.trig[self.t_active.astype(bool)]
+
     def objects(self):
         """The reference's world: every body at the pose the device holds, every active ghost at its posed pose."""
         pos, _ = self.w.download_pose()
         quat = self.w.download_bodies()["quat"].astype(np.float64)
         dims = self.dims()
-        live = np.nonzero(self.type != W.BODY_NONE)[0]
+        live, ghosts = self.bodies_in_world(), self.ghosts_in_world()
         gp, ge = self.ghost_pose
-        ghosts = self.trig[self.t_active.astype(bool)]
         gq = np.array([quat_from_euler(ge[e].astype(np.float64)) for e in ghosts]).reshape(-1, 4)
         ent = np.concatenate([live, ghosts])
         kind = np.concatenate([np.full(len(live), RAY_BODY), np.full(len(ghosts), RAY_TRIGGER)])
@@ -88,18 +93,6 @@ class Scene:
 
     def close(self):
         self.w.close()
-
-
-def random_rays(rng, n, scene_pos, spread=30.0):
-    o = np.stack([rng.uniform(-spread, spread, n), rng.uniform(-2.0, 12.0, n), rng.uniform(-spread, spread, n)], 1)
-    d = rng.normal(size=(n, 3))
-    aim = rng.random(n) < 0.6  # most rays aimed at a body, the rest anywhere
-    tgt = scene_pos[rng.integers(0, len(scene_pos), n)] + rng.normal(scale=0.3, size=(n, 3))
-    d[aim] = tgt[aim] - o[aim]
-    d *= rng.uniform(0.5, 2.0, (n, 1))
-    md = rng.uniform(0.5, 1.5, n) * np.where(aim, 1.0, 20.0)
-    mask = rng.choice(np.array([1, 2, 4, 8, 3, 6, 0xFFFFFFFF], np.uint32), n)
-    return o.astype(np.float32), d.astype(np.float32), md.astype(np.float32), mask
 
 
 def check_against_reference(ref, o, d, md, mask, got, need_hits=50):
@@ -132,6 +125,27 @@ def check_against_reference(ref, o, d, md, mask, got, need_hits=50):
     return hits
 
 
+def check_all_hits(ref, o, d, md, mask, got, allh):
+    """All hits: per-ray sets in (f, code) order, offsets, and the first one is the closest hit (got: the closest hits of the
+    same rays, or of a batch these rays begin)."""
+    off = allh["offsets"].astype(np.int64)
+    assert off[0] == 0 and np.all(np.diff(off) >= 0) and off[-1] == len(allh["kind"])
+    for i in range(len(o)):
+        want = ref.cast_all(o[i], d[i], md[i], mask[i])
+        seg = slice(off[i], off[i + 1])
+        if ref.clear(o[i], d[i], md[i], mask[i]):
+            got_set = sorted(zip(allh["kind"][seg].tolist(), allh["entity"][seg].tolist()))
+            assert got_set == sorted((h[2], h[3]) for h in want), f"ray {i}"
+        fr = allh["fraction"][seg]
+        assert np.all(np.diff(fr) >= 0)
+        if off[i + 1] > off[i]:
+            for k in ("kind", "entity", "fraction", "distance"):
+                assert allh[k][off[i]] == got[k][i], (i, k)
+            assert np.array_equal(allh["point"][off[i]], got["point"][i]) and np.array_equal(allh["normal"][off[i]], got["normal"][i])
+        else:
+            assert got["kind"][i] == RAY_MISS
+
+
 @pytest.mark.parametrize("n,seed", [(2000, 1), (20000, 2)])
 def test_random_scene_closest_and_all(n, seed):
     rng = np.random.default_rng(seed)
@@ -144,25 +158,8 @@ def test_random_scene_closest_and_all(n, seed):
         got = sc.w.raycast(o, d, md, mask)
         check_against_reference(ref, o, d, md, mask, got)
         assert (got["kind"] == RAY_BODY).any() and (got["kind"] == RAY_MISS).any()
-        # all hits: per-ray sets in (f, code) order, offsets, and the first one is the closest hit
         sub = slice(0, 256)
-        allh = sc.w.raycast_all(o[sub], d[sub], md[sub], mask[sub])
-        off = allh["offsets"].astype(np.int64)
-        assert off[0] == 0 and np.all(np.diff(off) >= 0) and off[-1] == len(allh["kind"])
-        for i in range(256):
-            want = ref.cast_all(o[i], d[i], md[i], mask[i])
-            seg = slice(off[i], off[i + 1])
-            if ref.clear(o[i], d[i], md[i], mask[i]):
-                got_set = sorted(zip(allh["kind"][seg].tolist(), allh["entity"][seg].tolist()))
-                assert got_set == sorted((h[2], h[3]) for h in want), f"ray {i}"
-            fr = allh["fraction"][seg]
-            assert np.all(np.diff(fr) >= 0)
-            if off[i + 1] > off[i]:
-                for k in ("kind", "entity", "fraction", "distance"):
-                    assert allh[k][off[i]] == got[k][i], (i, k)
-                assert np.array_equal(allh["point"][off[i]], got["point"][i]) and np.array_equal(allh["normal"][off[i]], got["normal"][i])
-            else:
-                assert got["kind"][i] == RAY_MISS
+        check_all_hits(ref, o[sub], d[sub], md[sub], mask[sub], got, sc.w.raycast_all(o[sub], d[sub], md[sub], mask[sub]))
     finally:
         sc.close()
 

@@ -91,6 +91,30 @@ def check_overlaps(ref, spheres, got, need_found=50):
     assert compared >= 0.9 * len(c) and found >= need_found, (compared, found)
 
 
+def check_all_casts(ref, casts, got, allh):
+    """All hits: per-cast sets in (f, code) order, offsets, and the first one is the closest hit (got: the closest hits of the
+    same casts, or of a batch these casts begin).  At least half of the casts must be compared."""
+    o, d, md, rad, mask = casts
+    off = allh["offsets"].astype(np.int64)
+    assert off[0] == 0 and np.all(np.diff(off) >= 0) and off[-1] == len(allh["kind"])
+    compared = 0
+    for i in range(len(o)):
+        want, clear = ref.sweep_clear(o[i], d[i], md[i], rad[i], mask[i])
+        seg = slice(off[i], off[i + 1])
+        if clear:
+            compared += 1
+            got_set = sorted(zip(allh["kind"][seg].tolist(), allh["entity"][seg].tolist()))
+            assert got_set == sorted((h[2], h[3]) for h in want), f"cast {i}"
+        assert np.all(np.diff(allh["fraction"][seg]) >= 0)
+        if off[i + 1] > off[i]:
+            for k in ("kind", "entity", "fraction", "distance"):
+                assert allh[k][off[i]] == got[k][i], (i, k)
+            assert np.array_equal(allh["point"][off[i]], got["point"][i]) and np.array_equal(allh["normal"][off[i]], got["normal"][i])
+        else:
+            assert got["kind"][i] == RAY_MISS
+    assert compared >= 0.5 * len(o)
+
+
 @pytest.mark.parametrize("n,seed", [(2000, 1), (20000, 2)])
 def test_random_scene_casts_all_hits_and_overlaps(n, seed):
     rng = np.random.default_rng(seed)
@@ -105,27 +129,8 @@ def test_random_scene_casts_all_hits_and_overlaps(n, seed):
         got = sc.w.sphere_cast(o, d, md, rad, mask)
         check_casts(ref, casts, got)
         assert (got["kind"] == RAY_BODY).any() and (got["kind"] == RAY_MISS).any() and (rad == 0).sum() >= 300
-        # all hits: per-cast sets in (f, code) order, offsets, and the first one is the closest hit
         sub = slice(0, 256)
-        allh = sc.w.sphere_cast_all(o[sub], d[sub], md[sub], rad[sub], mask[sub])
-        off = allh["offsets"].astype(np.int64)
-        assert off[0] == 0 and np.all(np.diff(off) >= 0) and off[-1] == len(allh["kind"])
-        compared = 0
-        for i in range(256):
-            want, clear = ref.sweep_clear(o[i], d[i], md[i], rad[i], mask[i])
-            seg = slice(off[i], off[i + 1])
-            if clear:
-                compared += 1
-                got_set = sorted(zip(allh["kind"][seg].tolist(), allh["entity"][seg].tolist()))
-                assert got_set == sorted((h[2], h[3]) for h in want), f"cast {i}"
-            assert np.all(np.diff(allh["fraction"][seg]) >= 0)
-            if off[i + 1] > off[i]:
-                for k in ("kind", "entity", "fraction", "distance"):
-                    assert allh[k][off[i]] == got[k][i], (i, k)
-                assert np.array_equal(allh["point"][off[i]], got["point"][i]) and np.array_equal(allh["normal"][off[i]], got["normal"][i])
-            else:
-                assert got["kind"][i] == RAY_MISS
-        assert compared >= 128
+        check_all_casts(ref, tuple(a[sub] for a in casts), got, sc.w.sphere_cast_all(o[sub], d[sub], md[sub], rad[sub], mask[sub]))
         check_overlaps(ref, spheres, sc.w.overlap_sphere(*spheres))
     finally:
         sc.close()
