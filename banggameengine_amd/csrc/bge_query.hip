@@ -1,20 +1,23 @@
-// bge_query.hip — batched queries against the device world: rays, sphere casts and sphere overlaps (include/bge_world.h
-// bge_world_raycast*, bge_world_sphere_cast*, bge_world_overlap_sphere).
+// bge_query.hip — batched queries against the device world: rays, sphere casts, sphere overlaps and sphere penetrations
+// (include/bge_world.h bge_world_raycast*, bge_world_sphere_cast*, bge_world_overlap_sphere, bge_world_sphere_penetration*;
+// DESIGN.md 4.11, 4.13, 4.14, 4.18).
 //
 // PhysicsSystem::Raycast / RaycastAll (src/physics/PhysicsSystem.cpp:1076-1146) ask Bullet's rayTest for one ray; the reference has
 // no sphere query (they are the two primitives its btKinematicCharacterController is made of).  Here a batch of queries of one
 // kind is tested against every body in one streaming pass over the body arrays.  The passes are written once, as templates over a
-// QUERY DESCRIPTION (RayQuery, SphereCastQuery, SphereOverlapQuery below) that supplies only the arithmetic of its kind:
+// QUERY DESCRIPTION (RayQuery, SphereCastQuery, SphereOverlapQuery, SpherePenetrationQuery below) that supplies only the arithmetic
+// of its kind:
 //   k_query_bodies<Q, ALL>  one body per lane, grid-stride over the slots.  The batch's queries are staged through LDS in chunks
 //                  of 256; the body stays in registers while its workgroup walks every chunk, so the body arrays are read once
 //                  per batch.  The cull reads flags, position, collider, contact word and the filter words (44 bytes a body) and
 //                  tests the body's bounding sphere against the query; only a candidate reads its quaternion and runs the exact
 //                  test.  Closest hit: one 64-bit atomicMin per hit on the query's key (fraction bits << 32 | object code) —
-//                  f >= 0, so the bit order is the value order and the tie rule (lowest object code) holds by construction.  All
+//                  f >= 0, so the bit order is the value order and the tie rule (lowest object code) holds by construction.  A
+//                  penetration's value is its depth and the LARGEST wins: its key carries the complemented depth bits.  All
 //                  hits: the (query, code, f, normal) records are appended behind one atomic per wave ballot.
 //   k_query_finish<Q>      one thread per query: the trigger ghosts (few) and the plane, then the winning key is decoded, the
-//                  normal of the winner recomputed with the same device functions, and the bge_ray_hit written.  The key goes
-//                  back to all ones.
+//                  normal of the winner recomputed with the same device functions, and the bge_ray_hit (bge_penetration_hit)
+//                  written.  The key goes back to all ones.
 //   k_query_all_finish<Q>  one thread per query: appends the ghosts' and the plane's hits to the list.
 // Each (Q, ALL) is a kernel of its own; nothing inside the loops asks for the kind at run time.
 #include <hip/hip_runtime.h>
@@ -41,9 +44,19 @@ __device__ __forceinline__ bool finite3(const F3& v)
 }
 __device__ __forceinline__ float abs_sum(const F3& v) { return __builtin_fabsf(v.x) + __builtin_fabsf(v.y) + __builtin_fabsf(v.z); }
 
+// The key of a hit of value f >= 0 by the object `code`: the smaller key wins.  Q::kLargest: the larger value wins instead (the
+// bits complemented; an object code is never all ones, so no key of a hit is the all-ones "no hit").
+template <class Q>
 __device__ __forceinline__ unsigned long long query_key(float f, uint32_t code)
 {
-    return (static_cast<unsigned long long>(__float_as_uint(f)) << 32) | code;
+    const uint32_t bits = Q::kLargest ? ~__float_as_uint(f) : __float_as_uint(f);
+    return (static_cast<unsigned long long>(bits) << 32) | code;
+}
+template <class Q>
+__device__ __forceinline__ float key_value(unsigned long long key)
+{
+    const uint32_t bits = static_cast<uint32_t>(key >> 32);
+    return __uint_as_float(Q::kLargest ? ~bits : bits);
 }
 
 // ---------------------------------------------------------------- the query descriptions
@@ -53,9 +66,12 @@ __device__ __forceinline__ unsigned long long query_key(float f, uint32_t code)
 //   Entry, entry(sh, k), mask(e)   what every lane reads back of entry k, the layer mask bits among it
 //   Extra, extra(sh, k)       what only a lane whose body the mask lets through reads on top
 //   cull(e, x, b)             may the body's bounding sphere be hit at all (conservative: the exact test decides)
-//   exact(e, x, b, q, n)      the value of the hit (fraction; overlap: distance) or -1, and the world normal
+//   exact(e, x, b, q, n)      the value of the hit (fraction; overlap: distance; penetration: depth) or -1, and the world normal
 //   shape(pr, ...), plane(pr, n)   the same exact test from a Prep against a shape given in full, and against the plane y = 0
-//   kClosest, point(pr, f, n, on_plane)   whether the value competes for a closest hit, and the contact point of that hit
+//   kClosest, kList, kLargest   whether the value competes for one winning hit, whether there is a list of all hits, and whether
+//                             the largest value wins instead of the smallest
+//   again(pr, ...), again_plane(pr, n)   the winner's test once more for its record: the normal, and a value handed to point()
+//   point(pr, f, v, n, on_plane), write(o, pr, kind, entity, f, at, n)   the contact point of the winner, and its 10-word record
 
 // The body of a lane as the cull needs it; cand = false when it is not in the world or no query can see it
 struct BodyLane {
@@ -89,12 +105,27 @@ __device__ __forceinline__ bool segment_near(const float4& a, const float4& d, c
     return ex * ex + ey * ey + ez * ez <= rr * rr;
 }
 
+// A bge_ray_hit, word by word (the records are 4-byte aligned)
+__device__ __forceinline__ void write_ray_hit(uint32_t* o, uint32_t kind, uint32_t entity, float f, float distance, const F3& at, const F3& n)
+{
+    o[0] = kind;
+    o[1] = entity;
+    o[2] = __float_as_uint(f);
+    o[3] = __float_as_uint(distance);
+    o[4] = __float_as_uint(at.x);
+    o[5] = __float_as_uint(at.y);
+    o[6] = __float_as_uint(at.z);
+    o[7] = __float_as_uint(n.x);
+    o[8] = __float_as_uint(n.y);
+    o[9] = __float_as_uint(n.z);
+}
+
 struct SegmentEntry {
     float4 a, d; // from.xyz, 1 / |delta|^2; delta.xyz, layer mask bits (0: the query sees nothing)
 };
 
 struct RayQuery { // bge_ray, 8 words
-    static constexpr bool kClosest = true;
+    static constexpr bool kClosest = true, kList = true, kLargest = false;
     struct Prep {
         F3 from, delta;
         float inv_len2, slack, max_distance;
@@ -142,15 +173,24 @@ struct RayQuery { // bge_ray, 8 words
         return ray_shape(p.from, p.delta, origin, q, capsule, dims, n);
     }
     static __device__ __forceinline__ float plane(const Prep& p, F3& n) { return ray_plane(p.from.y, p.from.y + p.delta.y, n); }
+    static __device__ __forceinline__ float again(const Prep& p, const F3& origin, const Q4& q, bool capsule, const F3& dims, F3& n)
+    {
+        return shape(p, origin, q, capsule, dims, n);
+    }
+    static __device__ __forceinline__ float again_plane(const Prep& p, F3& n) { return plane(p, n); }
     // (bge_world.cpp fill_ray_hit computes the same expressions on the host)
-    static __device__ __forceinline__ F3 point(const Prep& p, float f, const F3&, bool)
+    static __device__ __forceinline__ F3 point(const Prep& p, float f, float, const F3&, bool)
     {
         return F3{p.from.x + p.delta.x * f, p.from.y + p.delta.y * f, p.from.z + p.delta.z * f};
+    }
+    static __device__ __forceinline__ void write(uint32_t* o, const Prep& p, uint32_t kind, uint32_t entity, float f, const F3& at, const F3& n)
+    {
+        write_ray_hit(o, kind, entity, f, f * p.max_distance, at, n);
     }
 };
 
 struct SphereCastQuery { // bge_sphere_cast, 10 words
-    static constexpr bool kClosest = true;
+    static constexpr bool kClosest = true, kList = true, kLargest = false;
     struct Prep {
         F3 from, delta;
         float inv_len2, slack, max_distance, radius;
@@ -203,15 +243,24 @@ struct SphereCastQuery { // bge_sphere_cast, 10 words
     static __device__ __forceinline__ float plane(const Prep& p, F3& n) { return sphere_cast_plane(p.from.y, p.from.y + p.delta.y, p.radius, n); }
     // the contact point: the centre at the touch pulled back by the radius along the normal; on the plane y is 0 by definition
     // (bge_world.cpp fill_sphere_cast_hit computes the same expressions on the host)
-    static __device__ __forceinline__ F3 point(const Prep& p, float f, const F3& n, bool on_plane)
+    static __device__ __forceinline__ F3 point(const Prep& p, float f, float, const F3& n, bool on_plane)
     {
         const float py = (p.from.y + p.delta.y * f) - p.radius * n.y;
         return F3{(p.from.x + p.delta.x * f) - p.radius * n.x, on_plane ? 0.0f : py, (p.from.z + p.delta.z * f) - p.radius * n.z};
     }
+    static __device__ __forceinline__ float again(const Prep& p, const F3& origin, const Q4& q, bool capsule, const F3& dims, F3& n)
+    {
+        return shape(p, origin, q, capsule, dims, n);
+    }
+    static __device__ __forceinline__ float again_plane(const Prep& p, F3& n) { return plane(p, n); }
+    static __device__ __forceinline__ void write(uint32_t* o, const Prep& p, uint32_t kind, uint32_t entity, float f, const F3& at, const F3& n)
+    {
+        write_ray_hit(o, kind, entity, f, f * p.max_distance, at, n);
+    }
 };
 
 struct SphereOverlapQuery { // bge_sphere, 5 words: every object whose distance to the centre is at most the radius, with that distance
-    static constexpr bool kClosest = false;
+    static constexpr bool kClosest = false, kList = true; // (no winner: no kLargest)
     struct Prep {
         F3 c;
         float radius, slack;
@@ -265,6 +314,48 @@ struct SphereOverlapQuery { // bge_sphere, 5 words: every object whose distance 
         return dist <= p.radius ? dist : -1.0f;
     }
     static __device__ __forceinline__ float plane(const Prep& p, F3&) { return __builtin_fabsf(p.c.y) <= p.radius ? __builtin_fabsf(p.c.y) : -1.0f; }
+};
+
+// bge_sphere, 5 words: the object that reaches deepest into the sphere.  The value is depth = radius - sd(centre, S) >= 0 over the
+// objects the overlap reports (sd <= radius; outside a shape sd is the overlap's distance, from the same device functions); the
+// largest wins.  The record is a bge_penetration_hit; its point needs sd itself, which again() returns.
+struct SpherePenetrationQuery : SphereOverlapQuery {
+    static constexpr bool kClosest = true, kList = false, kLargest = true;
+    // radius - sd in one subtraction; + 0 makes the only possible zero of the other sign (-0 - +0) a +0, so that the bit order
+    // of the key is the value order
+    static __device__ __forceinline__ float depth(float sd, float radius) { return sd <= radius ? (radius - sd) + 0.0f : -1.0f; }
+    static __device__ __forceinline__ float exact(const Entry& e, Extra, const BodyLane& b, const Q4& q, F3& n)
+    {
+        return depth(point_shape_signed(F3{e.a.x, e.a.y, e.a.z}, b.c, q, b.capsule, b.dims, n), e.a.w);
+    }
+    static __device__ __forceinline__ float again(const Prep& p, const F3& origin, const Q4& q, bool capsule, const F3& dims, F3& n)
+    {
+        return point_shape_signed(p.c, origin, q, capsule, dims, n);
+    }
+    static __device__ __forceinline__ float again_plane(const Prep& p, F3& n) { return point_plane_signed(p.c.y, n); }
+    static __device__ __forceinline__ float shape(const Prep& p, const F3& origin, const Q4& q, bool capsule, const F3& dims, F3& n)
+    {
+        return depth(again(p, origin, q, capsule, dims, n), p.radius);
+    }
+    static __device__ __forceinline__ float plane(const Prep& p, F3& n) { return depth(again_plane(p, n), p.radius); }
+    // centre - normal * sd: on the surface
+    static __device__ __forceinline__ F3 point(const Prep& p, float, float sd, const F3& n, bool)
+    {
+        return F3{p.c.x - n.x * sd, p.c.y - n.y * sd, p.c.z - n.z * sd};
+    }
+    static __device__ __forceinline__ void write(uint32_t* o, const Prep&, uint32_t kind, uint32_t entity, float f, const F3& at, const F3& n)
+    {
+        o[0] = kind;
+        o[1] = entity;
+        o[2] = __float_as_uint(f);
+        o[3] = __float_as_uint(at.x);
+        o[4] = __float_as_uint(at.y);
+        o[5] = __float_as_uint(at.z);
+        o[6] = __float_as_uint(n.x);
+        o[7] = __float_as_uint(n.y);
+        o[8] = __float_as_uint(n.z);
+        o[9] = 0u;
+    }
 };
 
 // ---------------------------------------------------------------- the body pass
@@ -351,7 +442,7 @@ __global__ void __launch_bounds__(256) k_query_bodies(QueryParams p)
                         const float f = Q::exact(e, x, b, q, n);
                         if (f >= 0.0f) {
                             if constexpr (!ALL) {
-                                atomicMin(p.keys + r0 + k, query_key(f, p.entity_of_slot[s] & kQueryEntityMask));
+                                atomicMin(p.keys + r0 + k, query_key<Q>(f, p.entity_of_slot[s] & kQueryEntityMask));
                             } else {
                                 hit = true;
                                 fh = f;
@@ -367,15 +458,17 @@ __global__ void __launch_bounds__(256) k_query_bodies(QueryParams p)
 }
 
 // ---------------------------------------------------------------- the finish passes
-// ghost g of the list against the query pr: value or -1, world normal
-template <class Q>
+// ghost g of the list against the query pr: value or -1, world normal.  AGAIN: the winner's test once more (Q::again)
+template <class Q, bool AGAIN = false>
 __device__ __forceinline__ float query_ghost(const QueryParams& p, const typename Q::Prep& pr, uint32_t g, F3& n)
 {
     const QueryGhost gh = p.ghosts[g];
     if ((gh.group & pr.mask) == 0u || gh.mask == 0u) return -1.0f;
     const float* pose = p.ghost_pose + 8ull * gh.trigger;
-    return Q::shape(pr, F3{pose[0], pose[1], pose[2]}, Q4{pose[4], pose[5], pose[6], pose[7]}, gh.capsule != 0u,
-                    F3{gh.dims[0], gh.dims[1], gh.dims[2]}, n);
+    const F3 origin{pose[0], pose[1], pose[2]}, dims{gh.dims[0], gh.dims[1], gh.dims[2]};
+    const Q4 q{pose[4], pose[5], pose[6], pose[7]};
+    if constexpr (AGAIN) return Q::again(pr, origin, q, gh.capsule != 0u, dims, n);
+    else return Q::shape(pr, origin, q, gh.capsule != 0u, dims, n);
 }
 
 __device__ __forceinline__ bool sees_plane(const QueryParams& p, uint32_t mask)
@@ -397,7 +490,7 @@ __global__ void __launch_bounds__(64) k_query_finish(QueryParams p)
             F3 n;
             const float f = query_ghost<Q>(p, pr, g, n);
             if (f >= 0.0f) {
-                const unsigned long long k = query_key(f, kQueryCodeGhost | (p.ghosts[g].entity & kQueryEntityMask));
+                const unsigned long long k = query_key<Q>(f, kQueryCodeGhost | (p.ghosts[g].entity & kQueryEntityMask));
                 if (k < key) {
                     key = k;
                     gwin = g;
@@ -408,7 +501,7 @@ __global__ void __launch_bounds__(64) k_query_finish(QueryParams p)
             F3 n;
             const float f = Q::plane(pr, n);
             if (f >= 0.0f) {
-                const unsigned long long k = query_key(f, kQueryCodePlane | kQueryEntityMask);
+                const unsigned long long k = query_key<Q>(f, kQueryCodePlane | kQueryEntityMask);
                 if (k < key) key = k;
             }
         }
@@ -422,35 +515,26 @@ __global__ void __launch_bounds__(64) k_query_finish(QueryParams p)
         for (int i = 2; i < 10; ++i) o[i] = 0u;
         return;
     }
-    const float f = __uint_as_float(static_cast<uint32_t>(key >> 32));
+    const float f = key_value<Q>(key);
     const uint32_t code = static_cast<uint32_t>(key);
     const uint32_t kind = code >> 30, ent = code & kQueryEntityMask;
     F3 n{0.0f, 0.0f, 0.0f};
+    float v; // what the winner's test returns this time
     uint32_t out_kind, out_entity = ent;
     if (kind == 0u) {
         const uint32_t s = p.slot_of_entity[ent];
         const float4 cs = p.cshape[s];
-        (void)Q::shape(pr, ld3(p.pos, s), ld4(p.quat, s), (p.cinfo[s] & kCiCapsule) != 0u, F3{cs.x, cs.y, cs.z}, n);
+        v = Q::again(pr, ld3(p.pos, s), ld4(p.quat, s), (p.cinfo[s] & kCiCapsule) != 0u, F3{cs.x, cs.y, cs.z}, n);
         out_kind = BGE_RAY_BODY;
     } else if (kind == 1u) {
-        (void)query_ghost<Q>(p, pr, gwin, n);
+        v = query_ghost<Q, true>(p, pr, gwin, n);
         out_kind = BGE_RAY_TRIGGER;
     } else {
-        (void)Q::plane(pr, n);
+        v = Q::again_plane(pr, n);
         out_kind = BGE_RAY_GROUND;
         out_entity = BGE_RAY_NO_ENTITY;
     }
-    const F3 at = Q::point(pr, f, n, kind == 2u);
-    o[0] = out_kind;
-    o[1] = out_entity;
-    o[2] = __float_as_uint(f);
-    o[3] = __float_as_uint(f * pr.max_distance);
-    o[4] = __float_as_uint(at.x);
-    o[5] = __float_as_uint(at.y);
-    o[6] = __float_as_uint(at.z);
-    o[7] = __float_as_uint(n.x);
-    o[8] = __float_as_uint(n.y);
-    o[9] = __float_as_uint(n.z);
+    Q::write(o, pr, out_kind, out_entity, f, Q::point(pr, f, v, n, kind == 2u), n);
 }
 
 template <class Q>
@@ -479,8 +563,12 @@ hipError_t launch(hipStream_t stream, const QueryParams& p, bool all)
     const uint64_t blocks = (p.n_slots + 255) / 256;
     const dim3 body_grid(static_cast<uint32_t>(blocks < kMaxBlocks ? blocks : kMaxBlocks)), finish_grid((p.n_queries + 63u) / 64u);
     if (all) {
-        if (p.n_slots) hipLaunchKernelGGL((k_query_bodies<Q, true>), body_grid, dim3(256), 0, stream, p);
-        hipLaunchKernelGGL(k_query_all_finish<Q>, finish_grid, dim3(64), 0, stream, p);
+        if constexpr (Q::kList) {
+            if (p.n_slots) hipLaunchKernelGGL((k_query_bodies<Q, true>), body_grid, dim3(256), 0, stream, p);
+            hipLaunchKernelGGL(k_query_all_finish<Q>, finish_grid, dim3(64), 0, stream, p);
+        } else {
+            return hipErrorInvalidValue;
+        }
     } else if constexpr (Q::kClosest) {
         if (p.n_slots) hipLaunchKernelGGL((k_query_bodies<Q, false>), body_grid, dim3(256), 0, stream, p);
         hipLaunchKernelGGL(k_query_finish<Q>, finish_grid, dim3(64), 0, stream, p);
@@ -498,6 +586,7 @@ hipError_t launch_query(hipStream_t stream, QueryKind kind, const QueryParams& p
     case QueryKind::Ray: return launch<RayQuery>(stream, p, all);
     case QueryKind::SphereCast: return launch<SphereCastQuery>(stream, p, all);
     case QueryKind::SphereOverlap: return launch<SphereOverlapQuery>(stream, p, all);
+    case QueryKind::SpherePenetration: return launch<SpherePenetrationQuery>(stream, p, all);
     }
     return hipErrorInvalidValue;
 }

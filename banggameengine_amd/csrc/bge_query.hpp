@@ -1,5 +1,6 @@
 // bge_query.hpp — parameters, records and launch entry point of the batched queries against the device world (bge_query.hip;
-// include/bge_world.h bge_world_raycast*, bge_world_sphere_cast*, bge_world_overlap_sphere).
+// include/bge_world.h bge_world_raycast*, bge_world_sphere_cast*, bge_world_overlap_sphere, bge_world_sphere_penetration; DESIGN.md
+// 4.11, 4.13, 4.14, 4.18).
 #pragma once
 
 #include <hip/hip_runtime_api.h>
@@ -31,8 +32,8 @@ static_assert(sizeof(QueryRec) == 24, "24-byte hit record");
 // Object codes order the hits of one query at equal fraction: bodies, then ghosts, then the plane, each by entity index.
 constexpr uint32_t kQueryCodeGhost = 1u << 30, kQueryCodePlane = 2u << 30, kQueryEntityMask = (1u << 30) - 1u;
 
-// What is asked; the records of a batch are bge_ray, bge_sphere_cast or bge_sphere accordingly
-enum class QueryKind { Ray, SphereCast, SphereOverlap };
+// What is asked; the records of a batch are bge_ray, bge_sphere_cast or bge_sphere (overlap and penetration) accordingly
+enum class QueryKind { Ray, SphereCast, SphereOverlap, SpherePenetration };
 
 struct QueryParams {
     const void* records;            // [n_queries] records of the batch's kind (device)
@@ -55,7 +56,7 @@ struct QueryParams {
     uint32_t plane;
     // closest hit
     unsigned long long* keys;       // [n_queries] all ones between calls (k_query_finish puts them back)
-    void* hits;                     // bge_ray_hit[n_queries] (device)
+    void* hits;                     // bge_ray_hit[n_queries], SpherePenetration: bge_penetration_hit[n_queries] (device)
     // all hits
     QueryRec* all;                  // [all_cap]
     uint32_t* all_count;            // [1] records found (may exceed all_cap: nothing beyond it is written)
@@ -63,8 +64,9 @@ struct QueryParams {
 };
 
 // The body pass, then one thread per query (ghosts, plane).  all = false: the closest hit of each query into p.hits (rays and
-// sphere casts; an overlap has no closest hit: hipErrorInvalidValue).  all = true: every (query, object) hit is appended to p.all
-// behind p.all_count (zeroed before the call by the caller); an overlap's records carry the distance and no normal.
+// sphere casts; for a penetration the deepest; an overlap has no closest hit: hipErrorInvalidValue).  all = true: every (query,
+// object) hit is appended to p.all behind p.all_count (zeroed before the call by the caller); an overlap's records carry the
+// distance and no normal; a penetration has no list (the overlap is its list): hipErrorInvalidValue.
 hipError_t launch_query(hipStream_t stream, QueryKind kind, const QueryParams& p, bool all);
 
 } // namespace bge

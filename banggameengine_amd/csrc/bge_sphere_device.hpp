@@ -131,6 +131,49 @@ __device__ __forceinline__ float point_shape_distance(const F3& c, const F3& ori
     return __builtin_sqrtf(point_box_closest(p, dims, cl));
 }
 
+// Signed distance from the point c to the same shape and the unit direction n out of it, in world space (include/bge_world.h
+// "Signed distance").  Outside, the value is point_shape_distance's, from the same functions: point_box_closest,
+// point_capsule_closest.  Inside a box: minus the distance to the nearest face, n that face's axis (ties to the lowest axis, a zero
+// coordinate counts as positive).  A capsule: distance to the segment less the radius, n away from the segment; on the segment
+// itself n is the capsule's local +x.
+__device__ __forceinline__ float point_shape_signed(const F3& c, const F3& origin, const Q4& q, bool capsule, const F3& dims, F3& n)
+{
+    const M3 basis = bt_mat_from_quat(q);
+    const F3 p = ray_to_local(basis, F3{c.x - origin.x, c.y - origin.y, c.z - origin.z});
+    F3 nl;
+    float sd;
+    if (capsule) {
+        const float ey = p.y - sph_clamp(p.y, dims.y);
+        const float a = __builtin_sqrtf(p.x * p.x + ey * ey + p.z * p.z);
+        const float out = point_capsule_closest(p, dims.x, dims.y);
+        sd = out > 0.0f ? out : a - dims.x;
+        nl = a > 0.0f ? F3{p.x / a, ey / a, p.z / a} : F3{1.0f, 0.0f, 0.0f};
+    } else {
+        const float ax = __builtin_fabsf(p.x), ay = __builtin_fabsf(p.y), az = __builtin_fabsf(p.z);
+        if (ax > dims.x || ay > dims.y || az > dims.z) {
+            F3 cl;
+            sd = __builtin_sqrtf(point_box_closest(p, dims, cl));
+            nl = F3{(p.x - cl.x) / sd, (p.y - cl.y) / sd, (p.z - cl.z) / sd};
+        } else {
+            const float mx = dims.x - ax, my = dims.y - ay, mz = dims.z - az;
+            const int j = mx <= my ? (mx <= mz ? 0 : 2) : (my <= mz ? 1 : 2);
+            const float m = j == 0 ? mx : (j == 1 ? my : mz);
+            const float s = (j == 0 ? p.x : (j == 1 ? p.y : p.z)) < 0.0f ? -1.0f : 1.0f;
+            sd = -m;
+            nl = F3{j == 0 ? s : 0.0f, j == 1 ? s : 0.0f, j == 2 ? s : 0.0f};
+        }
+    }
+    n = ray_to_world(basis, nl);
+    return sd;
+}
+
+// The plane y = 0, two-sided as the casts treat it: |c.y|, n up for c.y >= 0 (-0 included) and down below.  It has no inside.
+__device__ __forceinline__ float point_plane_signed(float cy, F3& n)
+{
+    n = F3{0.0f, cy >= 0.0f ? 1.0f : -1.0f, 0.0f};
+    return __builtin_fabsf(cy);
+}
+
 // The plane y = 0 against a sphere of radius r moving from from_y to to_y: the centre's ray against y = r from above (it must
 // start above r and end below it) or y = -r from below; a sphere that starts within r of the plane does not hit it.
 __device__ __forceinline__ float sphere_cast_plane(float from_y, float to_y, float r, F3& n)

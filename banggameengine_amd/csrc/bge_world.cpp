@@ -30,6 +30,7 @@
 #include "bge_epochs.hpp"
 #include "bge_kernels.hpp"
 #include "bge_move.hpp"
+#include "bge_recover.hpp"
 #include "bge_query.hpp"
 
 namespace {
@@ -367,6 +368,8 @@ struct bge_world {
     std::vector<bge::QueryGhost> query_ghosts_host, query_ghosts_dev;
     // sphere moves (bge_move.hip): staging for the host entry point, the per-mover state, and the cast / hit records of the passes
     DevBuf move_in, move_out, move_state, move_casts, move_hits;
+    // sphere recovery (bge_recover.hip): the same for its passes, and its own (k_move_step relies on being the only writer of move_casts)
+    DevBuf recover_in, recover_out, recover_state, recover_queries, recover_hits;
     // debug overlay (bge_debug.hip): per-workgroup line counts and their offsets, the host entry point's line buffer and total
     DevBuf dbg_block_sum, dbg_block_off, dbg_lines, dbg_total;
     // frustum culling (bge_cull.hip): the model-space bounds per ENTITY (a row of NaNs = no bounds), the pass's ballots / counts /
@@ -457,7 +460,7 @@ struct bge_world {
         for (DevBuf* b : std::initializer_list<DevBuf*>{&flags, &parent, &tile_hdr, &slot_of_entity, &entity_of_slot, &root_slots, &root_index, &root_worlds, &counter, &stage,
                           &stage2, &mass_palette, &normal, &filter_table, &grav_palette, &bp_partials, &obstacle_slots, &obstacle_gen, &obstacles, &obstacle_grid, &box_list, &box_count, &frozen, &rs_word, &trig_slot, &trig_entity, &trig_he, &trig_group,
                           &trig_mask, &trig_active, &trig_aabb, &trig_pairs, &trig_count, &trig_lists, &ground_list, &ground_count, &trig_tab[0], &trig_tab[1],
-                          &trig_delta_dev, &trig_keys_dev, &trig_pose, &query_in, &query_out, &query_keys, &query_all, &query_all_count, &query_ghosts, &move_in, &move_out, &move_state, &move_casts, &move_hits, &dbg_block_sum, &dbg_block_off,
+                          &trig_delta_dev, &trig_keys_dev, &trig_pose, &query_in, &query_out, &query_keys, &query_all, &query_all_count, &query_ghosts, &move_in, &move_out, &move_state, &move_casts, &move_hits, &recover_in, &recover_out, &recover_state, &recover_queries, &recover_hits, &dbg_block_sum, &dbg_block_off,
                           &dbg_lines, &dbg_total, &bounds, &cull_ballots, &cull_block_sum, &cull_block_off, &cull_out, &cull_total, &draw_keys,
                           &batch_sort, &batch_hist, &batch_out}) {
             b->release();
@@ -2872,6 +2875,9 @@ static_assert(sizeof(bge_sphere) == 20, "bge_sphere is 20 bytes (include/bge_wor
 static_assert(sizeof(bge_overlap_hit) == 12, "bge_overlap_hit is 12 bytes (include/bge_world.h)");
 static_assert(sizeof(bge_sphere_move) == 48, "bge_sphere_move is 48 bytes (include/bge_world.h)");
 static_assert(sizeof(bge_sphere_move_result) == 80, "bge_sphere_move_result is 80 bytes (include/bge_world.h)");
+static_assert(sizeof(bge_penetration_hit) == 40, "bge_penetration_hit is 40 bytes (include/bge_world.h)");
+static_assert(sizeof(bge_sphere_recover) == 28, "bge_sphere_recover is 28 bytes (include/bge_world.h)");
+static_assert(sizeof(bge_sphere_recover_result) == 64, "bge_sphere_recover_result is 64 bytes (include/bge_world.h)");
 
 namespace {
 
@@ -3015,8 +3021,8 @@ void decode_code(uint32_t code, uint32_t& kind, uint32_t& entity)
     entity = k == 2u ? BGE_RAY_NO_ENTITY : (code & bge::kQueryEntityMask);
 }
 
-// Closest hit per query (rays, sphere casts), host records to host hits
-int query_closest(bge_world* w, bge::QueryKind kind, uint64_t n, size_t record_bytes, const void* records, bge_ray_hit* hits)
+// Closest hit per query (rays, sphere casts; the deepest of a penetration), host records to host hits of 40 bytes each
+int query_closest(bge_world* w, bge::QueryKind kind, uint64_t n, size_t record_bytes, const void* records, void* hits)
 {
     if (!w) return fail(BGE_ERR_INVALID, "world is NULL");
     if (n == 0) return BGE_OK;
@@ -3072,6 +3078,33 @@ int move_enqueue(bge_world* w, bge::QueryParams q, uint64_t n, const void* moves
     }
     HIP_TRY(bge::launch_query(w->stream, bge::QueryKind::SphereCast, q, false));
     HIP_TRY(bge::launch_move_finish(w->stream, m));
+    return BGE_OK;
+}
+
+// A batch of sphere recoveries between device buffers (include/bge_world.h "Sphere penetration and recovery"): begin,
+// BGE_RECOVER_ROUNDS rounds of a penetration pass and a step, the final check's pass, finish — all enqueued, nothing read in
+// between.  q comes from query_prepare(w, n, q).  The scratch is the recovery's own, not the mover's.
+int recover_enqueue(bge_world* w, bge::QueryParams q, uint64_t n, const void* records_device, void* results_device)
+{
+    HIP_TRY(w->recover_state.ensure(n * bge::kRecoverStateBytes));
+    HIP_TRY(w->recover_queries.ensure(n * sizeof(bge_sphere)));
+    HIP_TRY(w->recover_hits.ensure(n * sizeof(bge_penetration_hit)));
+    q.records = w->recover_queries.p;
+    q.hits = w->recover_hits.p;
+    bge::RecoverParams r{};
+    r.records = records_device;
+    r.results = results_device;
+    r.state = w->recover_state.as<float4>();
+    r.queries = w->recover_queries.p;
+    r.hits = w->recover_hits.p;
+    r.n = static_cast<uint32_t>(n);
+    HIP_TRY(bge::launch_recover_begin(w->stream, r));
+    for (uint32_t round = 0; round < BGE_RECOVER_ROUNDS; ++round) {
+        HIP_TRY(bge::launch_query(w->stream, bge::QueryKind::SpherePenetration, q, false));
+        HIP_TRY(bge::launch_recover_step(w->stream, r));
+    }
+    HIP_TRY(bge::launch_query(w->stream, bge::QueryKind::SpherePenetration, q, false));
+    HIP_TRY(bge::launch_recover_finish(w->stream, r));
     return BGE_OK;
 }
 
@@ -3232,6 +3265,55 @@ try {
     return query_list(w, kOverlapSphere, n, spheres, hits, cap, offsets, total);
 }
 BGE_CATCH_ALL("bge_world_overlap_sphere")
+
+int bge_world_sphere_penetration(bge_world* w, uint64_t n, const bge_sphere* spheres, bge_penetration_hit* hits)
+try {
+    static_assert(sizeof(bge_penetration_hit) == sizeof(bge_ray_hit), "the closest-hit records of every kind are 40 bytes");
+    return query_closest(w, bge::QueryKind::SpherePenetration, n, sizeof(bge_sphere), spheres, hits);
+}
+BGE_CATCH_ALL("bge_world_sphere_penetration")
+
+int bge_world_sphere_penetration_device(bge_world* w, uint64_t n, const void* spheres_device, void* hits_device)
+try {
+    if (n > 0 && ((reinterpret_cast<uintptr_t>(spheres_device) | reinterpret_cast<uintptr_t>(hits_device)) & 3u)) {
+        return fail(BGE_ERR_INVALID, "spheres_device and hits_device must be 4-byte aligned");
+    }
+    return query_closest_device(w, bge::QueryKind::SpherePenetration, n, spheres_device, hits_device);
+}
+BGE_CATCH_ALL("bge_world_sphere_penetration_device")
+
+int bge_world_sphere_recover(bge_world* w, uint64_t n, const bge_sphere_recover* records, bge_sphere_recover_result* results)
+try {
+    if (!w) return fail(BGE_ERR_INVALID, "world is NULL");
+    if (n == 0) return BGE_OK;
+    if (!records || !results) return fail(BGE_ERR_INVALID, "NULL argument");
+    DeviceGuard guard(w->device);
+    bge::QueryParams q;
+    if (int rc = query_prepare(w, n, q)) return rc; // (before the staging is sized: it refuses a batch that is too large)
+    HIP_TRY(w->recover_in.ensure(n * sizeof(bge_sphere_recover)));
+    HIP_TRY(w->recover_out.ensure(n * sizeof(bge_sphere_recover_result)));
+    HIP_TRY(hipMemcpyAsync(w->recover_in.p, records, n * sizeof(bge_sphere_recover), hipMemcpyHostToDevice, w->stream));
+    if (int rc = recover_enqueue(w, q, n, w->recover_in.p, w->recover_out.p)) return rc;
+    HIP_TRY(hipMemcpyAsync(results, w->recover_out.p, n * sizeof(bge_sphere_recover_result), hipMemcpyDeviceToHost, w->stream));
+    HIP_TRY(hipStreamSynchronize(w->stream));
+    return BGE_OK;
+}
+BGE_CATCH_ALL("bge_world_sphere_recover")
+
+int bge_world_sphere_recover_device(bge_world* w, uint64_t n, const void* records_device, void* results_device)
+try {
+    if (!w) return fail(BGE_ERR_INVALID, "world is NULL");
+    if (n == 0) return BGE_OK;
+    if (!records_device || !results_device) return fail(BGE_ERR_INVALID, "NULL argument");
+    if ((reinterpret_cast<uintptr_t>(records_device) | reinterpret_cast<uintptr_t>(results_device)) & 3u) {
+        return fail(BGE_ERR_INVALID, "records_device and results_device must be 4-byte aligned");
+    }
+    DeviceGuard guard(w->device);
+    bge::QueryParams q;
+    if (int rc = query_prepare(w, n, q)) return rc;
+    return recover_enqueue(w, q, n, records_device, results_device);
+}
+BGE_CATCH_ALL("bge_world_sphere_recover_device")
 
 // ---------------------------------------------------------------- debug overlay (bge_debug.hip)
 static_assert(sizeof(bge_debug_line) == 28, "bge_debug_line is 28 bytes (include/bge_world.h)");

@@ -91,6 +91,35 @@ template <class Vec3> struct GpuSphereMoveResult {
     Vec3 groundNormal{};
 };
 
+// What GpuPhysicsSystem::SpherePenetration finds, one sphere of RecoverSpheres and what a recovery returns (extensions:
+// include/bge_world.h "Sphere penetration and recovery").  Vec3 is the engine's float3 (members x, y, z).
+template <class Vec3> struct GpuPenetrationHit {
+    uint32_t entity = 0;  // EntityId of the body or trigger; kInvalidEntity (0) for the ground plane
+    bool trigger = false; // a trigger ghost, not a rigid body
+    float depth = 0.0f;   // how far the shape reaches into the sphere, >= 0
+    Vec3 point{};         // on the shape's surface
+    Vec3 normal{};        // unit: the way out
+};
+template <class Vec3> struct GpuSphereRecover {
+    Vec3 position{};
+    float radius = 0.5f;
+    float skin = 0.01f; // > 0: the gap left to what the sphere was pushed out of
+    uint32_t layerMask = 0xffffffffu;
+};
+template <class Vec3> struct GpuSphereRecoverResult {
+    Vec3 position{};     // centre after the recovery
+    Vec3 pushed{};       // position after - position before
+    bool valid = false;  // false: an input was not finite or out of range, or there is no world; position is echoed
+    bool moved = false;  // at least one push
+    bool stuck = false;  // still penetrating after BGE_RECOVER_ROUNDS pushes, by remainingDepth
+    uint32_t pushes = 0; // 0 .. BGE_RECOVER_ROUNDS
+    uint32_t hitEntity = 0; // EntityId of what the last push was out of; kInvalidEntity (0) for the ground plane or none
+    bool hitTrigger = false;
+    Vec3 hitNormal{};
+    float hitDepth = 0.0f;
+    float remainingDepth = 0.0f;
+};
+
 struct GpuTriggerEvent {
     enum class Type { Enter, Stay, Exit };
     Type type = Type::Enter;
@@ -535,6 +564,82 @@ public:
         one[0].layerMask = layerMask;
         std::vector<GpuSphereMoveResult<Vec3>> out;
         const bool done = MoveSpheres(one, out);
+        result = out[0];
+        return done && result.valid;
+    }
+
+    // EXTENSION: the object that reaches deepest into a sphere at rest, with the depth and the way out (include/bge_world.h
+    // "Sphere penetration and recovery"); false when nothing touches the sphere.
+    template <class Vec3> bool SpherePenetration(const Vec3& center, float radius, uint32_t layerMask, GpuPenetrationHit<Vec3>& outHit)
+    {
+        if (!ok() || !(radius >= 0.0f) || layerMask == 0u) return false;
+        bge_sphere s{};
+        s.center[0] = center.x, s.center[1] = center.y, s.center[2] = center.z;
+        s.radius = radius;
+        s.layer_mask = layerMask;
+        bge_penetration_hit h{};
+        if (bge_world_sphere_penetration(world_, 1, &s, &h) != BGE_OK) return Log("bge_world_sphere_penetration");
+        if (h.kind == BGE_RAY_MISS) return false;
+        outHit.entity = h.entity != BGE_RAY_NO_ENTITY && h.entity < ids_.size() ? ids_[h.entity] : Id{0};
+        outHit.trigger = h.kind == BGE_RAY_TRIGGER;
+        outHit.depth = h.depth;
+        outHit.point.x = h.point[0], outHit.point.y = h.point[1], outHit.point.z = h.point[2];
+        outHit.normal.x = h.normal[0], outHit.normal.y = h.normal[1], outHit.normal.z = h.normal[2];
+        return true;
+    }
+
+    // EXTENSION: a batch of spheres pushed out of what they touch or penetrate, before they are moved (recover, then
+    // MoveSpheres).  One call, no round trip per sphere or per push.  Nothing is written into a Transform.  false when there is
+    // no world or the call failed; results[i].valid tells an invalid record.
+    template <class Vec3>
+    bool RecoverSpheres(const std::vector<GpuSphereRecover<Vec3>>& spheres, std::vector<GpuSphereRecoverResult<Vec3>>& results)
+    {
+        results.assign(spheres.size(), GpuSphereRecoverResult<Vec3>{});
+        for (size_t i = 0; i < spheres.size(); ++i) results[i].position = spheres[i].position;
+        if (!ok()) return false;
+        if (spheres.empty()) return true;
+        recovers_.resize(spheres.size());
+        recover_results_.resize(spheres.size());
+        for (size_t i = 0; i < spheres.size(); ++i) {
+            const GpuSphereRecover<Vec3>& m = spheres[i];
+            bge_sphere_recover& o = recovers_[i];
+            o = bge_sphere_recover{};
+            o.position[0] = m.position.x, o.position[1] = m.position.y, o.position[2] = m.position.z;
+            o.radius = m.radius;
+            o.skin = m.skin;
+            o.layer_mask = m.layerMask;
+        }
+        if (bge_world_sphere_recover(world_, recovers_.size(), recovers_.data(), recover_results_.data()) != BGE_OK) {
+            return Log("bge_world_sphere_recover");
+        }
+        for (size_t i = 0; i < spheres.size(); ++i) {
+            const bge_sphere_recover_result& r = recover_results_[i];
+            GpuSphereRecoverResult<Vec3>& o = results[i];
+            o.position.x = r.position[0], o.position.y = r.position[1], o.position.z = r.position[2];
+            o.pushed.x = r.pushed[0], o.pushed.y = r.pushed[1], o.pushed.z = r.pushed[2];
+            o.valid = (r.flags & BGE_RECOVER_INVALID) == 0u;
+            o.moved = (r.flags & BGE_RECOVER_MOVED) != 0u;
+            o.stuck = (r.flags & BGE_RECOVER_STUCK) != 0u;
+            o.pushes = r.n_pushes;
+            o.hitEntity = r.hit_entity != BGE_RAY_NO_ENTITY && r.hit_entity < ids_.size() ? ids_[r.hit_entity] : Id{0};
+            o.hitTrigger = r.hit_kind == BGE_RAY_TRIGGER;
+            o.hitNormal.x = r.hit_normal[0], o.hitNormal.y = r.hit_normal[1], o.hitNormal.z = r.hit_normal[2];
+            o.hitDepth = r.hit_depth;
+            o.remainingDepth = r.remaining_depth;
+        }
+        return true;
+    }
+    // one sphere: true when it was recovered (a valid record on a world)
+    template <class Vec3>
+    bool RecoverSphere(const Vec3& position, float radius, float skin, uint32_t layerMask, GpuSphereRecoverResult<Vec3>& result)
+    {
+        std::vector<GpuSphereRecover<Vec3>> one(1);
+        one[0].position = position;
+        one[0].radius = radius;
+        one[0].skin = skin;
+        one[0].layerMask = layerMask;
+        std::vector<GpuSphereRecoverResult<Vec3>> out;
+        const bool done = RecoverSpheres(one, out);
         result = out[0];
         return done && result.valid;
     }
@@ -1051,6 +1156,8 @@ private:
     std::vector<bge_overlap_hit> overlap_hits_;
     std::vector<bge_sphere_move> moves_;
     std::vector<bge_sphere_move_result> move_results_;
+    std::vector<bge_sphere_recover> recovers_;
+    std::vector<bge_sphere_recover_result> recover_results_;
 
     template <class Vec3> static bge_sphere_cast MakeCast(const Vec3& o, const Vec3& d, float maxDistance, float radius, uint32_t layerMask)
     {
@@ -1230,6 +1337,33 @@ public:
             return false;
         }
         return GpuMirrors<SceneT>::Of(*lastScene_).MoveSpheres(movers, results);
+    }
+
+    // EXTENSION: sphere penetration and recovery against the same world, under the same call order as Raycast
+    // (include/bge_world.h "Sphere penetration and recovery"); false before the first Update, with every position echoed.
+    template <class Vec3> bool SpherePenetration(const Vec3& center, float radius, uint32_t layerMask, GpuPenetrationHit<Vec3>& outHit) const
+    {
+        return lastScene_ && GpuMirrors<SceneT>::Of(*lastScene_).SpherePenetration(center, radius, layerMask, outHit);
+    }
+    template <class Vec3>
+    bool RecoverSphere(const Vec3& position, float radius, float skin, uint32_t layerMask, GpuSphereRecoverResult<Vec3>& result) const
+    {
+        if (!lastScene_) {
+            result = GpuSphereRecoverResult<Vec3>{};
+            result.position = position;
+            return false;
+        }
+        return GpuMirrors<SceneT>::Of(*lastScene_).RecoverSphere(position, radius, skin, layerMask, result);
+    }
+    template <class Vec3>
+    bool RecoverSpheres(const std::vector<GpuSphereRecover<Vec3>>& spheres, std::vector<GpuSphereRecoverResult<Vec3>>& results) const
+    {
+        if (!lastScene_) {
+            results.assign(spheres.size(), GpuSphereRecoverResult<Vec3>{});
+            for (size_t i = 0; i < spheres.size(); ++i) results[i].position = spheres[i].position;
+            return false;
+        }
+        return GpuMirrors<SceneT>::Of(*lastScene_).RecoverSpheres(spheres, results);
     }
 
     // The debug overlay (src/physics/PhysicsSystem.h:77-82, bound to a key at src/core/Application.cpp:173; the renderer gets

@@ -38,6 +38,19 @@ def make_rays(origins, directions, max_distance=200.0, layer_mask=0xFFFFFFFF):
     return rays
 
 
+def _device_records(records, results, records_name, results_name, record_bytes, result_bytes):
+    """The count of whole records in a device tensor, after checking that the result tensor has room for as many."""
+    nb = records.numel() * records.element_size()
+    if nb % record_bytes:
+        raise ValueError(f"{records_name} holds {nb} bytes, not a whole number of {record_bytes}-byte records")
+    n = nb // record_bytes
+    if results.numel() * results.element_size() < result_bytes * n:
+        raise ValueError(f"{results_name} has room for {results.numel() * results.element_size()} bytes, {result_bytes * n} needed")
+    if not (records.is_cuda and results.is_cuda and records.is_contiguous() and results.is_contiguous()):
+        raise ValueError(f"{records_name} and {results_name} must be contiguous device tensors")
+    return n
+
+
 def _hit_fields(h):
     return {"kind": h["kind"].copy(), "entity": h["entity"].copy(), "fraction": h["fraction"].copy(),
             "distance": h["distance"].copy(), "point": h["point"].copy(), "normal": h["normal"].copy()}
@@ -96,6 +109,30 @@ def make_sphere_moves(positions, displacements, radius=0.5, skin=0.01, probe_dis
         moves[k] = np.broadcast_to(np.asarray(v, np.float32), (len(p),))
     moves["layer_mask"] = np.broadcast_to(np.asarray(layer_mask, np.uint64).astype(np.uint32), (len(p),))
     return moves
+
+
+# sphere penetration and recovery (bge_world_sphere_penetration*, bge_world_sphere_recover*): bge_recover_flags and the records; the
+# penetration query's input is a SPHERE_DTYPE record
+RECOVER_ROUNDS = 4
+RECOVER_INVALID, RECOVER_MOVED, RECOVER_STUCK = 1, 2, 4
+PENETRATION_HIT_DTYPE = np.dtype([("kind", "<u4"), ("entity", "<u4"), ("depth", "<f4"), ("point", "<f4", (3,)), ("normal", "<f4", (3,)),
+                                  ("reserved", "<u4")])
+SPHERE_RECOVER_DTYPE = np.dtype([("position", "<f4", (3,)), ("radius", "<f4"), ("skin", "<f4"), ("layer_mask", "<u4"), ("reserved", "<u4")])
+SPHERE_RECOVER_RESULT_DTYPE = np.dtype([("position", "<f4", (3,)), ("pushed", "<f4", (3,)), ("flags", "<u4"), ("n_pushes", "<u4"),
+                                        ("hit_kind", "<u4"), ("hit_entity", "<u4"), ("hit_normal", "<f4", (3,)), ("hit_depth", "<f4"),
+                                        ("remaining_depth", "<f4"), ("reserved", "<u4")])
+assert PENETRATION_HIT_DTYPE.itemsize == 40 and SPHERE_RECOVER_DTYPE.itemsize == 28 and SPHERE_RECOVER_RESULT_DTYPE.itemsize == 64
+
+
+def make_sphere_recovers(positions, radius=0.5, skin=0.01, layer_mask=0xFFFFFFFF):
+    """bge_sphere_recover records: positions (n, 3); every other argument a scalar or one value per sphere."""
+    p = np.ascontiguousarray(positions, np.float32).reshape(-1, 3)
+    records = np.zeros(len(p), SPHERE_RECOVER_DTYPE)
+    records["position"] = p
+    records["radius"] = np.broadcast_to(np.asarray(radius, np.float32), (len(p),))
+    records["skin"] = np.broadcast_to(np.asarray(skin, np.float32), (len(p),))
+    records["layer_mask"] = np.broadcast_to(np.asarray(layer_mask, np.uint64).astype(np.uint32), (len(p),))
+    return records
 
 
 # debug overlay (bge_world_debug_lines*): bge_debug_flags and the 28-byte line record
@@ -539,6 +576,38 @@ class World:
         if not (moves.is_cuda and results.is_cuda and moves.is_contiguous() and results.is_contiguous()):
             raise ValueError("moves and results must be contiguous device tensors")
         check(lib().bge_world_sphere_move_device(self._h, n, C.c_void_p(moves.data_ptr()), C.c_void_p(results.data_ptr())))
+
+    # -- sphere penetration and recovery (not in the reference; include/bge_world.h states the signed distance and the rule)
+    def sphere_penetration(self, centers, radius, layer_mask=0xFFFFFFFF):
+        """The object that reaches deepest into each sphere: dict of numpy arrays kind, entity, depth, point (n, 3), normal (n, 3);
+        kind RAY_MISS where nothing touches the sphere.  radius and layer_mask take a scalar or one value per sphere."""
+        spheres = make_spheres(centers, radius, layer_mask)
+        hits = np.zeros(len(spheres), PENETRATION_HIT_DTYPE)
+        check(lib().bge_world_sphere_penetration(self._h, len(spheres), _p(spheres), _p(hits)))
+        return {k: hits[k].copy() for k in ("kind", "entity", "depth", "point", "normal")}
+
+    def sphere_penetration_device(self, spheres, hits):
+        """The same between device tensors: spheres holds n bge_sphere records (20 bytes each, e.g. a uint8 tensor made from
+        make_spheres()), hits room for n bge_penetration_hit records (40 bytes each).  Enqueued on the world's stream without
+        synchronisation, as raycast_device()."""
+        n = _device_records(spheres, hits, "spheres", "hits", 20, 40)
+        check(lib().bge_world_sphere_penetration_device(self._h, n, C.c_void_p(spheres.data_ptr()), C.c_void_p(hits.data_ptr())))
+
+    def sphere_recover(self, positions, radius=0.5, skin=0.01, layer_mask=0xFFFFFFFF):
+        """Pushes each sphere out of what it touches or penetrates, in at most RECOVER_ROUNDS pushes: a
+        SPHERE_RECOVER_RESULT_DTYPE array (position, pushed, flags, n_pushes, the last push's hit, remaining_depth).  Every
+        argument but the first takes a scalar or one value per sphere.  Per frame: recover, then sphere_move()."""
+        records = make_sphere_recovers(positions, radius, skin, layer_mask)
+        results = np.zeros(len(records), SPHERE_RECOVER_RESULT_DTYPE)
+        check(lib().bge_world_sphere_recover(self._h, len(records), _p(records), _p(results)))
+        return results
+
+    def sphere_recover_device(self, records, results):
+        """The same between device tensors: records holds n bge_sphere_recover records (28 bytes each, e.g. a uint8 tensor made
+        from make_sphere_recovers()), results room for n bge_sphere_recover_result records (64 bytes each).  Enqueued on the
+        world's stream without synchronisation, as raycast_device()."""
+        n = _device_records(records, results, "records", "results", 28, 64)
+        check(lib().bge_world_sphere_recover_device(self._h, n, C.c_void_p(records.data_ptr()), C.c_void_p(results.data_ptr())))
 
     # -- debug overlay (PhysicsSystem::GetDebugLines; include/bge_world.h states what is drawn and in which order)
     def debug_lines(self, flags=DEBUG_ALL, region=None):

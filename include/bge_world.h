@@ -540,8 +540,9 @@ BGE_API int bge_world_overlap_sphere(bge_world* world, uint64_t n, const bge_sph
  *             16 skins of path, where the gap kept is then smaller than skin, never negative.  Choose skin well above the
  *             binary32 spacing at the scene's extent (1e-3 .. 1e-2 for a scene of a few hundred units).
  *   Not done  capsule or box movers; stepping up (composed by the caller from an up move, a forward move and a down move);
- *             recovery of a sphere that starts in penetration (the cast does not see what it starts in: bge_world_overlap_sphere
- *             finds those); moving platforms; the result is not written into any Transform.
+ *             moving platforms; the result is not written into any Transform.  A sphere that STARTS touching or inside a shape is
+ *             not this query's business (the cast does not see what it starts in): bge_world_sphere_recover below pushes it
+ *             out first, so the order per frame is recover, then move.
  *   The query changes no world state.  n = 0 is a no-op.  A NULL argument with n > 0 is BGE_ERR_INVALID.  Before
  *   bge_world_set_topology it returns what bge_world_sphere_cast returns there.
  *   bge_world_sphere_move         results[i] for moves[i].  Synchronises the world's stream.
@@ -577,6 +578,90 @@ typedef struct bge_sphere_move_result {
 } bge_sphere_move_result; /* 80 bytes */
 BGE_API int bge_world_sphere_move(bge_world* world, uint64_t n, const bge_sphere_move* moves, bge_sphere_move_result* results);
 BGE_API int bge_world_sphere_move_device(bge_world* world, uint64_t n, const void* moves_device, void* results_device);
+
+/*
+ * Sphere penetration and recovery: by how much and in which direction a sphere at rest reaches into the world
+ * (bge_world_sphere_penetration), and the iteration that pushes it out (bge_world_sphere_recover) — what a mover needs when a crate
+ * fell onto it, a platform moved into it or it was teleported, since bge_world_sphere_move does not see what it starts in.  NOT in
+ * the reference's PhysicsSystem (Bullet's btKinematicCharacterController::recoverFromPenetration plays this part there).  The rules
+ * below are the specification.  All arithmetic is binary32 with one rounding per operation; j runs over x, y, z.
+ *   Sees      Objects, poses, Filter, object codes, tie order and Call order are those of bge_world_sphere_cast, word for word:
+ *             rigid bodies at the pose of the last physics tick, live posed trigger ghosts, the plane when it is on; an object is
+ *             a candidate iff (objGroup & layer_mask) != 0 && objMask != 0.
+ *   Signed distance sd(c, S) and outward direction n(c, S).  q is c in the shape's frame, obtained as for dist(c, S) above.
+ *             Box (the sharp box of the half extents with margin, h):
+ *               if any |q_j| > h_j (outside): sd = dist(c, S), the value bge_world_overlap_sphere reports, bit for bit;
+ *                 n = (q - closest point of the box) / sd, taken through the pose.
+ *               otherwise (inside or on the surface): sd = -min_j (h_j - |q_j|); n is the box axis j of that minimum taken through
+ *                 the pose, ties to the lowest j, with the sign of q_j (q_j == 0, either zero, counts as +).
+ *             Capsule (radius R, Y segment): a = |q - closest point of the segment|, sd = a - R, n = (q - closest) / a through the
+ *               pose; when !(a > 0), n is the capsule's local +x axis through the pose (and sd = -R).
+ *             Plane (two-sided, as the casts treat it): sd = |c.y|; n = (0, 1, 0) when c.y >= 0 (so -0 goes up), otherwise
+ *               (0, -1, 0): a centre below the plane is pushed further down.  The plane has no inside.
+ *   Penetration   object S penetrates the sphere (center, radius) iff sd(center, S) <= radius: exactly the objects
+ *             bge_world_overlap_sphere reports, whose distance is max(sd, 0).  depth = radius - sd (one subtraction; a zero depth
+ *             is +0), so depth >= 0.  The answer is the object of the LARGEST depth, ties to the lowest object code: kind and
+ *             entity as bge_overlap_hit, normal = n(center, S), point_j = center_j - normal_j * sd (on the surface).
+ *   No hit    the conditions of bge_world_overlap_sphere: a non-finite input, radius < 0, layer_mask == 0, or no object
+ *             penetrating.  The miss record has kind = BGE_RAY_MISS, entity = BGE_RAY_NO_ENTITY and every other word 0.
+ *   Recover   A record is valid iff every float of it is finite, radius >= 0, skin > 0 and layer_mask != 0.  An invalid record
+ *             returns flags = BGE_RECOVER_INVALID, position echoed, the kind BGE_RAY_MISS, the entity BGE_RAY_NO_ENTITY,
+ *             everything else 0.
+ *             State   p = position, not finished, n_pushes = 0.
+ *             Rounds  for each of the BGE_RECOVER_ROUNDS rounds, unless finished:
+ *                     1. Take the penetration query {p, radius, layer_mask}.
+ *                     2. On a miss: finished.
+ *                     3. On a hit with depth e and normal n:  t = e + skin;  p_j = p_j + n_j * t;  n_pushes += 1;  hit_kind,
+ *                        hit_entity, hit_normal and hit_depth take the hit's kind, entity, normal and depth.
+ *             After   if not finished, one more penetration query at p: a hit sets BGE_RECOVER_STUCK and remaining_depth is its
+ *                     depth (hit_* stay those of the last push).
+ *             Result  pushed_j = p_j - position_j; BGE_RECOVER_MOVED iff n_pushes > 0; position = p.
+ *             A sphere clear of everything comes back unchanged with flags 0.  After one push against a flat surface the gap is
+ *             skin, so the cast sees that surface again.  A wedge or a slot narrower than the sphere may end STUCK; the result
+ *             is deterministic either way.  (Bullet's character controller also recovers in at most 4 iterations.)
+ *   The queries change no world state.  n = 0 is a no-op.  A NULL argument with n > 0 is BGE_ERR_INVALID.  Before
+ *   bge_world_set_topology they return what bge_world_overlap_sphere returns there.
+ *   bge_world_sphere_penetration         hits[i] for spheres[i].  Synchronises the world's stream.
+ *   bge_world_sphere_penetration_device  device pointers: spheres_device = bge_sphere[n], hits_device = bge_penetration_hit[n],
+ *                                        both 4-byte aligned (a misaligned pointer is BGE_ERR_INVALID); enqueued on the world's
+ *                                        stream, no synchronisation.
+ *   bge_world_sphere_recover             results[i] for records[i].  Synchronises the world's stream.
+ *   bge_world_sphere_recover_device      device pointers: records_device = bge_sphere_recover[n], results_device =
+ *                                        bge_sphere_recover_result[n], aligned, enqueued and not synchronised likewise.
+ */
+#define BGE_RECOVER_ROUNDS 4
+typedef struct bge_penetration_hit {
+    uint32_t kind;     /* bge_ray_kind: BGE_RAY_BODY, BGE_RAY_TRIGGER or BGE_RAY_GROUND; BGE_RAY_MISS when nothing penetrates */
+    uint32_t entity;   /* entity index of the body or trigger; BGE_RAY_NO_ENTITY for the plane and for a miss */
+    float depth;       /* radius - sd, >= 0 */
+    float point[3];    /* center - normal * sd: on the surface */
+    float normal[3];   /* n(center, S), unit: the way out */
+    uint32_t reserved; /* 0 */
+} bge_penetration_hit; /* 40 bytes */
+typedef struct bge_sphere_recover {
+    float position[3];
+    float radius;
+    float skin;        /* > 0: the gap left to what it was pushed out of */
+    uint32_t layer_mask;
+    uint32_t reserved; /* 0 */
+} bge_sphere_recover; /* 28 bytes */
+enum bge_recover_flags { BGE_RECOVER_INVALID = 1u, BGE_RECOVER_MOVED = 2u, BGE_RECOVER_STUCK = 4u };
+typedef struct bge_sphere_recover_result {
+    float position[3];     /* centre after the recovery */
+    float pushed[3];       /* position after - position before */
+    uint32_t flags;        /* bge_recover_flags */
+    uint32_t n_pushes;     /* 0 .. BGE_RECOVER_ROUNDS */
+    uint32_t hit_kind;     /* the last push: bge_ray_kind; BGE_RAY_MISS / BGE_RAY_NO_ENTITY / 0 if none */
+    uint32_t hit_entity;
+    float hit_normal[3];
+    float hit_depth;
+    float remaining_depth; /* with BGE_RECOVER_STUCK: the depth still found after the last round; otherwise 0 */
+    uint32_t reserved;     /* 0 */
+} bge_sphere_recover_result; /* 64 bytes */
+BGE_API int bge_world_sphere_penetration(bge_world* world, uint64_t n, const bge_sphere* spheres, bge_penetration_hit* hits);
+BGE_API int bge_world_sphere_penetration_device(bge_world* world, uint64_t n, const void* spheres_device, void* hits_device);
+BGE_API int bge_world_sphere_recover(bge_world* world, uint64_t n, const bge_sphere_recover* records, bge_sphere_recover_result* results);
+BGE_API int bge_world_sphere_recover_device(bge_world* world, uint64_t n, const void* records_device, void* results_device);
 
 /*
  * The physics debug overlay: what PhysicsSystem::GetDebugLines hands to the renderer while the overlay is on
