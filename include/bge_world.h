@@ -410,6 +410,15 @@ BGE_API int bge_world_trigger_query_stats(bge_world* world, uint32_t* through_gr
  *   Call order  the query reads the device state as it is: call it after a physics tick and before new poses are uploaded, as
  *             Application::Update does (src/core/Application.cpp:256-281).  A Transform uploaded between the tick and the query
  *             moves the body's position for the query (its orientation stays the one the tick left).
+ *   Range     everything is binary32.  An answer is the exact answer of a world whose shapes are moved by at most
+ *               B = 2e-6 * (|from|_1 + |to - from|_1 + |body origin|_1 + the body's bounding radius [+ the cast's radius]),
+ *             about 4e-6 of the distance from the world's origin for a query from nearby: 0.005 at 1,000 units, 0.04 at 10,000,
+ *             0.4 at 100,000 (one binary32 spacing there is 0.008).  A feature thinner than B (a body, a gap, an offset from a
+ *             face) is not resolved: a query may report or miss it either way.  Supported, and tested, are bodies whose smallest
+ *             half extent or radius is at least 30 B, that is 1.2e-4 of |origin|_1: 0.12 at 1,000 units, 1.2 at 10,000, 12 at
+ *             100,000.  Smaller bodies that far out are still found by overlaps and penetrations, whose distances are good to
+ *             the same B; for rays and casts at them keep the world within that range of its origin, or move the origin.
+ *             This holds for the sphere queries, the sphere moves and the recovery below as well.
  *   bge_world_raycast         hits[i] for rays[i]; a miss is kind BGE_RAY_MISS, entity BGE_RAY_NO_ENTITY, all floats 0.
  *                             Synchronises the world's stream.
  *   bge_world_raycast_all     offsets[0..n_rays] (offsets[i + 1] - offsets[i] hits of ray i at hits[offsets[i]..]) and *total,

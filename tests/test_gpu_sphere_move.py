@@ -108,6 +108,9 @@ def test_hand_worked_moves_on_the_device(case):
         w.close()
 
 
+NEVER_INSIDE_MARGIN = np.float32(1e-3)  # by how much a mover that started clear may end inside something
+
+
 def test_never_inside_and_never_backwards(shared):
     """A mover that starts clear of everything by radius + skin ends clear of everything by radius - 1e-3: the cast is exact, so
     the path it took is free; 1e-3 is over a hundred binary32 spacings at the scene's extent of 64.  And no move ends behind its
@@ -117,7 +120,7 @@ def test_never_inside_and_never_backwards(shared):
     m = moves[ok]
     start = shared.w.overlap_sphere(m["position"], m["radius"] + m["skin"], m["layer_mask"])
     clear = np.diff(start["offsets"].astype(np.int64)) == 0
-    end = shared.w.overlap_sphere(got["position"][ok][clear], m["radius"][clear] - np.float32(1e-3), m["layer_mask"][clear])
+    end = shared.w.overlap_sphere(got["position"][ok][clear], m["radius"][clear] - NEVER_INSIDE_MARGIN, m["layer_mask"][clear])
     inside = np.nonzero(np.diff(end["offsets"].astype(np.int64)) != 0)[0]
     print(f"{clear.sum()} of {len(ok)} valid movers start clear; {len(inside)} end inside something")
     assert clear.sum() >= 100

@@ -221,7 +221,8 @@ class World64:
 
     def _derive(self):
         self.code = np.where(self.kind == RAY_BODY, self.entity, CODE_GHOST | self.entity)
-        # bounding spheres: a cull before the exact tests (shapes grown by at most 1e-3 stay inside)
+        # bounding spheres: a cull before the exact tests (shapes grown by at most 1e-3 stay inside).  test_query_edges_cpu.py
+        # edits dims and calls this again, so the cull radius must stay a function of dims alone.
         self.radius = np.where(self.capsule, self.dims[:, 0] + self.dims[:, 1], np.linalg.norm(self.dims, axis=1)) + 2e-3
         self._min_dim = None
 
