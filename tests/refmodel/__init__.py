@@ -1,0 +1,15 @@
+"""The float64 reference model of the queries, the cases a CPU suite and its GPU twin share, and the GPU harness: what the tests
+import instead of each other.  A test file is never a library.
+
+Layers, each importing downward only:
+  records, tolerances                                   numpy alone
+  rays -> spheres -> moves -> recover -> sandwich       the model: nothing of the product package
+  visible, draw_batches, debug_lines                    the render references
+  *_cases                                               seeded generators and hand-worked tables; the package for dtypes and make_* only
+  device                                                the only module that opens a World; no *_cpu test reaches it
+"""
+import pytest
+
+# the checkers' bare asserts keep pytest's introspection outside test_*.py: registered before any submodule is imported
+pytest.register_assert_rewrite("refmodel.device", "refmodel.draw_batches", "refmodel.edge_cases", "refmodel.move_cases", "refmodel.recover_cases",
+                               "refmodel.sandwich", "refmodel.sphere_cases", "refmodel.visible")

@@ -1,0 +1,14 @@
+"""The tolerances of the comparisons between the device and the float64 reference: the one place they are stated.
+
+The reference takes the device's own binary32 poses (download_pose / download_bodies) and binary32 query inputs, so what differs
+is the kernel's binary32 arithmetic — a rotation into the body frame, one slab division or a quadratic solved about the point of
+closest approach.  Bounds: fraction 1e-5 relative + 1e-6 absolute; point 2e-5 per unit of coordinate magnitude; normal 1e-4 per
+component plus 2e-6 x (|origin|_1 + |direction * max_distance|_1) / (the hit shape's smallest half extent or radius) — the entry
+point is only known to a few binary32 ulp of the ray's magnitudes, and the normal of a small capsule turns by that error over its
+radius (measured: 1.3e-3 for a ray from ~700 units at a small capsule)."""
+from __future__ import annotations
+
+import numpy as np
+
+F_REL, F_ABS, P_REL, N_ABS, N_SCALE = 1e-5, 1e-6, 2e-5, 1e-4, 2e-6
+NEVER_INSIDE_MARGIN = np.float32(1e-3)  # by how much a mover that started clear may end inside something

@@ -1,11 +1,8 @@
-"""Draw batches (include/bge_world.h bge_world_draw_batches*): the grouping restated in numpy, hand-worked cases, the exported
+"""Draw batches (include/bge_world.h bge_world_draw_batches*): the grouping restated in numpy (refmodel/draw_batches.py), hand-worked cases, the exported
 symbols, the C99 view of the header and the C++20 compile of the adapter's members.
 
 The GPU tests (test_gpu_draw_batches.py) compare the device's batches and record order with draw_batches_ref() exactly."""
 from __future__ import annotations
-
-import os
-import subprocess
 
 import numpy as np
 
@@ -13,24 +10,8 @@ import banggameengine_amd as B
 from banggameengine_amd import _capi
 from banggameengine_amd import world as W
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NO_KEY = 0xFFFFFFFF
-
-
-def draw_batches_ref(visible_mask, keys, n_keys):
-    """batches (n_keys, 2) uint32 = (first_instance, instance_count) per key, and the entity indices in record order: the
-    visible entities whose key is below n_keys, sorted by (key, entity index)."""
-    visible_mask = np.asarray(visible_mask, bool)
-    keys = np.asarray(keys, np.uint32)
-    assert visible_mask.shape == keys.shape and keys.ndim == 1
-    entity = np.nonzero(visible_mask & (keys < np.uint32(min(n_keys, 2 ** 32 - 1))) & (n_keys > 0))[0].astype(np.uint32)
-    key = keys[entity]
-    order = np.lexsort((entity, key))
-    entity, key = entity[order], key[order]
-    count = np.bincount(key, minlength=n_keys).astype(np.uint64)
-    first = np.concatenate([[0], np.cumsum(count)[:-1]]).astype(np.uint64) if n_keys else count
-    batches = np.stack([first, count], axis=1).astype(np.uint32).reshape(n_keys, 2)
-    return batches, entity
+from abi import build_and_run_c99, compile_reference_shapes
+from refmodel.draw_batches import NO_KEY, draw_batches_ref
 
 
 def _check(mask, keys, n_keys, batches, entities):
@@ -79,16 +60,8 @@ def test_exported_symbols_are_present_and_declared():
 
 
 def test_c99_view_of_the_header(tmp_path):
-    exe = str(tmp_path / "abi_check_batches")
-    lib = os.path.join(ROOT, "banggameengine_amd")
-    subprocess.check_call(["gcc", "-std=c99", "-pedantic", "-Wall", "-Wextra", "-Werror", "-o", exe,
-                           os.path.join(ROOT, "tests", "cpp", "abi_check_batches.c"), f"-L{lib}", "-lbge_world", f"-Wl,-rpath,{lib}",
-                           "-Wl,-rpath,/opt/rocm/lib"])
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "batches abi ok" in r.stdout
+    build_and_run_c99(tmp_path, "abi_check_batches.c", "batches abi ok")
 
 
 def test_adapter_members_compile_against_reference_shapes(tmp_path):
-    subprocess.check_call(["g++", "-std=c++20", "-O0", "-Wall", "-Wextra", "-Werror", "-Wno-unused-parameter", "-c",
-                           os.path.join(ROOT, "tests", "cpp", "batches_reference_shapes.cpp"), "-o", str(tmp_path / "batches_reference_shapes.o")])
+    compile_reference_shapes(tmp_path, "batches_reference_shapes.cpp")

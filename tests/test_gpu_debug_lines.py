@@ -1,5 +1,5 @@
 """The debug overlay on the device (include/bge_world.h bge_world_debug_lines*) against the float64 reference of
-test_debug_lines_cpu.py.
+refmodel/debug_lines.py.
 
 Tolerance: the reference takes the device's own binary32 poses (download_pose / download_bodies), ghost poses as
 recorded before the tick and the dimensions the library holds, so what differs is the kernel's binary32 arithmetic — a rotation
@@ -19,9 +19,10 @@ import pytest
 import banggameengine_amd as B
 from banggameengine_amd import world as W
 
-from test_debug_lines_cpu import (ALL, COL_CONTACT, CONTACTS, DYNAMIC, GHOST, KINEMATIC, SHAPES, STATIC, Obj, debug_lines_ref, in_region)
-from test_gpu_raycast import FLAGS, P_REL, Scene
-from test_raycast_cpu import quat_from_euler
+from refmodel.tolerances import P_REL
+from refmodel.rays import quat_from_euler
+from refmodel.debug_lines import COL_CONTACT, CONTACTS, DYNAMIC, GHOST, KINEMATIC, SHAPES, STATIC, Obj, basis_of, debug_lines_ref, in_region
+from refmodel.device import FLAGS, Scene
 
 pytestmark = pytest.mark.gpu
 
@@ -201,7 +202,6 @@ def _contact_reference(w, n):
     """(pointOnB, normal) from the three contact downloads and the device's poses."""
     pos, _ = w.download_pose()
     quat = w.download_bodies()["quat"].astype(np.float64)
-    from test_debug_lines_cpu import basis_of
     out = []
     npl, ppl = w.download_contacts()
     for e in range(n):

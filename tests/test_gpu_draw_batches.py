@@ -1,4 +1,4 @@
-"""Draw batches on the device (include/bge_world.h bge_world_draw_batches*) against draw_batches_ref() of test_draw_batches_cpu.py.
+"""Draw batches on the device (include/bge_world.h bge_world_draw_batches*) against draw_batches_ref() of refmodel/draw_batches.py.
 
 Everything is integer work on top of the visibility rule, so every comparison is exact: the expected record order is
 draw_batches_ref() fed visible_ref32() of the DEVICE's own downloaded world matrices and the uploaded keys; batches, total,
@@ -20,8 +20,9 @@ import banggameengine_amd as B
 from banggameengine_amd import world as W
 from banggameengine_amd._capi import lib
 
-from test_draw_batches_cpu import NO_KEY, draw_batches_ref
-from test_visible_cpu import F, make_scene, narrow_view, visible_ref32, wide_view
+from refmodel.visible import F, visible_ref32
+from refmodel.draw_batches import NO_KEY, draw_batches_ref
+from refmodel.render_cases import make_scene, narrow_view, wide_view
 
 pytestmark = pytest.mark.gpu
 

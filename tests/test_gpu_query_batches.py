@@ -18,7 +18,7 @@ import pytest
 import banggameengine_amd as B
 from banggameengine_amd import world as W
 
-from test_raycast_cpu import RAY_BODY, RAY_GROUND, RAY_MISS, RAY_TRIGGER
+from refmodel.rays import RAY_BODY, RAY_GROUND, RAY_MISS, RAY_TRIGGER
 
 pytestmark = pytest.mark.gpu
 

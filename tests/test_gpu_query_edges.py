@@ -1,5 +1,5 @@
 """Edge geometry of the query kernels on the device (csrc/bge_query.hip, bge_ray_device.hpp, bge_sphere_device.hpp): the input
-families of test_query_edges_cpu.py — the outer shell of the bounding spheres, worlds 1e3 .. 1e5 from the origin, sizes 0.01 and
+families of refmodel/edge_cases.py — the outer shell of the bounding spheres, worlds 1e3 .. 1e5 from the origin, sizes 0.01 and
 500 in one world, grazing incidence and the seams of the rounded box, exact ties — asked of the device and checked by that file's
 sandwich: the answer must be the exact answer of a world whose shapes moved by at most B, a few binary32
 ulp of the query's and the body's magnitudes.  Overlaps and penetrations go through the existing forward checks at their existing
@@ -16,21 +16,19 @@ import pytest
 import banggameengine_amd as B
 from banggameengine_amd import world as W
 
-from test_gpu_query_layouts import ask
-from test_gpu_raycast import FLAGS, Scene
-from test_gpu_sphere_move import NEVER_INSIDE_MARGIN, device_caster, move
-from test_gpu_sphere_queries import check_overlaps
-from test_query_edges_cpu import (ALL, FAMILIES, KINDS, N_BODIES, TIE_BODIES, TIE_SPHERE, Sandwich, Spec, check_caps,
-                                  check_penetrations, check_ties, code_of, family_queries, overlap_counts, sphere_records)
-from test_raycast_cpu import RAY_BODY, RAY_MISS
-from test_sphere_move_cpu import move_ref
-from test_sphere_queries_cpu import SphereRef
+from refmodel.tolerances import NEVER_INSIDE_MARGIN
+from refmodel.rays import ALL, RAY_BODY, RAY_MISS
+from refmodel.spheres import SphereRef
+from refmodel.moves import move_ref
+from refmodel.sandwich import Sandwich, check_caps, check_penetrations, code_of
+from refmodel.edge_cases import FAMILIES, KINDS, N_BODIES, TIE_BODIES, TIE_SPHERE, Spec, check_ties, family_queries, overlap_counts, sphere_records
+from refmodel.device import FLAGS, Scene, ask, check_overlaps, device_caster, move
 
 pytestmark = pytest.mark.gpu
 
 
 class EdgeScene(Scene):
-    """test_gpu_raycast.Scene holding a family's world instead of its random one."""
+    """refmodel.device.Scene holding a family's world instead of its random one."""
 
     def __init__(self, spec):
         self.n = N_BODIES
@@ -128,7 +126,7 @@ def test_family_on_the_device(families, name, kind):
 
 # the far-1e3 world: movers beside its bodies.  The skin follows the header's rule for that extent ("well above the binary32
 # spacing at the scene's extent (1e-3 .. 1e-2 for a scene of a few hundred units)"): 1e-2 at a few hundred units is some 330
-# spacings; beyond 1,024 a spacing is 2^-13, so 0.04.  The never-inside margin is that of test_gpu_sphere_move.py, unchanged:
+# spacings; beyond 1,024 a spacing is 2^-13, so 0.04.  The never-inside margin is that of refmodel/tolerances.py, unchanged:
 # 8 spacings here.
 FAR_SKIN = 0.04
 FAR_EXTENT = 1024.0

@@ -1,14 +1,9 @@
-"""Ray queries on the device (include/bge_world.h bge_world_raycast*) against the float64 reference of test_raycast_cpu.py.
+"""Ray queries on the device (include/bge_world.h bge_world_raycast*) against the float64 reference of refmodel/rays.py.
 
-Tolerances: the reference takes the device's own binary32 poses (download_pose / download_bodies) and binary32
-ray inputs, so what differs is the kernel's binary32 arithmetic — a rotation into the body frame, one slab division or a
-quadratic solved about the point of closest approach.  Bounds: fraction 1e-5 relative + 1e-6 absolute; point 2e-5 per unit of
-coordinate magnitude; normal 1e-4 per component plus 2e-6 x (|origin|_1 + |direction * max_distance|_1) / (the hit shape's
-smallest half extent or radius) — the entry point is only known to a few binary32 ulp of the ray's magnitudes, and the normal
-of a small capsule turns by that error over its radius (measured: 1.3e-3 for a ray from ~700 units at a small capsule)."""
+The tolerances and the reasoning behind them are stated in refmodel/tolerances.py; Scene and the checkers that apply
+them are refmodel/device.py's."""
 from __future__ import annotations
 
-import math
 import os
 import subprocess
 
@@ -18,132 +13,13 @@ import pytest
 import banggameengine_amd as B
 from banggameengine_amd import world as W
 
-from test_raycast_cpu import RAY_BODY, RAY_GROUND, RAY_MISS, RAY_TRIGGER, NO_ENTITY, Obj, World64, quat_from_euler, random_rays
+from refmodel.rays import NO_ENTITY, RAY_BODY, RAY_GROUND, RAY_MISS, RAY_TRIGGER
+from refmodel.ray_cases import random_rays
+from refmodel.device import FLAGS, Scene, check_against_reference, check_all_hits
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-F_REL, F_ABS, P_REL, N_ABS, N_SCALE = 1e-5, 1e-6, 2e-5, 1e-4, 2e-6
-FLAGS = W.TICK_ALL | W.TICK_BROADPHASE
-
-
-class Scene:
-    """A world plus what the reference needs to rebuild its objects."""
-
-    def __init__(self, n, rng, n_triggers=0, spread=30.0, plane=True, parent=None, has_transform=None):
-        self.n = n
-        self.w = B.World(device=0)
-        self.w.set_topology(np.full(n, W.NO_PARENT, np.uint32) if parent is None else parent, has_transform)
-        pos = np.stack([rng.uniform(-spread, spread, n), rng.uniform(0.3, 6.0, n), rng.uniform(-spread, spread, n)], 1)
-        self.w.upload_trs(pos, rng.uniform(-math.pi, math.pi, (n, 3)), np.ones((n, 3)))
-        self.type = rng.choice([W.BODY_STATIC, W.BODY_DYNAMIC, W.BODY_KINEMATIC], n, p=[0.3, 0.5, 0.2]).astype(np.uint8)
-        self.trig = np.zeros(0, np.int64)
-        if n_triggers:
-            self.trig = rng.choice(n, n_triggers, replace=False)
-            self.type[self.trig] = W.BODY_NONE
-        self.shape = rng.integers(0, 2, n).astype(np.uint8)
-        self.size = rng.uniform(0.1, 1.5, (n, 3)).astype(np.float32)
-        self.layer = (1 << rng.integers(0, 4, n)).astype(np.uint32)
-        self.mask = rng.choice(np.array([0xFFFFFFFF, 0xFFFFFFFF, 0xFFFFFFFF, 0x3, 0], np.uint32), n)
-        self.w.upload_bodies(self.type, None, self.shape, self.size, self.layer, self.mask)
-        self.plane = plane
-        self.w.set_ground_plane(plane)
-        self.t_active = np.ones(len(self.trig), np.uint8)
-        self.t_oneshot = np.zeros(len(self.trig), np.uint8)
-        if len(self.trig):
-            self.upload_triggers()
-
-    def upload_triggers(self):
-        self.w.upload_triggers(self.trig, self.shape[self.trig], self.size[self.trig], self.layer[self.trig], self.mask[self.trig],
-                               self.t_oneshot, self.t_active)
-
-    def tick(self, k=1):
-        for _ in range(k):
-            self.ghost_pose = self.w.download_pose()  # ghosts are posed from the Transforms as they are before the step
-            self.w.tick(flags=FLAGS)
-
-    def dims(self):
-        """Per entity: the box's half extents with margin or the capsule's (radius, half height, radius), as the library holds them."""
-        h = np.maximum(self.size, np.float32(0.01))
-        m0 = np.float32(0.04)
-        safe = (np.float32(0.1) * h.min(axis=1))[:, None]
-        inner = h - m0
-        box = np.where(safe < m0, ((inner + m0) - safe) + safe, inner + m0).astype(np.float32)
-        cap = np.stack([h[:, 0], np.maximum(self.size[:, 1], np.float32(0)), h[:, 0]], 1)
-        return np.where(self.shape[:, None] == 1, cap, box)
-
-    def bodies_in_world(self):
-        return np.nonzero(self.type != W.BODY_NONE)[0]
-
-    def ghosts_in_world(self):
-        return self.trig[self.t_active.astype(bool)]
-
-    def objects(self):
-        """The reference's world: every body at the pose the device holds, every active ghost at its posed pose."""
-        pos, _ = self.w.download_pose()
-        quat = self.w.download_bodies()["quat"].astype(np.float64)
-        dims = self.dims()
-        live, ghosts = self.bodies_in_world(), self.ghosts_in_world()
-        gp, ge = self.ghost_pose
-        gq = np.array([quat_from_euler(ge[e].astype(np.float64)) for e in ghosts]).reshape(-1, 4)
-        ent = np.concatenate([live, ghosts])
-        kind = np.concatenate([np.full(len(live), RAY_BODY), np.full(len(ghosts), RAY_TRIGGER)])
-        return World64.from_arrays(kind, ent, self.layer[ent], self.mask[ent], self.shape[ent] == 1, dims[ent],
-                                   np.concatenate([pos[live], gp[ghosts]]), np.concatenate([quat[live], gq]), self.plane)
-
-    def close(self):
-        self.w.close()
-
-
-def check_against_reference(ref, o, d, md, mask, got, need_hits=50):
-    checked = hits = 0
-    err_f = err_p = err_n = 0.0
-    for i in range(len(o)):
-        if not ref.clear(o[i], d[i], md[i], mask[i]):
-            continue
-        checked += 1
-        want = ref.cast_all(o[i], d[i], md[i], mask[i])
-        if not want:
-            assert got["kind"][i] == RAY_MISS and got["entity"][i] == NO_ENTITY, f"ray {i}: hit where the reference misses"
-            continue
-        f, code, kind, ent, n = want[0]
-        assert (got["kind"][i], got["entity"][i]) == (kind, ent), f"ray {i}: {got['kind'][i]}/{got['entity'][i]} != {kind}/{ent}"
-        hits += 1
-        gf = float(got["fraction"][i])
-        assert abs(gf - f) <= F_REL * f + F_ABS, f"ray {i}: fraction {gf} vs {f}"
-        p = o[i].astype(np.float64) + (d[i] * md[i]).astype(np.float64) * f
-        assert np.all(np.abs(got["point"][i] - p) <= P_REL * (1.0 + np.abs(p))), f"ray {i}: point {got['point'][i]} vs {p}"
-        # the entry point carries binary32 rounding of the ray's magnitudes; the normal turns by that over the shape's size
-        n_tol = N_ABS + N_SCALE * float(np.abs(o[i]).sum() + np.abs(d[i] * md[i]).sum()) / ref.min_dim(code)
-        assert np.all(np.abs(got["normal"][i] - n) <= n_tol), f"ray {i}: normal {got['normal'][i]} vs {n}"
-        assert got["distance"][i] == np.float32(got["fraction"][i] * md[i])
-        err_f = max(err_f, abs(gf - f) / max(f, 1e-6))
-        err_p = max(err_p, float(np.max(np.abs(got["point"][i] - p) / (1.0 + np.abs(p)))))
-        err_n = max(err_n, float(np.max(np.abs(got["normal"][i] - n))))
-    assert checked >= 0.5 * len(o) and hits >= need_hits, (checked, hits)
-    print(f"checked {checked} of {len(o)} rays, {hits} hits; max rel err f {err_f:.2e}, point {err_p:.2e}, normal {err_n:.2e}")
-    return hits
-
-
-def check_all_hits(ref, o, d, md, mask, got, allh):
-    """All hits: per-ray sets in (f, code) order, offsets, and the first one is the closest hit (got: the closest hits of the
-    same rays, or of a batch these rays begin)."""
-    off = allh["offsets"].astype(np.int64)
-    assert off[0] == 0 and np.all(np.diff(off) >= 0) and off[-1] == len(allh["kind"])
-    for i in range(len(o)):
-        want = ref.cast_all(o[i], d[i], md[i], mask[i])
-        seg = slice(off[i], off[i + 1])
-        if ref.clear(o[i], d[i], md[i], mask[i]):
-            got_set = sorted(zip(allh["kind"][seg].tolist(), allh["entity"][seg].tolist()))
-            assert got_set == sorted((h[2], h[3]) for h in want), f"ray {i}"
-        fr = allh["fraction"][seg]
-        assert np.all(np.diff(fr) >= 0)
-        if off[i + 1] > off[i]:
-            for k in ("kind", "entity", "fraction", "distance"):
-                assert allh[k][off[i]] == got[k][i], (i, k)
-            assert np.array_equal(allh["point"][off[i]], got["point"][i]) and np.array_equal(allh["normal"][off[i]], got["normal"][i])
-        else:
-            assert got["kind"][i] == RAY_MISS
 
 
 @pytest.mark.parametrize("n,seed", [(2000, 1), (20000, 2)])

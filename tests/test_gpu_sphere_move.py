@@ -1,6 +1,6 @@
 """Sphere moves on the device (include/bge_world.h "Sphere moves", bge_world_sphere_move*).
 
-The reference is move_ref of test_sphere_move_cpu.py — the header's rule in numpy float32 scalars — with World.sphere_cast on the
+The reference is move_ref of refmodel/moves.py — the header's rule in numpy float32 scalars — with World.sphere_cast on the
 same world as its caster: the device runs the same casts and the same binary32 arithmetic between them, so the 80-byte records
 must be equal byte for byte.  The batches, the scene and the coverage floors are those test_sphere_move_cpu.py checks on the
 float64 shape reference alone.  The hand-worked cases carry the numbers derived there, on real shapes, to 1e-5."""
@@ -15,29 +15,17 @@ import pytest
 import banggameengine_amd as B
 from banggameengine_amd import world as W
 
-from test_gpu_raycast import FLAGS, Scene
-from test_sphere_move_cpu import (ALL, BATCHES, HAND_MOVES, MOVER_SEED, SCENE_N, SCENE_SEED, check_coverage, check_hand_move, check_invalid,
-                                  coverage, ghost_positions, hand_mover, invalid_movers, move_ref, mover_batch)
-from test_sphere_queries_cpu import scene_world64
+from refmodel.tolerances import NEVER_INSIDE_MARGIN
+from refmodel.rays import ALL
+from refmodel.moves import move_ref
+from refmodel.sphere_cases import scene_world64
+from refmodel.move_cases import (BATCHES, HAND_MOVES, MOVER_SEED, SCENE_N, SCENE_SEED, check_coverage, check_hand_move, check_invalid, coverage,
+                                 ghost_positions, hand_mover, invalid_movers, mover_batch)
+from refmodel.device import FLAGS, Scene, device_caster, move
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FIELDS = ("position", "displacement", "radius", "skin", "probe_distance", "min_ground_ny", "layer_mask")
-
-
-def device_caster(w):
-    def cast_fn(casts):
-        h = w.sphere_cast(casts["origin"], casts["direction"], casts["max_distance"], casts["radius"], casts["layer_mask"])
-        hits = np.zeros(len(casts), W.RAY_HIT_DTYPE)
-        for k, v in h.items():
-            hits[k] = v
-        return hits
-    return cast_fn
-
-
-def move(w, moves):
-    return w.sphere_move(*(moves[k] for k in FIELDS))
 
 
 class Shared:
@@ -106,9 +94,6 @@ def test_hand_worked_moves_on_the_device(case):
         assert got[0].tobytes() == move_ref(device_caster(w), moves)[0].tobytes()
     finally:
         w.close()
-
-
-NEVER_INSIDE_MARGIN = np.float32(1e-3)  # by how much a mover that started clear may end inside something
 
 
 def test_never_inside_and_never_backwards(shared):

@@ -1,7 +1,7 @@
 """Sphere casts and sphere overlaps on the device (include/bge_world.h bge_world_sphere_cast*, bge_world_overlap_sphere) against the
-float64 reference of test_sphere_queries_cpu.py (the rounded box as a union of fifteen parts; not the kernel's method).
+float64 reference of refmodel/spheres.py (the rounded box as a union of fifteen parts; not the kernel's method).
 
-Tolerances are the ray tests' constants, imported from test_gpu_raycast.py: the arithmetic is of the same kind (a
+Tolerances are the ray tests' constants, imported from refmodel/tolerances.py: the arithmetic is of the same kind (a
 rotation into the body frame, one slab division or one quadratic about the point of closest approach) against the same kind of
 reference, fed the device's own binary32 poses.  Fraction 1e-5 relative + 1e-6 absolute; point 2e-5 per unit of magnitude;
 normal 1e-4 + 2e-6 x (|origin|_1 + |travel|_1 + radius) / d, where d is the shape's smallest half extent or radius and, on an
@@ -24,95 +24,14 @@ import pytest
 import banggameengine_amd as B
 from banggameengine_amd import world as W
 
-from test_gpu_raycast import F_ABS, F_REL, FLAGS, N_ABS, N_SCALE, P_REL, Scene
-from test_raycast_cpu import NO_ENTITY, RAY_BODY, RAY_GROUND, RAY_MISS, RAY_TRIGGER
-from test_sphere_queries_cpu import HAND_CASES, SphereRef, check_hand_case, random_casts, random_spheres
+from refmodel.rays import NO_ENTITY, RAY_BODY, RAY_GROUND, RAY_MISS, RAY_TRIGGER
+from refmodel.spheres import SphereRef
+from refmodel.sphere_cases import HAND_CASES, check_hand_case, random_casts, random_spheres
+from refmodel.device import FLAGS, Scene, check_all_casts, check_casts, check_overlaps
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def check_casts(ref, casts, got, need_hits=50):
-    o, d, md, rad, mask = casts
-    w64 = ref.w
-    index_of = {int(c): i for i, c in enumerate(w64.code)}
-    checked = hits = 0
-    share_f = share_p = share_n = 0.0
-    for i in range(len(o)):
-        want, clear = ref.sweep_clear(o[i], d[i], md[i], rad[i], mask[i])
-        if not clear:
-            continue
-        checked += 1
-        if not want:
-            assert got["kind"][i] == RAY_MISS and got["entity"][i] == NO_ENTITY, f"cast {i}: hit where the reference misses"
-            continue
-        f, code, kind, ent, n, p = want[0]
-        assert (got["kind"][i], got["entity"][i]) == (kind, ent), f"cast {i}: {got['kind'][i]}/{got['entity'][i]} != {kind}/{ent}"
-        hits += 1
-        gf = float(got["fraction"][i])
-        ef = abs(gf - f) / (F_REL * f + F_ABS)
-        ep = float(np.max(np.abs(got["point"][i] - p) / (P_REL * (1.0 + np.abs(p)))))
-        small = w64.min_dim(code)
-        k = index_of.get(code)
-        if k is not None and not w64.capsule[k] and np.count_nonzero(np.abs(w64.basis[k].T @ n) > 1e-6) > 1:
-            small = min(small, float(rad[i]))  # an edge or a corner of a box
-        n_tol = N_ABS + N_SCALE * float(np.abs(o[i]).sum() + np.abs(d[i] * md[i]).sum() + rad[i]) / small
-        en = float(np.max(np.abs(got["normal"][i] - n))) / n_tol
-        print_line = f"cast {i}: f {gf} vs {f}, point {got['point'][i]} vs {p}, normal {got['normal'][i]} vs {n}; shares {ef:.2f} {ep:.2f} {en:.2f}"
-        assert ef <= 1.0 and ep <= 1.0 and en <= 1.0, print_line
-        assert got["distance"][i] == np.float32(got["fraction"][i] * md[i])
-        share_f, share_p, share_n = max(share_f, ef), max(share_p, ep), max(share_n, en)
-    print(f"checked {checked} of {len(o)} casts, {hits} hits; worst share of tolerance: f {share_f:.2f}, point {share_p:.2f}, normal {share_n:.2f}")
-    assert checked >= 0.5 * len(o) and hits >= need_hits, (checked, hits)
-    return hits
-
-
-def check_overlaps(ref, spheres, got, need_found=50):
-    c, rad, mask = spheres
-    off = got["offsets"].astype(np.int64)
-    assert off[0] == 0 and np.all(np.diff(off) >= 0) and off[-1] == len(got["kind"])
-    compared = found = 0
-    share_d = 0.0
-    for i in range(len(c)):
-        want, clear = ref.overlap(c[i], rad[i], mask[i])
-        if not clear:
-            continue
-        compared += 1
-        seg = slice(off[i], off[i + 1])
-        have = list(zip(got["kind"][seg].tolist(), got["entity"][seg].tolist()))
-        assert have == [(h[1], h[2]) for h in want], f"sphere {i}: {have} vs {[(h[1], h[2]) for h in want]}"
-        tol = P_REL * (1.0 + float(np.abs(c[i]).max()))
-        for g, h in zip(got["distance"][seg], want):
-            share_d = max(share_d, abs(float(g) - h[3]) / tol)
-        found += len(want)
-    print(f"compared {compared} of {len(c)} spheres, {found} objects; worst share of the distance tolerance {share_d:.2f}")
-    assert share_d <= 1.0
-    assert compared >= 0.9 * len(c) and found >= need_found, (compared, found)
-
-
-def check_all_casts(ref, casts, got, allh):
-    """All hits: per-cast sets in (f, code) order, offsets, and the first one is the closest hit (got: the closest hits of the
-    same casts, or of a batch these casts begin).  At least half of the casts must be compared."""
-    o, d, md, rad, mask = casts
-    off = allh["offsets"].astype(np.int64)
-    assert off[0] == 0 and np.all(np.diff(off) >= 0) and off[-1] == len(allh["kind"])
-    compared = 0
-    for i in range(len(o)):
-        want, clear = ref.sweep_clear(o[i], d[i], md[i], rad[i], mask[i])
-        seg = slice(off[i], off[i + 1])
-        if clear:
-            compared += 1
-            got_set = sorted(zip(allh["kind"][seg].tolist(), allh["entity"][seg].tolist()))
-            assert got_set == sorted((h[2], h[3]) for h in want), f"cast {i}"
-        assert np.all(np.diff(allh["fraction"][seg]) >= 0)
-        if off[i + 1] > off[i]:
-            for k in ("kind", "entity", "fraction", "distance"):
-                assert allh[k][off[i]] == got[k][i], (i, k)
-            assert np.array_equal(allh["point"][off[i]], got["point"][i]) and np.array_equal(allh["normal"][off[i]], got["normal"][i])
-        else:
-            assert got["kind"][i] == RAY_MISS
-    assert compared >= 0.5 * len(o)
 
 
 @pytest.mark.parametrize("n,seed", [(2000, 1), (20000, 2)])

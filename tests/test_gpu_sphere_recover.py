@@ -4,7 +4,7 @@ bge_world_sphere_penetration*, bge_world_sphere_recover*).
 Three references, each for what it can say:
   - the device's own overlap_sphere, exactly: a sphere is penetrated iff its overlap list is not empty, the winner is in that
     list, and outside a shape the signed distance is the overlap's distance bit for bit, so depth == float32(radius - distance);
-  - signed_ref of test_sphere_recover_cpu.py, the header's rule in float64 fed the device's binary32 poses, within the tolerances of
+  - signed_ref of refmodel/recover.py, the header's rule in float64 fed the device's binary32 poses, within the tolerances of
     test_gpu_sphere_queries.py: depth and point as the overlap's distance there, P_REL x (1 + |centre|_inf); the
     normal N_ABS + N_SCALE x (|centre|_1 + radius) / d, where d is the shape's smallest half extent or radius and, where the
     normal is a difference of points divided by its length (outside a box, anywhere about a capsule), the smaller of that and the
@@ -25,12 +25,14 @@ import pytest
 import banggameengine_amd as B
 from banggameengine_amd import world as W
 
-from test_gpu_raycast import FLAGS, N_ABS, N_SCALE, P_REL, Scene
-from test_raycast_cpu import NO_ENTITY, RAY_BODY, RAY_GROUND, RAY_MISS, RAY_TRIGGER
-from test_sphere_move_cpu import BATCHES, SCENE_N, SCENE_SEED, ghost_positions
-from test_sphere_queries_cpu import scene_world64
-from test_sphere_recover_cpu import (ALL, HAND_RECOVERS, SPHERE_SEED, check_caps, check_hand_recover, check_invalid, classify, hand_record,
-                                     invalid_records, record_valid, recover_ref, sphere_batch)
+from refmodel.tolerances import N_ABS, N_SCALE, P_REL
+from refmodel.rays import ALL, NO_ENTITY, RAY_BODY, RAY_GROUND, RAY_MISS, RAY_TRIGGER
+from refmodel.recover import classify, record_valid, recover_ref
+from refmodel.sphere_cases import scene_world64
+from refmodel.move_cases import BATCHES, SCENE_N, SCENE_SEED, ghost_positions
+from refmodel.recover_cases import (HAND_RECOVERS, SPHERE_SEED, check_caps, check_hand_recover, check_invalid, hand_record, invalid_records,
+                                    sphere_batch)
+from refmodel.device import FLAGS, Scene
 
 pytestmark = pytest.mark.gpu
 

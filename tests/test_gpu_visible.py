@@ -1,4 +1,4 @@
-"""Frustum culling on the device (include/bge_world.h bge_world_visible*) against the two references of test_visible_cpu.py.
+"""Frustum culling on the device (include/bge_world.h bge_world_visible*) against the two references of refmodel/visible.py.
 
 Exactness: the entity list equals the binary32 restatement of the rule fed the DEVICE's own downloaded world matrices — exactly,
 the rule fixes every rounding.  Against the float64 geometry it must agree for every entity that reference does not call
@@ -17,7 +17,8 @@ import banggameengine_amd as B
 from banggameengine_amd import world as W
 from banggameengine_amd._capi import CullDesc, lib
 
-from test_visible_cpu import F, make_scene, narrow_view, renderable, visible_ref32, visible_ref64, wide_view
+from refmodel.visible import F, renderable, visible_ref32, visible_ref64
+from refmodel.render_cases import make_scene, narrow_view, wide_view
 
 pytestmark = pytest.mark.gpu
 

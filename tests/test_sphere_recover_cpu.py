@@ -1,8 +1,8 @@
 """Sphere penetration and recovery (include/bge_world.h "Sphere penetration and recovery", bge_world_sphere_penetration*,
-bge_world_sphere_recover*) without a GPU: signed_ref, the signed-distance rule in float64 on the World64 of test_raycast_cpu.py;
-recover_ref, the Recover rule in numpy float32 scalars (written from the header, not from the kernel) over a penetration function
-handed in; hand-worked cases on an analytic penetration function of half-spaces and on the float64 shapes; the batch and the caps
-the GPU comparison relies on; the exported symbols, the C99 view of the records and the adapter's SpherePenetration /
+bge_world_sphere_recover*) without a GPU: the references of refmodel/recover.py (signed_ref, the signed-distance rule in float64 on a World64;
+recover_ref, the Recover rule in numpy float32 scalars over a penetration function handed in) on the hand-worked cases of
+refmodel/recover_cases.py, through an analytic penetration function of half-spaces and through the float64 shapes; the batch and the
+caps the GPU comparison relies on; the exported symbols, the C99 view of the records and the adapter's SpherePenetration /
 RecoverSphere / RecoverSpheres on the reference's types.
 
 recover_ref(pen_fn, records) is the reference of the GPU tests: there pen_fn is World.sphere_penetration on the same world, and the
@@ -10,280 +10,24 @@ device's result must equal it byte for byte."""
 from __future__ import annotations
 
 import collections
-import math
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from banggameengine_amd.world import (PENETRATION_HIT_DTYPE, RECOVER_INVALID, RECOVER_MOVED, RECOVER_ROUNDS, RECOVER_STUCK, SPHERE_DTYPE,
-                                      SPHERE_RECOVER_DTYPE, SPHERE_RECOVER_RESULT_DTYPE, make_sphere_recovers, make_spheres)
+from banggameengine_amd.world import (PENETRATION_HIT_DTYPE, RECOVER_INVALID, RECOVER_MOVED, RECOVER_ROUNDS, RECOVER_STUCK, SPHERE_RECOVER_DTYPE,
+                                      SPHERE_RECOVER_RESULT_DTYPE, make_sphere_recovers, make_spheres)
 
-from test_raycast_cpu import (CODE_PLANE, NO_ENTITY, RAY_BODY, RAY_GROUND, RAY_MISS, RAY_TRIGGER, Obj, World64, box_half_extents, capsule_dims,
-                              quat_from_euler, quat_to_mat)
-from test_sphere_move_cpu import BATCHES, SCENE_N, SCENE_SEED, ghost_positions, wall_box
-from test_sphere_queries_cpu import EPS_CLEAR, SphereRef, scene_world64, sphere_valid
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CPP = os.path.join(ROOT, "tests", "cpp")
-LIBDIR = os.path.join(ROOT, "banggameengine_amd")
-ALL = 0xFFFFFFFF
-F = np.float32
-
-# ------------------------------------------------------------------------------------------------ the signed distance, float64
-
-# One candidate of a sphere: depth = radius - sd; gap = inside a box, how much further the runner-up face is than the nearest
-# (inf elsewhere); cond = the length the normal was divided by (outside a box: sd; a capsule: the distance to its segment; inf for
-# an axis normal and the plane)
-Cand = collections.namedtuple("Cand", "depth code kind entity sd normal point gap cond")
-
-
-def signed_ref(w64, center, radius, mask, slack=0.0):
-    """The header's signed distance and outward direction of every candidate of the World64 with sd <= radius + slack, in the
-    order of the penetration query: largest depth first, ties to the lowest object code.  center and radius are rounded to
-    binary32 first (they are the record's), everything after is float64."""
-    if not sphere_valid(center, radius, mask):
-        return []
-    w = w64
-    c, r = np.asarray(center, np.float32).astype(np.float64), float(np.float32(radius))
-    out = []
-    near = ((w.origin - c) ** 2).sum(axis=1) <= (w.radius + r + slack) ** 2
-    sel = np.nonzero(near & ((w.group & int(mask)) != 0) & (w.omask != 0))[0]
-    if len(sel):
-        B = w.basis[sel]
-        q = np.einsum("nji,nj->ni", B, c - w.origin[sel])
-        h, cap, rows = w.dims[sel], w.capsule[sel], np.arange(len(sel))
-        with np.errstate(all="ignore"):
-            # box: outside, the distance to the closest point and the direction from it; inside, the nearest face
-            a = np.abs(q)
-            outside = (a > h).any(axis=1)
-            e = q - np.clip(q, -h, h)
-            dist = np.linalg.norm(e, axis=1)
-            m = h - a
-            j = np.argmin(m, axis=1)  # (the first minimum: ties to the lowest axis)
-            axis_n = np.zeros_like(q)
-            axis_n[rows, j] = np.where(q[rows, j] < 0, -1.0, 1.0)
-            ms = np.sort(m, axis=1)
-            sd_box = np.where(outside, dist, -m[rows, j])
-            n_box = np.where(outside[:, None], e / dist[:, None], axis_n)
-            gap_box = np.where(outside, np.inf, ms[:, 1] - ms[:, 0])
-            cond_box = np.where(outside, dist, np.inf)
-            # capsule: the distance to the segment less the radius; on the segment itself out along the local +x
-            s = np.zeros_like(q)
-            s[:, 1] = np.clip(q[:, 1], -h[:, 1], h[:, 1])
-            ec = q - s
-            al = np.linalg.norm(ec, axis=1)
-            n_cap = np.where((al > 0)[:, None], ec / al[:, None], np.array([1.0, 0.0, 0.0]))
-        sd = np.where(cap, al - h[:, 0], sd_box)
-        nl = np.where(cap[:, None], n_cap, n_box)
-        gap = np.where(cap, np.inf, gap_box)
-        cond = np.where(cap, al, cond_box)
-        nw = np.einsum("nij,nj->ni", B, nl)
-        for k in np.nonzero(sd <= r + slack)[0]:
-            i = sel[k]
-            out.append(Cand(r - sd[k], int(w.code[i]), int(w.kind[i]), int(w.entity[i]), float(sd[k]), nw[k], c - nw[k] * sd[k], float(gap[k]),
-                            float(cond[k])))
-    if w.plane and (int(mask) & 2) and abs(c[1]) <= r + slack:
-        n = np.array([0.0, 1.0 if c[1] >= 0 else -1.0, 0.0])
-        out.append(Cand(r - abs(c[1]), CODE_PLANE, RAY_GROUND, NO_ENTITY, abs(c[1]), n, c - n * abs(c[1]), math.inf, math.inf))
-    out.sort(key=lambda h: (-h.depth, h.code))
-    return out
-
-
-def _miss(hits, i):
-    hits[i] = (RAY_MISS, NO_ENTITY, 0, (0, 0, 0), (0, 0, 0), 0)
-
-
-def pen_of(w64):
-    """The penetration function of a World64: signed_ref's winner, rounded to the binary32 record."""
-    def pen_fn(spheres):
-        hits = np.zeros(len(spheres), PENETRATION_HIT_DTYPE)
-        for i, s in enumerate(spheres):
-            _miss(hits, i)
-            got = signed_ref(w64, s["center"], s["radius"], s["layer_mask"])
-            if got:
-                h = got[0]
-                hits[i] = (h.kind, h.entity, h.depth, h.point, h.normal, 0)
-        return hits
-    return pen_fn
-
-
-class HalfSpacesPen:
-    """An analytic penetration function: solids {x: n.x <= c}, given as (unit normal, a point of the surface, kind, entity).
-    sd = n.x - c, negative inside; the deepest wins, ties to the earlier entry.  float64, rounded to the binary32 record."""
-
-    def __init__(self, walls):
-        self.walls = [(np.asarray(n, np.float64), float(np.dot(n, pt)), kind, ent) for n, pt, kind, ent in walls]
-
-    def __call__(self, spheres):
-        hits = np.zeros(len(spheres), PENETRATION_HIT_DTYPE)
-        for i, s in enumerate(spheres):
-            _miss(hits, i)
-            if not sphere_valid(s["center"], s["radius"], s["layer_mask"]):
-                continue
-            c, r, best = s["center"].astype(np.float64), float(s["radius"]), None
-            for n, off, kind, ent in self.walls:
-                sd = float(n @ c) - off
-                if sd <= r and (best is None or r - sd > best[0]):
-                    best = (r - sd, sd, n, kind, ent)
-            if best is not None:
-                depth, sd, n, kind, ent = best
-                hits[i] = (kind, ent, depth, c - n * sd, n, 0)
-        return hits
-
-
-# ------------------------------------------------------------------------------------------------ the Recover rule
-
-
-def record_valid(m):
-    floats = [*m["position"], m["radius"], m["skin"]]
-    return bool(all(np.isfinite(v) for v in floats) and m["radius"] >= 0 and m["skin"] > 0 and m["layer_mask"] != 0)
-
-
-def recover_ref(pen_fn, records):
-    """The header's rule.  pen_fn(spheres: SPHERE_DTYPE[n]) -> PENETRATION_HIT_DTYPE[n] answers one pass (a sphere with layer_mask
-    0 stands for one that asks nothing); it is called RECOVER_ROUNDS + 1 times."""
-    n = len(records)
-    out = np.zeros(n, SPHERE_RECOVER_RESULT_DTYPE)
-    out["hit_entity"] = NO_ENTITY
-    p = [[F(v) for v in m["position"]] for m in records]
-    valid = [record_valid(m) for m in records]
-    done = [not v for v in valid]
-
-    def ask():
-        spheres = np.zeros(n, SPHERE_DTYPE)
-        for i in range(n):
-            if not done[i]:
-                spheres[i] = (p[i], records["radius"][i], records["layer_mask"][i])
-        return pen_fn(spheres)
-
-    with np.errstate(all="ignore"):
-        for _ in range(RECOVER_ROUNDS):
-            hits = ask()  # step 1
-            for i in range(n):
-                if done[i]:
-                    continue
-                h = hits[i]
-                if h["kind"] == RAY_MISS:  # step 2
-                    done[i] = True
-                    continue
-                e, nrm = F(h["depth"]), [F(v) for v in h["normal"]]  # step 3
-                t = e + F(records["skin"][i])
-                p[i] = [p[i][j] + nrm[j] * t for j in range(3)]
-                out["n_pushes"][i] += 1
-                out["hit_kind"][i], out["hit_entity"][i], out["hit_normal"][i], out["hit_depth"][i] = h["kind"], h["entity"], nrm, e
-        hits = ask()  # after
-        for i in range(n):
-            if not valid[i]:
-                out["flags"][i] = RECOVER_INVALID
-                out["position"][i] = records["position"][i]
-                continue
-            if not done[i] and hits[i]["kind"] != RAY_MISS:
-                out["flags"][i] |= RECOVER_STUCK
-                out["remaining_depth"][i] = hits[i]["depth"]
-            if out["n_pushes"][i] > 0:
-                out["flags"][i] |= RECOVER_MOVED
-            out["pushed"][i] = [p[i][j] - F(records["position"][i][j]) for j in range(3)]
-            out["position"][i] = p[i]
-    return out
-
+from abi import assert_exported, build_and_run_c99, compile_reference_shapes
+from refmodel.rays import ALL, CODE_PLANE, RAY_BODY, RAY_GROUND, RAY_TRIGGER, Obj, World64
+from refmodel.spheres import SphereRef
+from refmodel.moves import F
+from refmodel.recover import HalfSpacesPen, classify, pen_of, record_valid, recover_ref, signed_ref
+from refmodel.sphere_cases import scene_world64
+from refmodel.move_cases import BATCHES, SCENE_N, SCENE_SEED, ghost_positions
+from refmodel.recover_cases import (DOWN, EAST, HAND_RECOVERS, PLANE, S2, SKIN, SPHERE_SEED, UP, check_caps, check_hand_recover, check_invalid,
+                                    hand_objects, hand_record, invalid_records, sphere_batch)
 
 # ------------------------------------------------------------------------------------------------ hand-worked cases
-
-UP, DOWN, WEST, EAST = (0.0, 1.0, 0.0), (0.0, -1.0, 0.0), (-1.0, 0.0, 0.0), (1.0, 0.0, 0.0)
-PLANE = (UP, (0.0, 0.0, 0.0), RAY_GROUND, NO_ENTITY)
-R, SKIN = 0.5, 0.01
-S2 = math.sqrt(2.0)
-TILT = (0.3, 0.5, math.pi / 2)  # the pose of the capsule whose axis the sphere is centred on
-TILT_X = tuple(quat_to_mat(quat_from_euler(np.asarray(TILT)))[:, 0])  # its local +x in the world
-
-
-def body(capsule, size, position, euler=(0.0, 0.0, 0.0), group=1, ghost=False):
-    return (capsule, size, position, euler, group, ghost)
-
-
-def cube(position, **kw):
-    return body(False, (1.0, 1.0, 1.0), position, **kw)
-
-
-# (name, half-spaces of the analytic function or None where they cannot say it, bodies of the shape reference and of the device
-#  (body(...); body i of the list is entity i), plane, sphere (position, layer mask), expected fields).  Every sphere has radius
-#  0.5 and skin 0.01.  Sizes of 1, 2, 3, 4, 8 and 0.5 keep the library's half extents at the sizes themselves.
-HAND_RECOVERS = [
-    # 0.3 above the plane: sd = 0.3, depth 0.2, t = 0.21: up to y = 0.51 = radius + skin, where the next query finds nothing
-    ("over the plane", [PLANE], [], True, ((0, 0.3, 0), ALL),
-     dict(position=(0, 0.51, 0), pushed=(0, 0.21, 0), flags=RECOVER_MOVED, n_pushes=1, hit_kind=RAY_GROUND, hit_entity=NO_ENTITY, hit_normal=UP,
-          hit_depth=0.2)),
-    # the same below it: the plane is two-sided, the centre goes further down
-    ("under the plane", None, [], True, ((0, -0.3, 0), ALL),
-     dict(position=(0, -0.51, 0), pushed=(0, -0.21, 0), flags=RECOVER_MOVED, n_pushes=1, hit_kind=RAY_GROUND, hit_entity=NO_ENTITY, hit_normal=DOWN,
-          hit_depth=0.2)),
-    # the centre inside the box (1, 2, 3), 0.2 from its +x face (1.9 and 2.8 from the others): sd = -0.2, depth 0.7, t = 0.71: one
-    # push to x = 1.51 = h.x + radius + skin
-    ("inside a box near its +x face", [(EAST, (1, 0, 0), RAY_BODY, 0)], [body(False, (1.0, 2.0, 3.0), (0, 5, 0))], False, ((0.8, 5.1, 0.2), ALL),
-     dict(position=(1.51, 5.1, 0.2), pushed=(0.71, 0, 0), flags=RECOVER_MOVED, n_pushes=1, hit_kind=RAY_BODY, hit_entity=0, hit_normal=EAST,
-          hit_depth=0.7)),
-    # 0.5 from the -x, +y and +z faces of a cube alike: the lowest axis wins, x, with the sign of q.x: out to x = -1 - 0.51
-    ("face tie inside a cube", None, [cube((0, 5, 0))], False, ((-0.5, 5.5, 0.5), ALL),
-     dict(position=(-1.51, 5.5, 0.5), pushed=(-1.01, 0, 0), flags=RECOVER_MOVED, n_pushes=1, hit_kind=RAY_BODY, hit_entity=0, hit_normal=WEST,
-          hit_depth=1.0)),
-    # the centre of a tilted capsule (radius 0.5) is on its axis: a = 0, sd = -0.5, depth 1, out along the capsule's local +x by 1.01
-    ("on a capsule's axis", None, [body(True, (0.5, 1.0, 0.5), (2, 5, -1), TILT)], False, ((2, 5, -1), ALL),
-     dict(position=tuple(np.array([2.0, 5.0, -1.0]) + 1.01 * np.array(TILT_X)), pushed=tuple(1.01 * np.array(TILT_X)), flags=RECOVER_MOVED,
-          n_pushes=1, hit_kind=RAY_BODY, hit_entity=0, hit_normal=TILT_X, hit_depth=1.0)),
-    # the corner of the floor and the wall x = 2: the wall is deeper (sd 0.2, depth 0.3) than the floor (sd 0.3, depth 0.2): first out
-    # of the wall to x = 1.8 - 0.31, then out of the floor to y = 0.3 + 0.21; the third query finds nothing
-    ("floor and wall corner", [PLANE, (WEST, (2, 0, 0), RAY_BODY, 0)], [wall_box(WEST, (2, 1, 0)) + (1, False)], True, ((1.8, 0.3, 0), ALL),
-     dict(position=(1.49, 0.51, 0), pushed=(-0.31, 0.21, 0), flags=RECOVER_MOVED, n_pushes=2, hit_kind=RAY_GROUND, hit_entity=NO_ENTITY, hit_normal=UP,
-          hit_depth=0.2)),
-    # a slot 0.8 wide between the faces x = -0.4 (cube 0) and x = 0.4 (cube 1): from x = 0.05 cube 1 is deeper (0.15 against 0.05):
-    # to -0.11; there cube 0 reaches in by 0.21: to 0.11; then cube 1 by 0.21: to -0.11; then cube 0: to 0.11.  Four pushes, and
-    # the check still finds cube 1 in by 0.21: STUCK
-    ("slot narrower than the sphere", [(EAST, (-0.4, 0, 0), RAY_BODY, 0), (WEST, (0.4, 0, 0), RAY_BODY, 1)],
-     [cube((-1.4, 5, 0)), cube((1.4, 5, 0))], False, ((0.05, 5, 0), ALL),
-     dict(position=(0.11, 5, 0), pushed=(0.06, 0, 0), flags=RECOVER_MOVED | RECOVER_STUCK, n_pushes=4, hit_kind=RAY_BODY, hit_entity=0,
-          hit_normal=EAST, hit_depth=0.21, remaining_depth=0.21)),
-    # two cubes at the same place reach equally deep: the lower object code wins
-    ("equal depth: lowest code", [(EAST, (1, 0, 0), RAY_BODY, 0), (EAST, (1, 0, 0), RAY_BODY, 1)], [cube((0, 5, 0)), cube((0, 5, 0))], False,
-     ((1.2, 5, 0), ALL),
-     dict(position=(1.51, 5, 0), pushed=(0.31, 0, 0), flags=RECOVER_MOVED, n_pushes=1, hit_kind=RAY_BODY, hit_entity=0, hit_normal=EAST, hit_depth=0.3)),
-    # a trigger ghost on layer 4: a sphere that sees layer 4 is pushed out of it, one that sees layers 1 and 2 is left where it is
-    ("ghost through its layer", [(EAST, (1, 0, 0), RAY_TRIGGER, 0)], [cube((0, 5, 0), group=4, ghost=True)], False, ((1.2, 5, 0), 4),
-     dict(position=(1.51, 5, 0), pushed=(0.31, 0, 0), flags=RECOVER_MOVED, n_pushes=1, hit_kind=RAY_TRIGGER, hit_entity=0, hit_normal=EAST,
-          hit_depth=0.3)),
-    ("ghost on a layer not asked", [], [cube((0, 5, 0), group=4, ghost=True)], False, ((1.2, 5, 0), 3),
-     dict(position=(1.2, 5, 0), pushed=(0, 0, 0), flags=0, n_pushes=0, hit_kind=RAY_MISS, hit_entity=NO_ENTITY, hit_normal=(0, 0, 0), hit_depth=0)),
-    # a cube turned 45 degrees about y (the library's euler.x: quat_from_euler): its vertical edge at sqrt 2 on the x axis.  From
-    # x = 1.8 the edge is 0.3858 away, depth 0.1142, and the way out is along x: to sqrt 2 + radius + skin
-    ("rotated box", [(EAST, (S2, 0, 0), RAY_BODY, 0)], [cube((0, 5, 0), euler=(math.pi / 4, 0.0, 0.0))], False, ((1.8, 5.5, 0), ALL),
-     dict(position=(S2 + 0.51, 5.5, 0), pushed=(S2 + 0.51 - 1.8, 0, 0), flags=RECOVER_MOVED, n_pushes=1, hit_kind=RAY_BODY, hit_entity=0,
-          hit_normal=EAST, hit_depth=0.5 - (1.8 - S2))),
-    # clear of everything: back unchanged
-    ("clear", [PLANE], [cube((0, 5, 0))], True, ((3, 2, 0), ALL),
-     dict(position=(3, 2, 0), pushed=(0, 0, 0), flags=0, n_pushes=0, hit_kind=RAY_MISS, hit_entity=NO_ENTITY, hit_normal=(0, 0, 0), hit_depth=0)),
-]
-
-
-def hand_record(case):
-    pos, mask = case[4]
-    return make_sphere_recovers([pos], R, SKIN, mask)
-
-
-def hand_objects(bodies):
-    return [Obj(RAY_TRIGGER if ghost else RAY_BODY, i, group, ALL, cap, capsule_dims(size) if cap else box_half_extents(size), pos,
-                quat_from_euler(np.asarray(e, np.float64))) for i, (cap, size, pos, e, group, ghost) in enumerate(bodies)]
-
-
-def check_hand_recover(name, got, want, tol=1e-5):
-    for k, v in want.items():
-        if k in ("position", "pushed", "hit_normal", "hit_depth", "remaining_depth"):
-            assert np.allclose(got[k], v, atol=tol, rtol=0), f"{name}: {k} {got[k]} vs {v}"
-        else:
-            assert int(got[k]) == int(v), f"{name}: {k} {got[k]} vs {v}"
-    if "remaining_depth" not in want:
-        assert got["remaining_depth"] == 0, name
-    assert got["reserved"] == 0
 
 
 @pytest.mark.parametrize("case", HAND_RECOVERS, ids=[c[0] for c in HAND_RECOVERS])
@@ -354,29 +98,6 @@ def test_signed_reference_agrees_with_the_overlap_reference():
     assert n > 200
 
 
-INVALID_RECORDS = [
-    ("nan position", dict(position=(0, float("nan"), 0))), ("inf position", dict(position=(float("inf"), 0, 0))),
-    ("negative radius", dict(radius=-0.5)), ("nan radius", dict(radius=float("nan"))), ("inf radius", dict(radius=float("inf"))),
-    ("zero skin", dict(skin=0.0)), ("negative skin", dict(skin=-0.01)), ("nan skin", dict(skin=float("nan"))), ("inf skin", dict(skin=float("inf"))),
-    ("empty mask", dict(layer_mask=0)),
-]
-
-
-def invalid_records():
-    recs = make_sphere_recovers([(0, 0.3, 0)] * len(INVALID_RECORDS), R, SKIN, ALL)
-    for i, (_, fields) in enumerate(INVALID_RECORDS):
-        for k, v in fields.items():
-            recs[k][i] = v
-    return recs
-
-
-def check_invalid(recs, got):
-    for i in range(len(recs)):
-        want = np.zeros(1, SPHERE_RECOVER_RESULT_DTYPE)
-        want["position"], want["flags"], want["hit_entity"] = recs["position"][i], RECOVER_INVALID, NO_ENTITY
-        assert got[i].tobytes() == want[0].tobytes(), (i, got[i])
-
-
 def test_invalid_records_echo_the_position():
     recs = invalid_records()
     check_invalid(recs, recover_ref(HalfSpacesPen([PLANE]), recs))
@@ -386,57 +107,6 @@ def test_invalid_records_echo_the_position():
 
 
 # ------------------------------------------------------------------------------------------------ the batch of the GPU comparison
-
-SPHERE_SEED = 71
-DEPTH_CLEAR = 1e-4  # the runner-up object (inside a box: the runner-up face) must be further behind than this
-MIN_COND = 1e-3     # a normal divided by a length below this is not compared: its error is the rounding of the centre over that length
-
-
-def sphere_batch(rng, n, body_pos, ghost_pos, spread=28.0):
-    """Spheres where there is something to be pushed out of: centres drawn around body positions.  Every 5th is near the plane
-    beside the cluster instead (above and below it, seeing every layer), every 7th free in the air above the cluster, every 19th
-    around a trigger ghost's position seeing every layer.  Every 37th is invalid (the classes of INVALID_RECORDS in turn)."""
-    pos = body_pos[rng.integers(0, len(body_pos), n)] + rng.normal(scale=0.45, size=(n, 3))
-    recs = make_sphere_recovers(pos, rng.uniform(0.1, 0.5, n), rng.choice([0.002, 0.01, 0.05], n),
-                                rng.choice(np.array([1, 2, 3, 6, ALL, ALL, ALL], np.uint32), n))
-    low = np.arange(3, n, 5)
-    recs["position"][low] = np.stack([rng.uniform(spread + 4, spread + 12, len(low)) * rng.choice([-1.0, 1.0], len(low)),
-                                      rng.uniform(-0.45, 0.45, len(low)), rng.uniform(-spread, spread, len(low))], 1)
-    recs["radius"][low] = rng.uniform(0.3, 0.5, len(low))
-    recs["layer_mask"][low] = ALL
-    air = np.arange(5, n, 7)
-    recs["position"][air] = np.stack([rng.uniform(-spread, spread, len(air)), rng.uniform(9.0, 12.0, len(air)), rng.uniform(-spread, spread, len(air))], 1)
-    aim = np.arange(7, n, 19)
-    recs["position"][aim] = ghost_pos[rng.integers(0, len(ghost_pos), len(aim))] + rng.normal(scale=0.1, size=(len(aim), 3))
-    recs["layer_mask"][aim] = ALL
-    for k, i in enumerate(range(36, n, 37)):
-        for f, v in INVALID_RECORDS[k % len(INVALID_RECORDS)][1].items():
-            recs[f][i] = v
-    return recs
-
-
-def classify(w64, m):
-    """What the comparison with the float64 reference may rely on for the sphere m of a batch (conditions on the reference alone):
-    (candidates in order, winner_clear, normal_clear).  winner_clear: the deepest candidate is at least DEPTH_CLEAR inside the
-    sphere and the runner-up — among everything within the overlap's band EPS_CLEAR x (1 + |centre|_inf) of the radius — is more
-    than DEPTH_CLEAR behind.  normal_clear: additionally the winner's normal is well defined: inside a box the runner-up face is
-    more than DEPTH_CLEAR further, elsewhere the length it is divided by is at least MIN_COND."""
-    c = np.asarray(m["position"], np.float32).astype(np.float64)
-    band = EPS_CLEAR * (1.0 + float(np.abs(c).max())) if np.isfinite(c).all() else 0.0
-    cands = signed_ref(w64, m["position"], m["radius"], m["layer_mask"], slack=band)
-    if not cands:
-        return cands, True, True
-    winner_clear = cands[0].depth > DEPTH_CLEAR and (len(cands) == 1 or cands[0].depth - cands[1].depth > DEPTH_CLEAR)
-    return cands, winner_clear, winner_clear and cands[0].gap > DEPTH_CLEAR and cands[0].cond >= MIN_COND
-
-
-def check_caps(n_valid, n_pen, n_skipped, kinds, n_axis):
-    print(f"{n_pen} of {n_valid} valid spheres start in penetration; {n_skipped} of them set aside as ambiguous; winners by kind {dict(kinds)}; "
-          f"{n_axis} compared axis normals inside boxes")
-    assert n_axis >= 20, n_axis
-    assert 2 * n_pen >= n_valid, (n_pen, n_valid)
-    assert 2 * n_skipped <= n_pen, (n_skipped, n_pen)
-    assert all(kinds.get(k, 0) >= 1 for k in (RAY_BODY, RAY_TRIGGER, RAY_GROUND)), kinds
 
 
 def test_reference_alone_stays_inside_the_caps_of_the_gpu_comparison():
@@ -476,11 +146,8 @@ def test_reference_alone_stays_inside_the_caps_of_the_gpu_comparison():
 
 def test_recover_symbols_exported():
     import banggameengine_amd as B
-    from banggameengine_amd import _capi
-    lib = _capi.lib()
-    for name in ("bge_world_sphere_penetration", "bge_world_sphere_penetration_device", "bge_world_sphere_recover", "bge_world_sphere_recover_device"):
-        assert name in _capi.SYMBOLS
-        assert getattr(lib, name) is not None
+    assert_exported(("bge_world_sphere_penetration", "bge_world_sphere_penetration_device", "bge_world_sphere_recover",
+                     "bge_world_sphere_recover_device"))
     from banggameengine_amd.world import World
     assert PENETRATION_HIT_DTYPE.itemsize == 40 and SPHERE_RECOVER_DTYPE.itemsize == 28 and SPHERE_RECOVER_RESULT_DTYPE.itemsize == 64
     assert PENETRATION_HIT_DTYPE.fields["normal"][1] == 24 and SPHERE_RECOVER_DTYPE.fields["layer_mask"][1] == 20
@@ -507,14 +174,8 @@ def test_recover_entry_points_reject_null_world_and_zero_count():
 
 
 def test_abi_c99_recover_records(tmp_path):
-    exe = str(tmp_path / "abi_check_recover")
-    subprocess.check_call(["gcc", "-std=c99", "-pedantic", "-Wall", "-Wextra", "-Werror", "-o", exe, os.path.join(CPP, "abi_check_recover.c"),
-                           f"-L{LIBDIR}", "-lbge_world", f"-Wl,-rpath,{LIBDIR}", "-Wl,-rpath,/opt/rocm/lib"])
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "recover abi ok" in r.stdout
+    build_and_run_c99(tmp_path, "abi_check_recover.c", "recover abi ok")
 
 
 def test_adapter_recovery_compiles_on_reference_shapes(tmp_path):
-    subprocess.check_call(["g++", "-std=c++20", "-O0", "-Wall", "-Wextra", "-Werror", "-Wno-unused-parameter", "-c",
-                           os.path.join(CPP, "recover_reference_shapes.cpp"), "-o", str(tmp_path / "recover_reference_shapes.o")])
+    compile_reference_shapes(tmp_path, "recover_reference_shapes.cpp")
