@@ -227,6 +227,7 @@ __global__ void __launch_bounds__(kThreads) k_batch_ranges(const uint32_t* __res
 __global__ void __launch_bounds__(kThreads) k_batch_gather(BatchParams bp, const uint32_t* __restrict__ entities)
 {
     __shared__ uint32_t s_slot[kThreads];
+    __shared__ float4 s_row3[kThreads]; // as in k_cull_emit: the deferred translation row composed by the record's own lane, or w = 0
     const CullParams& p = bp.cull;
     const uint64_t total = *p.total;
     const uint64_t m = total < p.cap ? total : p.cap;
@@ -235,7 +236,12 @@ __global__ void __launch_bounds__(kThreads) k_batch_gather(BatchParams bp, const
     const uint32_t count = m - r0 < kThreads ? static_cast<uint32_t>(m - r0) : kThreads;
     if (threadIdx.x < count) {
         const uint32_t e = entities[r0 + threadIdx.x];
-        s_slot[threadIdx.x] = e < p.n_entities ? p.slot_of_entity[e] : 0u; // (always a member's index)
+        const uint32_t s = e < p.n_entities ? p.slot_of_entity[e] : 0u; // (always a member's index)
+        s_slot[threadIdx.x] = s;
+        if (p.out_world && p.row3.epoch != 0u) {
+            const bool composed = s < p.n_slots && dev::row3_deferred(s, p.row3.rs_word, p.row3.epoch);
+            s_row3[threadIdx.x] = composed ? dev::world_row3(nullptr, s, p.row3.pos, true) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        }
         if (p.out_entities) p.out_entities[r0 + threadIdx.x] = e;
     }
     if (!p.out_world && !p.out_normal) return;
@@ -249,7 +255,12 @@ __global__ void __launch_bounds__(kThreads) k_batch_gather(BatchParams bp, const
         const uint32_t slot = s_slot[k];
         if (slot >= p.n_slots) continue; // (never: a member owns a slot)
         const uint64_t src = 4ull * slot + q, dst = 4ull * (r0 + k) + q;
-        if (out_world) out_world[dst] = world[src];
+        if (out_world) {
+            float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            if (q == 3u && p.row3.epoch != 0u) v = s_row3[k];
+            if (v.w == 0.0f) v = world[src]; // (a composed row has w = 1)
+            out_world[dst] = v;
+        }
         if (out_normal) out_normal[dst] = normal[src];
     }
 }

@@ -4,6 +4,8 @@
 // world matrices resident in HBM the visible set is found where they are: an oriented-box test of each entity's model-space
 // bounds against up to 16 planes, then a stream compaction in ENTITY order.  Items are the entities through slot_of_entity, as
 // bge_debug.hip walks them.  Bandwidth-bound: 4 + 1 + 24 + 64 bytes read per tested entity, 4 + 64 (+ 64) written per visible one.
+// A translation row that the tick has deferred (CullParams::row3) is read from the position array instead: 12 bytes more per entity of
+// such a wave, in the test and in the emit (the matrix line is fetched for rows 0..2 either way).
 //   k_cull_test   one entity per lane; the matrix is loaded only by lanes that are renderable and clean.  One 64-bit ballot word
 //                 per wave, one count per workgroup (256 entities).
 //   k_cull_scan   one workgroup: exclusive sum of the workgroups' counts (64-bit), *total.  A thread sums a run of counts, so
@@ -73,6 +75,7 @@ __global__ void __launch_bounds__(1024) k_cull_scan(CullParams p)
 __global__ void __launch_bounds__(kThreads) k_cull_emit(CullParams p)
 {
     __shared__ uint32_t s_slot[kThreads]; // slot of the workgroup's k-th visible entity
+    __shared__ float4 s_row3[kThreads];   // its translation row where the tick deferred it (CullParams::row3), w = 1; else w = 0: copy the stored one
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const uint32_t count = p.block_sum[blockIdx.x];
     if (count == 0u) return;
@@ -90,7 +93,13 @@ __global__ void __launch_bounds__(kThreads) k_cull_emit(CullParams p)
     if ((mine >> lane) & 1ull) {
         const uint32_t k = before + static_cast<uint32_t>(__popcll(mine & ((1ull << lane) - 1ull)));
         const uint64_t e = blockIdx.x * static_cast<uint64_t>(kThreads) + threadIdx.x;
-        s_slot[k] = p.slot_of_entity[e];
+        const uint32_t s = p.slot_of_entity[e];
+        s_slot[k] = s;
+        // composed by the entity's own lane: consecutive lanes read consecutive positions, and the loads leave before the barrier
+        if (p.out_world && p.row3.epoch != 0u) {
+            const bool composed = dev::row3_deferred(s, p.row3.rs_word, p.row3.epoch);
+            s_row3[k] = composed ? dev::world_row3(nullptr, s, p.row3.pos, true) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        }
         if (p.out_entities && base + k < p.cap) p.out_entities[base + k] = static_cast<uint32_t>(e);
     }
     if (!p.out_world && !p.out_normal) return;
@@ -103,7 +112,12 @@ __global__ void __launch_bounds__(kThreads) k_cull_emit(CullParams p)
         const uint32_t k = piece >> 2, q = piece & 3u;
         if (base + k >= p.cap) break;
         const uint64_t src = 4ull * s_slot[k] + q, dst = 4ull * (base + k) + q;
-        if (out_world) out_world[dst] = world[src];
+        if (out_world) {
+            float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            if (q == 3u && p.row3.epoch != 0u) v = s_row3[k];
+            if (v.w == 0.0f) v = world[src]; // (a composed row has w = 1)
+            out_world[dst] = v;
+        }
         if (out_normal) out_normal[dst] = normal[src];
     }
 }

@@ -5,6 +5,8 @@
 
 #include <cstdint>
 
+#include "bge_kernels.hpp"
+
 namespace bge {
 
 constexpr uint32_t kCullEntitiesPerBlock = 256; // entities one workgroup tests and emits (four ballot words)
@@ -19,6 +21,7 @@ struct CullParams {
     const uint32_t* flag_words;
     const float* bounds;            // [n_entities][6] centre, half extents (null: nobody is renderable)
     const float* world;             // [n_slots][16]
+    Row3View row3;                  // translation rows the tick has deferred are composed from the position array (bge_kernels.hpp)
     const float* normal;            // [n_slots][16] (null unless out_normal is set)
     // scratch
     unsigned long long* ballots;    // [n_blocks * 4] one word per wave: the lanes whose entity is visible

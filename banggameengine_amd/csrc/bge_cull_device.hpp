@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include "bge_cull.hpp"
+#include "bge_device_math.hpp"
 #include "bge_flatten.hpp"
 
 namespace bge {
@@ -18,13 +19,15 @@ __device__ __forceinline__ bool entity_visible(const CullParams& p, uint64_t e)
     const uint32_t s = p.slot_of_entity[e];
     if (s == kNone || s >= p.n_slots) return false;
     const uint32_t f = p.flag_words[s];
+    const bool composed = dev::row3_deferred(s, p.row3.rs_word, p.row3.epoch); // (asked for with the flag word: one round trip)
     if (!(f & kValid) || (f & kTDirty)) return false; // no Transform here (a body kept without one), or limbo / not ticked yet
     const float* b = p.bounds + 6ull * e;
     const float cx = b[0], cy = b[1], cz = b[2], hx = b[3], hy = b[4], hz = b[5];
     if (!(hx >= 0.0f && hy >= 0.0f && hz >= 0.0f && finite_f(hx) && finite_f(hy) && finite_f(hz))) return false;
     if (!(finite_f(cx) && finite_f(cy) && finite_f(cz))) return false;
-    const float4* m = reinterpret_cast<const float4*>(p.world) + 4ull * s;
-    const float4 r0 = m[0], r1 = m[1], r2 = m[2], r3 = m[3];
+    const float4* world = reinterpret_cast<const float4*>(p.world);
+    const float4* m = world + 4ull * s;
+    const float4 r0 = m[0], r1 = m[1], r2 = m[2], r3 = dev::world_row3(world, s, p.row3.pos, composed);
     const float wx = ((cx * r0.x + cy * r1.x) + cz * r2.x) + r3.x;
     const float wy = ((cx * r0.y + cy * r1.y) + cz * r2.y) + r3.y;
     const float wz = ((cx * r0.z + cy * r1.z) + cz * r2.z) + r3.z;

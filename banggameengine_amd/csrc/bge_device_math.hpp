@@ -83,6 +83,25 @@ __device__ __forceinline__ void st4(float* __restrict__ base, uint32_t slot, con
     reinterpret_cast<float4*>(base)[slot] = make_float4(q.x, q.y, q.z, q.w);
 }
 
+// Row 3 of a slot's world matrix for a reader outside the tick, while translation rows may be deferred (bge_kernels.hpp Row3View,
+// DESIGN.md §4.1): the wave's rows word (rs_word[4 * (slot >> 6)]) equal to defer_epoch means that the row is (pos, 1) of the
+// position array — either the tick left it unstored, or it stored these very bits.  defer_epoch == 0 (uniform): nothing is deferred
+// and neither rs_word nor pos is read.  Only for slots that hold a Transform (kValid): the tick stores no row for any other.
+// In two steps, so that a reader can ask for the word together with whatever else it needs of the slot first (its flag word, say)
+// and knows where the row comes from by the time it loads the matrix.
+__device__ __forceinline__ bool row3_deferred(uint32_t slot, const uint32_t* __restrict__ rs_word, uint32_t defer_epoch)
+{
+    return defer_epoch != 0u && rs_word[4u * (slot >> 6)] == defer_epoch;
+}
+__device__ __forceinline__ float4 world_row3(const float4* __restrict__ world, uint32_t slot, const float* __restrict__ pos, bool deferred)
+{
+    if (deferred) {
+        const F3 p = ld3(pos, slot);
+        return make_float4(p.x, p.y, p.z, 1.0f);
+    }
+    return world[4ull * slot + 3u];
+}
+
 // ------------------------------------------------------------------ bx
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 

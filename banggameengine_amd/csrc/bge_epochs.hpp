@@ -1,5 +1,6 @@
-// bge_epochs.hpp — the two epochs the tick kernel's per-wave words (WorldView::rs_word) are compared with.  Host-only, no HIP:
-// tests/test_rest_epoch_cpu.py compiles this header on its own.
+// bge_epochs.hpp — the two epochs the tick kernel's per-wave words (WorldView::rs_word) are compared with, and the bookkeeping of
+// the deferred translation row (Row3State, below).  Host-only, no HIP: tests/test_rest_epoch_cpu.py and tests/test_row3_epoch_cpu.py
+// compile this header on its own.
 //   rows  what word 0 must equal for the translation-row path (TickParams::rs_epoch)
 //   rest  what word 1 must equal for the rest path (TickParams::rest_epoch)
 // A bump invalidates every word of its kind at once.  The rules:
@@ -10,6 +11,7 @@
 //   tick_without_rest()  a tick launched in a variant without the rest path: only `rest` moves.
 // Each returns true when its epoch wrapped (after 2^32 - 1 bumps a word may still hold the new value): the caller zeroes the words.
 #pragma once
+#include <cstddef>
 #include <cstdint>
 
 namespace bge {
@@ -30,6 +32,33 @@ private:
         if (++e != 0) return false;
         e = 1;
         return true;
+    }
+};
+
+// The deferred translation row (DESIGN.md §4.1 "Deferred translation row"): host bookkeeping, no device state of its own.
+// A deferring tick (TickParams::defer_row3) leaves world row 3 of every wave that takes the translation-row path unstored; until
+// the next k_row3_sync, row 3 of slot s is  (pos[s], 1)  if  rs_word[wave(s)].x == pending  and what memory holds otherwise.
+//   pending  the rows epoch the deferring ticks since the last sync ran under; 0: every stored row 3 is current.  Readers that
+//            compose pass it on as their epoch (0 never equals a word of a live path: PathEpochs never hands out 0).
+//   pinned   the world or position array was handed out as a raw pointer (bge_world_device_array): no tick defers again.
+// The one rule the callers keep: take_sync() — and the kernel launch it asks for — comes BEFORE the rows epoch moves, before the
+// words are zeroed, and before anything but a rows-path tick writes pos or world.
+struct Row3State {
+    uint32_t pending = 0;
+    bool pinned = false;
+    // May this tick defer?  Only a translation-row tick of a scene with a single pass and no frozen root: in any other scene a
+    // child of a later pass (or a frozen root) reads a stored matrix from memory inside the tick.
+    bool may_defer(bool rows_path, size_t n_passes, bool any_frozen, bool enabled) const
+    {
+        return rows_path && enabled && !pinned && n_passes == 1 && !any_frozen;
+    }
+    void deferred(uint32_t rows_epoch) { pending = rows_epoch; }
+    // The epoch k_row3_sync has to run with, or 0 when nothing is due; memory counts as current from here on.
+    uint32_t take_sync()
+    {
+        const uint32_t e = pending;
+        pending = 0;
+        return e;
     }
 };
 

@@ -26,6 +26,8 @@
 //   Of those, waves whose 64 flag words are vouched for (WorldView::rs_word words 2 and 3: one clean value, nothing has stored to
 //   flags since) do not read flags either: the wave's 16-B record and one palette entry through wave-uniform addresses stand in
 //   for 64 x 4 B, 56 B per flat body.  k_tick<PHYS, XFORM> only; BGE_FLAG_WORD=0 turns it off.
+//   With TickParams::defer_row3 the translation-row waves do not store row 3 either — it is (pos, 1) of the position they store;
+//   readers compose it, k_row3_sync stores it before anything else may write pos or world: 40 B per flat body.
 //   Waves whose bodies are all asleep (rest word, WorldView::rs_word word 1) read flags, the deactivation record and the contact
 //   word, 8..12 B per body, and store nothing.
 //   The world matrices leave through LDS so that every wave-level store instruction writes 1 KiB of
@@ -269,7 +271,8 @@ __global__ void __launch_bounds__(kTile, NORMAL ? 4 : (AABB ? BGE_AABB_MIN_WAVES
                     st_vel_if(w.vel, slot, v1, vel_xz_changed(v1, v), vel_y_changed(v1, v));
                     const F3 x1{x0.x + v1.x * p.dt, x0.y + v1.y * p.dt, x0.z + v1.z * p.dt};
                     st3(w.pos, slot, x1);
-                    reinterpret_cast<float4*>(w.world)[4ull * slot + 3u] = make_float4(x1.x, x1.y, x1.z, 1.0f);
+                    // (deferred: the row is (x1, 1) of the position just stored; readers compose it, k_row3_sync stores it — DESIGN.md §4.1)
+                    if (p.defer_row3 == 0u) reinterpret_cast<float4*>(w.world)[4ull * slot + 3u] = make_float4(x1.x, x1.y, x1.z, 1.0f);
                     return;
                 }
             }
@@ -603,7 +606,10 @@ __global__ void __launch_bounds__(kTile, NORMAL ? 4 : (AABB ? BGE_AABB_MIN_WAVES
         // rows 0..2 in memory are what bx_mtx_srt would store; row 3 is (pos, 1) (bx::mtxSRT, m[12..15]).  16 B at a 64-B stride,
         // plain stores: tools/ubench_world_rows.hip measured non-temporal ones twice as slow for this shape, and the host keeps
         // the path off where the working set outgrows the Infinity Cache (16 M slots: partially written lines cost 2.7x whole ones)
-        if (valid) reinterpret_cast<float4*>(w.world)[4ull * slot + 3u] = make_float4(pos.x, pos.y, pos.z, 1.0f);
+        // unless the tick defers the row, which writes no partial line at all
+        // With p.defer_row3 not even that: pos in memory is this lane's pos (stored above if it moved), and the wave's rows word stays
+        // current, which is what tells every reader to take the row from there (world_row3)
+        if (valid && p.defer_row3 == 0u) reinterpret_cast<float4*>(w.world)[4ull * slot + 3u] = make_float4(pos.x, pos.y, pos.z, 1.0f);
         f &= ~kTDirty; // transform->dirty = false
         if (kRowsPath && PHYS && p.rest_epoch != 0u) {
             // rows 0..2 were current and row 3 is stored: the rest word says so when every lane ends the tick at rest (written only when it changes)
@@ -841,6 +847,35 @@ __global__ void k_gather_rows(const uint32_t* __restrict__ slot_of_entity, const
     }
 }
 
+// k_gather_rows of the world matrices with the deferred translation rows composed (launch_gather_world).  A slot without a
+// Transform (a body kept without one) has no row the tick would have stored: memory as it is.
+__global__ void k_gather_world(const uint32_t* __restrict__ slot_of_entity, const uint32_t* __restrict__ index, uint64_t first, uint64_t count,
+                               const float4* __restrict__ world, const uint32_t* __restrict__ flags, Row3View d, float4* __restrict__ stage)
+{
+    const uint64_t t = blockIdx.x * static_cast<uint64_t>(blockDim.x) + threadIdx.x;
+    const uint64_t i = t >> 2;
+    if (i >= count) return;
+    const uint32_t r = static_cast<uint32_t>(t & 3u);
+    const uint32_t slot = slot_of_entity[index ? index[i] : first + i];
+    float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (slot != kNone) {
+        v = (r == 3u && (flags[slot] & kValid)) ? world_row3(world, slot, d.pos, row3_deferred(slot, d.rs_word, d.epoch)) : world[4ull * slot + r];
+    }
+    stage[t] = v;
+}
+
+// The deferred translation rows into memory: one workgroup per tile, the wave's rows word through a wave-uniform address as in k_tick.
+// What a deferring tick skipped, lane for lane: valid slots of waves whose word equals `epoch` get row 3 = (pos, 1).
+__global__ void __launch_bounds__(kTile) k_row3_sync(WorldView w, uint32_t epoch)
+{
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (w.rs_word[4u * (blockIdx.x * 4u + wave)] != epoch) return;
+    const uint32_t slot = blockIdx.x * kTile + threadIdx.x;
+    if (!(w.flags[slot] & kValid)) return;
+    const F3 x = ld3(w.pos, slot);
+    reinterpret_cast<float4*>(w.world)[4ull * slot + 3u] = make_float4(x.x, x.y, x.z, 1.0f);
+}
+
 // Body upload: type/shape bits + dirty, inverse mass, AABB half extents, group/mask.
 __global__ void k_scatter_bodies(const uint32_t* __restrict__ slot_of_entity, const uint32_t* __restrict__ index,
                                  uint64_t first, uint64_t count,
@@ -958,31 +993,40 @@ __global__ void k_dirty_bytes(const uint32_t* __restrict__ slot_of_entity, uint6
 }
 
 // Compact root rows (12 floats, see store_root): 3 lanes per root, 16 B each.
-__global__ void k_pack_roots_compact(uint64_t n_roots, const uint32_t* __restrict__ root_slots, const float* __restrict__ world,
+// (a root's slot holds a Transform: its deferred translation row is composed, Row3View)
+__global__ void k_pack_roots_compact(uint64_t n_roots, const uint32_t* __restrict__ root_slots, const float* __restrict__ world, Row3View d,
                                      float4* __restrict__ dst)
 {
     const uint64_t t = blockIdx.x * static_cast<uint64_t>(blockDim.x) + threadIdx.x;
     const uint64_t r = t / 3;
     if (r >= n_roots) return;
     const uint32_t q = static_cast<uint32_t>(t - 3 * r);
-    const float* m = world + 16ull * root_slots[r];
+    const uint32_t slot = root_slots[r];
+    const float* m = world + 16ull * slot;
     float v[4];
 #pragma unroll
     for (uint32_t k = 0; k < 4; ++k) {
         const uint32_t cidx = 4u * q + k; // position in the compact row -> element of the 4x4 (skip column 3)
         v[k] = m[cidx + cidx / 3u];
     }
+    if (q == 2u) { // compact floats 9..11 are m[12..14]
+        const float4 r3 = world_row3(reinterpret_cast<const float4*>(world), slot, d.pos, row3_deferred(slot, d.rs_word, d.epoch));
+        v[1] = r3.x;
+        v[2] = r3.y;
+        v[3] = r3.z;
+    }
     dst[t] = make_float4(v[0], v[1], v[2], v[3]);
 }
 
 // Full 4x4 rows (the torch.distributed path of sharding.RootTable): 4 lanes per root, 16 B each.
-__global__ void k_pack_roots(uint64_t n_roots, const uint32_t* __restrict__ root_slots, const float4* __restrict__ world,
+__global__ void k_pack_roots(uint64_t n_roots, const uint32_t* __restrict__ root_slots, const float4* __restrict__ world, Row3View d,
                              float4* __restrict__ dst)
 {
     const uint64_t t = blockIdx.x * static_cast<uint64_t>(blockDim.x) + threadIdx.x;
     const uint64_t r = t >> 2;
     if (r >= n_roots) return;
-    dst[t] = world[4ull * root_slots[r] + (t & 3u)];
+    const uint32_t slot = root_slots[r];
+    dst[t] = (t & 3u) == 3u ? world_row3(world, slot, d.pos, row3_deferred(slot, d.rs_word, d.epoch)) : world[4ull * slot + (t & 3u)];
 }
 
 // ---- trigger volumes (ghost objects): AABB of the ghost at its entity's Transform, taken BEFORE the tick integrates
@@ -1188,6 +1232,15 @@ hipError_t launch_gather_rows(hipStream_t stream, const uint32_t* slot_of_entity
     return hipGetLastError();
 }
 
+hipError_t launch_gather_world(hipStream_t stream, const uint32_t* slot_of_entity, uint64_t first, uint64_t count, const WorldView& w,
+                               const Row3View& d, void* stage, const uint32_t* index)
+{
+    if (count == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_gather_world, grid_for(count * 4, 256), dim3(256), 0, stream, slot_of_entity, index, first, count,
+                       reinterpret_cast<const float4*>(w.world), w.flags, d, static_cast<float4*>(stage));
+    return hipGetLastError();
+}
+
 hipError_t launch_scatter_bodies(hipStream_t stream, const uint32_t* slot_of_entity, uint64_t first, uint64_t count,
                                  const uint32_t* type_bits, const float* inv_mass, const float* half_extent3,
                                  const uint32_t* group, const uint32_t* mask, const uint32_t* filter_class, const WorldView& w,
@@ -1375,17 +1428,24 @@ hipError_t launch_trigger_ghost_pairs(hipStream_t stream, uint32_t n_triggers, c
     return hipGetLastError();
 }
 
-hipError_t launch_pack_roots(hipStream_t stream, uint64_t n_roots, const uint32_t* root_slots, const float* world, float* dst,
-                             bool compact)
+hipError_t launch_pack_roots(hipStream_t stream, uint64_t n_roots, const uint32_t* root_slots, const float* world, const Row3View& d,
+                             float* dst, bool compact)
 {
     if (n_roots == 0) return hipSuccess;
     if (compact) {
-        hipLaunchKernelGGL(k_pack_roots_compact, grid_for(n_roots * 3, 256), dim3(256), 0, stream, n_roots, root_slots, world,
+        hipLaunchKernelGGL(k_pack_roots_compact, grid_for(n_roots * 3, 256), dim3(256), 0, stream, n_roots, root_slots, world, d,
                            reinterpret_cast<float4*>(dst));
     } else {
         hipLaunchKernelGGL(k_pack_roots, grid_for(n_roots * 4, 256), dim3(256), 0, stream, n_roots, root_slots,
-                           reinterpret_cast<const float4*>(world), reinterpret_cast<float4*>(dst));
+                           reinterpret_cast<const float4*>(world), d, reinterpret_cast<float4*>(dst));
     }
+    return hipGetLastError();
+}
+
+hipError_t launch_row3_sync(hipStream_t stream, const WorldView& w, uint32_t n_tiles, uint32_t epoch)
+{
+    if (n_tiles == 0 || epoch == 0u) return hipSuccess;
+    hipLaunchKernelGGL(k_row3_sync, dim3(n_tiles), dim3(kTile), 0, stream, w, epoch);
     return hipGetLastError();
 }
 

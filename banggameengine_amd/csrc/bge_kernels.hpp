@@ -64,6 +64,15 @@ struct WorldView {
                               //             it or an ancestor is dirty, and Scene::RemoveTransform marks nobody (tiles with kHdrFrozen look here)
 };
 
+// What a reader of world matrices needs to compose a deferred translation row (bge_device_math.hpp world_row3; bge_epochs.hpp
+// Row3State): row 3 of slot s is (pos[s], 1) while rs_word[4 * (s >> 6)] == epoch, and what the world array holds otherwise.
+// epoch 0 (no live word is ever 0): nothing is deferred, the other two members are not read.
+struct Row3View {
+    const uint32_t* rs_word;
+    const float* pos;
+    uint32_t epoch;
+};
+
 // per-slot contact word (the flag word has no bit left)
 constexpr uint32_t kCiCapsule = 1u;      // collider is a capsule (else a box)
 constexpr uint32_t kCiGroundMask = 2u;   // the body's mask contains the ground's group (btBroadphaseProxy::StaticFilter = 2)
@@ -217,12 +226,18 @@ struct TickParams {
     uint32_t flag_word; // non-zero: a translation-row wave whose flag epoch (WorldView::rs_word word 3) equals rs_epoch takes its flag
                         // word from the record and does not read flags; 0: every wave reads them (BGE_FLAG_WORD=0).  Words 2 and 3
                         // are kept either way
+    uint32_t defer_row3; // non-zero: a wave on the translation-row path does not store row 3 either — it is (pos, 1) of the position it
+                         // has just stored, readers compose it (Row3View) and k_row3_sync stores it before the rows epoch moves.  The
+                         // full path stores all four rows as ever.  Only with rs_epoch != 0, in a scene of one pass without frozen roots
     uint32_t no_repose; // this tick is the 2nd..nth sub-step of ONE stepSimulation call (bge_world_step_simulation): dirty flags
                         // do not re-pose bodies — SyncKinematicBodiesToPhysics ran once, before the first sub-step
 };
 
 // flags: bit0 physics, bit1 transforms, bit2 / bit5 aabb, bit4 normal matrices (bge_tick_flags)
 hipError_t launch_tick(hipStream_t stream, const WorldView& w, const TickParams& p, uint32_t n_tiles, uint32_t flags);
+
+// Stores the deferred translation rows: in every wave whose rows word equals `epoch`, valid slots get row 3 = (pos, 1)
+hipError_t launch_row3_sync(hipStream_t stream, const WorldView& w, uint32_t n_tiles, uint32_t epoch);
 
 // PhysicsSystem::Update around a stepSimulation call that runs ZERO sub-steps (accumulated time < fixedStep): re-pose dirty
 // bodies, write Dynamic poses back, mark them dirty — no integration (bge_world_step_simulation)
@@ -246,6 +261,9 @@ hipError_t launch_scatter_rows(hipStream_t stream, const uint32_t* slot_of_entit
                                const uint32_t* index = nullptr, uint32_t need_bits = 0, bool vel_blocks = false);
 hipError_t launch_gather_rows(hipStream_t stream, const uint32_t* slot_of_entity, uint64_t first, uint64_t count,
                               uint32_t width, const void* src, void* stage, const uint32_t* index = nullptr, bool vel_blocks = false);
+// launch_gather_rows of the world matrices while translation rows are deferred (d.epoch != 0): row 3 of a slot with a Transform is composed
+hipError_t launch_gather_world(hipStream_t stream, const uint32_t* slot_of_entity, uint64_t first, uint64_t count, const WorldView& w,
+                               const Row3View& d, void* stage, const uint32_t* index = nullptr);
 hipError_t launch_scatter_bodies(hipStream_t stream, const uint32_t* slot_of_entity, uint64_t first, uint64_t count,
                                  const uint32_t* type_bits, const float* inv_mass, const float* half_extent3,
                                  const uint32_t* group, const uint32_t* mask, const uint32_t* filter_class, const WorldView& w,
@@ -289,7 +307,7 @@ hipError_t launch_trigger_diff(hipStream_t stream, const TriggerDiff& d);
 hipError_t launch_trigger_table_build(hipStream_t stream, uint64_t* table, uint32_t log2_cap, const uint64_t* keys, uint32_t n, uint32_t* header);
 
 // compact: 12 floats per root (4x3, the constant fourth column dropped) instead of 16
-hipError_t launch_pack_roots(hipStream_t stream, uint64_t n_roots, const uint32_t* root_slots, const float* world, float* dst,
-                             bool compact = false);
+hipError_t launch_pack_roots(hipStream_t stream, uint64_t n_roots, const uint32_t* root_slots, const float* world, const Row3View& d,
+                             float* dst, bool compact = false);
 
 } // namespace bge

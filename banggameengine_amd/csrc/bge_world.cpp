@@ -238,12 +238,27 @@ struct bge_world {
     // of a variant without the rest path moves the rest epoch alone.
     DevBuf rs_word;
     bge::PathEpochs epochs;
+    // The deferred translation row (bge_epochs.hpp Row3State): a tick with TickParams::defer_row3 leaves row 3 of the
+    // translation-row waves unstored.  ensure_row3_current() stores them (k_row3_sync) and runs BEFORE the rows epoch moves, before the
+    // words are zeroed and before anything but a translation-row tick writes pos or world — words_clear() and epochs_edit() see to
+    // the first two themselves; a call that writes pos before its epochs_edit() (upload_trs, bge_world_set_topology) and a tick
+    // without the translation-row path call it first.  Readers that run every frame compose instead (row3_view()).
+    bge::Row3State row3;
+    bge::Row3View row3_view() const { return bge::Row3View{view.rs_word, view.pos, row3.pending}; }
+    hipError_t ensure_row3_current()
+    {
+        const uint32_t due = row3.take_sync();
+        if (due == 0u || !rs_word.p) return hipSuccess;
+        return bge::launch_row3_sync(stream, view, flat.n_tiles_ticked, due);
+    }
     void words_clear()
     {
+        (void)ensure_row3_current();
         if (rs_word.p) (void)hipMemsetAsync(rs_word.p, 0, rs_word.bytes, stream);
     }
     void epochs_edit()
     {
+        (void)ensure_row3_current();
         if (epochs.host_edit()) words_clear();
     }
     // Dynamic boxes on the Static / Kinematic box colliders of the scene (round 3, bge_contact.hip): off by default, like the plane
@@ -584,6 +599,14 @@ int upload_rows(bge_world* w, uint64_t first, uint64_t count, const void* host, 
 int download_rows(bge_world* w, uint64_t first, uint64_t count, const SlotBuf& src, void* host, const uint32_t* dev_index = nullptr)
 {
     const size_t bytes = src.bytes_for(count);
+    if (&src == &w->world && w->row3.pending != 0u) {
+        // translation rows are deferred: the gather composes them (a frame that ticks and downloads does not pay for the store as well)
+        HIP_TRY(w->stage.ensure(bytes));
+        HIP_TRY(bge::launch_gather_world(w->stream, w->slot_of_entity.as<uint32_t>(), first, count, w->view, w->row3_view(), w->stage.p, dev_index));
+        HIP_TRY(hipMemcpyAsync(host, w->stage.p, bytes, hipMemcpyDeviceToHost, w->stream));
+        HIP_TRY(hipStreamSynchronize(w->stream));
+        return BGE_OK;
+    }
     if (w->flat.identity && !dev_index && !src.vel_blocks) {
         // flat scene: slot == entity index, the rows are already contiguous in entity order
         HIP_TRY(hipMemcpyAsync(host, src.as<char>() + src.bytes_for(first), bytes, hipMemcpyDeviceToHost, w->stream));
@@ -1295,6 +1318,7 @@ try {
     if (!w) return fail(BGE_ERR_INVALID, "world is NULL");
     if (n >= 0xfffffff0ull) return fail(BGE_ERR_INVALID, "too many entities (%llu)", (unsigned long long)n);
     DeviceGuard guard(w->device);
+    HIP_TRY(w->ensure_row3_current()); // (the carry below moves stored matrices to new slots, and the words are zeroed)
 
     // An entity that loses its Transform while its body exists keeps a slot for the body (kValid clear): the reference keeps
     // stepping that Bullet body (PhysicsSystem.cpp:389-393).  To the hierarchy it is an entity without a Transform: it is
@@ -1562,6 +1586,8 @@ static int upload_trs(bge_world* w, const Entities& e, const float* pos3, const 
     return with_entities(
         w, e, [&] { return e.count ? BGE_OK : kNothingToDo; },
         [&](const uint32_t* di) -> int {
+            // (Transform::world keeps the old translation until the next TransformSystem::Update: stored before pos is overwritten)
+            HIP_TRY(w->ensure_row3_current());
             for (auto [host, dst] : {std::pair{pos3, &w->pos}, {euler3, &w->euler}, {scale3, &w->scale}}) {
                 if (!host) continue;
                 if (int rc = upload_rows(w, e.first, e.count, host, *dst, 0, di, bge::kValid)) return rc;
@@ -1953,13 +1979,22 @@ int tick_impl(bge_world* w, uint32_t ticks, float dt, const float gravity[3], ui
     if (const char* e = std::getenv("BGE_NT_STORES")) nt_out = std::atoi(e) != 0;
     // Translation-row fast path of the tick kernel (WorldView::rs_word): only in the variants it exists in (transforms, with or
     // without the default physics step, nothing else), and only where no other kernel of the tick writes euler, scale, world
-    // or quat (ground plane, obstacles, Dynamic contacts).  Only while the working set fits the Infinity Cache: beyond it a
-    // 16-B store into every 64-B matrix costs more than the whole matrix (tools/ubench_world_rows.hip: 16 M slots, 2.7x).
+    // or quat (ground plane, obstacles, Dynamic contacts).  Only while the working set fits the Infinity Cache, unless the
+    // tick defers the row (below): beyond it a 16-B store into every 64-B matrix costs more than the whole matrix
+    // (tools/ubench_world_rows.hip: 16 M slots, 2.7x).
     // BGE_WORLD_ROWS=0 turns it off (A/B runs); a tick without it moves the epoch on, so that no word outlives what it vouched for.
     const bool contacts = phys && (w->ground_plane || w->static_contacts || w->dynamic_contacts);
-    bool rows_path = xform && !contacts && !nt_out &&
+    // Deferred translation row (bge_epochs.hpp Row3State): translation-row waves do not store row 3 either; the readers that run every
+    // frame compose it, everything else stores it first (bge_world::ensure_row3_current).  BGE_DEFER_ROW3=0 turns it off (A/B runs).
+    // A deferring tick writes no partial matrix line, so the Infinity Cache limit above does not apply to it (the first, full-path
+    // ticks keep their non-temporal stores).
+    bool defer_env = true;
+    if (const char* e = std::getenv("BGE_DEFER_ROW3")) defer_env = std::atoi(e) != 0;
+    const bool can_defer = w->row3.may_defer(true, w->flat.pass_tile_begin.size() - 1, w->any_frozen, defer_env);
+    bool rows_path = xform && !contacts && (!nt_out || can_defer) &&
                      !(flags & (BGE_TICK_AABBS | BGE_TICK_BROADPHASE | BGE_TICK_NORMAL_MATRICES | BGE_TICK_BULLET_BASIS | BGE_TICK_GATHER_ROOTS));
     if (const char* e = std::getenv("BGE_WORLD_ROWS")) rows_path = rows_path && std::atoi(e) != 0;
+    const bool defer_row3 = rows_path && can_defer;
     // Vouched waves of the translation-row path (WorldView::rs_word, words 2 and 3): a wave whose 64 flag words are known to be one
     // clean value skips the flags read.  The words are kept whether or not the block runs; BGE_FLAG_WORD=0 turns the block off (A/B runs).
     bool flag_word = rows_path;
@@ -1990,8 +2025,14 @@ int tick_impl(bge_world* w, uint32_t ticks, float dt, const float gravity[3], ui
         p.nt_out = nt_out ? 1u : 0u;
         p.no_repose = sub.no_repose ? 1u : 0u;
         p.flag_word = flag_word ? 1u : 0u;
+        // (a tick without the translation-row path may write pos or world from any of its kernels, and moves the rows epoch)
+        if (!rows_path) HIP_TRY(w->ensure_row3_current());
         if (rows_path) p.rs_epoch = w->epochs.rows;
         else if (w->epochs.tick_without_rows()) w->words_clear();
+        if (defer_row3) {
+            p.defer_row3 = 1u;
+            w->row3.deferred(w->epochs.rows);
+        }
         if (rest_path) p.rest_epoch = w->epochs.rest;
         else if (w->epochs.tick_without_rest()) w->words_clear();
         w->fill_sleep(p);
@@ -2113,6 +2154,7 @@ try {
         // no sub-step: no collision detection, no integration — but the calls around stepSimulation still run
         if (!w->has_topology) return fail(BGE_ERR_STATE, "bge_world_set_topology has not been called");
         DeviceGuard guard(w->device);
+        HIP_TRY(w->ensure_row3_current());
         HIP_TRY(bge::launch_pose_only(w->stream, w->view, ticked_slots(w), (flags & BGE_TICK_BULLET_BASIS) != 0));
         w->maybe_dirty = true;
         w->epochs_edit(); // (k_pose_only re-poses: it writes quat, euler, velocities, and marks every Dynamic Transform dirty)
@@ -2486,6 +2528,7 @@ try {
     if (!w) return fail(BGE_ERR_INVALID, "NULL argument");
     if (!(linear_threshold >= 0.0f) || !(angular_threshold >= 0.0f) || !(seconds >= 0.0f))
         return fail(BGE_ERR_INVALID, "sleeping thresholds must be >= 0");
+    DeviceGuard guard(w->device);
     w->sleep_lin = linear_threshold;
     w->sleep_ang = angular_threshold;
     w->sleep_time = seconds;
@@ -3478,6 +3521,7 @@ int cull_params(bge_world* w, const bge_cull_desc* desc, bool want_normal, bge::
     p.flag_words = w->view.flags;
     p.bounds = w->bounds.as<float>();
     p.world = w->view.world;
+    p.row3 = w->row3_view();
     const uint64_t blocks = (p.n_entities + bge::kCullEntitiesPerBlock - 1) / bge::kCullEntitiesPerBlock;
     p.n_blocks = static_cast<uint32_t>(blocks);
     HIP_TRY(w->cull_ballots.ensure(std::max<uint64_t>(blocks, 1) * (bge::kCullEntitiesPerBlock / 64) * 8));
@@ -3713,7 +3757,7 @@ try {
     if (!w->has_topology) return fail(BGE_ERR_STATE, "bge_world_set_topology has not been called");
     DeviceGuard guard(w->device);
     float* dst = dst_device ? static_cast<float*>(dst_device) : w->root_worlds.as<float>();
-    HIP_TRY(bge::launch_pack_roots(w->stream, w->flat.root_slots.size(), w->root_slots.as<uint32_t>(), w->world.as<float>(), dst));
+    HIP_TRY(bge::launch_pack_roots(w->stream, w->flat.root_slots.size(), w->root_slots.as<uint32_t>(), w->world.as<float>(), w->row3_view(), dst));
     return BGE_OK;
 }
 BGE_CATCH_ALL("bge_world_pack_roots")
@@ -3725,10 +3769,20 @@ try {
     uint64_t n = 0;
     void* p = nullptr;
     switch (which) {
-    case BGE_ARRAY_WORLD: p = w->world.p; n = w->flat.n_slots; break;
+    case BGE_ARRAY_WORLD:
+    case BGE_ARRAY_POSITION: {
+        // A raw pointer sees memory, not a composed row — and a holder of the position pointer could move a body without the world
+        // knowing: the deferred rows are stored now and no tick of this world defers again (bge_epochs.hpp Row3State::pinned)
+        DeviceGuard guard(w->device);
+        w->row3.pinned = true;
+        HIP_TRY(w->ensure_row3_current());
+        HIP_TRY(hipStreamSynchronize(w->stream));
+        p = which == BGE_ARRAY_WORLD ? w->world.p : w->pos.p;
+        n = w->flat.n_slots;
+        break;
+    }
     case BGE_ARRAY_ROOT_WORLDS: p = w->root_worlds.p; n = w->flat.root_slots.size(); break;
     case BGE_ARRAY_SLOT_OF_ENTITY: p = w->slot_of_entity.p; n = w->flat.n_entities; break;
-    case BGE_ARRAY_POSITION: p = w->pos.p; n = w->flat.n_slots; break;
     case BGE_ARRAY_PAIRS: {
         bge::Broadphase& bp = w->pairs_from_slab ? w->slab_broadphase : w->broadphase;
         DeviceGuard guard(w->device);
@@ -3780,7 +3834,7 @@ try {
     float* send = nullptr;
     int rc = w->comm.begin_frame(w->stream, &send);
     if (rc != BGE_OK) return fail(rc, "%s", w->comm.error());
-    HIP_TRY(bge::launch_pack_roots(w->stream, w->flat.root_slots.size(), w->root_slots.as<uint32_t>(), w->world.as<float>(), send,
+    HIP_TRY(bge::launch_pack_roots(w->stream, w->flat.root_slots.size(), w->root_slots.as<uint32_t>(), w->world.as<float>(), w->row3_view(), send,
                                    /*compact=*/true));
     rc = w->comm.gather(w->stream, table_device);
     if (rc != BGE_OK) return fail(rc, "%s", w->comm.error());

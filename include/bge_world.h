@@ -80,10 +80,19 @@ enum bge_tick_flags {
 enum bge_device_array {
     BGE_ARRAY_WORLD = 0,          /* float[n_slots][16], slot order; READ-ONLY to consumers: a tick rewrites only the
                                      translation row of a matrix whose rotation rows it knows to be current,
-                                     so a value written here into rows 0..2 may persist */
+                                     so a value written here into rows 0..2 may persist.  Asking for this pointer (or for
+                                     BGE_ARRAY_POSITION) PINS the world: a tick of a flat scene otherwise leaves the
+                                     translation row of such a matrix unstored (it is a copy of the position; downloads, the
+                                     visible list, draw batches and bge_world_pack_roots compose it).  The call stores what
+                                     is outstanding, waits for it, and no later tick of this world defers a row, so the
+                                     memory behind the pointer is complete after every tick, at the cost of that store
+                                     (about three times the time of a flat tick at 1 M bodies).  Consumers
+                                     that can use bge_world_visible_device / bge_world_draw_batches_device /
+                                     bge_world_pack_roots instead keep the cheaper tick. */
     BGE_ARRAY_ROOT_WORLDS = 1,    /* float[n_roots][16], filled by bge_world_pack_roots */
     BGE_ARRAY_SLOT_OF_ENTITY = 2, /* uint32[n_entities], BGE_NO_PARENT where the entity has no Transform */
-    BGE_ARRAY_POSITION = 3,       /* float[n_slots][3] */
+    BGE_ARRAY_POSITION = 3,       /* float[n_slots][3]; pins the world like BGE_ARRAY_WORLD (a write through this pointer
+                                     must not reach a matrix before the next tick) */
     BGE_ARRAY_PAIRS = 4,          /* uint32[pair_capacity][2], entity indices */
     BGE_ARRAY_NORMAL = 5          /* float[n_slots][16] normal matrices, slot order (after a NORMAL_MATRICES tick) */
 };

@@ -11,6 +11,10 @@ count) to roughly 1 %, 10 % and 100 % visible.  Per view:
            host, wall time (median of three at 1 M, of two beyond).
 Bytes are the algorithmic ones: 4 (slot) + 24 (bounds) + 1 (dirty) + 64 (matrix) read per entity, 4 + 64 written
 per visible entity; the rate is set against the 8 TB/s HBM peak.  One JSON line per row.
+
+--frames K: a frame instead — N flat Dynamic bodies falling, per frame one bge_world_tick and one bge_world_visible_device (10 % and
+100 % visible), HIP events around five regions of K frames, the median region / K; and, the same way, K ticks alone and K queries
+alone (the queries right after a tick, so with whatever the tick leaves to its readers).  BGE_WORLD_LIB gives the A/B.
 """
 import argparse
 import json
@@ -123,14 +127,63 @@ def measure(n, label):
             print(json.dumps(row), flush=True)
 
 
+def measure_frames(n, label, frames):
+    rng = np.random.default_rng(9)
+    stream = torch.cuda.Stream()
+    pos = rng.uniform(-EXTENT, EXTENT, (n, 3)).astype(F)
+    vel = np.zeros((n, 3), F)
+    vel[:, 1] = rng.uniform(-3, -1, n).astype(F)  # (faster than the sleeping threshold from the start)
+    with B.World(device=0, stream=stream.cuda_stream) as w:
+        w.set_topology(np.full(n, W.NO_PARENT, np.uint32))
+        w.upload_trs(pos, rng.uniform(-3, 3, (n, 3)).astype(F), rng.uniform(0.25, 4, (n, 3)).astype(F))
+        w.upload_bodies(np.ones(n, np.uint8))
+        w.upload_bounds(rng.uniform(-1, 1, (n, 3)).astype(F), rng.uniform(0.05, 2, (n, 3)).astype(F))
+        w.tick()
+        w.set_velocities(vel)
+        w.tick(ticks=20)
+        d_total = torch.zeros(1, dtype=torch.int64, device="cuda:0")
+        d_ent = torch.empty(n, dtype=torch.int32, device="cuda:0")
+        d_world = torch.empty((n, 16), dtype=torch.float32, device="cuda:0")
+        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+
+        def regions(body):
+            for _ in range(10):
+                body()
+            w.sync()
+            out = []
+            for _ in range(5):
+                ev0.record(stream)
+                for _ in range(frames):
+                    body()
+                ev1.record(stream)
+                ev1.synchronize()
+                out.append(ev0.elapsed_time(ev1) * 1e3 / frames)
+            return [round(x, 2) for x in out]
+
+        for target in (0.10, 1.00):
+            planes = planes_of(tune(w, n, target)) if target < 1.0 else None
+            cull = lambda: w.visible_device(planes, d_ent.data_ptr(), d_world.data_ptr(), 0, n, d_total.data_ptr())
+            frame = regions(lambda: (w.tick(), cull()))
+            tick = regions(lambda: w.tick())
+            query = regions(cull)
+            print(json.dumps({"label": label, "entities": n, "share": round(w.visible_count(planes) / n, 4), "frames_per_region": frames,
+                              "frame_us": float(np.median(frame)), "frame_us_all": frame, "tick_us": float(np.median(tick)),
+                              "tick_us_all": tick, "query_us": float(np.median(query)), "query_us_all": query,
+                              "lib": os.environ.get("BGE_WORLD_LIB", "in-tree")}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="1048576,4194304")
     ap.add_argument("--label", default="")
+    ap.add_argument("--frames", type=int, default=0, help="measure frames of one tick and one query instead (see above)")
     args = ap.parse_args()
     torch.cuda.set_device(0)
     for n in (int(s) for s in args.sizes.split(",")):
-        measure(n, args.label)
+        if args.frames:
+            measure_frames(n, args.label, args.frames)
+        else:
+            measure(n, args.label)
 
 
 if __name__ == "__main__":

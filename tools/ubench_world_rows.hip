@@ -12,6 +12,7 @@
 //   f  fast path, vel in per-wave component blocks (ld_vel / st_vel_changed): only vel.y changes, only vel.y is stored
 //   g  as f with all three components stored (st_vel): the layout alone, without the skipped stores
 //   h  as f without the per-lane flags load: one 16-B per-wave record through a wave-uniform address stands in for it
+//   i  as h without the row-3 store: the translation row stays in the position array, no matrix line is dirtied
 // Each kernel runs `reps` times back to back between two events after a warm-up; one JSON line per (kernel, store
 // policy, size).  Built by tools/ubench_world_rows.sh; no part of the product library.
 #include <hip/hip_runtime.h>
@@ -216,6 +217,27 @@ __global__ void __launch_bounds__(kBlock, 8) k_flat_row3_wave(Soa s, const uint4
     }
 }
 
+// (i) as (h) with the translation row left where st3 has just put it: no store into the matrix array at all
+__global__ void __launch_bounds__(kBlock, 8) k_flat_norow_wave(Soa s, const uint4* __restrict__ words, uint32_t epoch, uint32_t n_slots, float dt)
+{
+    const uint32_t slot = blockIdx.x * kBlock + threadIdx.x;
+    const uint32_t wave = blockIdx.x * 4u + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint4 w = words[wave];
+    if (((w.x ^ epoch) | (w.w ^ epoch)) != 0u) return;
+    const uint32_t f = w.z;
+    F3 pos = ld3(s.pos, slot), vel = ld_vel(s.vel, slot);
+    if (f & 1u) {
+        const F3 old = vel;
+        vel.y = vel.y + -9.81f * dt;
+        const bool cxz = vel_xz_changed(vel, old), cy = vel_y_changed(vel, old);
+        pos.x = pos.x + vel.x * dt;
+        pos.y = pos.y + vel.y * dt;
+        pos.z = pos.z + vel.z * dt;
+        st_vel_if(s.vel, slot, vel, cxz, cy);
+        st3(s.pos, slot, pos);
+    }
+}
+
 template <typename F> float time_us(F launch, int warm, int reps)
 {
     hipEvent_t a, b;
@@ -266,6 +288,14 @@ template <bool NT> void run_size(uint32_t n, int reps, Soa s, const uint4* words
     report("f_flat_row3_vy", NT, n, time_us([&] { k_flat_row3_vy<NT><<<g_slot, blk>>>(s, n, 1.0f / 60.0f); }, warm, reps), 60.0);
     report("h_flat_row3_wave", NT, n, time_us([&] { k_flat_row3_wave<NT><<<g_slot, blk>>>(s, words, kEpoch, n, 1.0f / 60.0f); }, warm, reps), 56.25);
     report("f_flat_row3_vy", NT, n, time_us([&] { k_flat_row3_vy<NT><<<g_slot, blk>>>(s, n, 1.0f / 60.0f); }, warm, reps), 60.0);
+    // (i) between (h)s: (h), (i), (h), (i), (h).  (i) stores nothing into the matrices, so it has no non-temporal form: plain pass only
+    if (!NT) {
+        report("h_flat_row3_wave", NT, n, time_us([&] { k_flat_row3_wave<NT><<<g_slot, blk>>>(s, words, kEpoch, n, 1.0f / 60.0f); }, warm, reps), 56.25);
+        report("i_flat_norow_wave", NT, n, time_us([&] { k_flat_norow_wave<<<g_slot, blk>>>(s, words, kEpoch, n, 1.0f / 60.0f); }, warm, reps), 40.25);
+        report("h_flat_row3_wave", NT, n, time_us([&] { k_flat_row3_wave<NT><<<g_slot, blk>>>(s, words, kEpoch, n, 1.0f / 60.0f); }, warm, reps), 56.25);
+        report("i_flat_norow_wave", NT, n, time_us([&] { k_flat_norow_wave<<<g_slot, blk>>>(s, words, kEpoch, n, 1.0f / 60.0f); }, warm, reps), 40.25);
+        report("h_flat_row3_wave", NT, n, time_us([&] { k_flat_row3_wave<NT><<<g_slot, blk>>>(s, words, kEpoch, n, 1.0f / 60.0f); }, warm, reps), 56.25);
+    }
     CK(hipGetLastError());
     CK(hipDeviceSynchronize());
 }

@@ -4,7 +4,8 @@
 # 1. event timing of every kernel, plain and non-temporal stores, 1 M and 16 M slots  -> times.jsonl
 # 2. rocprofv3 --kernel-trace --stats                                                      -> stats/
 # 3. rocprofv3 --pmc FETCH_SIZE, then --pmc WRITE_SIZE, each a run of its own              -> pmc_FETCH_SIZE/, pmc_WRITE_SIZE/
-# then a per-kernel digest of all three (tools/ubench_world_rows_digest.py), which also prints the gate of kernel (h) against (f).
+# then a per-kernel digest of all three (tools/ubench_world_rows_digest.py), which also prints the gates of kernel (h) against (f)
+# and of kernel (i) against (h).
 set -o pipefail
 R=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$(realpath -m "${1:-$R/build/ubench_world_rows_out}")

@@ -19,7 +19,7 @@ def key(name, grid):
     name = name.replace("(anonymous namespace)::", "").replace("void ", "").split("(")[0]
     base, _, arg = name.partition("<")
     slots = grid // 4 if base == "k_full_rows" else grid
-    return base, arg.rstrip(">") == "true", slots
+    return base, arg.rstrip(">") == "true", slots  # (kernel (i) has no store policy: nt = False)
 
 
 def grid_of(row):
@@ -31,7 +31,8 @@ def main():
     times = {}
     names = {"a_full_rows": "k_full_rows", "b_row3": "k_row3", "c_flat_full": "k_flat_full", "d_flat_row3": "k_flat_row3",
              "b2_rows23": "k_rows23", "e_flat_rows23": "k_flat_rows23", "f_flat_row3_vy": "k_flat_row3_vy",
-             "g_flat_row3_vblk": "k_flat_row3_vblk", "h_flat_row3_wave": "k_flat_row3_wave"}
+             "g_flat_row3_vblk": "k_flat_row3_vblk", "h_flat_row3_wave": "k_flat_row3_wave",
+             "i_flat_norow_wave": "k_flat_norow_wave"}
     for line in open(os.path.join(out, "times.jsonl")):
         d = json.loads(line)
         times.setdefault((names[d["kernel"]], bool(d["nt"]), d["slots"]), []).append(d["us"])  # (d), (f) and (h) run more than once
@@ -65,6 +66,14 @@ def main():
         gain, spread = min(f) - max(h), max(f) - min(f)
         print(f"gate (h): f {f} h {h}: min f - max h = {gain:.3f} us, 2 x (max f - min f) = {2 * spread:.3f} us: "
               f"{'PASS' if gain >= 2 * spread else 'FAIL'}")
+    # the gate of (i): its slowest run against the fastest of the three (h) runs around it, at 1 M slots and 16 M slots
+    for n in (1 << 20, 1 << 24):
+        h = times.get(("k_flat_row3_wave", False, n), [])[-3:]
+        i = times.get(("k_flat_norow_wave", False, n), [])
+        if len(h) == 3 and i:
+            gain, spread = min(h) - max(i), max(h) - min(h)
+            print(f"gate (i) at {n}: h {h} i {i}: min h - max i = {gain:.3f} us, 2 x (max h - min h) = {2 * spread:.3f} us: "
+                  f"{'PASS' if gain > 2 * spread else 'FAIL'}")
 
 
 if __name__ == "__main__":
