@@ -104,6 +104,8 @@ SYMBOLS = {
     "bge_world_overlap_sphere": (C.c_int, [_vp, _u64, _vp, _vp, _u64, _vp, C.POINTER(_u64)]),
     "bge_world_sphere_move": (C.c_int, [_vp, _u64, _vp, _vp]),
     "bge_world_sphere_move_device": (C.c_int, [_vp, _u64, _vp, _vp]),
+    "bge_world_sphere_step_move": (C.c_int, [_vp, _u64, _vp, _vp]),
+    "bge_world_sphere_step_move_device": (C.c_int, [_vp, _u64, _vp, _vp]),
     "bge_world_sphere_penetration": (C.c_int, [_vp, _u64, _vp, _vp]),
     "bge_world_sphere_penetration_device": (C.c_int, [_vp, _u64, _vp, _vp]),
     "bge_world_sphere_recover": (C.c_int, [_vp, _u64, _vp, _vp]),

@@ -30,6 +30,7 @@
 #include "bge_epochs.hpp"
 #include "bge_kernels.hpp"
 #include "bge_move.hpp"
+#include "bge_step.hpp"
 #include "bge_recover.hpp"
 #include "bge_query.hpp"
 
@@ -383,6 +384,8 @@ struct bge_world {
     std::vector<bge::QueryGhost> query_ghosts_host, query_ghosts_dev;
     // sphere moves (bge_move.hip): staging for the host entry point, the per-mover state, and the cast / hit records of the passes
     DevBuf move_in, move_out, move_state, move_casts, move_hits;
+    // sphere step moves (bge_step.hip): the same, its own; the cast / hit records hold two lanes per mover
+    DevBuf step_in, step_out, step_state, step_casts, step_hits;
     // sphere recovery (bge_recover.hip): the same for its passes, and its own (k_move_step relies on being the only writer of move_casts)
     DevBuf recover_in, recover_out, recover_state, recover_queries, recover_hits;
     // debug overlay (bge_debug.hip): per-workgroup line counts and their offsets, the host entry point's line buffer and total
@@ -475,7 +478,7 @@ struct bge_world {
         for (DevBuf* b : std::initializer_list<DevBuf*>{&flags, &parent, &tile_hdr, &slot_of_entity, &entity_of_slot, &root_slots, &root_index, &root_worlds, &counter, &stage,
                           &stage2, &mass_palette, &normal, &filter_table, &grav_palette, &bp_partials, &obstacle_slots, &obstacle_gen, &obstacles, &obstacle_grid, &box_list, &box_count, &frozen, &rs_word, &trig_slot, &trig_entity, &trig_he, &trig_group,
                           &trig_mask, &trig_active, &trig_aabb, &trig_pairs, &trig_count, &trig_lists, &ground_list, &ground_count, &trig_tab[0], &trig_tab[1],
-                          &trig_delta_dev, &trig_keys_dev, &trig_pose, &query_in, &query_out, &query_keys, &query_all, &query_all_count, &query_ghosts, &move_in, &move_out, &move_state, &move_casts, &move_hits, &recover_in, &recover_out, &recover_state, &recover_queries, &recover_hits, &dbg_block_sum, &dbg_block_off,
+                          &trig_delta_dev, &trig_keys_dev, &trig_pose, &query_in, &query_out, &query_keys, &query_all, &query_all_count, &query_ghosts, &move_in, &move_out, &move_state, &move_casts, &move_hits, &step_in, &step_out, &step_state, &step_casts, &step_hits, &recover_in, &recover_out, &recover_state, &recover_queries, &recover_hits, &dbg_block_sum, &dbg_block_off,
                           &dbg_lines, &dbg_total, &bounds, &cull_ballots, &cull_block_sum, &cull_block_off, &cull_out, &cull_total, &draw_keys,
                           &batch_sort, &batch_hist, &batch_out}) {
             b->release();
@@ -2918,6 +2921,8 @@ static_assert(sizeof(bge_sphere) == 20, "bge_sphere is 20 bytes (include/bge_wor
 static_assert(sizeof(bge_overlap_hit) == 12, "bge_overlap_hit is 12 bytes (include/bge_world.h)");
 static_assert(sizeof(bge_sphere_move) == 48, "bge_sphere_move is 48 bytes (include/bge_world.h)");
 static_assert(sizeof(bge_sphere_move_result) == 80, "bge_sphere_move_result is 80 bytes (include/bge_world.h)");
+static_assert(sizeof(bge_sphere_step_move) == 48, "bge_sphere_step_move is 48 bytes (include/bge_world.h)");
+static_assert(sizeof(bge_sphere_step_result) == 80, "bge_sphere_step_result is 80 bytes (include/bge_world.h)");
 static_assert(sizeof(bge_penetration_hit) == 40, "bge_penetration_hit is 40 bytes (include/bge_world.h)");
 static_assert(sizeof(bge_sphere_recover) == 28, "bge_sphere_recover is 28 bytes (include/bge_world.h)");
 static_assert(sizeof(bge_sphere_recover_result) == 64, "bge_sphere_recover_result is 64 bytes (include/bge_world.h)");
@@ -3124,6 +3129,38 @@ int move_enqueue(bge_world* w, bge::QueryParams q, uint64_t n, const void* moves
     return BGE_OK;
 }
 
+// A batch of sphere step moves between device buffers (include/bge_world.h "Sphere step moves"; the schedule is DESIGN.md 4.19's):
+// begin, then BGE_MOVE_SLIDES passes over both lanes (2n casts: the plain slide at i, the step at n + i), two passes over the step's
+// half alone (its last Forward round, its Down cast), the selection, the probe's pass over the first half, finish — all enqueued,
+// nothing read in between.  q comes from query_prepare(w, 2 * n, q).  The scratch is the step mover's own.
+int step_enqueue(bge_world* w, bge::QueryParams q, uint64_t n, const void* moves_device, void* results_device)
+{
+    HIP_TRY(w->step_state.ensure(n * bge::kStepStateBytes));
+    HIP_TRY(w->step_casts.ensure(2 * n * sizeof(bge_sphere_cast)));
+    HIP_TRY(w->step_hits.ensure(2 * n * sizeof(bge_ray_hit)));
+    bge::StepParams m{};
+    m.moves = moves_device;
+    m.results = results_device;
+    m.state = w->step_state.as<float4>();
+    m.casts = w->step_casts.p;
+    m.hits = w->step_hits.p;
+    m.n = static_cast<uint32_t>(n);
+    bge::QueryParams both = q, step_half = q, plain_half = q;
+    both.records = plain_half.records = w->step_casts.p;
+    both.hits = plain_half.hits = w->step_hits.p;
+    step_half.records = static_cast<const char*>(w->step_casts.p) + n * sizeof(bge_sphere_cast);
+    step_half.hits = static_cast<char*>(w->step_hits.p) + n * sizeof(bge_ray_hit);
+    step_half.n_queries = plain_half.n_queries = static_cast<uint32_t>(n);
+    HIP_TRY(bge::launch_step_begin(w->stream, m));
+    for (uint32_t stage = 1; stage <= bge::kStepStages; ++stage) {
+        HIP_TRY(bge::launch_query(w->stream, bge::QueryKind::SphereCast, stage <= BGE_MOVE_SLIDES ? both : step_half, false));
+        HIP_TRY(bge::launch_step_advance(w->stream, m, stage));
+    }
+    HIP_TRY(bge::launch_query(w->stream, bge::QueryKind::SphereCast, plain_half, false));
+    HIP_TRY(bge::launch_step_finish(w->stream, m));
+    return BGE_OK;
+}
+
 // A batch of sphere recoveries between device buffers (include/bge_world.h "Sphere penetration and recovery"): begin,
 // BGE_RECOVER_ROUNDS rounds of a penetration pass and a step, the final check's pass, finish — all enqueued, nothing read in
 // between.  q comes from query_prepare(w, n, q).  The scratch is the recovery's own, not the mover's.
@@ -3301,6 +3338,41 @@ try {
     return move_enqueue(w, q, n, moves_device, results_device);
 }
 BGE_CATCH_ALL("bge_world_sphere_move_device")
+
+int bge_world_sphere_step_move(bge_world* w, uint64_t n, const bge_sphere_step_move* moves, bge_sphere_step_result* results)
+try {
+    if (!w) return fail(BGE_ERR_INVALID, "world is NULL");
+    if (n == 0) return BGE_OK;
+    if (!moves || !results) return fail(BGE_ERR_INVALID, "NULL argument");
+    if (n > 0x3fffffffull) return fail(BGE_ERR_INVALID, "n = %llu: a step move asks 2 n casts per pass, at most 2^31 - 1", (unsigned long long)n);
+    DeviceGuard guard(w->device);
+    bge::QueryParams q;
+    if (int rc = query_prepare(w, 2 * n, q)) return rc; // (before the staging is sized: it refuses a batch that is too large)
+    HIP_TRY(w->step_in.ensure(n * sizeof(bge_sphere_step_move)));
+    HIP_TRY(w->step_out.ensure(n * sizeof(bge_sphere_step_result)));
+    HIP_TRY(hipMemcpyAsync(w->step_in.p, moves, n * sizeof(bge_sphere_step_move), hipMemcpyHostToDevice, w->stream));
+    if (int rc = step_enqueue(w, q, n, w->step_in.p, w->step_out.p)) return rc;
+    HIP_TRY(hipMemcpyAsync(results, w->step_out.p, n * sizeof(bge_sphere_step_result), hipMemcpyDeviceToHost, w->stream));
+    HIP_TRY(hipStreamSynchronize(w->stream));
+    return BGE_OK;
+}
+BGE_CATCH_ALL("bge_world_sphere_step_move")
+
+int bge_world_sphere_step_move_device(bge_world* w, uint64_t n, const void* moves_device, void* results_device)
+try {
+    if (!w) return fail(BGE_ERR_INVALID, "world is NULL");
+    if (n == 0) return BGE_OK;
+    if (!moves_device || !results_device) return fail(BGE_ERR_INVALID, "NULL argument");
+    if ((reinterpret_cast<uintptr_t>(moves_device) | reinterpret_cast<uintptr_t>(results_device)) & 3u) {
+        return fail(BGE_ERR_INVALID, "moves_device and results_device must be 4-byte aligned");
+    }
+    if (n > 0x3fffffffull) return fail(BGE_ERR_INVALID, "n = %llu: a step move asks 2 n casts per pass, at most 2^31 - 1", (unsigned long long)n);
+    DeviceGuard guard(w->device);
+    bge::QueryParams q;
+    if (int rc = query_prepare(w, 2 * n, q)) return rc;
+    return step_enqueue(w, q, n, moves_device, results_device);
+}
+BGE_CATCH_ALL("bge_world_sphere_step_move_device")
 
 int bge_world_overlap_sphere(bge_world* w, uint64_t n, const bge_sphere* spheres, bge_overlap_hit* hits, uint64_t cap, uint64_t* offsets,
                              uint64_t* total)

@@ -91,6 +91,17 @@ template <class Vec3> struct GpuSphereMoveResult {
     Vec3 groundNormal{};
 };
 
+// One sphere of GpuPhysicsSystem::StepMoveSpheres and what a step move returns (extensions: include/bge_world.h "Sphere step
+// moves"): the mover and the result of MoveSpheres with the step height, and with whether a step was tried and taken.
+template <class Vec3> struct GpuSphereStepMover : GpuSphereMover<Vec3> {
+    float stepHeight = 0.0f; // >= 0: how far the sphere may rise to get over an obstacle; 0 = the plain move
+};
+template <class Vec3> struct GpuSphereStepResult : GpuSphereMoveResult<Vec3> {
+    bool stepTried = false; // the first thing met was no walkable ground, and a step was looked for
+    bool stepped = false;   // the step was taken: position is on top of (or behind) the obstacle
+    float stepRise = 0.0f;  // how far it rose for it; 0 unless stepped
+};
+
 // What GpuPhysicsSystem::SpherePenetration finds, one sphere of RecoverSpheres and what a recovery returns (extensions:
 // include/bge_world.h "Sphere penetration and recovery").  Vec3 is the engine's float3 (members x, y, z).
 template <class Vec3> struct GpuPenetrationHit {
@@ -564,6 +575,77 @@ public:
         one[0].layerMask = layerMask;
         std::vector<GpuSphereMoveResult<Vec3>> out;
         const bool done = MoveSpheres(one, out);
+        result = out[0];
+        return done && result.valid;
+    }
+
+    // EXTENSION: the same moves, stepping up over low obstacles (include/bge_world.h "Sphere step moves"): where the first thing
+    // met is not walkable, the sphere is tried stepHeight higher, and the result is taken if it lands on walkable ground further
+    // along.  One call, no round trip per sphere or per stage.  false when there is no world or the call failed.
+    template <class Vec3>
+    bool StepMoveSpheres(const std::vector<GpuSphereStepMover<Vec3>>& movers, std::vector<GpuSphereStepResult<Vec3>>& results)
+    {
+        results.assign(movers.size(), GpuSphereStepResult<Vec3>{});
+        for (size_t i = 0; i < movers.size(); ++i) results[i].position = movers[i].position;
+        if (!ok()) return false;
+        if (movers.empty()) return true;
+        step_moves_.resize(movers.size());
+        step_results_.resize(movers.size());
+        for (size_t i = 0; i < movers.size(); ++i) {
+            const GpuSphereStepMover<Vec3>& m = movers[i];
+            bge_sphere_step_move& o = step_moves_[i];
+            o = bge_sphere_step_move{};
+            o.position[0] = m.position.x, o.position[1] = m.position.y, o.position[2] = m.position.z;
+            o.displacement[0] = m.displacement.x, o.displacement[1] = m.displacement.y, o.displacement[2] = m.displacement.z;
+            o.radius = m.radius;
+            o.skin = m.skin;
+            o.probe_distance = m.probeDistance;
+            o.min_ground_ny = std::cos(m.maxSlopeRad);
+            o.layer_mask = m.layerMask;
+            o.step_height = m.stepHeight;
+        }
+        if (bge_world_sphere_step_move(world_, step_moves_.size(), step_moves_.data(), step_results_.data()) != BGE_OK) {
+            return Log("bge_world_sphere_step_move");
+        }
+        for (size_t i = 0; i < movers.size(); ++i) {
+            const bge_sphere_step_result& r = step_results_[i];
+            GpuSphereStepResult<Vec3>& o = results[i];
+            o.position.x = r.position[0], o.position.y = r.position[1], o.position.z = r.position[2];
+            o.remaining.x = r.remaining[0], o.remaining.y = r.remaining[1], o.remaining.z = r.remaining[2];
+            o.valid = (r.flags & BGE_MOVE_INVALID) == 0u;
+            o.grounded = (r.flags & BGE_MOVE_GROUNDED) != 0u;
+            o.probeHit = (r.flags & BGE_MOVE_PROBE_HIT) != 0u;
+            o.outOfSlides = (r.flags & BGE_MOVE_OUT_OF_SLIDES) != 0u;
+            o.stepTried = (r.flags & BGE_MOVE_STEP_TRIED) != 0u;
+            o.stepped = (r.flags & BGE_MOVE_STEPPED) != 0u;
+            o.stepRise = r.step_rise;
+            o.hits = r.n_hits;
+            o.hitEntity = r.hit_entity != BGE_RAY_NO_ENTITY && r.hit_entity < ids_.size() ? ids_[r.hit_entity] : Id{0};
+            o.hitTrigger = r.hit_kind == BGE_RAY_TRIGGER;
+            o.hitNormal.x = r.hit_normal[0], o.hitNormal.y = r.hit_normal[1], o.hitNormal.z = r.hit_normal[2];
+            o.groundEntity = r.ground_entity != BGE_RAY_NO_ENTITY && r.ground_entity < ids_.size() ? ids_[r.ground_entity] : Id{0};
+            o.groundTrigger = r.ground_kind == BGE_RAY_TRIGGER;
+            o.groundDistance = r.ground_distance;
+            o.groundNormal.x = r.ground_normal[0], o.groundNormal.y = r.ground_normal[1], o.groundNormal.z = r.ground_normal[2];
+        }
+        return true;
+    }
+    // one sphere: true when it was moved (a valid mover on a world)
+    template <class Vec3>
+    bool StepMoveSphere(const Vec3& position, const Vec3& displacement, float radius, float skin, float probeDistance, float maxSlopeRad,
+                        uint32_t layerMask, float stepHeight, GpuSphereStepResult<Vec3>& result)
+    {
+        std::vector<GpuSphereStepMover<Vec3>> one(1);
+        one[0].position = position;
+        one[0].displacement = displacement;
+        one[0].radius = radius;
+        one[0].skin = skin;
+        one[0].probeDistance = probeDistance;
+        one[0].maxSlopeRad = maxSlopeRad;
+        one[0].layerMask = layerMask;
+        one[0].stepHeight = stepHeight;
+        std::vector<GpuSphereStepResult<Vec3>> out;
+        const bool done = StepMoveSpheres(one, out);
         result = out[0];
         return done && result.valid;
     }
@@ -1156,6 +1238,8 @@ private:
     std::vector<bge_overlap_hit> overlap_hits_;
     std::vector<bge_sphere_move> moves_;
     std::vector<bge_sphere_move_result> move_results_;
+    std::vector<bge_sphere_step_move> step_moves_;
+    std::vector<bge_sphere_step_result> step_results_;
     std::vector<bge_sphere_recover> recovers_;
     std::vector<bge_sphere_recover_result> recover_results_;
 
@@ -1337,6 +1421,31 @@ public:
             return false;
         }
         return GpuMirrors<SceneT>::Of(*lastScene_).MoveSpheres(movers, results);
+    }
+
+    // EXTENSION: the same moves, stepping up over low obstacles (include/bge_world.h "Sphere step moves"); false before the first
+    // Update, with every position echoed.
+    template <class Vec3>
+    bool StepMoveSphere(const Vec3& position, const Vec3& displacement, float radius, float skin, float probeDistance, float maxSlopeRad,
+                        uint32_t layerMask, float stepHeight, GpuSphereStepResult<Vec3>& result) const
+    {
+        if (!lastScene_) {
+            result = GpuSphereStepResult<Vec3>{};
+            result.position = position;
+            return false;
+        }
+        return GpuMirrors<SceneT>::Of(*lastScene_).StepMoveSphere(position, displacement, radius, skin, probeDistance, maxSlopeRad, layerMask,
+                                                                  stepHeight, result);
+    }
+    template <class Vec3>
+    bool StepMoveSpheres(const std::vector<GpuSphereStepMover<Vec3>>& movers, std::vector<GpuSphereStepResult<Vec3>>& results) const
+    {
+        if (!lastScene_) {
+            results.assign(movers.size(), GpuSphereStepResult<Vec3>{});
+            for (size_t i = 0; i < movers.size(); ++i) results[i].position = movers[i].position;
+            return false;
+        }
+        return GpuMirrors<SceneT>::Of(*lastScene_).StepMoveSpheres(movers, results);
     }
 
     // EXTENSION: sphere penetration and recovery against the same world, under the same call order as Raycast

@@ -111,6 +111,27 @@ def make_sphere_moves(positions, displacements, radius=0.5, skin=0.01, probe_dis
     return moves
 
 
+# sphere step moves (bge_world_sphere_step_move*): the two further flag bits and the records, which are the move's with step_height
+# and step_rise where those have their reserved words
+MOVE_STEP_TRIED, MOVE_STEPPED = 16, 32
+SPHERE_STEP_MOVE_DTYPE = np.dtype([("position", "<f4", (3,)), ("displacement", "<f4", (3,)), ("radius", "<f4"), ("skin", "<f4"),
+                                   ("probe_distance", "<f4"), ("min_ground_ny", "<f4"), ("layer_mask", "<u4"), ("step_height", "<f4")])
+SPHERE_STEP_RESULT_DTYPE = np.dtype([("position", "<f4", (3,)), ("remaining", "<f4", (3,)), ("flags", "<u4"), ("n_hits", "<u4"),
+                                     ("hit_kind", "<u4"), ("hit_entity", "<u4"), ("hit_normal", "<f4", (3,)), ("ground_kind", "<u4"),
+                                     ("ground_entity", "<u4"), ("ground_distance", "<f4"), ("ground_normal", "<f4", (3,)),
+                                     ("step_rise", "<f4")])
+assert SPHERE_STEP_MOVE_DTYPE.itemsize == 48 and SPHERE_STEP_RESULT_DTYPE.itemsize == 80
+
+
+def make_sphere_step_moves(positions, displacements, radius=0.5, skin=0.01, probe_distance=0.0, min_ground_ny=0.7071068, layer_mask=0xFFFFFFFF,
+                           step_height=0.0):
+    """bge_sphere_step_move records: make_sphere_moves() with step_height, a scalar or one value per mover."""
+    plain = make_sphere_moves(positions, displacements, radius, skin, probe_distance, min_ground_ny, layer_mask)
+    moves = plain.view(SPHERE_STEP_MOVE_DTYPE)
+    moves["step_height"] = np.broadcast_to(np.asarray(step_height, np.float32), (len(moves),))
+    return moves
+
+
 # sphere penetration and recovery (bge_world_sphere_penetration*, bge_world_sphere_recover*): bge_recover_flags and the records; the
 # penetration query's input is a SPHERE_DTYPE record
 RECOVER_ROUNDS = 4
@@ -576,6 +597,30 @@ class World:
         if not (moves.is_cuda and results.is_cuda and moves.is_contiguous() and results.is_contiguous()):
             raise ValueError("moves and results must be contiguous device tensors")
         check(lib().bge_world_sphere_move_device(self._h, n, C.c_void_p(moves.data_ptr()), C.c_void_p(results.data_ptr())))
+
+    # -- sphere step moves (not in the reference; include/bge_world.h states the rule: the move, stepping up over low obstacles)
+    def sphere_step_move(self, positions, displacements, radius=0.5, skin=0.01, probe_distance=0.0, min_ground_ny=0.7071068,
+                         layer_mask=0xFFFFFFFF, step_height=0.0):
+        """One step move per sphere: a SPHERE_STEP_RESULT_DTYPE array (the fields of sphere_move() and step_rise; MOVE_STEP_TRIED and
+        MOVE_STEPPED in flags).  Every argument but the first two takes a scalar or one value per mover."""
+        moves = make_sphere_step_moves(positions, displacements, radius, skin, probe_distance, min_ground_ny, layer_mask, step_height)
+        results = np.zeros(len(moves), SPHERE_STEP_RESULT_DTYPE)
+        check(lib().bge_world_sphere_step_move(self._h, len(moves), _p(moves), _p(results)))
+        return results
+
+    def sphere_step_move_device(self, moves, results):
+        """The same between device tensors: moves holds n bge_sphere_step_move records (48 bytes each, e.g. a uint8 tensor made from
+        make_sphere_step_moves()), results room for n bge_sphere_step_result records (80 bytes each).  Enqueued on the world's
+        stream without synchronisation, as sphere_move_device()."""
+        nb = moves.numel() * moves.element_size()
+        if nb % 48:
+            raise ValueError(f"moves holds {nb} bytes, not a whole number of 48-byte records")
+        n = nb // 48
+        if results.numel() * results.element_size() < 80 * n:
+            raise ValueError(f"results has room for {results.numel() * results.element_size()} bytes, {80 * n} needed")
+        if not (moves.is_cuda and results.is_cuda and moves.is_contiguous() and results.is_contiguous()):
+            raise ValueError("moves and results must be contiguous device tensors")
+        check(lib().bge_world_sphere_step_move_device(self._h, n, C.c_void_p(moves.data_ptr()), C.c_void_p(results.data_ptr())))
 
     # -- sphere penetration and recovery (not in the reference; include/bge_world.h states the signed distance and the rule)
     def sphere_penetration(self, centers, radius, layer_mask=0xFFFFFFFF):

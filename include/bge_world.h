@@ -557,8 +557,8 @@ BGE_API int bge_world_overlap_sphere(bge_world* world, uint64_t n, const bge_sph
  *             to a flat surface (a is the cosine of the approach).  The clamp at a = 1/16 bounds the back-off at grazing angles to
  *             16 skins of path, where the gap kept is then smaller than skin, never negative.  Choose skin well above the
  *             binary32 spacing at the scene's extent (1e-3 .. 1e-2 for a scene of a few hundred units).
- *   Not done  capsule or box movers; stepping up (composed by the caller from an up move, a forward move and a down move);
- *             moving platforms; the result is not written into any Transform.  A sphere that STARTS touching or inside a shape is
+ *   Not done  capsule or box movers; moving platforms; the result is not written into any Transform.  Stepping up over a kerb or a
+ *             stair is bge_world_sphere_step_move ("Sphere step moves" below).  A sphere that STARTS touching or inside a shape is
  *             not this query's business (the cast does not see what it starts in): bge_world_sphere_recover below pushes it
  *             out first, so the order per frame is recover, then move.
  *   The query changes no world state.  n = 0 is a no-op.  A NULL argument with n > 0 is BGE_ERR_INVALID.  Before
@@ -596,6 +596,81 @@ typedef struct bge_sphere_move_result {
 } bge_sphere_move_result; /* 80 bytes */
 BGE_API int bge_world_sphere_move(bge_world* world, uint64_t n, const bge_sphere_move* moves, bge_sphere_move_result* results);
 BGE_API int bge_world_sphere_move_device(bge_world* world, uint64_t n, const void* moves_device, void* results_device);
+
+/*
+ * Sphere step moves: a sphere move that steps up over low obstacles — what a caller of bge_world_sphere_move composes from an up
+ * move, a forward move and a down move, done once on the device with no host round trip.  NOT in the reference's
+ * PhysicsSystem.  The rule below is the specification.  All arithmetic is binary32, one rounding per operation, left to right, as
+ * in "Sphere moves".
+ *   Slide(p, d)  the State and the rounds 1-7 of "Sphere moves", word for word, run for BGE_MOVE_SLIDES rounds from p with
+ *             r = d0 = d and no previous normal.  It yields p', r' (zero unless (r'.x*r'.x + r'.y*r'.y) + r'.z*r'.z > 1e-12f, then
+ *             OUT_OF_SLIDES), n_hits, the last hit, and the normal n1 of the first round's hit.
+ *   Cast      the closest hit of bge_world_sphere_cast with the mover's radius and layer_mask: Objects, poses, Filter, tie order,
+ *             start rule and Call order are the cast's by construction.
+ *   Valid     a mover is valid iff it is a valid bge_sphere_move and step_height is finite and >= 0.  An invalid mover returns the
+ *             INVALID record of "Sphere moves", with step_rise = 0.
+ *   Plain     P = Slide(position, displacement).
+ *   Gate      BGE_MOVE_STEP_TRIED is set, and the stages below are run, iff step_height > 0, P.n_hits >= 1,
+ *             n1.y < min_ground_ny (the first thing met is not walkable ground) and
+ *             displacement.x*displacement.x + displacement.z*displacement.z > 1e-12f.
+ *   Up        Cast {position, (0, 1, 0), max_distance step_height}.  Miss: u = step_height.  Hit at distance t: u = t - skin.
+ *             If !(u > 0) the step fails.  q = (position.x, position.y + u, position.z).
+ *   Forward   F = Slide(q, (displacement.x, 0, displacement.z)).
+ *   Down      m = u + probe_distance.  Cast {F.p, (0, -1, 0), max_distance m}.  A miss fails the step; a hit whose normal.y is not
+ *             >= min_ground_ny fails the step.  Otherwise e = distance - skin; if !(e > 0) then e = 0;
+ *             S = (F.p.x, F.p.y - e, F.p.z).  The back-off is vertical, so the gap kept to a slope is skin * normal.y > 0.
+ *   Gain      gs = (S.x - position.x)*displacement.x + (S.z - position.z)*displacement.z, and gp the same with P.p for S.  The
+ *             step fails unless gs > gp.
+ *   Result    if the step did not fail: BGE_MOVE_STEPPED is set, position = S; remaining, OUT_OF_SLIDES, n_hits and hit_* are
+ *             those of F; step_rise = u.  Otherwise every field is that of P, and step_rise = 0.
+ *   Probe     one probe from the chosen position, by the Probe rule of "Sphere moves": ground_*, PROBE_HIT and GROUNDED.
+ *   Hence     with STEP_TRIED masked off, a record without STEPPED equals, byte for byte, what bge_world_sphere_move returns for
+ *             the same 48 bytes read as a bge_sphere_move (whose reserved word it does not look at); step_height == 0 is
+ *             therefore exactly the plain move.  A stepped result is reproducible from public calls: bge_world_sphere_cast up,
+ *             bge_world_sphere_move with probe 0 forward, bge_world_sphere_cast down.  A low fence is hopped only when
+ *             probe_distance reaches the ground behind it: Down looks u + probe_distance below F.p, and the fence was cleared by u.
+ *   Example   radius 0.5, skin 0.01, min_ground_ny cos 45 degrees, plane on.  A Static box with half extents (2, 0.3, 2) at
+ *             (3, 0.3, 0): top y = 0.6, near face x = 1.  Mover at (0, 0.51, 0), displacement (2, 0, 0), step_height 0.7, probe
+ *             0.1.  Plain: the face head-on, P.p = (0.49, 0.51, 0), n1 = (-1, 0, 0): the gate passes.  Up: free, u = 0.7,
+ *             q = (0, 1.21, 0).  Forward: the underside at 0.71 > 0.6 is free, F.p = (2, 1.21, 0).  Down: m = 0.8, the top is
+ *             touched at centre y = 1.1, distance 0.11, normal (0, 1, 0): e = 0.10, S = (2, 1.11, 0).  Gain: gs = 4 > gp = 0.98.
+ *             Result: position (2, 1.11, 0), flags STEP_TRIED | STEPPED | GROUNDED | PROBE_HIT, n_hits 0, hit_kind MISS,
+ *             ground_kind BODY, entity 0, ground_distance 0.01, step_rise 0.7.
+ *   Not done  capsule and box movers, moving platforms, writing into a Transform.
+ *   The query changes no world state.  n = 0 is a no-op.  A NULL argument with n > 0 is BGE_ERR_INVALID.  n is at most 2^30 - 1
+ *   (a pass asks two casts per mover).  Before bge_world_set_topology it returns what bge_world_sphere_cast returns there.
+ *   bge_world_sphere_step_move         results[i] for moves[i].  Synchronises the world's stream.
+ *   bge_world_sphere_step_move_device  device pointers: moves_device = bge_sphere_step_move[n], results_device =
+ *                                      bge_sphere_step_result[n], both 4-byte aligned (a misaligned pointer is BGE_ERR_INVALID);
+ *                                      enqueued on the world's stream, no synchronisation.
+ */
+typedef struct bge_sphere_step_move { /* bge_sphere_move with step_height where its reserved word is */
+    float position[3];
+    float displacement[3];
+    float radius;
+    float skin;
+    float probe_distance;
+    float min_ground_ny;
+    uint32_t layer_mask;
+    float step_height; /* >= 0: how far the sphere may rise to get over an obstacle; 0 = plain move */
+} bge_sphere_step_move; /* 48 bytes */
+enum bge_step_move_flags { BGE_MOVE_STEP_TRIED = 16u, BGE_MOVE_STEPPED = 32u }; /* two more bits of the result's flags word */
+typedef struct bge_sphere_step_result { /* bge_sphere_move_result with step_rise where its reserved word is */
+    float position[3];
+    float remaining[3];
+    uint32_t flags; /* bge_move_flags | bge_step_move_flags */
+    uint32_t n_hits;
+    uint32_t hit_kind;
+    uint32_t hit_entity;
+    float hit_normal[3];
+    uint32_t ground_kind;
+    uint32_t ground_entity;
+    float ground_distance;
+    float ground_normal[3];
+    float step_rise; /* u of the Up stage when STEPPED, otherwise 0 */
+} bge_sphere_step_result; /* 80 bytes */
+BGE_API int bge_world_sphere_step_move(bge_world* world, uint64_t n, const bge_sphere_step_move* moves, bge_sphere_step_result* results);
+BGE_API int bge_world_sphere_step_move_device(bge_world* world, uint64_t n, const void* moves_device, void* results_device);
 
 /*
  * Sphere penetration and recovery: by how much and in which direction a sphere at rest reaches into the world
