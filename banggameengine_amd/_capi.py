@@ -110,6 +110,13 @@ SYMBOLS = {
     "bge_world_sphere_penetration_device": (C.c_int, [_vp, _u64, _vp, _vp]),
     "bge_world_sphere_recover": (C.c_int, [_vp, _u64, _vp, _vp]),
     "bge_world_sphere_recover_device": (C.c_int, [_vp, _u64, _vp, _vp]),
+    "bge_world_characters_create": (C.c_int, [_vp, _u64, _vp]),
+    "bge_world_characters_set_input": (C.c_int, [_vp, _u64, _u64, _vp]),
+    "bge_world_characters_set_input_device": (C.c_int, [_vp, _u64, _u64, _vp]),
+    "bge_world_characters_warp": (C.c_int, [_vp, _u64, _vp, _vp]),
+    "bge_world_characters_update": (C.c_int, [_vp, _f, _u32]),
+    "bge_world_characters_download": (C.c_int, [_vp, _u64, _u64, _vp]),
+    "bge_world_characters_state_device": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_u64)]),
     "bge_world_debug_lines": (C.c_int, [_vp, _vp, _vp, _u64, C.POINTER(_u64)]),
     "bge_world_debug_lines_device": (C.c_int, [_vp, _vp, _vp, _u64, _vp]),
     "bge_world_upload_bounds": (C.c_int, [_vp, _u64, _u64, _vp, _vp]),

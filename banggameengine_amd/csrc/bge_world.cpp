@@ -32,6 +32,7 @@
 #include "bge_move.hpp"
 #include "bge_step.hpp"
 #include "bge_recover.hpp"
+#include "bge_character.hpp"
 #include "bge_query.hpp"
 
 namespace {
@@ -388,6 +389,10 @@ struct bge_world {
     DevBuf step_in, step_out, step_state, step_casts, step_hits;
     // sphere recovery (bge_recover.hip): the same for its passes, and its own (k_move_step relies on being the only writer of move_casts)
     DevBuf recover_in, recover_out, recover_state, recover_queries, recover_hits;
+    // characters (bge_character.hip): the resident desc / input / state records of the set, the records its steps hand to the
+    // recovery and the step move and get back, and the step's scratch
+    DevBuf char_desc, char_input, char_state, char_recover_in, char_recover_out, char_step_in, char_step_out, char_scratch;
+    uint64_t n_characters = 0;
     // debug overlay (bge_debug.hip): per-workgroup line counts and their offsets, the host entry point's line buffer and total
     DevBuf dbg_block_sum, dbg_block_off, dbg_lines, dbg_total;
     // frustum culling (bge_cull.hip): the model-space bounds per ENTITY (a row of NaNs = no bounds), the pass's ballots / counts /
@@ -478,7 +483,7 @@ struct bge_world {
         for (DevBuf* b : std::initializer_list<DevBuf*>{&flags, &parent, &tile_hdr, &slot_of_entity, &entity_of_slot, &root_slots, &root_index, &root_worlds, &counter, &stage,
                           &stage2, &mass_palette, &normal, &filter_table, &grav_palette, &bp_partials, &obstacle_slots, &obstacle_gen, &obstacles, &obstacle_grid, &box_list, &box_count, &frozen, &rs_word, &trig_slot, &trig_entity, &trig_he, &trig_group,
                           &trig_mask, &trig_active, &trig_aabb, &trig_pairs, &trig_count, &trig_lists, &ground_list, &ground_count, &trig_tab[0], &trig_tab[1],
-                          &trig_delta_dev, &trig_keys_dev, &trig_pose, &query_in, &query_out, &query_keys, &query_all, &query_all_count, &query_ghosts, &move_in, &move_out, &move_state, &move_casts, &move_hits, &step_in, &step_out, &step_state, &step_casts, &step_hits, &recover_in, &recover_out, &recover_state, &recover_queries, &recover_hits, &dbg_block_sum, &dbg_block_off,
+                          &trig_delta_dev, &trig_keys_dev, &trig_pose, &query_in, &query_out, &query_keys, &query_all, &query_all_count, &query_ghosts, &move_in, &move_out, &move_state, &move_casts, &move_hits, &step_in, &step_out, &step_state, &step_casts, &step_hits, &recover_in, &recover_out, &recover_state, &recover_queries, &recover_hits, &char_desc, &char_input, &char_state, &char_recover_in, &char_recover_out, &char_step_in, &char_step_out, &char_scratch, &dbg_block_sum, &dbg_block_off,
                           &dbg_lines, &dbg_total, &bounds, &cull_ballots, &cull_block_sum, &cull_block_off, &cull_out, &cull_total, &draw_keys,
                           &batch_sort, &batch_hist, &batch_out}) {
             b->release();
@@ -3429,6 +3434,200 @@ try {
     return recover_enqueue(w, q, n, records_device, results_device);
 }
 BGE_CATCH_ALL("bge_world_sphere_recover_device")
+
+// ---------------------------------------------------------------- characters (bge_character.hip)
+static_assert(sizeof(bge_character_desc) == 48, "bge_character_desc is 48 bytes (include/bge_world.h)");
+static_assert(sizeof(bge_character_input) == 16, "bge_character_input is 16 bytes (include/bge_world.h)");
+static_assert(sizeof(bge_character_state) == 80, "bge_character_state is 80 bytes (include/bge_world.h)");
+
+namespace {
+
+int check_character_range(const bge_world* w, uint64_t first, uint64_t count)
+{
+    if (first > w->n_characters || count > w->n_characters - first) {
+        return fail(BGE_ERR_INVALID, "character range [%llu, +%llu) outside [0, %llu)", (unsigned long long)first, (unsigned long long)count,
+                    (unsigned long long)w->n_characters);
+    }
+    return BGE_OK;
+}
+
+// What is wrong with a desc, or NULL
+const char* character_desc_fault(const bge_character_desc& d)
+{
+    const float floats[] = {d.position[0], d.position[1], d.position[2], d.radius, d.skin, d.step_height, d.min_ground_ny, d.probe_distance,
+                            d.gravity, d.jump_speed, d.fall_speed};
+    for (float v : floats) {
+        if (!std::isfinite(v)) return "a value is not finite";
+    }
+    if (!(d.radius >= 0.0f)) return "radius < 0";
+    if (!(d.skin > 0.0f)) return "skin <= 0";
+    if (!(d.step_height >= 0.0f)) return "step_height < 0";
+    if (!(d.probe_distance >= 0.0f)) return "probe_distance < 0";
+    if (!(d.gravity >= 0.0f)) return "gravity < 0";
+    if (!(d.jump_speed >= 0.0f)) return "jump_speed < 0";
+    if (!(d.fall_speed > 0.0f)) return "fall_speed <= 0";
+    if (d.layer_mask == 0u) return "layer_mask == 0";
+    return nullptr;
+}
+
+} // namespace
+
+int bge_world_characters_create(bge_world* w, uint64_t n, const bge_character_desc* descs)
+try {
+    if (!w) return fail(BGE_ERR_INVALID, "world is NULL");
+    if (n > 0 && !descs) return fail(BGE_ERR_INVALID, "descs is NULL");
+    if (n > 0x3fffffffull) return fail(BGE_ERR_INVALID, "n = %llu: a character's step move asks 2 n casts per pass, at most 2^31 - 1", (unsigned long long)n);
+    for (uint64_t i = 0; i < n; ++i) {
+        if (const char* what = character_desc_fault(descs[i])) return fail(BGE_ERR_INVALID, "character desc %llu: %s", (unsigned long long)i, what);
+    }
+    DeviceGuard guard(w->device);
+    HIP_TRY(hipStreamSynchronize(w->stream)); // (an update of the old set may still be running on its buffers)
+    w->n_characters = 0;
+    if (n == 0) {
+        for (DevBuf* b : {&w->char_desc, &w->char_input, &w->char_state, &w->char_recover_in, &w->char_recover_out, &w->char_step_in, &w->char_step_out,
+                          &w->char_scratch}) {
+            b->release();
+        }
+        return BGE_OK;
+    }
+    HIP_TRY(w->char_desc.ensure(n * sizeof(bge_character_desc)));
+    HIP_TRY(w->char_input.ensure(n * sizeof(bge_character_input)));
+    HIP_TRY(w->char_state.ensure(n * sizeof(bge_character_state)));
+    HIP_TRY(w->char_recover_in.ensure(n * sizeof(bge_sphere_recover)));
+    HIP_TRY(w->char_recover_out.ensure(n * sizeof(bge_sphere_recover_result)));
+    HIP_TRY(w->char_step_in.ensure(n * sizeof(bge_sphere_step_move)));
+    HIP_TRY(w->char_step_out.ensure(n * sizeof(bge_sphere_step_result)));
+    HIP_TRY(w->char_scratch.ensure(n * sizeof(uint2)));
+    std::vector<bge_character_state> states(n);
+    for (uint64_t i = 0; i < n; ++i) {
+        bge_character_state& s = states[i];
+        s = bge_character_state{};
+        for (int a = 0; a < 3; ++a) s.position[a] = descs[i].position[a];
+        s.ground_kind = s.hit_kind = BGE_RAY_MISS;
+        s.ground_entity = s.hit_entity = BGE_RAY_NO_ENTITY;
+    }
+    HIP_TRY(hipMemcpyAsync(w->char_desc.p, descs, n * sizeof(bge_character_desc), hipMemcpyHostToDevice, w->stream));
+    HIP_TRY(hipMemcpyAsync(w->char_state.p, states.data(), n * sizeof(bge_character_state), hipMemcpyHostToDevice, w->stream));
+    HIP_TRY(hipMemsetAsync(w->char_input.p, 0, n * sizeof(bge_character_input), w->stream));
+    HIP_TRY(hipStreamSynchronize(w->stream)); // (the copies read the caller's and this function's memory)
+    w->n_characters = n;
+    return BGE_OK;
+}
+BGE_CATCH_ALL("bge_world_characters_create")
+
+int bge_world_characters_set_input(bge_world* w, uint64_t first, uint64_t count, const bge_character_input* inputs)
+try {
+    if (!w) return fail(BGE_ERR_INVALID, "world is NULL");
+    if (int rc = check_character_range(w, first, count)) return rc;
+    if (count == 0) return BGE_OK;
+    if (!inputs) return fail(BGE_ERR_INVALID, "inputs is NULL");
+    DeviceGuard guard(w->device);
+    HIP_TRY(hipMemcpyAsync(w->char_input.as<bge_character_input>() + first, inputs, count * sizeof(bge_character_input), hipMemcpyHostToDevice,
+                           w->stream));
+    HIP_TRY(hipStreamSynchronize(w->stream)); // (the caller's memory is free again on return)
+    return BGE_OK;
+}
+BGE_CATCH_ALL("bge_world_characters_set_input")
+
+int bge_world_characters_set_input_device(bge_world* w, uint64_t first, uint64_t count, const void* inputs_device)
+try {
+    if (!w) return fail(BGE_ERR_INVALID, "world is NULL");
+    if (int rc = check_character_range(w, first, count)) return rc;
+    if (count == 0) return BGE_OK;
+    if (!inputs_device) return fail(BGE_ERR_INVALID, "inputs_device is NULL");
+    if (reinterpret_cast<uintptr_t>(inputs_device) & 3u) return fail(BGE_ERR_INVALID, "inputs_device must be 4-byte aligned");
+    DeviceGuard guard(w->device);
+    HIP_TRY(hipMemcpyAsync(w->char_input.as<bge_character_input>() + first, inputs_device, count * sizeof(bge_character_input),
+                           hipMemcpyDeviceToDevice, w->stream));
+    return BGE_OK;
+}
+BGE_CATCH_ALL("bge_world_characters_set_input_device")
+
+int bge_world_characters_warp(bge_world* w, uint64_t count, const uint32_t* index, const float* position3)
+try {
+    if (!w) return fail(BGE_ERR_INVALID, "world is NULL");
+    if (count == 0) return BGE_OK;
+    if (!index || !position3) return fail(BGE_ERR_INVALID, "NULL argument");
+    for (uint64_t k = 0; k < count; ++k) {
+        if (index[k] >= w->n_characters) {
+            return fail(BGE_ERR_INVALID, "warp %llu: character %u outside [0, %llu)", (unsigned long long)k, index[k], (unsigned long long)w->n_characters);
+        }
+        for (int a = 0; a < 3; ++a) {
+            if (!std::isfinite(position3[3 * k + a])) return fail(BGE_ERR_INVALID, "warp %llu: the position is not finite", (unsigned long long)k);
+        }
+    }
+    DeviceGuard guard(w->device);
+    // the first five words of a state: position, vertical_velocity, flags (everything but GROUNDED stays: they are the last step's)
+    HIP_TRY(hipStreamSynchronize(w->stream));
+    for (uint64_t k = 0; k < count; ++k) {
+        char* s = w->char_state.as<char>() + uint64_t(index[k]) * sizeof(bge_character_state);
+        uint32_t head[5];
+        HIP_TRY(hipMemcpy(head, s, sizeof head, hipMemcpyDeviceToHost));
+        std::memcpy(head, position3 + 3 * k, 12);
+        head[3] = 0u; // vv = +0
+        head[4] &= ~uint32_t(BGE_CHAR_GROUNDED);
+        HIP_TRY(hipMemcpy(s, head, sizeof head, hipMemcpyHostToDevice));
+    }
+    return BGE_OK;
+}
+BGE_CATCH_ALL("bge_world_characters_warp")
+
+int bge_world_characters_update(bge_world* w, float dt, uint32_t steps)
+try {
+    if (!w) return fail(BGE_ERR_INVALID, "world is NULL");
+    if (!(std::isfinite(dt) && dt > 0.0f)) return fail(BGE_ERR_INVALID, "dt = %g: must be finite and > 0", (double)dt);
+    if (steps < 1u) return fail(BGE_ERR_INVALID, "steps = 0: at least one step");
+    const uint64_t n = w->n_characters;
+    if (n == 0) return BGE_OK;
+    DeviceGuard guard(w->device);
+    bge::QueryParams q;
+    if (int rc = query_prepare(w, 2 * n, q)) return rc; // (the step move's 2 n casts per pass; the recovery asks n of them)
+    bge::QueryParams qr = q;
+    qr.n_queries = static_cast<uint32_t>(n);
+    bge::CharacterParams c{};
+    c.desc = w->char_desc.p;
+    c.input = w->char_input.p;
+    c.state = w->char_state.p;
+    c.recover_in = w->char_recover_in.p;
+    c.recover_out = w->char_recover_out.p;
+    c.step_in = w->char_step_in.p;
+    c.step_out = w->char_step_out.p;
+    c.scratch = w->char_scratch.as<uint2>();
+    c.dt = dt;
+    c.n = static_cast<uint32_t>(n);
+    for (uint32_t k = 0; k < steps; ++k) {
+        HIP_TRY(bge::launch_char_begin(w->stream, c, k == 0 ? 1u : 0u));
+        if (int rc = recover_enqueue(w, qr, n, w->char_recover_in.p, w->char_recover_out.p)) return rc;
+        HIP_TRY(bge::launch_char_move(w->stream, c));
+        if (int rc = step_enqueue(w, q, n, w->char_step_in.p, w->char_step_out.p)) return rc;
+        HIP_TRY(bge::launch_char_finish(w->stream, c));
+    }
+    return BGE_OK;
+}
+BGE_CATCH_ALL("bge_world_characters_update")
+
+int bge_world_characters_download(bge_world* w, uint64_t first, uint64_t count, bge_character_state* states)
+try {
+    if (!w) return fail(BGE_ERR_INVALID, "world is NULL");
+    if (int rc = check_character_range(w, first, count)) return rc;
+    if (count == 0) return BGE_OK;
+    if (!states) return fail(BGE_ERR_INVALID, "states is NULL");
+    DeviceGuard guard(w->device);
+    HIP_TRY(hipMemcpyAsync(states, w->char_state.as<bge_character_state>() + first, count * sizeof(bge_character_state), hipMemcpyDeviceToHost,
+                           w->stream));
+    HIP_TRY(hipStreamSynchronize(w->stream));
+    return BGE_OK;
+}
+BGE_CATCH_ALL("bge_world_characters_download")
+
+int bge_world_characters_state_device(bge_world* w, void** states_device, uint64_t* n)
+try {
+    if (!w || !states_device || !n) return fail(BGE_ERR_INVALID, "NULL argument");
+    *states_device = w->n_characters ? w->char_state.p : nullptr;
+    *n = w->n_characters;
+    return BGE_OK;
+}
+BGE_CATCH_ALL("bge_world_characters_state_device")
 
 // ---------------------------------------------------------------- debug overlay (bge_debug.hip)
 static_assert(sizeof(bge_debug_line) == 28, "bge_debug_line is 28 bytes (include/bge_world.h)");

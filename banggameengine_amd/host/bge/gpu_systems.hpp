@@ -131,6 +131,35 @@ template <class Vec3> struct GpuSphereRecoverResult {
     float remainingDepth = 0.0f;
 };
 
+// What a character of GpuPhysicsSystem::AddCharacter is made with and what GetCharacterState returns (extensions:
+// include/bge_world.h "Characters").  The state is that of the last SyncCharacters.
+struct GpuCharacterKnobs {
+    float radius = 0.35f;
+    float skin = 0.01f;
+    float stepHeight = 0.35f;
+    float maxSlopeRad = 0.8726646f; // 50 degrees
+    float probeDistance = 0.1f;
+    float gravity = 9.81f;    // >= 0, downwards
+    float jumpSpeed = 5.0f;
+    float fallSpeed = 29.43f; // |gravity| * 3
+    uint32_t layerMask = 0xffffffffu;
+};
+template <class Vec3> struct GpuCharacterState {
+    Vec3 position{};
+    float verticalVelocity = 0.0f;
+    bool valid = false; // the last step was valid
+    bool grounded = false, jumped = false, landed = false, headBump = false, recovered = false, stuck = false, stepped = false, outOfSlides = false;
+    uint32_t groundEntity = 0; // EntityId of what the character stands on; kInvalidEntity (0) for the ground plane or none
+    bool groundTrigger = false;
+    Vec3 groundNormal{};
+    uint32_t hitEntity = 0; // EntityId of the last thing the last step's slides hit; kInvalidEntity (0) for the plane or none
+    bool hitTrigger = false;
+    Vec3 hitNormal{};
+    float stepRise = 0.0f;
+    Vec3 recoveredBy{}; // what the last step's recovery pushed the character by
+    uint32_t steps = 0;
+};
+
 struct GpuTriggerEvent {
     enum class Type { Enter, Stay, Exit };
     Type type = Type::Enter;
@@ -726,6 +755,142 @@ public:
         return done && result.valid;
     }
 
+    // EXTENSION: the scene's characters (include/bge_world.h "Characters"): a set of sphere characters that lives on the device;
+    // one UpdateCharacters runs a frame's sub-steps for all of them, one SyncCharacters brings the states back.  The device's set is
+    // replaced as a whole, so adding a character re-creates it on the next UpdateCharacters: the others keep their position as of
+    // the last SyncCharacters and are, like the new one, at rest and not grounded.
+    bool AddCharacter(SceneT& scene, Id entity, const GpuCharacterKnobs& k)
+    {
+        auto* t = scene.GetTransform(entity);
+        if (!t || char_index_.count(entity)) return false;
+        bge_character_desc d{};
+        d.position[0] = t->position.x, d.position[1] = t->position.y, d.position[2] = t->position.z;
+        d.radius = k.radius;
+        d.skin = k.skin;
+        d.step_height = k.stepHeight;
+        d.min_ground_ny = std::cos(k.maxSlopeRad);
+        d.probe_distance = k.probeDistance;
+        d.gravity = k.gravity;
+        d.jump_speed = k.jumpSpeed;
+        d.fall_speed = k.fallSpeed;
+        d.layer_mask = k.layerMask;
+        for (size_t i = 0; i < char_states_.size() && i < char_descs_.size(); ++i) std::memcpy(char_descs_[i].position, char_states_[i].position, 12);
+        char_index_[entity] = static_cast<uint32_t>(char_ids_.size());
+        char_ids_.push_back(entity);
+        char_descs_.push_back(d);
+        char_inputs_.push_back(bge_character_input{});
+        chars_stale_ = true;
+        return true;
+    }
+    void RemoveCharacters()
+    {
+        char_ids_.clear();
+        char_index_.clear();
+        char_descs_.clear();
+        char_inputs_.clear();
+        char_states_.clear();
+        chars_stale_ = char_inputs_stale_ = false;
+        if (ok() && bge_world_characters_create(world_, 0, nullptr) != BGE_OK) Log("bge_world_characters_create");
+    }
+    size_t CharacterCount() const { return char_ids_.size(); }
+    bool SetCharacterWalk(Id entity, float dx, float dz)
+    {
+        auto it = char_index_.find(entity);
+        if (it == char_index_.end()) return false;
+        char_inputs_[it->second].walk_x = dx;
+        char_inputs_[it->second].walk_z = dz;
+        char_inputs_stale_ = true;
+        return true;
+    }
+    bool CharacterJump(Id entity) // the edge; the device jumps only a character that stands on ground
+    {
+        auto it = char_index_.find(entity);
+        if (it == char_index_.end()) return false;
+        char_inputs_[it->second].buttons |= BGE_CHAR_BUTTON_JUMP;
+        char_inputs_stale_ = true;
+        return true;
+    }
+    template <class Vec3> bool WarpCharacter(Id entity, const Vec3& position)
+    {
+        auto it = char_index_.find(entity);
+        if (it == char_index_.end()) return false;
+        const float p[3] = {position.x, position.y, position.z};
+        if (it->second < char_states_.size()) std::memcpy(char_states_[it->second].position, p, 12);
+        if (chars_stale_) { // not on the device yet: it will be created there
+            std::memcpy(char_descs_[it->second].position, p, 12);
+            return true;
+        }
+        if (!ok()) return false;
+        if (bge_world_characters_warp(world_, 1, &it->second, p) != BGE_OK) return Log("bge_world_characters_warp");
+        return true;
+    }
+    // `steps` steps of length dt for every character, enqueued; nothing is read back (SyncCharacters does that)
+    bool UpdateCharacters(float dt, uint32_t steps)
+    {
+        if (!ok()) return false;
+        if (char_ids_.empty() || steps == 0u) return true; // (a frame without a sub-step: the walk and a pending jump wait for the next)
+        if (chars_stale_) {
+            if (bge_world_characters_create(world_, char_descs_.size(), char_descs_.data()) != BGE_OK) return Log("bge_world_characters_create");
+            chars_stale_ = false;
+            char_inputs_stale_ = true;
+        }
+        if (char_inputs_stale_) {
+            if (bge_world_characters_set_input(world_, 0, char_inputs_.size(), char_inputs_.data()) != BGE_OK) return Log("bge_world_characters_set_input");
+            char_inputs_stale_ = false;
+        }
+        if (bge_world_characters_update(world_, dt, steps) != BGE_OK) return Log("bge_world_characters_update");
+        for (bge_character_input& in : char_inputs_) in.buttons &= ~static_cast<uint32_t>(BGE_CHAR_BUTTON_JUMP); // (the update consumed the edges)
+        return true;
+    }
+    // One download; each character's position goes into its Transform, as SyncRigidBodiesFromPhysics does for bodies
+    bool SyncCharacters(SceneT& scene)
+    {
+        if (!ok()) return false;
+        if (char_ids_.empty() || chars_stale_) return true;
+        char_states_.resize(char_ids_.size());
+        if (bge_world_characters_download(world_, 0, char_states_.size(), char_states_.data()) != BGE_OK) return Log("bge_world_characters_download");
+        for (size_t i = 0; i < char_ids_.size(); ++i) {
+            auto* t = scene.GetTransform(char_ids_[i]);
+            if (!t) continue;
+            std::memcpy(static_cast<void*>(&t->position), char_states_[i].position, 12);
+            t->MarkDirty();
+        }
+        return true;
+    }
+    bool CharacterOnGround(Id entity) const
+    {
+        auto it = char_index_.find(entity);
+        return it != char_index_.end() && it->second < char_states_.size() && (char_states_[it->second].flags & BGE_CHAR_GROUNDED) != 0u;
+    }
+    template <class Vec3> bool GetCharacterState(Id entity, GpuCharacterState<Vec3>& out) const
+    {
+        auto it = char_index_.find(entity);
+        if (it == char_index_.end() || it->second >= char_states_.size()) return false;
+        const bge_character_state& s = char_states_[it->second];
+        out = GpuCharacterState<Vec3>{};
+        out.position.x = s.position[0], out.position.y = s.position[1], out.position.z = s.position[2];
+        out.verticalVelocity = s.vertical_velocity;
+        out.valid = (s.flags & BGE_CHAR_INVALID) == 0u;
+        out.grounded = (s.flags & BGE_CHAR_GROUNDED) != 0u;
+        out.jumped = (s.flags & BGE_CHAR_JUMPED) != 0u;
+        out.landed = (s.flags & BGE_CHAR_LANDED) != 0u;
+        out.headBump = (s.flags & BGE_CHAR_HEAD_BUMP) != 0u;
+        out.recovered = (s.flags & BGE_CHAR_RECOVERED) != 0u;
+        out.stuck = (s.flags & BGE_CHAR_STUCK) != 0u;
+        out.stepped = (s.flags & BGE_CHAR_STEPPED) != 0u;
+        out.outOfSlides = (s.flags & BGE_CHAR_OUT_OF_SLIDES) != 0u;
+        out.groundEntity = s.ground_entity != BGE_RAY_NO_ENTITY && s.ground_entity < ids_.size() ? ids_[s.ground_entity] : Id{0};
+        out.groundTrigger = s.ground_kind == BGE_RAY_TRIGGER;
+        out.groundNormal.x = s.ground_normal[0], out.groundNormal.y = s.ground_normal[1], out.groundNormal.z = s.ground_normal[2];
+        out.hitEntity = s.hit_entity != BGE_RAY_NO_ENTITY && s.hit_entity < ids_.size() ? ids_[s.hit_entity] : Id{0};
+        out.hitTrigger = s.hit_kind == BGE_RAY_TRIGGER;
+        out.hitNormal.x = s.hit_normal[0], out.hitNormal.y = s.hit_normal[1], out.hitNormal.z = s.hit_normal[2];
+        out.stepRise = s.step_rise;
+        out.recoveredBy.x = s.recovered[0], out.recoveredBy.y = s.recovered[1], out.recoveredBy.z = s.recovered[2];
+        out.steps = s.steps;
+        return true;
+    }
+
     // CollectDebugLines + debugDrawWorld(DBG_DrawContactPoints) (PhysicsSystem.cpp:857-873, 1148-1175) on the device world as
     // the last Update left it: the count, then the lines (include/bge_world.h states what is drawn and in which order)
     bool DebugLines(const bge_debug_desc& desc, DebugLineBuffer& out)
@@ -1242,6 +1407,13 @@ private:
     std::vector<bge_sphere_step_result> step_results_;
     std::vector<bge_sphere_recover> recovers_;
     std::vector<bge_sphere_recover_result> recover_results_;
+    // characters: the set in the order it was added; the descs and inputs as the device should hold them, the states as last synced
+    std::vector<Id> char_ids_;
+    std::unordered_map<Id, uint32_t> char_index_;
+    std::vector<bge_character_desc> char_descs_;
+    std::vector<bge_character_input> char_inputs_;
+    std::vector<bge_character_state> char_states_;
+    bool chars_stale_ = false, char_inputs_stale_ = false;
 
     template <class Vec3> static bge_sphere_cast MakeCast(const Vec3& o, const Vec3& d, float maxDistance, float radius, uint32_t layerMask)
     {
@@ -1351,7 +1523,7 @@ public:
     void LogStats() const
     {
         std::printf("[Physics] bodies=%d characters=%zu stepTime=%.4fms substeps=%d fixedStep=%.4f actualDt=%.4f\n", lastBodies_,
-                    static_cast<size_t>(0), lastStepDurationMs_, lastStepSubsteps_, config_.fixedStep, lastStepDt_);
+                    lastScene_ ? GpuMirrors<SceneT>::Of(*lastScene_).CharacterCount() : static_cast<size_t>(0), lastStepDurationMs_, lastStepSubsteps_, config_.fixedStep, lastStepDt_);
     }
     double GetFixedStep() const { return config_.fixedStep; }
 
@@ -1475,6 +1647,77 @@ public:
         return GpuMirrors<SceneT>::Of(*lastScene_).RecoverSpheres(spheres, results);
     }
 
+    // EXTENSION: sphere characters on the device (include/bge_world.h "Characters") in the place of the reference's
+    // btKinematicCharacterController (PhysicsSystem.cpp:709-846).  The surface follows the reference's use of Bullet's controller;
+    // the shape is a sphere of the capsule's radius, and capsules, pushing Dynamic bodies and riding platforms are not done.
+    // Per frame, after Update: SetCharacterWalk / CharacterJump from the input, UpdateCharacters(fixed step, the Update's
+    // sub-steps), SyncCharacters.  They act on the scene of the last Update and return false before it.
+    // AddCharacter: the position is the entity's Transform's; radius, step height, max slope, jump speed and gravity are the
+    // Config's, as EnsureCharacter takes them (:735-760); the fall speed is |gravity| * 3 (:761).  The ground probe reaches 0.1 below the
+    // character: a descending character within that of walkable ground is put on it, so a longer probe would end a jump early.
+    bool AddCharacter(typename GpuSceneMirror<SceneT>::Id entity)
+    {
+        if (!lastScene_) return false;
+        GpuCharacterKnobs k;
+        k.radius = config_.capsuleRadius;
+        k.stepHeight = std::max(config_.stepHeight, 0.0f);
+        k.maxSlopeRad = config_.maxSlopeDeg * 0.017453292f;
+        k.probeDistance = 0.1f;
+        k.gravity = std::max(-config_.gravity, 0.0f);
+        k.jumpSpeed = std::max(config_.jumpImpulse, 0.0f);
+        k.fallSpeed = std::max(std::fabs(config_.gravity) * 3.0f, 1.0f);
+        return GpuMirrors<SceneT>::Of(*lastScene_).AddCharacter(*lastScene_, entity, k);
+    }
+    void RemoveCharacters()
+    {
+        if (lastScene_) GpuMirrors<SceneT>::Of(*lastScene_).RemoveCharacters();
+    }
+    // the level displacement of one step: what setWalkDirection takes (:827)
+    bool SetCharacterWalk(typename GpuSceneMirror<SceneT>::Id entity, float dx, float dz)
+    {
+        return lastScene_ && GpuMirrors<SceneT>::Of(*lastScene_).SetCharacterWalk(entity, dx, dz);
+    }
+    // jump.pressed (:834): sets the edge; "only on the ground" (:840) is applied on the device
+    bool CharacterJump(typename GpuSceneMirror<SceneT>::Id entity) { return lastScene_ && GpuMirrors<SceneT>::Of(*lastScene_).CharacterJump(entity); }
+    template <class Vec3> bool WarpCharacter(typename GpuSceneMirror<SceneT>::Id entity, const Vec3& position)
+    {
+        return lastScene_ && GpuMirrors<SceneT>::Of(*lastScene_).WarpCharacter(entity, position);
+    }
+    bool UpdateCharacters(float dt, uint32_t steps) { return lastScene_ && GpuMirrors<SceneT>::Of(*lastScene_).UpdateCharacters(dt, steps); }
+    bool SyncCharacters(SceneT& scene) { return GpuMirrors<SceneT>::Of(scene).SyncCharacters(scene); }
+    // as of the last SyncCharacters
+    bool CharacterOnGround(typename GpuSceneMirror<SceneT>::Id entity) const
+    {
+        return lastScene_ && GpuMirrors<SceneT>::Of(*lastScene_).CharacterOnGround(entity);
+    }
+    template <class Vec3> bool GetCharacterState(typename GpuSceneMirror<SceneT>::Id entity, GpuCharacterState<Vec3>& out) const
+    {
+        return lastScene_ && GpuMirrors<SceneT>::Of(*lastScene_).GetCharacterState(entity, out);
+    }
+    // The walk displacement of one step from the camera's yaw, the MoveForward and MoveRight axes, Sprint, the walk speed and dt, with
+    // the arithmetic of HandleCharacterInput (:797-832): no walk unless the direction's squared length exceeds 1e-5; the sprint
+    // multiplier is the reference's 1.8.
+    static void CharacterWalkFromInput(float yaw, float moveForward, float moveRight, bool sprint, float walkSpeed, double dt, float& dx, float& dz)
+    {
+        const float forwardX = std::cos(yaw);
+        const float forwardZ = std::sin(yaw);
+        const float rightX = forwardZ;
+        const float rightZ = -forwardX;
+        const float multiplier = sprint ? 1.8f : 1.0f;
+        float x = forwardX * moveForward + rightX * moveRight;
+        float z = forwardZ * moveForward + rightZ * moveRight;
+        dx = dz = 0.0f;
+        const float length2 = x * x + z * z;
+        if (length2 > 1e-5f) {
+            const float inv = 1.0f / std::sqrt(length2); // btVector3::normalize
+            x *= inv;
+            z *= inv;
+            const float speed = walkSpeed * multiplier;
+            dx = x * speed * static_cast<float>(dt);
+            dz = z * speed * static_cast<float>(dt);
+        }
+    }
+
     // The debug overlay (src/physics/PhysicsSystem.h:77-82, bound to a key at src/core/Application.cpp:173; the renderer gets
     // GetDebugLines() every frame, :359).  While it is on, Update refills the buffer after the step (one bge_world_debug_lines
     // query on the scene's mirror); while it is off GetDebugLines() is empty and Update does nothing for it.
@@ -1498,7 +1741,8 @@ public:
     }
     void ClearDebugRegion() { debugDesc_.use_region = 0u; }
 
-    // PhysicsSystem::Config (src/physics/PhysicsSystem.h:85-95); the character fields are read and kept, nothing here uses them
+    // PhysicsSystem::Config (src/physics/PhysicsSystem.h:85-95); AddCharacter takes the character fields (capsuleHeight has no use
+    // for a sphere; walkSpeed is the caller's, for CharacterWalkFromInput)
     struct Config {
         float gravity = -9.81f;
         float fixedStep = 1.0f / 120.0f;

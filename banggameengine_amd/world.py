@@ -156,6 +156,42 @@ def make_sphere_recovers(positions, radius=0.5, skin=0.01, layer_mask=0xFFFFFFFF
     return records
 
 
+# characters (bge_world_characters_*): bge_character_flags, bge_character_buttons and the three records
+CHAR_INVALID, CHAR_GROUNDED, CHAR_JUMPED, CHAR_LANDED, CHAR_HEAD_BUMP = 1, 2, 4, 8, 16
+CHAR_RECOVERED, CHAR_STUCK, CHAR_STEPPED, CHAR_OUT_OF_SLIDES = 32, 64, 128, 256
+CHAR_BUTTON_JUMP = 1
+CHARACTER_DESC_DTYPE = np.dtype([("position", "<f4", (3,)), ("radius", "<f4"), ("skin", "<f4"), ("step_height", "<f4"), ("min_ground_ny", "<f4"),
+                                 ("probe_distance", "<f4"), ("gravity", "<f4"), ("jump_speed", "<f4"), ("fall_speed", "<f4"), ("layer_mask", "<u4")])
+CHARACTER_INPUT_DTYPE = np.dtype([("walk_x", "<f4"), ("walk_z", "<f4"), ("buttons", "<u4"), ("reserved", "<u4")])
+CHARACTER_STATE_DTYPE = np.dtype([("position", "<f4", (3,)), ("vertical_velocity", "<f4"), ("flags", "<u4"), ("ground_kind", "<u4"),
+                                  ("ground_entity", "<u4"), ("ground_normal", "<f4", (3,)), ("hit_kind", "<u4"), ("hit_entity", "<u4"),
+                                  ("hit_normal", "<f4", (3,)), ("step_rise", "<f4"), ("recovered", "<f4", (3,)), ("steps", "<u4")])
+assert CHARACTER_DESC_DTYPE.itemsize == 48 and CHARACTER_INPUT_DTYPE.itemsize == 16 and CHARACTER_STATE_DTYPE.itemsize == 80
+
+
+def make_characters(positions, radius=0.5, skin=0.01, step_height=0.35, min_ground_ny=0.7071068, probe_distance=0.1, gravity=9.81, jump_speed=5.0,
+                    fall_speed=29.43, layer_mask=0xFFFFFFFF):
+    """bge_character_desc records: positions (n, 3); every other argument a scalar or one value per character."""
+    p = np.ascontiguousarray(positions, np.float32).reshape(-1, 3)
+    descs = np.zeros(len(p), CHARACTER_DESC_DTYPE)
+    descs["position"] = p
+    for k, v in (("radius", radius), ("skin", skin), ("step_height", step_height), ("min_ground_ny", min_ground_ny),
+                 ("probe_distance", probe_distance), ("gravity", gravity), ("jump_speed", jump_speed), ("fall_speed", fall_speed)):
+        descs[k] = np.broadcast_to(np.asarray(v, np.float32), (len(p),))
+    descs["layer_mask"] = np.broadcast_to(np.asarray(layer_mask, np.uint64).astype(np.uint32), (len(p),))
+    return descs
+
+
+def make_character_inputs(walk_x, walk_z, jump=False):
+    """bge_character_input records: the level displacement of one step per character, and whether the JUMP edge is set."""
+    x = np.atleast_1d(np.asarray(walk_x, np.float32))
+    inputs = np.zeros(len(x), CHARACTER_INPUT_DTYPE)
+    inputs["walk_x"] = x
+    inputs["walk_z"] = np.broadcast_to(np.asarray(walk_z, np.float32), (len(x),))
+    inputs["buttons"] = np.where(np.broadcast_to(np.asarray(jump, bool), (len(x),)), CHAR_BUTTON_JUMP, 0)
+    return inputs
+
+
 # debug overlay (bge_world_debug_lines*): bge_debug_flags and the 28-byte line record
 DEBUG_SHAPES, DEBUG_CONTACTS, DEBUG_ALL = 1, 2, 3
 DEBUG_LINE_DTYPE = np.dtype([("from", "<f4", (3,)), ("to", "<f4", (3,)), ("abgr", "<u4")])
@@ -653,6 +689,54 @@ class World:
         world's stream without synchronisation, as raycast_device()."""
         n = _device_records(records, results, "records", "results", 28, 64)
         check(lib().bge_world_sphere_recover_device(self._h, n, C.c_void_p(records.data_ptr()), C.c_void_p(results.data_ptr())))
+
+    # -- characters (an extension; include/bge_world.h "Characters" states the rule: recover, gravity and jump, step move, ground snap)
+    def characters_create(self, descs):
+        """Replaces the world's character set: descs is a CHARACTER_DESC_DTYPE array (make_characters()); an empty one removes
+        the set.  Characters start at their desc's position, not grounded, at rest."""
+        descs = np.ascontiguousarray(descs, CHARACTER_DESC_DTYPE)
+        check(lib().bge_world_characters_create(self._h, len(descs), _p(descs) if len(descs) else None))
+
+    def characters_set_input(self, inputs, first=0):
+        """inputs: a CHARACTER_INPUT_DTYPE array (make_character_inputs()) for characters first .., or a contiguous device tensor
+        holding such records (16 bytes each), which is copied on the world's stream without synchronisation."""
+        if hasattr(inputs, "data_ptr"):
+            nb = inputs.numel() * inputs.element_size()
+            if nb % 16:
+                raise ValueError(f"inputs holds {nb} bytes, not a whole number of 16-byte records")
+            if not (inputs.is_cuda and inputs.is_contiguous()):
+                raise ValueError("inputs must be a contiguous device tensor")
+            check(lib().bge_world_characters_set_input_device(self._h, first, nb // 16, C.c_void_p(inputs.data_ptr())))
+            return
+        inputs = np.ascontiguousarray(inputs, CHARACTER_INPUT_DTYPE)
+        check(lib().bge_world_characters_set_input(self._h, first, len(inputs), _p(inputs)))
+
+    def characters_warp(self, index, positions):
+        """Puts the characters index[k] at positions[k], at rest and not grounded."""
+        index = np.ascontiguousarray(np.atleast_1d(index), np.uint32)
+        positions = np.ascontiguousarray(positions, np.float32).reshape(-1, 3)
+        if len(index) != len(positions):
+            raise ValueError(f"{len(index)} indices, {len(positions)} positions")
+        check(lib().bge_world_characters_warp(self._h, len(index), _p(index), _p(positions)))
+
+    def characters_update(self, dt, steps=1):
+        """Enqueues `steps` steps of length dt for every character on the world's stream; nothing is read back."""
+        check(lib().bge_world_characters_update(self._h, float(dt), int(steps)))
+
+    def characters_state(self, first=0, count=None):
+        """The states of characters first .. first + count (all of them by default) as a CHARACTER_STATE_DTYPE array.
+        Synchronises the world's stream."""
+        if count is None:
+            count = self.characters_state_device()[1] - first
+        states = np.zeros(max(count, 0), CHARACTER_STATE_DTYPE)
+        check(lib().bge_world_characters_download(self._h, first, count, _p(states) if count > 0 else None))
+        return states
+
+    def characters_state_device(self):
+        """(device pointer, n) of the resident bge_character_state[n]; (0, 0) without characters."""
+        ptr, n = C.c_void_p(), C.c_uint64()
+        check(lib().bge_world_characters_state_device(self._h, C.byref(ptr), C.byref(n)))
+        return int(ptr.value or 0), int(n.value)
 
     # -- debug overlay (PhysicsSystem::GetDebugLines; include/bge_world.h states what is drawn and in which order)
     def debug_lines(self, flags=DEBUG_ALL, region=None):

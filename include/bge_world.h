@@ -757,6 +757,125 @@ BGE_API int bge_world_sphere_recover(bge_world* world, uint64_t n, const bge_sph
 BGE_API int bge_world_sphere_recover_device(bge_world* world, uint64_t n, const void* records_device, void* results_device);
 
 /*
+ * Characters: a set of sphere characters that lives on the device between frames — position, vertical velocity and whether the
+ * character stands on ground — with gravity, jump, the fall-speed clamp, the snap that keeps a walker on a downward slope, and one
+ * call that runs a frame, or several sub-steps, for all of them with no host round trip.  An extension, as every
+ * sphere mover: the reference drives one btKinematicCharacterController on a capsule (src/physics/PhysicsSystem.cpp:709-846); the
+ * surface here (walk displacement, jump, on-ground, warp, gravity, jump speed, fall speed, max slope, step height) and the meaning
+ * of its knobs follow that use, the shape is a sphere, and the rule below is the specification.  All arithmetic is binary32, one
+ * rounding per operation, left to right.
+ *   Recover, StepMove  are bge_world_sphere_recover and bge_world_sphere_step_move, word for word.  The character sees the world
+ *             only through them, so Objects, poses (the last physics tick), Filter and tie order are theirs by construction.
+ *   One step of length dt, per character:
+ *   Input     walk_x and walk_z are the level displacement of this step (what setWalkDirection takes: direction * speed * dt).
+ *             BGE_CHAR_BUTTON_JUMP is an edge: the first step of an update call reads it and clears it, whether or not it led to
+ *             a jump; the further steps of that call see it clear.
+ *   Valid     the step is valid iff walk_x and walk_z are finite and neither the recovery nor the step move below comes back
+ *             INVALID.  An invalid step sets BGE_CHAR_INVALID, leaves position, vertical_velocity and GROUNDED as they were before
+ *             the step and clears every other flag; ground_* and hit_* take the miss convention (BGE_RAY_MISS, BGE_RAY_NO_ENTITY,
+ *             0), step_rise and recovered are 0, steps += 1.
+ *   Recover   R = Recover{position, radius, skin, layer_mask}.  p = R.position.  RECOVERED iff R is MOVED, STUCK iff R is STUCK,
+ *             recovered = R.pushed.
+ *   Vertical  was = GROUNDED before the step.  jumped = JUMP && was.
+ *             If jumped: vv = jump_speed.  Else if was: vv = 0, the character is walking and dy = 0.
+ *             When not walking:  vv = vv - gravity*dt;  if vv > jump_speed then vv = jump_speed;
+ *                                if vv < -fall_speed then vv = -fall_speed;  dy = vv*dt.
+ *   Move      M = StepMove{p, (walk_x, dy, walk_z), radius, skin, probe_distance, min_ground_ny, layer_mask,
+ *             step_height if walking else 0}.  q = M.position.
+ *   Ground    grounded = M.GROUNDED && !(vv > 0).  If grounded: e = M.ground_distance - skin; if !(e > 0) then e = 0;
+ *             q.y = q.y - e; vv = 0.  This is the vertical back-off of the step move's Down stage, so the gap kept to a slope is
+ *             skin * normal.y > 0.  LANDED iff grounded && !was.
+ *   Head      if vv > 0 && M.n_hits >= 1 && M.hit_normal[1] < 0: vv = 0 and HEAD_BUMP is set.
+ *   State     position = q, vertical_velocity = vv; the flags GROUNDED, JUMPED, LANDED, HEAD_BUMP, RECOVERED, STUCK, and STEPPED and
+ *             OUT_OF_SLIDES from M; ground_kind, ground_entity and ground_normal from M's probe (its miss convention where it
+ *             found nothing); hit_kind, hit_entity, hit_normal and step_rise from M; recovered; steps += 1.
+ *   Hence     a walker stays on a downward slope only while probe_distance covers the drop of one step: a walker moves level, the
+ *             probe finds the slope below and Ground brings it down; where the probe misses, GROUNDED is lost and the character
+ *             falls from the next step on.  probe_distance = 0 never grounds.  Step-up happens only while walking (a character in
+ *             the air asks step_height 0, the plain move).  A character that walks off an edge loses GROUNDED without JUMPED.
+ *             A kerb is stepped in the step whose walk brings the centre far enough over its edge that the Down stage lands on
+ *             walkable ground (within radius * sqrt(1 - min_ground_ny^2) of the edge, level): a walk much shorter than that per
+ *             step rests at the kerb's face.  A sphere whose radius exceeds the kerb's height meets its upper edge, not its face,
+ *             and may roll over it by the plain slide.
+ *   Example   radius 0.5, skin 0.01, gravity 9.81, jump_speed 5, fall_speed 30, probe_distance 0.1, dt = 1/60 (0.0166667), plane
+ *             on.  A character GROUNDED at (0, 0.51, 0) with JUMP set and no walk.  Step 1: jumped, vv = 5 - 9.81 dt = 4.8365,
+ *             dy = 0.0806083, nothing is met: position y = 0.5906083; the probe finds the plane 0.0906 below but vv > 0: not
+ *             grounded; flags JUMPED.  Step 2: vv = 4.673, dy = 0.0778833, y = 0.6684917, flags 0.  Step 3: vv = 4.5095,
+ *             dy = 0.0751583, y = 0.74365.  vv turns negative in step 31; in step 60 the move ends 0.02325 above the touching
+ *             height, the probe finds the plane at that distance, e = 0.01325: y = 0.51, vv = 0, flags GROUNDED | LANDED.
+ *             The kerb of "Sphere step moves" (min_ground_ny cos 45 degrees, step_height 0.7): a character GROUNDED at
+ *             (0, 0.51, 0) with walk (2, 0): walking, dy = 0, M is that example's result: position (2, 1.11, 0), ground_distance
+ *             0.01, e = 0: flags GROUNDED | STEPPED, step_rise 0.7, ground_kind BODY, entity 0.
+ *   Not done  capsule characters; pushing Dynamic bodies; riding moving platforms (a platform that moves INTO a character pushes
+ *             it out through Recover, one that moves away or along does not carry it); trigger events for characters; writing into
+ *             a Transform on the device (the adapter does that on the host).
+ *   Characters are not bodies: no query sees them, they do not see each other, and no call here changes any other world state.
+ *   bge_world_characters_create   replaces the set with n characters made from descs; n = 0 removes it (descs may then be NULL).
+ *                                 Every desc is checked on the host: every float finite, radius >= 0, skin > 0, step_height >= 0,
+ *                                 probe_distance >= 0, gravity >= 0, jump_speed >= 0, fall_speed > 0, layer_mask != 0; a bad desc is
+ *                                 BGE_ERR_INVALID with its index in bge_last_error, and the set is left as it was.  Characters start
+ *                                 at desc.position, not grounded, vertical_velocity 0, steps 0, inputs zero.  n is at most 2^30 - 1
+ *                                 (the step move's bound).  May be called before bge_world_set_topology.
+ *   bge_world_characters_set_input         inputs[0 .. count) for characters first .. first + count (host memory).
+ *   bge_world_characters_set_input_device  the same from a device pointer, 4-byte aligned (a misaligned pointer is
+ *                                 BGE_ERR_INVALID); enqueued on the world's stream, no synchronisation.  A range outside the set is
+ *                                 BGE_ERR_INVALID for both.
+ *   bge_world_characters_warp     for k < count: character index[k] takes position3[3k ..], vertical_velocity 0 and loses GROUNDED,
+ *                                 as warp does in the reference (:1315).  Positions must be finite and indices inside the set.
+ *   bge_world_characters_update   dt finite and > 0 and steps >= 1, otherwise BGE_ERR_INVALID.  Enqueues `steps` steps on the
+ *                                 world's stream: no synchronisation and nothing read in between.  With no characters it is a
+ *                                 no-op; with characters before bge_world_set_topology it returns what bge_world_sphere_cast returns
+ *                                 there.  A step is 5 penetration passes and 7 sphere-cast passes over the world
+ *                                 (4 of them over two casts per character).
+ *   bge_world_characters_download states[0 .. count) of characters first .. first + count.  Synchronises the world's stream.
+ *   bge_world_characters_state_device  the resident bge_character_state[n] (NULL and 0 without characters), valid until the next
+ *                                 bge_world_characters_create; reads must be ordered after the world's stream.
+ */
+typedef struct bge_character_desc {
+    float position[3];    /* where the character starts */
+    float radius;
+    float skin;           /* > 0 */
+    float step_height;    /* >= 0: the kerb a walking character gets over; 0 = none */
+    float min_ground_ny;  /* GROUNDED needs ground normal.y >= this (cos of the max slope) */
+    float probe_distance; /* >= 0: how far below itself the character looks for ground; 0 never grounds */
+    float gravity;        /* >= 0, downwards */
+    float jump_speed;     /* >= 0: vertical_velocity after a jump, and its upper clamp */
+    float fall_speed;     /* > 0: vertical_velocity is never below -fall_speed */
+    uint32_t layer_mask;
+} bge_character_desc; /* 48 bytes */
+enum bge_character_buttons { BGE_CHAR_BUTTON_JUMP = 1u };
+typedef struct bge_character_input {
+    float walk_x, walk_z; /* level displacement of one step */
+    uint32_t buttons;     /* bge_character_buttons: edges, cleared by the step that reads them */
+    uint32_t reserved;    /* 0 */
+} bge_character_input; /* 16 bytes */
+enum bge_character_flags {
+    BGE_CHAR_INVALID = 1u, BGE_CHAR_GROUNDED = 2u, BGE_CHAR_JUMPED = 4u, BGE_CHAR_LANDED = 8u, BGE_CHAR_HEAD_BUMP = 16u,
+    BGE_CHAR_RECOVERED = 32u, BGE_CHAR_STUCK = 64u, BGE_CHAR_STEPPED = 128u, BGE_CHAR_OUT_OF_SLIDES = 256u
+};
+typedef struct bge_character_state {
+    float position[3];
+    float vertical_velocity;
+    uint32_t flags;        /* bge_character_flags of the last step (GROUNDED is also state) */
+    uint32_t ground_kind;  /* the last step's ground probe: bge_ray_kind; BGE_RAY_MISS / BGE_RAY_NO_ENTITY / 0 if none */
+    uint32_t ground_entity;
+    float ground_normal[3];
+    uint32_t hit_kind;     /* the last hit of the last step's slides, same convention */
+    uint32_t hit_entity;
+    float hit_normal[3];
+    float step_rise;       /* with STEPPED: how far the last step rose */
+    float recovered[3];    /* what the last step's recovery pushed the character by */
+    uint32_t steps;        /* steps run since the set was created */
+} bge_character_state; /* 80 bytes */
+BGE_API int bge_world_characters_create(bge_world* world, uint64_t n, const bge_character_desc* descs);
+BGE_API int bge_world_characters_set_input(bge_world* world, uint64_t first, uint64_t count, const bge_character_input* inputs);
+BGE_API int bge_world_characters_set_input_device(bge_world* world, uint64_t first, uint64_t count, const void* inputs_device);
+BGE_API int bge_world_characters_warp(bge_world* world, uint64_t count, const uint32_t* index, const float* position3);
+BGE_API int bge_world_characters_update(bge_world* world, float dt, uint32_t steps);
+BGE_API int bge_world_characters_download(bge_world* world, uint64_t first, uint64_t count, bge_character_state* states);
+BGE_API int bge_world_characters_state_device(bge_world* world, void** states_device, uint64_t* n);
+
+/*
  * The physics debug overlay: what PhysicsSystem::GetDebugLines hands to the renderer while the overlay is on
  * (src/physics/PhysicsSystem.cpp:857-873, 1148-1175; src/physics/BulletDebugDrawer.cpp) — every collision object's shape as
  * wireframe lines in one colour, then one short red line per contact point — made on the device from the state the last tick
