@@ -117,6 +117,12 @@ SYMBOLS = {
     "bge_world_characters_update": (C.c_int, [_vp, _f, _u32]),
     "bge_world_characters_download": (C.c_int, [_vp, _u64, _u64, _vp]),
     "bge_world_characters_state_device": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_u64)]),
+    "bge_world_characters_watch_triggers": (C.c_int, [_vp, _u64, _vp, _vp, _u32, _u64]),
+    "bge_world_characters_trigger_events": (C.c_int, [_vp, _vp, _u64, C.POINTER(_u64)]),
+    "bge_world_characters_trigger_events_device": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_u64)]),
+    "bge_world_characters_trigger_overlaps": (C.c_int, [_vp, _u64, _vp, C.POINTER(_u64)]),
+    "bge_world_characters_set_trigger_overlaps": (C.c_int, [_vp, _u64, _vp]),
+    "bge_world_trigger_boxes": (C.c_int, [_vp, _u64, _vp, _vp, _vp]),
     "bge_world_debug_lines": (C.c_int, [_vp, _vp, _vp, _u64, C.POINTER(_u64)]),
     "bge_world_debug_lines_device": (C.c_int, [_vp, _vp, _vp, _u64, _vp]),
     "bge_world_upload_bounds": (C.c_int, [_vp, _u64, _u64, _vp, _vp]),

@@ -33,6 +33,7 @@
 #include "bge_step.hpp"
 #include "bge_recover.hpp"
 #include "bge_character.hpp"
+#include "bge_chartrig.hpp"
 #include "bge_query.hpp"
 
 namespace {
@@ -393,6 +394,15 @@ struct bge_world {
     // recovery and the step move and get back, and the step's scratch
     DevBuf char_desc, char_input, char_state, char_recover_in, char_recover_out, char_step_in, char_step_out, char_scratch;
     uint64_t n_characters = 0;
+    // character trigger events (bge_chartrig.hip): the per-character filters, the two [triggers][ceil(n / 64)] bitmaps
+    // (ct_bits[ct_rem] = remembered, the other = remembered before the last update call), the per-(ghost, word) counts / offsets, the
+    // per-ghost totals, bases and {trigger, entity} of the last call, the event list and its count
+    DevBuf ct_group, ct_mask, ct_bits[2], ct_counts, ct_row_total, ct_row_base, ct_ghost_rec, ct_events, ct_count, ct_src_row;
+    bool ct_on = false;
+    uint32_t ct_flags = 0;
+    int ct_rem = 0;
+    uint64_t ct_rows = 0, ct_words = 0, ct_cap = 0;
+    uint32_t ct_last_ghosts = 0; // ghosts of the last update call: with ct_bits and the offsets, what makes its list again
     // debug overlay (bge_debug.hip): per-workgroup line counts and their offsets, the host entry point's line buffer and total
     DevBuf dbg_block_sum, dbg_block_off, dbg_lines, dbg_total;
     // frustum culling (bge_cull.hip): the model-space bounds per ENTITY (a row of NaNs = no bounds), the pass's ballots / counts /
@@ -483,7 +493,7 @@ struct bge_world {
         for (DevBuf* b : std::initializer_list<DevBuf*>{&flags, &parent, &tile_hdr, &slot_of_entity, &entity_of_slot, &root_slots, &root_index, &root_worlds, &counter, &stage,
                           &stage2, &mass_palette, &normal, &filter_table, &grav_palette, &bp_partials, &obstacle_slots, &obstacle_gen, &obstacles, &obstacle_grid, &box_list, &box_count, &frozen, &rs_word, &trig_slot, &trig_entity, &trig_he, &trig_group,
                           &trig_mask, &trig_active, &trig_aabb, &trig_pairs, &trig_count, &trig_lists, &ground_list, &ground_count, &trig_tab[0], &trig_tab[1],
-                          &trig_delta_dev, &trig_keys_dev, &trig_pose, &query_in, &query_out, &query_keys, &query_all, &query_all_count, &query_ghosts, &move_in, &move_out, &move_state, &move_casts, &move_hits, &step_in, &step_out, &step_state, &step_casts, &step_hits, &recover_in, &recover_out, &recover_state, &recover_queries, &recover_hits, &char_desc, &char_input, &char_state, &char_recover_in, &char_recover_out, &char_step_in, &char_step_out, &char_scratch, &dbg_block_sum, &dbg_block_off,
+                          &trig_delta_dev, &trig_keys_dev, &trig_pose, &query_in, &query_out, &query_keys, &query_all, &query_all_count, &query_ghosts, &move_in, &move_out, &move_state, &move_casts, &move_hits, &step_in, &step_out, &step_state, &step_casts, &step_hits, &recover_in, &recover_out, &recover_state, &recover_queries, &recover_hits, &char_desc, &char_input, &char_state, &char_recover_in, &char_recover_out, &char_step_in, &char_step_out, &char_scratch, &ct_group, &ct_mask, &ct_bits[0], &ct_bits[1], &ct_counts, &ct_row_total, &ct_row_base, &ct_ghost_rec, &ct_events, &ct_count, &ct_src_row, &dbg_block_sum, &dbg_block_off,
                           &dbg_lines, &dbg_total, &bounds, &cull_ballots, &cull_block_sum, &cull_block_off, &cull_out, &cull_total, &draw_keys,
                           &batch_sort, &batch_hist, &batch_out}) {
             b->release();
@@ -2804,11 +2814,154 @@ try {
 }
 BGE_CATCH_ALL("bge_world_bp_exchange")
 
+// ---------------------------------------------------------------- character trigger events: state (bge_chartrig.hip)
+namespace {
+
+constexpr uint64_t kCharTrigMaxWords = 1ull << 28;              // 64-bit words of one bitmap
+constexpr uint64_t kCharTrigMaxRows = 65535ull * bge::kCharTrigChunk; // (one grid row per chunk of ghosts)
+
+// NULL, or why a watch over `rows` triggers and n characters cannot be kept
+const char* chartrig_bound_fault(uint64_t rows, uint64_t n)
+{
+    const uint64_t words = (n + 63u) / 64u;
+    if (rows > kCharTrigMaxRows) return "more than 65535 * 64 triggers";
+    if (words != 0 && rows > kCharTrigMaxWords / words) return "triggers x ceil(n / 64) exceeds 2^28 words";
+    return nullptr;
+}
+
+// The arrays whose size follows the trigger array, for `rows` triggers.  Their contents are lost: only after chartrig_settle.
+int chartrig_size_rows(bge_world* w, uint64_t rows)
+{
+    const uint64_t r = std::max<uint64_t>(rows, 1);
+    HIP_TRY(w->ct_counts.ensure(r * w->ct_words * 8));
+    HIP_TRY(w->ct_row_total.ensure(r * 8));
+    HIP_TRY(w->ct_row_base.ensure(r * 8));
+    HIP_TRY(w->ct_ghost_rec.ensure(r * 8));
+    HIP_TRY(w->ct_src_row.ensure(r * 4));
+    return BGE_OK;
+}
+
+// the passes' parameters: `cur` is ct_bits[cur_buf], `prev` the other
+bge::CharTrigParams chartrig_params(bge_world* w, int cur_buf, uint32_t n_ghosts)
+{
+    bge::CharTrigParams p{};
+    p.state = w->char_state.p;
+    p.desc = w->char_desc.p;
+    p.group = w->ct_group.as<uint32_t>();
+    p.mask = w->ct_mask.as<uint32_t>();
+    p.n = static_cast<uint32_t>(w->n_characters);
+    p.words = static_cast<uint32_t>(w->ct_words);
+    p.ghosts = w->query_ghosts.as<bge::QueryGhost>();
+    p.n_ghosts = n_ghosts;
+    p.aabb = w->trig_aabb.as<float>();
+    p.prev = w->ct_bits[1 - cur_buf].as<unsigned long long>();
+    p.cur = w->ct_bits[cur_buf].as<unsigned long long>();
+    p.counts = w->ct_counts.as<unsigned long long>();
+    p.row_total = w->ct_row_total.as<unsigned long long>();
+    p.row_base = w->ct_row_base.as<unsigned long long>();
+    p.ghost_rec = w->ct_ghost_rec.as<uint2>();
+    p.count = w->ct_count.as<uint32_t>();
+    p.events = w->ct_events.p;
+    p.cap = w->ct_cap;
+    p.stay = (w->ct_flags & BGE_CHAR_TRIGGER_STAY_EVENTS) ? 1u : 0u;
+    return p;
+}
+
+// Waits for the stream, reads the last call's count and makes the device list hold all of it (and at least min_cap records): where
+// the call found more than the list holds, the list grows and is made again from the two bitmaps and the offsets the call left.
+// After this the list no longer depends on the bitmaps.
+int chartrig_settle(bge_world* w, uint64_t min_cap, uint32_t* count_out)
+{
+    HIP_TRY(hipStreamSynchronize(w->stream));
+    uint32_t count = 0;
+    if (w->ct_on) HIP_TRY(hipMemcpy(&count, w->ct_count.p, 4, hipMemcpyDeviceToHost));
+    if (count_out) *count_out = count;
+    if (!w->ct_on) return BGE_OK;
+    if (count == 0xffffffffu) return fail(BGE_ERR_UNSUPPORTED, "more than 2^32 - 2 character trigger events in one call");
+    const uint64_t need = std::max<uint64_t>(count, min_cap);
+    if (need <= w->ct_cap) return BGE_OK;
+    TmpBuf grown;
+    HIP_TRY(grown.ensure(need * sizeof(bge_character_trigger_event)));
+    if (count <= w->ct_cap) { // (complete as it is)
+        if (count) HIP_TRY(hipMemcpy(grown.p, w->ct_events.p, uint64_t(count) * sizeof(bge_character_trigger_event), hipMemcpyDeviceToDevice));
+    }
+    std::swap(static_cast<DevBuf&>(grown), w->ct_events);
+    const bool remake = count > w->ct_cap;
+    w->ct_cap = need;
+    if (remake) {
+        HIP_TRY(bge::launch_chartrig_emit(w->stream, chartrig_params(w, w->ct_rem, w->ct_last_ghosts)));
+        HIP_TRY(hipStreamSynchronize(w->stream));
+    }
+    return BGE_OK;
+}
+
+void chartrig_off(bge_world* w)
+{
+    w->ct_on = false;
+    w->ct_flags = 0;
+    w->ct_rem = 0;
+    w->ct_rows = w->ct_words = w->ct_cap = 0;
+    w->ct_last_ghosts = 0;
+    for (DevBuf* b : {&w->ct_group, &w->ct_mask, &w->ct_bits[0], &w->ct_bits[1], &w->ct_counts, &w->ct_row_total, &w->ct_row_base, &w->ct_ghost_rec,
+                      &w->ct_events, &w->ct_count, &w->ct_src_row}) {
+        b->release();
+    }
+}
+
+// bge_world_characters_update's last enqueue with the watch on, after query_prepare listed the ghosts: no synchronisation, nothing
+// read back, no allocation (the arrays were sized when the watch was turned on and when the trigger array was uploaded).
+int chartrig_enqueue(bge_world* w, uint32_t n_ghosts)
+{
+    if (w->ct_rows != w->triggers.size()) return fail(BGE_ERR_STATE, "character trigger bitmaps hold %llu rows for %llu triggers",
+                                                       (unsigned long long)w->ct_rows, (unsigned long long)w->triggers.size());
+    w->ct_last_ghosts = n_ghosts;
+    if (n_ghosts == 0) { // every trigger is skipped: no event, the remembered sets stay
+        HIP_TRY(hipMemsetAsync(w->ct_count.p, 0, 4, w->stream));
+        return BGE_OK;
+    }
+    const int cur = 1 - w->ct_rem;
+    // the rows of triggers that are not listed carry over; k_ct_test overwrites the listed ones
+    HIP_TRY(hipMemcpyAsync(w->ct_bits[cur].p, w->ct_bits[w->ct_rem].p, w->ct_rows * w->ct_words * 8, hipMemcpyDeviceToDevice, w->stream));
+    HIP_TRY(bge::launch_chartrig(w->stream, chartrig_params(w, cur, n_ghosts)));
+    w->ct_rem = cur;
+    return BGE_OK;
+}
+
+// bge_world_upload_triggers with the watch on: row i of the remembered bitmap becomes old row src_row[i], or empty.
+int chartrig_permute_rows(bge_world* w, const std::vector<uint32_t>& src_row)
+{
+    DeviceGuard guard(w->device);
+    if (int rc = chartrig_settle(w, 0, nullptr)) return rc; // (the last call's list is whole before its bitmaps go)
+    const uint64_t rows = src_row.size();
+    if (int rc = chartrig_size_rows(w, rows)) return rc;
+    const uint64_t bytes = std::max<uint64_t>(rows * w->ct_words * 8, 8);
+    TmpBuf next;
+    HIP_TRY(next.ensure(bytes));
+    if (rows) {
+        HIP_TRY(hipMemcpyAsync(w->ct_src_row.p, src_row.data(), rows * 4, hipMemcpyHostToDevice, w->stream));
+        HIP_TRY(bge::launch_chartrig_gather(w->stream, static_cast<uint32_t>(rows), static_cast<uint32_t>(w->ct_words), w->ct_src_row.as<uint32_t>(),
+                                            w->ct_bits[w->ct_rem].as<unsigned long long>(), next.as<unsigned long long>()));
+        HIP_TRY(hipStreamSynchronize(w->stream)); // (src_row and the old bitmap die here)
+    }
+    std::swap(static_cast<DevBuf&>(next), w->ct_bits[w->ct_rem]);
+    DevBuf& other = w->ct_bits[1 - w->ct_rem];
+    if (other.bytes < bytes) HIP_TRY(other.ensure(bytes));
+    w->ct_rows = rows;
+    w->ct_last_ghosts = 0;
+    return BGE_OK;
+}
+
+} // namespace
+
 int bge_world_upload_triggers(bge_world* w, uint64_t count, const uint32_t* entity_index, const uint8_t* shape, const float* size3,
                               const uint32_t* layer, const uint32_t* mask, const uint8_t* one_shot, const uint8_t* active)
 try {
     if (int rc = check_range(w, 0, 0)) return rc;
     if (count && !entity_index) return fail(BGE_ERR_INVALID, "entity_index is NULL");
+    if (w->ct_on) {
+        if (const char* what = chartrig_bound_fault(count, w->n_characters)) return fail(BGE_ERR_UNSUPPORTED, "character trigger events: %s", what);
+    }
+    std::vector<uint32_t> ct_src_row(w->ct_on ? count : 0, bge::kCharTrigNoRow);
     std::unordered_map<uint32_t, size_t> old_index;
     for (size_t i = 0; i < w->triggers.size(); ++i) old_index[w->triggers[i].entity] = i;
     std::vector<bge_world::Trigger> next(count);
@@ -2853,7 +3006,12 @@ try {
                     t.overlap_ghosts.swap(o.overlap_ghosts);
                 }
             }
+            // remembered characters follow the same rule: the same entity, layer and mask keep their row
+            if (w->ct_on && o.layer == t.layer && o.mask == t.mask) ct_src_row[i] = static_cast<uint32_t>(it->second);
         }
+    }
+    if (w->ct_on) {
+        if (int rc = chartrig_permute_rows(w, ct_src_row)) return rc;
     }
     w->triggers.swap(next);
     w->trig_index_of_entity.clear();
@@ -3483,6 +3641,7 @@ try {
     DeviceGuard guard(w->device);
     HIP_TRY(hipStreamSynchronize(w->stream)); // (an update of the old set may still be running on its buffers)
     w->n_characters = 0;
+    chartrig_off(w); // (the watch belongs to the set: its filters and bitmaps are per character)
     if (n == 0) {
         for (DevBuf* b : {&w->char_desc, &w->char_input, &w->char_state, &w->char_recover_in, &w->char_recover_out, &w->char_step_in, &w->char_step_out,
                           &w->char_scratch}) {
@@ -3602,6 +3761,9 @@ try {
         if (int rc = step_enqueue(w, q, n, w->char_step_in.p, w->char_step_out.p)) return rc;
         HIP_TRY(bge::launch_char_finish(w->stream, c));
     }
+    if (w->ct_on) {
+        if (int rc = chartrig_enqueue(w, q.n_ghosts)) return rc;
+    }
     return BGE_OK;
 }
 BGE_CATCH_ALL("bge_world_characters_update")
@@ -3628,6 +3790,159 @@ try {
     return BGE_OK;
 }
 BGE_CATCH_ALL("bge_world_characters_state_device")
+
+// ---------------------------------------------------------------- character trigger events (bge_chartrig.hip)
+static_assert(sizeof(bge_character_trigger_event) == 12, "bge_character_trigger_event is 12 bytes (include/bge_world.h)");
+
+int bge_world_characters_watch_triggers(bge_world* w, uint64_t n, const uint32_t* group, const uint32_t* mask, uint32_t flags,
+                                        uint64_t event_capacity)
+try {
+    if (!w) return fail(BGE_ERR_INVALID, "world is NULL");
+    if (flags & ~uint32_t(BGE_CHAR_TRIGGER_STAY_EVENTS)) return fail(BGE_ERR_INVALID, "flags = 0x%x: unknown bits", flags);
+    if (n != 0 && n != w->n_characters) {
+        return fail(BGE_ERR_INVALID, "n = %llu, the set holds %llu characters", (unsigned long long)n, (unsigned long long)w->n_characters);
+    }
+    DeviceGuard guard(w->device);
+    if (n == 0) {
+        HIP_TRY(hipStreamSynchronize(w->stream));
+        chartrig_off(w);
+        return BGE_OK;
+    }
+    const uint64_t rows = w->triggers.size();
+    if (const char* what = chartrig_bound_fault(rows, n)) return fail(BGE_ERR_UNSUPPORTED, "character trigger events: %s", what);
+    const uint64_t cap = event_capacity ? event_capacity : n + 1024u;
+    if (w->ct_on) {
+        if (int rc = chartrig_settle(w, cap, nullptr)) return rc; // (the remembered sets and the list stay; the list only grows)
+    } else {
+        HIP_TRY(hipStreamSynchronize(w->stream));
+        w->ct_words = (n + 63u) / 64u;
+        const uint64_t bytes = std::max<uint64_t>(rows * w->ct_words * 8, 8);
+        HIP_TRY(w->ct_group.ensure(n * 4));
+        HIP_TRY(w->ct_mask.ensure(n * 4));
+        HIP_TRY(w->ct_bits[0].ensure(bytes));
+        HIP_TRY(w->ct_bits[1].ensure(bytes));
+        HIP_TRY(w->ct_events.ensure(cap * sizeof(bge_character_trigger_event)));
+        HIP_TRY(w->ct_count.ensure(64));
+        if (int rc = chartrig_size_rows(w, rows)) return rc;
+        HIP_TRY(hipMemsetAsync(w->ct_bits[0].p, 0, bytes, w->stream));
+        HIP_TRY(hipMemsetAsync(w->ct_bits[1].p, 0, bytes, w->stream));
+        HIP_TRY(hipMemsetAsync(w->ct_count.p, 0, 64, w->stream));
+        w->ct_rows = rows;
+        w->ct_cap = cap;
+        w->ct_rem = 0;
+        w->ct_last_ghosts = 0;
+    }
+    std::vector<uint32_t> g(n, 2u), m(n, 0xffffffffu); // kDefaultCharacterLayer, mask all (PhysicsSystem.cpp:763)
+    if (group) std::memcpy(g.data(), group, n * 4);
+    if (mask) std::memcpy(m.data(), mask, n * 4);
+    HIP_TRY(hipMemcpyAsync(w->ct_group.p, g.data(), n * 4, hipMemcpyHostToDevice, w->stream));
+    HIP_TRY(hipMemcpyAsync(w->ct_mask.p, m.data(), n * 4, hipMemcpyHostToDevice, w->stream));
+    HIP_TRY(hipStreamSynchronize(w->stream)); // (the vectors die here)
+    w->ct_flags = flags;
+    w->ct_on = true;
+    return BGE_OK;
+}
+BGE_CATCH_ALL("bge_world_characters_watch_triggers")
+
+int bge_world_characters_trigger_events(bge_world* w, bge_character_trigger_event* out, uint64_t cap, uint64_t* total)
+try {
+    if (!w || !total) return fail(BGE_ERR_INVALID, "NULL argument");
+    *total = 0;
+    if (!w->ct_on) return BGE_OK;
+    DeviceGuard guard(w->device);
+    uint32_t count = 0;
+    if (int rc = chartrig_settle(w, 0, &count)) return rc;
+    *total = count;
+    const uint64_t take = out ? std::min<uint64_t>(cap, count) : 0;
+    if (take) HIP_TRY(hipMemcpy(out, w->ct_events.p, take * sizeof(bge_character_trigger_event), hipMemcpyDeviceToHost));
+    return BGE_OK;
+}
+BGE_CATCH_ALL("bge_world_characters_trigger_events")
+
+int bge_world_characters_trigger_events_device(bge_world* w, void** events, void** count, uint64_t* capacity)
+try {
+    if (!w || !events || !count || !capacity) return fail(BGE_ERR_INVALID, "NULL argument");
+    *events = w->ct_on ? w->ct_events.p : nullptr;
+    *count = w->ct_on ? w->ct_count.p : nullptr;
+    *capacity = w->ct_on ? w->ct_cap : 0;
+    return BGE_OK;
+}
+BGE_CATCH_ALL("bge_world_characters_trigger_events_device")
+
+int bge_world_characters_trigger_overlaps(bge_world* w, uint64_t cap, uint32_t* pairs2, uint64_t* total)
+try {
+    if (!w || !total) return fail(BGE_ERR_INVALID, "NULL argument");
+    *total = 0;
+    if (!w->ct_on || w->ct_rows == 0) return BGE_OK;
+    DeviceGuard guard(w->device);
+    std::vector<uint64_t> bits(w->ct_rows * w->ct_words);
+    HIP_TRY(hipStreamSynchronize(w->stream));
+    HIP_TRY(hipMemcpy(bits.data(), w->ct_bits[w->ct_rem].p, bits.size() * 8, hipMemcpyDeviceToHost));
+    uint64_t k = 0;
+    for (uint64_t r = 0; r < w->ct_rows; ++r) {
+        for (uint64_t wd = 0; wd < w->ct_words; ++wd) {
+            for (uint64_t word = bits[r * w->ct_words + wd]; word; word &= word - 1) {
+                if (pairs2 && k < cap) {
+                    pairs2[2 * k] = w->triggers[r].entity;
+                    pairs2[2 * k + 1] = static_cast<uint32_t>(64 * wd + static_cast<uint64_t>(__builtin_ctzll(word)));
+                }
+                ++k;
+            }
+        }
+    }
+    *total = k;
+    return BGE_OK;
+}
+BGE_CATCH_ALL("bge_world_characters_trigger_overlaps")
+
+int bge_world_characters_set_trigger_overlaps(bge_world* w, uint64_t count, const uint32_t* pairs2)
+try {
+    if (!w) return fail(BGE_ERR_INVALID, "world is NULL");
+    if (count && !pairs2) return fail(BGE_ERR_INVALID, "pairs2 is NULL");
+    const uint64_t n = w->ct_on ? w->n_characters : 0;
+    std::vector<uint64_t> bits(w->ct_on ? w->ct_rows * w->ct_words : 0, 0);
+    for (uint64_t k = 0; k < count; ++k) {
+        const uint32_t e = pairs2[2 * k], c = pairs2[2 * k + 1];
+        auto it = w->trig_index_of_entity.find(e);
+        if (it == w->trig_index_of_entity.end()) return fail(BGE_ERR_INVALID, "pair %llu: entity %u carries no trigger", (unsigned long long)k, e);
+        if (c >= n) return fail(BGE_ERR_INVALID, "pair %llu: character %u outside [0, %llu)", (unsigned long long)k, c, (unsigned long long)n);
+        bits[uint64_t(it->second) * w->ct_words + (c >> 6)] |= 1ull << (c & 63u);
+    }
+    if (!w->ct_on) return BGE_OK;
+    DeviceGuard guard(w->device);
+    if (int rc = chartrig_settle(w, 0, nullptr)) return rc; // (the last call's list is whole before its bitmap goes)
+    if (!bits.empty()) HIP_TRY(hipMemcpy(w->ct_bits[w->ct_rem].p, bits.data(), bits.size() * 8, hipMemcpyHostToDevice));
+    return BGE_OK;
+}
+BGE_CATCH_ALL("bge_world_characters_set_trigger_overlaps")
+
+int bge_world_trigger_boxes(bge_world* w, uint64_t count, const uint32_t* entity_index, float* aabb6, uint8_t* listed)
+try {
+    if (!w || (count && !entity_index)) return fail(BGE_ERR_INVALID, "NULL argument");
+    if (count == 0) return BGE_OK;
+    DeviceGuard guard(w->device);
+    HIP_TRY(hipStreamSynchronize(w->stream));
+    std::vector<float> boxes;
+    const bool on_device = w->trig_list_on_device && w->trig_pose.p && w->trig_aabb.p && !w->triggers.empty();
+    if (on_device) {
+        boxes.resize(6 * w->triggers.size());
+        HIP_TRY(hipMemcpy(boxes.data(), w->trig_aabb.p, boxes.size() * 4, hipMemcpyDeviceToHost));
+    }
+    for (uint64_t k = 0; k < count; ++k) {
+        bool is_listed = false;
+        auto it = w->trig_index_of_entity.find(entity_index[k]);
+        if (on_device && it != w->trig_index_of_entity.end()) { // the rule of sync_query_ghosts
+            const bge_world::Trigger& t = w->triggers[it->second];
+            is_listed = t.runtime_active && (t.posed || t.frozen);
+        }
+        if (listed) listed[k] = is_listed ? 1 : 0;
+        if (aabb6) {
+            for (int a = 0; a < 6; ++a) aabb6[6 * k + a] = is_listed ? boxes[6 * it->second + a] : (a < 3 ? INFINITY : -INFINITY);
+        }
+    }
+    return BGE_OK;
+}
+BGE_CATCH_ALL("bge_world_trigger_boxes")
 
 // ---------------------------------------------------------------- debug overlay (bge_debug.hip)
 static_assert(sizeof(bge_debug_line) == 28, "bge_debug_line is 28 bytes (include/bge_world.h)");

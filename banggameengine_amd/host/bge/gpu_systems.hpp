@@ -790,8 +790,21 @@ public:
         char_inputs_.clear();
         char_states_.clear();
         chars_stale_ = char_inputs_stale_ = false;
+        char_trig_watching_ = char_trig_pending_ = false; // (creating the set turns the device's watch off)
+        char_trigger_events_.clear();
         if (ok() && bge_world_characters_create(world_, 0, nullptr) != BGE_OK) Log("bge_world_characters_create");
     }
+    // EXTENSION: trigger events for the characters (include/bge_world.h "Character trigger events"), off by default: every
+    // UpdateCharacters makes the Enter / Stay / Exit list of the characters against the trigger volumes on the device, SyncCharacters
+    // fetches it.  `other` of an event is the character's EntityId.  TriggerEvents() is untouched.
+    void SetCharacterTriggerEvents(bool on)
+    {
+        if (on == char_trig_on_) return;
+        char_trig_on_ = on;
+        if (!on) char_trigger_events_.clear();
+    }
+    // the list of the last UpdateCharacters, as of the last SyncCharacters, in the device's order
+    const std::vector<GpuTriggerEvent>& CharacterTriggerEvents() const { return char_trigger_events_; }
     size_t CharacterCount() const { return char_ids_.size(); }
     bool SetCharacterWalk(Id entity, float dx, float dz)
     {
@@ -830,9 +843,34 @@ public:
         if (!ok()) return false;
         if (char_ids_.empty() || steps == 0u) return true; // (a frame without a sub-step: the walk and a pending jump wait for the next)
         if (chars_stale_) {
+            // Re-creating the set forgets which volume each character stands in: read that before and put it back after (the
+            // indices of the characters that were there do not change), so that nobody Enters a volume again because another
+            // character was added
+            char_overlaps_.clear();
+            if (char_trig_watching_) {
+                uint64_t total = 0;
+                if (bge_world_characters_trigger_overlaps(world_, 0, nullptr, &total) != BGE_OK) return Log("bge_world_characters_trigger_overlaps");
+                char_overlaps_.resize(2 * total);
+                if (total && bge_world_characters_trigger_overlaps(world_, total, char_overlaps_.data(), &total) != BGE_OK) {
+                    return Log("bge_world_characters_trigger_overlaps");
+                }
+            }
             if (bge_world_characters_create(world_, char_descs_.size(), char_descs_.data()) != BGE_OK) return Log("bge_world_characters_create");
             chars_stale_ = false;
             char_inputs_stale_ = true;
+            char_trig_watching_ = false;
+        }
+        if (char_trig_on_ != char_trig_watching_) {
+            if (bge_world_characters_watch_triggers(world_, char_trig_on_ ? char_descs_.size() : 0, nullptr, nullptr, BGE_CHAR_TRIGGER_STAY_EVENTS, 0) !=
+                BGE_OK) {
+                return Log("bge_world_characters_watch_triggers");
+            }
+            char_trig_watching_ = char_trig_on_;
+            if (char_trig_on_ && !char_overlaps_.empty() &&
+                bge_world_characters_set_trigger_overlaps(world_, char_overlaps_.size() / 2, char_overlaps_.data()) != BGE_OK) {
+                return Log("bge_world_characters_set_trigger_overlaps");
+            }
+            char_overlaps_.clear();
         }
         if (char_inputs_stale_) {
             if (bge_world_characters_set_input(world_, 0, char_inputs_.size(), char_inputs_.data()) != BGE_OK) return Log("bge_world_characters_set_input");
@@ -840,6 +878,7 @@ public:
         }
         if (bge_world_characters_update(world_, dt, steps) != BGE_OK) return Log("bge_world_characters_update");
         for (bge_character_input& in : char_inputs_) in.buttons &= ~static_cast<uint32_t>(BGE_CHAR_BUTTON_JUMP); // (the update consumed the edges)
+        char_trig_pending_ = char_trig_watching_;
         return true;
     }
     // One download; each character's position goes into its Transform, as SyncRigidBodiesFromPhysics does for bodies
@@ -855,7 +894,7 @@ public:
             std::memcpy(static_cast<void*>(&t->position), char_states_[i].position, 12);
             t->MarkDirty();
         }
-        return true;
+        return FetchCharacterTriggerEvents(scene);
     }
     bool CharacterOnGround(Id entity) const
     {
@@ -975,6 +1014,31 @@ private:
         if (bge_world_upload_triggers(world_, t_entity_.size(), t_entity_.data(), t_shape_.data(), t_size_.data(), t_layer_.data(),
                                       t_mask_.data(), t_oneshot_.data(), t_active_.data()) != BGE_OK) {
             return Log("bge_world_upload_triggers");
+        }
+        return true;
+    }
+
+    // The list of the last UpdateCharacters, once.  A one-shot volume with an Enter in it is switched off in the scene, so the next
+    // trigger upload takes its ghost out of the world (PhysicsSystem.cpp:1062-1072) and it reports nothing further.
+    bool FetchCharacterTriggerEvents(SceneT& scene)
+    {
+        char_trigger_events_.clear();
+        if (!char_trig_pending_) return true;
+        char_trig_pending_ = false;
+        uint64_t total = 0;
+        if (bge_world_characters_trigger_events(world_, nullptr, 0, &total) != BGE_OK) return Log("bge_world_characters_trigger_events");
+        raw_char_events_.resize(total);
+        if (total && bge_world_characters_trigger_events(world_, raw_char_events_.data(), total, &total) != BGE_OK) {
+            return Log("bge_world_characters_trigger_events");
+        }
+        for (const bge_character_trigger_event& e : raw_char_events_) {
+            if (e.trigger >= ids_.size() || e.character >= char_ids_.size()) continue;
+            char_trigger_events_.push_back(GpuTriggerEvent{static_cast<GpuTriggerEvent::Type>(e.type), ids_[e.trigger], char_ids_[e.character]});
+            if (e.type == BGE_CHAR_TRIGGER_ENTER) {
+                if (auto* tv = scene.GetTriggerVolume(ids_[e.trigger])) {
+                    if (tv->oneShot && tv->active) tv->active = false;
+                }
+            }
         }
         return true;
     }
@@ -1414,6 +1478,11 @@ private:
     std::vector<bge_character_input> char_inputs_;
     std::vector<bge_character_state> char_states_;
     bool chars_stale_ = false, char_inputs_stale_ = false;
+    // character trigger events: wanted, on on the device, an UpdateCharacters' list waits for SyncCharacters
+    bool char_trig_on_ = false, char_trig_watching_ = false, char_trig_pending_ = false;
+    std::vector<uint32_t> char_overlaps_; // (trigger entity, character) pairs carried over a re-creation of the set
+    std::vector<bge_character_trigger_event> raw_char_events_;
+    std::vector<GpuTriggerEvent> char_trigger_events_;
 
     template <class Vec3> static bge_sphere_cast MakeCast(const Vec3& o, const Vec3& d, float maxDistance, float radius, uint32_t layerMask)
     {
@@ -1683,8 +1752,26 @@ public:
     {
         return lastScene_ && GpuMirrors<SceneT>::Of(*lastScene_).WarpCharacter(entity, position);
     }
-    bool UpdateCharacters(float dt, uint32_t steps) { return lastScene_ && GpuMirrors<SceneT>::Of(*lastScene_).UpdateCharacters(dt, steps); }
+    bool UpdateCharacters(float dt, uint32_t steps)
+    {
+        if (!lastScene_) return false;
+        GpuMirrors<SceneT>::Of(*lastScene_).SetCharacterTriggerEvents(characterTriggerEvents_);
+        return GpuMirrors<SceneT>::Of(*lastScene_).UpdateCharacters(dt, steps);
+    }
     bool SyncCharacters(SceneT& scene) { return GpuMirrors<SceneT>::Of(scene).SyncCharacters(scene); }
+    // EXTENSION: Enter / Stay / Exit of the characters against the trigger volumes (include/bge_world.h "Character trigger
+    // events"), off by default.  UpdateCharacters makes the list on the device, SyncCharacters fetches it and switches off a one-shot
+    // volume that a character Entered; `other` of an event is the character's EntityId.  TriggerEvents() stays as it is.
+    void SetCharacterTriggerEvents(bool on)
+    {
+        characterTriggerEvents_ = on;
+        if (lastScene_) GpuMirrors<SceneT>::Of(*lastScene_).SetCharacterTriggerEvents(on);
+    }
+    const std::vector<GpuTriggerEvent>& CharacterTriggerEvents() const
+    {
+        static const std::vector<GpuTriggerEvent> none;
+        return lastScene_ ? GpuMirrors<SceneT>::Of(*lastScene_).CharacterTriggerEvents() : none;
+    }
     // as of the last SyncCharacters
     bool CharacterOnGround(typename GpuSceneMirror<SceneT>::Id entity) const
     {
@@ -1821,6 +1908,7 @@ private:
     bool bulletBasis_ = false;
     bool groundPlane_ = true;
     SceneT* lastScene_ = nullptr; // the scene whose world the ray queries read
+    bool characterTriggerEvents_ = false; // SetCharacterTriggerEvents: handed to the scene's mirror by UpdateCharacters
     bool debugDrawEnabled_ = false;
     bge_debug_desc debugDesc_{static_cast<uint32_t>(sizeof(bge_debug_desc)), BGE_DEBUG_ALL, 0u, {0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f}};
     DebugLineBuffer debugLines_;

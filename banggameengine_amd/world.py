@@ -160,6 +160,9 @@ def make_sphere_recovers(positions, radius=0.5, skin=0.01, layer_mask=0xFFFFFFFF
 CHAR_INVALID, CHAR_GROUNDED, CHAR_JUMPED, CHAR_LANDED, CHAR_HEAD_BUMP = 1, 2, 4, 8, 16
 CHAR_RECOVERED, CHAR_STUCK, CHAR_STEPPED, CHAR_OUT_OF_SLIDES = 32, 64, 128, 256
 CHAR_BUTTON_JUMP = 1
+# character trigger events (bge_world_characters_watch_triggers ..): bge_character_trigger_event_type and the watch's flag
+CHAR_TRIGGER_ENTER, CHAR_TRIGGER_STAY, CHAR_TRIGGER_EXIT = 0, 1, 2
+CHAR_TRIGGER_STAY_EVENTS = 1
 CHARACTER_DESC_DTYPE = np.dtype([("position", "<f4", (3,)), ("radius", "<f4"), ("skin", "<f4"), ("step_height", "<f4"), ("min_ground_ny", "<f4"),
                                  ("probe_distance", "<f4"), ("gravity", "<f4"), ("jump_speed", "<f4"), ("fall_speed", "<f4"), ("layer_mask", "<u4")])
 CHARACTER_INPUT_DTYPE = np.dtype([("walk_x", "<f4"), ("walk_z", "<f4"), ("buttons", "<u4"), ("reserved", "<u4")])
@@ -737,6 +740,57 @@ class World:
         ptr, n = C.c_void_p(), C.c_uint64()
         check(lib().bge_world_characters_state_device(self._h, C.byref(ptr), C.byref(n)))
         return int(ptr.value or 0), int(n.value)
+
+    # -- character trigger events (include/bge_world.h "Character trigger events" states the rule and the order of the list)
+    def characters_watch_triggers(self, group=None, mask=None, stay=True, event_capacity=0):
+        """Turns on Enter / Stay / Exit of the characters against the trigger volumes, made by every characters_update() call.
+        group, mask: one value per character or a scalar (default 2 and 0xffffffff).  With no characters the watch is off."""
+        n = self.characters_state_device()[1]
+        pick = lambda a: None if a is None else np.ascontiguousarray(np.broadcast_to(np.asarray(a, np.uint64).astype(np.uint32), (n,)))
+        g, m = pick(group), pick(mask)
+        check(lib().bge_world_characters_watch_triggers(self._h, n, _p(g), _p(m), CHAR_TRIGGER_STAY_EVENTS if stay else 0, int(event_capacity)))
+
+    def characters_unwatch_triggers(self):
+        """Turns the watch off (bge_world_characters_watch_triggers with n = 0): the remembered pairs and the list are forgotten."""
+        check(lib().bge_world_characters_watch_triggers(self._h, 0, None, None, 0, 0))
+
+    def characters_trigger_events(self):
+        """(type, trigger entity, character index) rows of the last characters_update() call in the list's own order (the order
+        is part of the rule, so nothing is sorted); type 0 Enter, 1 Stay, 2 Exit.  Synchronises the world's stream."""
+        total = C.c_uint64(0)
+        check(lib().bge_world_characters_trigger_events(self._h, None, 0, C.byref(total)))
+        out = np.empty((int(total.value), 3), np.uint32)
+        check(lib().bge_world_characters_trigger_events(self._h, _p(out), len(out), C.byref(total)))
+        return out
+
+    def characters_trigger_events_device(self):
+        """(device pointer of the records, device pointer of the 4-byte count, capacity in records); (0, 0, 0) with the watch
+        off.  count may exceed capacity; reads must be ordered after the world's stream."""
+        ev, cnt, cap = C.c_void_p(), C.c_void_p(), C.c_uint64()
+        check(lib().bge_world_characters_trigger_events_device(self._h, C.byref(ev), C.byref(cnt), C.byref(cap)))
+        return int(ev.value or 0), int(cnt.value or 0), int(cap.value)
+
+    def characters_trigger_overlaps(self):
+        """The remembered (trigger entity, character index) pairs as a (k, 2) uint32 array, by trigger array order, then character."""
+        total = C.c_uint64(0)
+        check(lib().bge_world_characters_trigger_overlaps(self._h, 0, None, C.byref(total)))
+        out = np.empty((int(total.value), 2), np.uint32)
+        check(lib().bge_world_characters_trigger_overlaps(self._h, len(out), _p(out), C.byref(total)))
+        return out
+
+    def characters_set_trigger_overlaps(self, pairs):
+        """Replaces the remembered set by (trigger entity, character index) pairs."""
+        pairs = np.ascontiguousarray(pairs, np.uint32).reshape(-1, 2)
+        check(lib().bge_world_characters_set_trigger_overlaps(self._h, len(pairs), _p(pairs) if len(pairs) else None))
+
+    def trigger_boxes(self, entity_index):
+        """(boxes (k, 6) float32: min xyz, max xyz; listed (k,) bool) of the triggers on these entities as the queries' ghost list
+        has them; an entity that is not a listed trigger gets the empty box (+inf, -inf)."""
+        e = np.ascontiguousarray(np.atleast_1d(entity_index), np.uint32)
+        boxes = np.empty((len(e), 6), np.float32)
+        listed = np.empty(len(e), np.uint8)
+        check(lib().bge_world_trigger_boxes(self._h, len(e), _p(e), _p(boxes), _p(listed)))
+        return boxes, listed.astype(bool)
 
     # -- debug overlay (PhysicsSystem::GetDebugLines; include/bge_world.h states what is drawn and in which order)
     def debug_lines(self, flags=DEBUG_ALL, region=None):

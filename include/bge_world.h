@@ -807,8 +807,10 @@ BGE_API int bge_world_sphere_recover_device(bge_world* world, uint64_t n, const 
  *             (0, 0.51, 0) with walk (2, 0): walking, dy = 0, M is that example's result: position (2, 1.11, 0), ground_distance
  *             0.01, e = 0: flags GROUNDED | STEPPED, step_rise 0.7, ground_kind BODY, entity 0.
  *   Not done  capsule characters; pushing Dynamic bodies; riding moving platforms (a platform that moves INTO a character pushes
- *             it out through Recover, one that moves away or along does not carry it); trigger events for characters; writing into
- *             a Transform on the device (the adapter does that on the host).
+ *             it out through Recover, one that moves away or along does not carry it); writing into a Transform on the device
+ *             (the adapter does that on the host).  Trigger volumes report characters through "Character trigger events" below,
+ *             with what remains open there: the box is the sphere's, not a capsule's; the world's own bge_world_trigger_events
+ *             still does not see characters; characters do not report each other.
  *   Characters are not bodies: no query sees them, they do not see each other, and no call here changes any other world state.
  *   bge_world_characters_create   replaces the set with n characters made from descs; n = 0 removes it (descs may then be NULL).
  *                                 Every desc is checked on the host: every float finite, radius >= 0, skin > 0, step_height >= 0,
@@ -874,6 +876,80 @@ BGE_API int bge_world_characters_warp(bge_world* world, uint64_t count, const ui
 BGE_API int bge_world_characters_update(bge_world* world, float dt, uint32_t steps);
 BGE_API int bge_world_characters_download(bge_world* world, uint64_t first, uint64_t count, bge_character_state* states);
 BGE_API int bge_world_characters_state_device(bge_world* world, void** states_device, uint64_t* n);
+
+/*
+ * Character trigger events: Enter / Stay / Exit of the device's characters against the trigger volumes, made on the device once
+ * per bge_world_characters_update call.  In the reference the character is a btPairCachingGhostObject of group
+ * kDefaultCharacterLayer = 2 and mask all (src/physics/PhysicsSystem.cpp:741-766), every trigger ghost's pair cache lists it and
+ * ProcessTriggerEvents (:1017-1074) publishes its events once per frame.  Opt-in: until bge_world_characters_watch_triggers turns
+ * the watch on, every other call does what it did without this section.  The rule below is the specification.
+ *   Character box  for a character at p with radius r, on axis a: lower corner (p[a] - r) - 0.02f, upper corner (p[a] + r) + 0.02f;
+ *             binary32, one rounding per operation, left to right: the sphere's AABB plus updateSingleAabb's contact threshold.
+ *   Trigger box    the fed AABB of the trigger as the last BGE_TICK_BROADPHASE tick posed it; for a ghost whose entity lost its
+ *             Transform, the frozen box.  bge_world_trigger_boxes returns these boxes.
+ *   Overlap   on every axis tmin <= cmax && tmax >= cmin: closed intervals (the test of the world's own trigger pass).
+ *   Filter    (trigger.layer & char.mask) != 0 && (char.group & trigger.mask) != 0.  Group and mask are per character; NULL arrays
+ *             mean group 2 and mask 0xffffffff.  A character with group 0 overlaps nothing.
+ *   When      once per bge_world_characters_update call, after its last step, from the positions that step left (not per step: a
+ *             volume crossed inside one call is not reported).  A BGE_CHAR_INVALID character is tested where it stands.
+ *   Which     exactly the ghosts the queries see at that call: active, and posed by a tick or frozen.  A trigger that is not among
+ *             them during a call is skipped: it is not tested, produces no event, and its remembered overlaps stay as they are.
+ *   Events    for each such trigger, in the order of the uploaded trigger array, with cur = overlapping now and prev = remembered:
+ *             first, in ascending character index, BGE_CHAR_TRIGGER_ENTER for cur & ~prev and BGE_CHAR_TRIGGER_STAY for cur & prev;
+ *             then, in ascending character index, BGE_CHAR_TRIGGER_EXIT for prev & ~cur; then remembered := cur.  Without
+ *             BGE_CHAR_TRIGGER_STAY_EVENTS the Stay records are left out and nothing else changes.  (The reference's order inside
+ *             one trigger is that of an unordered_set; this fixes one.)  record.trigger is the trigger's entity index,
+ *             record.character the index in the set.
+ *   The list  is that of the last update call: each call replaces it, fetching does not clear it.
+ *   one_shot  has no effect here, and no call of this section changes the trigger set or any other world state: consuming a
+ *             one-shot trigger is the caller's job (the adapter does it).
+ *   bge_world_upload_triggers     a trigger that was present before with the same entity, layer and mask keeps its remembered
+ *                                 characters, any other starts empty; no Exit is reported for a removed trigger (the rule for
+ *                                 remembered bodies).  With the watch on it synchronises the world's stream.
+ *   bge_world_characters_create   turns the watch off and forgets the remembered sets and the list.
+ *   bge_world_characters_warp     does nothing special: the next update call reports what the new position gives.
+ *   Not done  the box is the sphere's, not a capsule's; characters stay invisible to the world's own bge_world_trigger_events;
+ *             characters do not report each other.
+ *   bge_world_characters_watch_triggers  n must equal the set's size; n = 0 turns the watch off (group and mask may be NULL).
+ *                                 event_capacity = 0 picks n + 1024.  Calling it again replaces the filters and keeps the remembered
+ *                                 sets and the list (the list's capacity only grows).  BGE_ERR_INVALID for a wrong n or unknown flag
+ *                                 bits.  BGE_ERR_UNSUPPORTED where a bitmap, triggers x ceil(n / 64) 64-bit words, would exceed 2^28
+ *                                 words, or with more than 65535 * 64 triggers; bge_world_upload_triggers answers the same, before
+ *                                 it changes anything, for a trigger array that would.  Synchronises the world's stream.
+ *   bge_world_characters_trigger_events  the list of the last update call into out[0 .. cap), and its length in total (out = NULL
+ *                                 asks for total only).  Synchronises the world's stream.  If the call found more events than the
+ *                                 device list holds, the list is grown and made again from the two bitmaps: nothing is lost, and the
+ *                                 new capacity stays.  More than 2^32 - 2 events in one call is BGE_ERR_UNSUPPORTED.  total is 0
+ *                                 while the watch is off.
+ *   bge_world_characters_trigger_events_device  the resident list, its 4-byte count and the list's capacity in records, for a
+ *                                 consumer on the device (NULL, NULL, 0 while the watch is off).  count may exceed capacity: records
+ *                                 beyond capacity are not written.  Valid until the next bge_world_characters_watch_triggers,
+ *                                 bge_world_characters_create, bge_world_upload_triggers or a host fetch that grows the list; reads
+ *                                 must be ordered after the world's stream.
+ *   bge_world_characters_trigger_overlaps      the remembered set as pairs2[2k] = trigger entity, pairs2[2k + 1] = character
+ *                                 index, sorted by trigger array order and then by character; at most cap pairs are written, total
+ *                                 is their number.  Synchronises the world's stream.
+ *   bge_world_characters_set_trigger_overlaps  replaces the remembered set by `count` such pairs (any order).  A pair naming an
+ *                                 entity that carries no trigger or an index outside the set (every index while the watch is off)
+ *                                 is BGE_ERR_INVALID, and the set is left as it was.  For save / load and re-creating the set.
+ *   bge_world_trigger_boxes       aabb6[6k ..] = the fed AABB (min xyz, max xyz) of the trigger on entity_index[k] and listed[k] = 1
+ *                                 where that trigger is in the queries' ghost list now; otherwise listed[k] = 0 and the empty box
+ *                                 (+inf x 3, -inf x 3).  Read-only; synchronises the world's stream.  aabb6 or listed may be NULL.
+ */
+enum bge_character_trigger_event_type { BGE_CHAR_TRIGGER_ENTER = 0, BGE_CHAR_TRIGGER_STAY = 1, BGE_CHAR_TRIGGER_EXIT = 2 };
+enum bge_character_trigger_flags { BGE_CHAR_TRIGGER_STAY_EVENTS = 1u };
+typedef struct bge_character_trigger_event {
+    uint32_t type;      /* bge_character_trigger_event_type */
+    uint32_t trigger;   /* the trigger's entity index */
+    uint32_t character; /* index in the character set */
+} bge_character_trigger_event; /* 12 bytes */
+BGE_API int bge_world_characters_watch_triggers(bge_world* world, uint64_t n, const uint32_t* group, const uint32_t* mask, uint32_t flags,
+                                                uint64_t event_capacity);
+BGE_API int bge_world_characters_trigger_events(bge_world* world, bge_character_trigger_event* out, uint64_t cap, uint64_t* total);
+BGE_API int bge_world_characters_trigger_events_device(bge_world* world, void** events, void** count, uint64_t* capacity);
+BGE_API int bge_world_characters_trigger_overlaps(bge_world* world, uint64_t cap, uint32_t* pairs2, uint64_t* total);
+BGE_API int bge_world_characters_set_trigger_overlaps(bge_world* world, uint64_t count, const uint32_t* pairs2);
+BGE_API int bge_world_trigger_boxes(bge_world* world, uint64_t count, const uint32_t* entity_index, float* aabb6, uint8_t* listed);
 
 /*
  * The physics debug overlay: what PhysicsSystem::GetDebugLines hands to the renderer while the overlay is on
