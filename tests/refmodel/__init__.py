@@ -6,10 +6,10 @@ Layers, each importing downward only:
   rays -> spheres -> moves -> recover -> sandwich       the model: nothing of the product package
   visible, draw_batches, debug_lines                    the render references
   *_cases                                               seeded generators and hand-worked tables; the package for dtypes and make_* only
-  device                                                the only module that opens a World; no *_cpu test reaches it
+  device, *_device                                      the only modules that open a World; no *_cpu test reaches them
 """
 import pytest
 
 # the checkers' bare asserts keep pytest's introspection outside test_*.py: registered before any submodule is imported
-pytest.register_assert_rewrite("refmodel.device", "refmodel.draw_batches", "refmodel.edge_cases", "refmodel.move_cases", "refmodel.recover_cases",
-                               "refmodel.sandwich", "refmodel.sphere_cases", "refmodel.visible")
+pytest.register_assert_rewrite("refmodel.device", "refmodel.draw_batches", "refmodel.edge_cases", "refmodel.layout_cases", "refmodel.layout_device", "refmodel.move_cases",
+                               "refmodel.recover_cases", "refmodel.sandwich", "refmodel.sphere_cases", "refmodel.visible")

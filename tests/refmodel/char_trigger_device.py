@@ -20,16 +20,25 @@ def upload_walk_triggers(w, walk, order, active=None, mask=None):
                       np.zeros(k, np.uint8), np.ones(k, np.uint8) if active is None else np.asarray(active, np.uint8), keep_order=True)
 
 
-def trigger_world(walk, n_triggers=None):
+def trigger_world(walk, n_triggers=None, topology=None):
     """A World with one entity per trigger of the walk, no bodies and no plane; the first n_triggers (all by default) are uploaded as
-    triggers in entity order, and one BGE_TICK_BROADPHASE tick poses them.  The caller closes it."""
+    triggers in entity order, and one BGE_TICK_BROADPHASE tick poses them.  topology = (parent, has_transform) makes it a world of
+    len(parent) entities under that hierarchy instead of a flat one: the entities beyond the walk's are BODY_NONE with the identity
+    TRS.  The caller closes it."""
     T = len(walk.entity)
+    n = T if topology is None else len(topology[0])
+    assert n >= T
+    pad = n - T
     w = B.World(device=0)
     try:
-        w.set_topology(np.full(T, W.NO_PARENT, np.uint32))
-        w.upload_trs(walk.pos, walk.euler, np.ones((T, 3)))
-        w.upload_bodies(np.full(T, W.BODY_NONE, np.uint8), None, np.zeros(T, np.uint8), walk.size, np.full(T, 1, np.uint32),
-                        np.full(T, 0xFFFFFFFF, np.uint32))
+        if topology is None:
+            w.set_topology(np.full(T, W.NO_PARENT, np.uint32))
+        else:
+            w.set_topology(*topology)
+        w.upload_trs(np.concatenate([walk.pos, np.zeros((pad, 3), np.float32)]), np.concatenate([walk.euler, np.zeros((pad, 3), np.float32)]),
+                     np.ones((n, 3)))
+        w.upload_bodies(np.full(n, W.BODY_NONE, np.uint8), None, np.zeros(n, np.uint8), np.concatenate([walk.size, np.full((pad, 3), 0.5, np.float32)]),
+                        np.full(n, 1, np.uint32), np.full(n, 0xFFFFFFFF, np.uint32))
         upload_walk_triggers(w, walk, np.arange(T if n_triggers is None else n_triggers))
         w.set_ground_plane(False)
         w.tick(flags=FLAGS)

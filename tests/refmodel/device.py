@@ -1,6 +1,7 @@
 """The GPU side of the comparisons: Scene drives a World and rebuilds the reference's objects from what the device holds; the
-check_* functions compare device answers with the float64 reference within refmodel/tolerances.py; device_caster, move and ask
-call the device in the forms the references expect.  The only refmodel module that opens a World."""
+check_* functions compare device answers with the float64 reference within refmodel/tolerances.py; device_caster, move, ask,
+penetration and recover call the device in the forms the references expect.  With the *_device modules built on it, the only part
+of refmodel that opens a World."""
 from __future__ import annotations
 
 import math
@@ -12,6 +13,7 @@ from banggameengine_amd import world as W
 
 from .tolerances import F_ABS, F_REL, N_ABS, N_SCALE, P_REL
 from .rays import NO_ENTITY, RAY_BODY, RAY_MISS, RAY_TRIGGER, World64, quat_from_euler
+from .recover_cases import check_penetrations  # noqa: F401  (kept where a *_cpu test can reach it; the GPU tests take it from here)
 
 FLAGS = W.TICK_ALL | W.TICK_BROADPHASE
 
@@ -232,6 +234,53 @@ def device_caster(w):
 
 def move(w, moves):
     return w.sphere_move(*(moves[k] for k in FIELDS))
+
+
+RECOVER_FIELDS = ("position", "radius", "skin", "layer_mask")
+
+
+def penetration(w, spheres):
+    """World.sphere_penetration as a PENETRATION_HIT_DTYPE array; spheres: any records with center / position, radius, layer_mask."""
+    centers = spheres["center"] if "center" in spheres.dtype.names else spheres["position"]
+    h = w.sphere_penetration(centers, spheres["radius"], spheres["layer_mask"])
+    hits = np.zeros(len(spheres), W.PENETRATION_HIT_DTYPE)
+    for k, v in h.items():
+        hits[k] = v
+    return hits
+
+
+def recover(w, recs):
+    return w.sphere_recover(*(recs[k] for k in RECOVER_FIELDS))
+
+
+def check_penetration_against_overlap(w, recs, pen, floors):
+    """The penetration hits against the device's own overlap_sphere, exactly: a sphere is penetrated iff its overlap list is not
+    empty, the winner is in that list, and outside a shape depth == float32(radius - distance) bit for bit.  floors = (penetrated
+    spheres, winners with the centre outside the shape) the batch must show."""
+    ov = w.overlap_sphere(recs["position"], recs["radius"], recs["layer_mask"])
+    off = ov["offsets"].astype(np.int64)
+    n_hit = n_outside = 0
+    for i in range(len(recs)):
+        seg = slice(off[i], off[i + 1])
+        listed = list(zip(ov["kind"][seg].tolist(), ov["entity"][seg].tolist()))
+        if not listed:
+            assert pen[i].tobytes() == np.array([(RAY_MISS, NO_ENTITY, 0, (0, 0, 0), (0, 0, 0), 0)], W.PENETRATION_HIT_DTYPE)[0].tobytes(), i
+            continue
+        n_hit += 1
+        assert (int(pen["kind"][i]), int(pen["entity"][i])) in listed, (i, pen[i], listed)
+        assert pen["depth"][i] >= 0 and pen["reserved"][i] == 0
+        r = recs["radius"][i]
+        for (kind, ent), dist in zip(listed, ov["distance"][seg]):
+            if dist > 0:  # outside the shape the signed distance is this distance: no object reaches deeper than the winner
+                depth = np.float32(r - dist)
+                assert depth <= pen["depth"][i], (i, kind, ent)
+                if (kind, ent) == (pen["kind"][i], pen["entity"][i]):
+                    n_outside += 1
+                    assert depth.tobytes() == pen["depth"][i].tobytes(), (i, depth, pen["depth"][i])
+            else:  # inside it, or on its surface: at least the radius deep
+                assert pen["depth"][i] >= r or (kind, ent) != (pen["kind"][i], pen["entity"][i]), i
+    print(f"{n_hit} of {len(recs)} spheres penetrated, {n_outside} winners with the centre outside the shape")
+    assert n_hit >= floors[0] and n_outside >= floors[1], (n_hit, n_outside, floors)
 
 
 def ask(w, batches):

@@ -2,6 +2,7 @@
 shared by test_sphere_recover_cpu.py and test_gpu_sphere_recover.py."""
 from __future__ import annotations
 
+import collections
 import math
 
 import numpy as np
@@ -9,6 +10,8 @@ import numpy as np
 from banggameengine_amd.world import RECOVER_INVALID, RECOVER_MOVED, RECOVER_STUCK, SPHERE_RECOVER_RESULT_DTYPE, make_sphere_recovers
 
 from .rays import ALL, NO_ENTITY, RAY_BODY, RAY_GROUND, RAY_MISS, RAY_TRIGGER, Obj, box_half_extents, capsule_dims, quat_from_euler, quat_to_mat
+from .tolerances import N_ABS, N_SCALE, P_REL
+from .recover import classify
 from .move_cases import wall_box
 
 UP, DOWN, WEST, EAST = (0.0, 1.0, 0.0), (0.0, -1.0, 0.0), (-1.0, 0.0, 0.0), (1.0, 0.0, 0.0)
@@ -162,3 +165,42 @@ def check_caps(n_valid, n_pen, n_skipped, kinds, n_axis):
     assert 2 * n_pen >= n_valid, (n_pen, n_valid)
     assert 2 * n_skipped <= n_pen, (n_skipped, n_pen)
     assert all(kinds.get(k, 0) >= 1 for k in (RAY_BODY, RAY_TRIGGER, RAY_GROUND)), kinds
+
+
+def check_penetrations(w64, recs, valid, pen):
+    """The penetration hits of the valid records against signed_ref on the World64, within refmodel/tolerances.py; a sphere is set
+    aside where classify() finds the reference's own answer ambiguous.  Ends in check_caps."""
+    n_valid = n_pen = n_skipped = n_axis = 0
+    kinds = collections.Counter()
+    share_d = share_p = share_n = 0.0
+    for i in np.nonzero(valid)[0]:
+        m, got = recs[i], pen[i]
+        n_valid += 1
+        cands, winner_clear, normal_clear = classify(w64, m)
+        if not cands:
+            assert got["kind"] == RAY_MISS, f"sphere {i}: hit where the reference finds nothing near"
+            continue
+        if cands[0].depth < 0:
+            continue  # (only grazing candidates: hit or miss is the overlap's to say, exactly)
+        n_pen += 1
+        n_skipped += not normal_clear
+        if not winner_clear:
+            continue
+        h = cands[0]
+        kinds[h.kind] += 1
+        assert (got["kind"], got["entity"]) == (h.kind, h.entity), f"sphere {i}: {got['kind']}/{got['entity']} != {h.kind}/{h.entity}"
+        c = m["position"].astype(np.float64)
+        tol = P_REL * (1.0 + float(np.abs(c).max()))
+        ed = abs(float(got["depth"]) - h.depth) / tol
+        assert ed <= 1.0, f"sphere {i}: depth {got['depth']} vs {h.depth}"
+        share_d = max(share_d, ed)
+        if not normal_clear:
+            continue
+        ep = float(np.max(np.abs(got["point"] - h.point))) / tol
+        n_tol = N_ABS + N_SCALE * float(np.abs(c).sum() + m["radius"]) / min(w64.min_dim(h.code), h.cond)
+        en = float(np.max(np.abs(got["normal"] - h.normal))) / n_tol
+        assert ep <= 1.0 and en <= 1.0, f"sphere {i}: point {got['point']} vs {h.point}, normal {got['normal']} vs {h.normal}; shares {ep:.2f} {en:.2f}"
+        share_p, share_n = max(share_p, ep), max(share_n, en)
+        n_axis += h.kind != RAY_GROUND and np.isfinite(h.gap)  # the centre inside a box: one of its axes, chosen as the reference does
+    print(f"worst share of tolerance: depth {share_d:.3g}, point {share_p:.3g}, normal {share_n:.3g}")
+    check_caps(n_valid, n_pen, n_skipped, kinds, n_axis)

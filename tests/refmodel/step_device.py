@@ -13,19 +13,33 @@ from .device import FIELDS, FLAGS
 STEP_FIELDS = FIELDS + ("step_height",)
 
 
-def static_world(capsule, size, pos, euler, ghosts, plane=True):
+def static_world(capsule, size, pos, euler, ghosts, plane=True, topology=None):
     """A World of Static bodies (entity i = row i; layer 1, seen by every mask), the rows of `ghosts` trigger ghosts instead,
-    ticked once so that the queries see it.  The caller closes it."""
-    n = max(len(pos), 1)
-    empty = len(pos) == 0
+    ticked once so that the queries see it.  topology = (parent, has_transform) makes it a world of len(parent) entities under
+    that hierarchy instead of a flat one: the entities beyond the rows given are BODY_NONE with the identity TRS.  The caller
+    closes it."""
+    own = len(pos)
+    n = max(own, 1) if topology is None else len(topology[0])
+    empty = own == 0
+    assert n >= max(own, 1)
+
+    def rows(given, fill, dtype):
+        """The rows given, then `fill` for the entities beyond them."""
+        given = np.asarray([fill] if empty else given, dtype)
+        return np.concatenate([given, np.tile(np.asarray([fill], dtype), (n - len(given),) + (1,) * (given.ndim - 1))])
+
     w = B.World(device=0)
     try:
-        w.set_topology(np.full(n, W.NO_PARENT, np.uint32))
-        w.upload_trs(np.float32([[0, 0, 0]] if empty else pos), np.float32([[0, 0, 0]] if empty else euler), np.ones((n, 3)))
-        types = np.full(n, W.BODY_NONE if empty else W.BODY_STATIC, np.uint8)
+        if topology is None:
+            w.set_topology(np.full(n, W.NO_PARENT, np.uint32))
+        else:
+            w.set_topology(*topology)
+        w.upload_trs(rows(pos, [0, 0, 0], np.float32), rows(euler, [0, 0, 0], np.float32), np.ones((n, 3)))
+        types = np.full(n, W.BODY_NONE, np.uint8)
+        types[:own] = W.BODY_STATIC
         types[list(ghosts)] = W.BODY_NONE
-        shapes = np.uint8([0] if empty else capsule)
-        sizes = np.float32([[0.5, 0.5, 0.5]] if empty else size)
+        shapes = rows(capsule, 0, np.uint8)
+        sizes = rows(size, [0.5, 0.5, 0.5], np.float32)
         w.upload_bodies(types, None, shapes, sizes, np.full(n, 1, np.uint32), np.full(n, ALL, np.uint32))
         if len(ghosts):
             g = np.uint32(list(ghosts))
@@ -43,8 +57,8 @@ def hand_world(bodies, ghosts, plane):
     return static_world([b[0] for b in bodies], [b[1] for b in bodies], [b[2] for b in bodies], [b[3] for b in bodies], ghosts, plane)
 
 
-def field_world(field):
-    return static_world(field.capsule, field.size, field.pos, field.euler, field.ghosts)
+def field_world(field, topology=None):
+    return static_world(field.capsule, field.size, field.pos, field.euler, field.ghosts, topology=topology)
 
 
 def step_move(w, moves):

@@ -16,7 +16,6 @@ Three references, each for what it can say:
     equal byte for byte."""
 from __future__ import annotations
 
-import collections
 import ctypes as C
 
 import numpy as np
@@ -25,32 +24,14 @@ import pytest
 import banggameengine_amd as B
 from banggameengine_amd import world as W
 
-from refmodel.tolerances import N_ABS, N_SCALE, P_REL
 from refmodel.rays import ALL, NO_ENTITY, RAY_BODY, RAY_GROUND, RAY_MISS, RAY_TRIGGER
-from refmodel.recover import classify, record_valid, recover_ref
+from refmodel.recover import record_valid, recover_ref
 from refmodel.sphere_cases import scene_world64
 from refmodel.move_cases import BATCHES, SCENE_N, SCENE_SEED, ghost_positions
-from refmodel.recover_cases import (HAND_RECOVERS, SPHERE_SEED, check_caps, check_hand_recover, check_invalid, hand_record, invalid_records,
-                                    sphere_batch)
-from refmodel.device import FLAGS, Scene
+from refmodel.recover_cases import HAND_RECOVERS, SPHERE_SEED, check_hand_recover, check_invalid, hand_record, invalid_records, sphere_batch
+from refmodel.device import FLAGS, Scene, check_penetration_against_overlap, check_penetrations, penetration, recover
 
 pytestmark = pytest.mark.gpu
-
-FIELDS = ("position", "radius", "skin", "layer_mask")
-
-
-def penetration(w, spheres):
-    """World.sphere_penetration as a PENETRATION_HIT_DTYPE array; spheres: any records with center / position, radius, layer_mask."""
-    centers = spheres["center"] if "center" in spheres.dtype.names else spheres["position"]
-    h = w.sphere_penetration(centers, spheres["radius"], spheres["layer_mask"])
-    hits = np.zeros(len(spheres), W.PENETRATION_HIT_DTYPE)
-    for k, v in h.items():
-        hits[k] = v
-    return hits
-
-
-def recover(w, recs):
-    return w.sphere_recover(*(recs[k] for k in FIELDS))
 
 
 class Shared:
@@ -77,70 +58,11 @@ def shared():
 
 
 def test_penetration_equals_the_devices_own_overlap_exactly(shared):
-    recs, pen = shared.recs, shared.pen
-    ov = shared.w.overlap_sphere(recs["position"], recs["radius"], recs["layer_mask"])
-    off = ov["offsets"].astype(np.int64)
-    n_hit = n_outside = 0
-    for i in range(len(recs)):
-        seg = slice(off[i], off[i + 1])
-        listed = list(zip(ov["kind"][seg].tolist(), ov["entity"][seg].tolist()))
-        if not listed:
-            assert pen[i].tobytes() == np.array([(RAY_MISS, NO_ENTITY, 0, (0, 0, 0), (0, 0, 0), 0)], W.PENETRATION_HIT_DTYPE)[0].tobytes(), i
-            continue
-        n_hit += 1
-        assert (int(pen["kind"][i]), int(pen["entity"][i])) in listed, (i, pen[i], listed)
-        assert pen["depth"][i] >= 0 and pen["reserved"][i] == 0
-        r = recs["radius"][i]
-        for (kind, ent), dist in zip(listed, ov["distance"][seg]):
-            if dist > 0:  # outside the shape the signed distance is this distance: no object reaches deeper than the winner
-                depth = np.float32(r - dist)
-                assert depth <= pen["depth"][i], (i, kind, ent)
-                if (kind, ent) == (pen["kind"][i], pen["entity"][i]):
-                    n_outside += 1
-                    assert depth.tobytes() == pen["depth"][i].tobytes(), (i, depth, pen["depth"][i])
-            else:  # inside it, or on its surface: at least the radius deep
-                assert pen["depth"][i] >= r or (kind, ent) != (pen["kind"][i], pen["entity"][i]), i
-    print(f"{n_hit} of {len(recs)} spheres penetrated, {n_outside} winners with the centre outside the shape")
-    assert n_hit >= 200 and n_outside >= 50
+    check_penetration_against_overlap(shared.w, shared.recs, shared.pen, (200, 50))
 
 
 def test_penetration_against_the_float64_reference(shared):
-    w64 = shared.sc.objects()
-    recs, pen = shared.recs, shared.pen
-    n_valid = n_pen = n_skipped = n_axis = 0
-    kinds = collections.Counter()
-    share_d = share_p = share_n = 0.0
-    for i in np.nonzero(shared.valid)[0]:
-        m, got = recs[i], pen[i]
-        n_valid += 1
-        cands, winner_clear, normal_clear = classify(w64, m)
-        if not cands:
-            assert got["kind"] == RAY_MISS, f"sphere {i}: hit where the reference finds nothing near"
-            continue
-        if cands[0].depth < 0:
-            continue  # (only grazing candidates: hit or miss is the overlap's to say, exactly)
-        n_pen += 1
-        n_skipped += not normal_clear
-        if not winner_clear:
-            continue
-        h = cands[0]
-        kinds[h.kind] += 1
-        assert (got["kind"], got["entity"]) == (h.kind, h.entity), f"sphere {i}: {got['kind']}/{got['entity']} != {h.kind}/{h.entity}"
-        c = m["position"].astype(np.float64)
-        tol = P_REL * (1.0 + float(np.abs(c).max()))
-        ed = abs(float(got["depth"]) - h.depth) / tol
-        assert ed <= 1.0, f"sphere {i}: depth {got['depth']} vs {h.depth}"
-        share_d = max(share_d, ed)
-        if not normal_clear:
-            continue
-        ep = float(np.max(np.abs(got["point"] - h.point))) / tol
-        n_tol = N_ABS + N_SCALE * float(np.abs(c).sum() + m["radius"]) / min(w64.min_dim(h.code), h.cond)
-        en = float(np.max(np.abs(got["normal"] - h.normal))) / n_tol
-        assert ep <= 1.0 and en <= 1.0, f"sphere {i}: point {got['point']} vs {h.point}, normal {got['normal']} vs {h.normal}; shares {ep:.2f} {en:.2f}"
-        share_p, share_n = max(share_p, ep), max(share_n, en)
-        n_axis += h.kind != RAY_GROUND and np.isfinite(h.gap)  # the centre inside a box: one of its axes, chosen as the reference does
-    print(f"worst share of tolerance: depth {share_d:.3g}, point {share_p:.3g}, normal {share_n:.3g}")
-    check_caps(n_valid, n_pen, n_skipped, kinds, n_axis)
+    check_penetrations(shared.sc.objects(), shared.recs, shared.valid, shared.pen)
 
 
 @pytest.mark.parametrize("n", BATCHES)
