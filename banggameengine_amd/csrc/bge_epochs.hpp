@@ -1,5 +1,5 @@
 // bge_epochs.hpp — the two epochs the tick kernel's per-wave words (WorldView::rs_word) are compared with, and the bookkeeping of
-// the deferred translation row (Row3State, below).  Host-only, no HIP: tests/test_rest_epoch_cpu.py and tests/test_row3_epoch_cpu.py
+// the deferred translation row (Row3State, below) and of fused ticks (FuseClock, below).  Host-only, no HIP: tests/test_rest_epoch_cpu.py and tests/test_row3_epoch_cpu.py
 // compile this header on its own.
 //   rows  what word 0 must equal for the translation-row path (TickParams::rs_epoch)
 //   rest  what word 1 must equal for the rest path (TickParams::rest_epoch)
@@ -60,6 +60,28 @@ struct Row3State {
         pending = 0;
         return e;
     }
+};
+
+// Fused ticks (DESIGN.md §4.1 "Fused ticks"): the serials that the launches of a bge_world_tick_many call carry (TickParams::serial) and
+// the per-wave words WorldView::adv are compared with.  Host bookkeeping only.  The K ticks of a call are cut into groups of at
+// most T; launch i (0-based) of a group of n carries serial first + i and n_left = n - i, and a vouched wave that runs the n_left
+// ticks in one launch writes adv = first + n - 1, the group's last serial.  Serials only ever rise, so a word written by one group
+// is below every serial of every later group; groups never span calls, so between calls every wave's memory is at the same tick.
+//   next         the first serial of the next group, >= 1 (0 is "off" in TickParams, and what a zeroed word holds)
+//   begin_group  hands out n consecutive serials and returns the first.  *wrapped = true: the 32-bit range is used up, the serials
+//                restart at 1 and the caller zeroes the adv array with a memset ordered on the stream BEFORE the group's launches
+struct FuseClock {
+    uint32_t next = 1;
+    uint32_t begin_group(uint32_t n, bool* wrapped)
+    {
+        *wrapped = n > 0xffffffffu - next; // (next + n - 1 must be a serial, and next + n the next group's first)
+        if (*wrapped) next = 1;
+        const uint32_t first = next;
+        next += n;
+        return first;
+    }
+    // Ticks in the group that begins at tick t of a call of `ticks`, for groups of at most T (T >= 1): the last takes the remainder
+    static uint32_t group_size(uint32_t t, uint32_t ticks, uint32_t T) { return ticks - t < T ? ticks - t : T; }
 };
 
 } // namespace bge

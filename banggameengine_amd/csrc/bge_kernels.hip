@@ -28,6 +28,9 @@
 //   for 64 x 4 B, 56 B per flat body.  k_tick<PHYS, XFORM> only; BGE_FLAG_WORD=0 turns it off.
 //   With TickParams::defer_row3 the translation-row waves do not store row 3 either — it is (pos, 1) of the position they store;
 //   readers compose it, k_row3_sync stores it before anything else may write pos or world: 40 B per flat body.
+//   With TickParams::serial (fused ticks) a vouched wave runs the n_left ticks that remain of its group of launches
+//   in registers, stores once and says so in WorldView::adv; the group's later launches return at once for it.  k_tick<PHYS, XFORM>
+//   only; BGE_FUSE_TICKS=1 turns it off.
 //   Waves whose bodies are all asleep (rest word, WorldView::rs_word word 1) read flags, the deactivation record and the contact
 //   word, 8..12 B per body, and store nothing.
 //   The world matrices leave through LDS so that every wave-level store instruction writes 1 KiB of
@@ -212,6 +215,18 @@ __global__ void __launch_bounds__(kTile, NORMAL ? 4 : (AABB ? BGE_AABB_MIN_WAVES
     const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     // The wave's record {rows word, rest word, flag value, flag epoch} (WorldView::rs_word) in one wave-uniform 16-B load.
     const uint4 rec = (kRowsPath && (p.rs_epoch | p.rest_epoch) != 0u) ? reinterpret_cast<const uint4*>(w.rs_word)[tile * 4u + wave] : make_uint4(0u, 0u, 0u, 0u);
+    // Fused ticks (WorldView::adv, TickParams::serial / n_left; DESIGN.md §4.1 "Fused ticks"): the wave's state in memory is already
+    // the state after the tick with serial adv — an earlier launch of this group ran the ticks up to it in registers — so a launch
+    // whose serial is not beyond it has nothing to do.  Wave-uniform, nothing stored; only a flat wave-local tile can have set the
+    // word, and those have no workgroup barrier to miss (the rest path returns per wave in the same way).
+    constexpr bool kFuse = PHYS && kRowsPath;
+    // (The test on the header bit is always true where the word can be that high.  It is there for the schedule: without it the
+    //  compiler sinks the header's load behind the return, and a wave that goes on pays a second scalar round trip; with it header,
+    //  record and word leave together and are waited for once, as header and record were.  An empty asm would pin the load as well,
+    //  but counts as a store to memory: the palette entry below then comes through a vector load.)
+    if (kFuse && p.serial != 0u) {
+        if (w.adv[tile * 4u + wave] >= p.serial && (hdr & kHdrWaveLocal) != 0u) return;
+    }
     const uint32_t rs_old = p.rs_epoch != 0u ? rec.x : 0u;
     // (header: wave-local, max level 0, no frozen root, no external parent)
     const bool flat_tile = kRowsPath && (hdr & (kHdrWaveLocal | kHdrFrozen | kHdrExt | kHdrLevelMask)) == kHdrWaveLocal;
@@ -265,6 +280,30 @@ __global__ void __launch_bounds__(kTile, NORMAL ? 4 : (AABB ? BGE_AABB_MIN_WAVES
                 // (pins the position load here, next to the velocity loads: the compiler otherwise sinks it behind the ballot below,
                 //  a second memory round trip in the wave's life)
                 asm volatile("" : "+v"(x0.x), "+v"(x0.y), "+v"(x0.z));
+                // Fused ticks: nothing can observe the state between the ticks of one bge_world_tick_many call, and a vouched wave's tick
+                // is lane-local arithmetic on six floats — so the wave runs the n_left ticks that remain of its group here, each with the
+                // single tick's expressions and its ballot, and touches memory once.  It decides before any store: if a lane turns slow
+                // in any of the ticks, nothing is stored and the wave goes on as a launch with n_left = 1 does (below); the launches
+                // that follow in the group give it the same chance again with what is left.
+                if (kFuse && p.serial != 0u && p.n_left > 1u) {
+                    F3 vn = v, xn = x0;
+                    bool all_fast = true;
+                    for (uint32_t i = 0; i < p.n_left; ++i) {
+                        vn = F3{vn.x + (gf.x * gf.w) * p.dt, vn.y + (gf.y * gf.w) * p.dt, vn.z + (gf.z * gf.w) * p.dt};
+                        if (__ballot(!(fabsf(vn.y) >= p.sleep_lin)) != 0ull) {
+                            all_fast = false;
+                            break;
+                        }
+                        xn = F3{xn.x + vn.x * p.dt, xn.y + vn.y * p.dt, xn.z + vn.z * p.dt};
+                    }
+                    if (all_fast) {
+                        st_vel_if(w.vel, slot, vn, vel_xz_changed(vn, v), vel_y_changed(vn, v));
+                        st3(w.pos, slot, xn);
+                        if (p.defer_row3 == 0u) reinterpret_cast<float4*>(w.world)[4ull * slot + 3u] = make_float4(xn.x, xn.y, xn.z, 1.0f);
+                        if ((tid & 63u) == 0u) w.adv[tile * 4u + wave] = p.serial + p.n_left - 1u;
+                        return;
+                    }
+                }
                 // (the expressions of applyGravity and integrateTransforms below, in their order)
                 const F3 v1{v.x + (gf.x * gf.w) * p.dt, v.y + (gf.y * gf.w) * p.dt, v.z + (gf.z * gf.w) * p.dt};
                 if (__ballot(!(fabsf(v1.y) >= p.sleep_lin)) == 0ull) {

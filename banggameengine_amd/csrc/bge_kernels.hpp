@@ -62,6 +62,10 @@ struct WorldView {
     uint32_t* frozen;         // [slots / 32] bit per slot, or null: a root whose parent entity lost its Transform keeps the world matrix it had
                               //             (parent * local) until something marks it dirty — TransformSystem::Update recomputes a node only when
                               //             it or an ancestor is dirty, and Scene::RemoveTransform marks nobody (tiles with kHdrFrozen look here)
+    uint32_t* adv;            // [tiles * 4]  one word per wave64, zeroed with every layout (fused ticks, TickParams::serial): the wave's
+                              //             state in memory is the state after the tick with serial adv.  Set by vouched waves of
+                              //             k_tick<PHYS, XFORM> alone, in flat wave-local tiles, to the last serial of a group of ticks
+                              //             they ran in one launch; 0 or a serial of an earlier group everywhere else
 };
 
 // What a reader of world matrices needs to compose a deferred translation row (bge_device_math.hpp world_row3; bge_epochs.hpp
@@ -231,6 +235,10 @@ struct TickParams {
                          // full path stores all four rows as ever.  Only with rs_epoch != 0, in a scene of one pass without frozen roots
     uint32_t no_repose; // this tick is the 2nd..nth sub-step of ONE stepSimulation call (bge_world_step_simulation): dirty flags
                         // do not re-pose bodies — SyncKinematicBodiesToPhysics ran once, before the first sub-step
+    uint32_t serial;    // fused ticks (bge_epochs.hpp FuseClock): non-zero: this launch is tick `serial` of a group of consecutive
+                        // serials; a wave whose WorldView::adv is not below it returns at once, and a vouched wave runs n_left ticks in
+                        // registers and sets adv = serial + n_left - 1.  0: off, adv is neither loaded nor compared nor written
+    uint32_t n_left;    // with serial != 0: the ticks from this launch to the end of its group, this one included (>= 1)
 };
 
 // flags: bit0 physics, bit1 transforms, bit2 / bit5 aabb, bit4 normal matrices (bge_tick_flags)

@@ -246,6 +246,10 @@ struct bge_world {
     // words are zeroed and before anything but a translation-row tick writes pos or world — words_clear() and epochs_edit() see to
     // the first two themselves; a call that writes pos before its epochs_edit() (upload_trs, bge_world_set_topology) and a tick
     // without the translation-row path call it first.  Readers that run every frame compose instead (row3_view()).
+    // Fused ticks (bge_epochs.hpp FuseClock): one word per wave64, zeroed with every layout, and the serials of the
+    // launches it is compared with.  No host call but tick_impl and the layout touches either.
+    DevBuf adv;
+    bge::FuseClock fuse;
     bge::Row3State row3;
     bge::Row3View row3_view() const { return bge::Row3View{view.rs_word, view.pos, row3.pending}; }
     hipError_t ensure_row3_current()
@@ -486,12 +490,13 @@ struct bge_world {
         view.bmanifold = bmanifold.as<uint32_t>();
         view.frozen = frozen.as<uint32_t>();
         view.rs_word = rs_word.as<uint32_t>();
+        view.adv = adv.as<uint32_t>();
     }
     void release_all()
     {
         for (SlotBuf* a : carried) a->release();
         for (DevBuf* b : std::initializer_list<DevBuf*>{&flags, &parent, &tile_hdr, &slot_of_entity, &entity_of_slot, &root_slots, &root_index, &root_worlds, &counter, &stage,
-                          &stage2, &mass_palette, &normal, &filter_table, &grav_palette, &bp_partials, &obstacle_slots, &obstacle_gen, &obstacles, &obstacle_grid, &box_list, &box_count, &frozen, &rs_word, &trig_slot, &trig_entity, &trig_he, &trig_group,
+                          &stage2, &mass_palette, &normal, &filter_table, &grav_palette, &bp_partials, &obstacle_slots, &obstacle_gen, &obstacles, &obstacle_grid, &box_list, &box_count, &frozen, &rs_word, &adv, &trig_slot, &trig_entity, &trig_he, &trig_group,
                           &trig_mask, &trig_active, &trig_aabb, &trig_pairs, &trig_count, &trig_lists, &ground_list, &ground_count, &trig_tab[0], &trig_tab[1],
                           &trig_delta_dev, &trig_keys_dev, &trig_pose, &query_in, &query_out, &query_keys, &query_all, &query_all_count, &query_ghosts, &move_in, &move_out, &move_state, &move_casts, &move_hits, &step_in, &step_out, &step_state, &step_casts, &step_hits, &recover_in, &recover_out, &recover_state, &recover_queries, &recover_hits, &char_desc, &char_input, &char_state, &char_recover_in, &char_recover_out, &char_step_in, &char_step_out, &char_scratch, &ct_group, &ct_mask, &ct_bits[0], &ct_bits[1], &ct_counts, &ct_row_total, &ct_row_base, &ct_ghost_rec, &ct_events, &ct_count, &ct_src_row, &dbg_block_sum, &dbg_block_off,
                           &dbg_lines, &dbg_total, &bounds, &cull_ballots, &cull_block_sum, &cull_block_off, &cull_out, &cull_total, &draw_keys,
@@ -656,6 +661,7 @@ int make_store(bge_world* w, SlotBuf& a, bool synced = false)
 
 namespace {
 constexpr uint32_t kTriggerPairCap = 1u << 20;
+constexpr uint32_t kFuseTicksDefault = 8; // ticks per fused group of a bge_world_tick_many call (BGE_FUSE_TICKS; DESIGN.md §4.1 "Fused ticks": measured)
 constexpr double kNtThresholdBytes = 300.0e6; // measured crossover between 2 M (plain wins) and 4 M slots (nt wins)
 
 // device mirrors of the trigger set (slots follow the current topology)
@@ -1503,6 +1509,8 @@ try {
     HIP_TRY(w->tile_hdr.ensure(T * 4));
     HIP_TRY(w->rs_word.ensure(T * 64));
     HIP_TRY(hipMemsetAsync(w->rs_word.p, 0, T * 64, w->stream));
+    HIP_TRY(w->adv.ensure(T * 16));
+    HIP_TRY(hipMemsetAsync(w->adv.p, 0, T * 16, w->stream));
     w->epochs_edit();
     HIP_TRY(w->slot_of_entity.ensure(std::max<uint64_t>(n, 1) * 4));
     HIP_TRY(w->entity_of_slot.ensure(S * 4));
@@ -2024,6 +2032,18 @@ int tick_impl(bge_world* w, uint32_t ticks, float dt, const float gravity[3], ui
     // exclusion.  BGE_REST_PATH=0 turns it off (A/B runs); a tick without it moves its epoch on.
     bool rest_path = xform && !(flags & (BGE_TICK_AABBS | BGE_TICK_BROADPHASE | BGE_TICK_NORMAL_MATRICES | BGE_TICK_BULLET_BASIS | BGE_TICK_GATHER_ROOTS));
     if (const char* e = std::getenv("BGE_REST_PATH")) rest_path = rest_path && std::atoi(e) != 0;
+    // Fused ticks (bge_epochs.hpp FuseClock, TickParams::serial): the ticks of this call go out in groups of at most fuse_T launches, and
+    // a vouched wave runs the ticks that remain of its group in the first launch that finds it vouched; the group's later launches
+    // return at once for it.  Only the physics + transform tick on the translation-row path with the flag word, only in a scene of
+    // one pass without a frozen root (Row3State::may_defer's conditions without `pinned`: in any other scene a child of a later pass
+    // reads a flat root's matrix inside the tick, and that must be the matrix of that very tick), and not with an event pair per
+    // tick, which wants launches of equal meaning.  BGE_FUSE_TICKS=T sets the group size; 1 is off (A/B runs).  Groups never span calls.
+    // If a launch fails in the middle of a group, some waves are ahead of others: the error is returned as ever, and the world is
+    // not usable after a failed tick call (include/bge_world.h).
+    uint32_t fuse_T = kFuseTicksDefault;
+    if (const char* e = std::getenv("BGE_FUSE_TICKS")) fuse_T = static_cast<uint32_t>(std::max(1, std::atoi(e)));
+    const bool fusable = phys && rows_path && flag_word && w->flat.pass_tile_begin.size() - 1 == 1 && !w->any_frozen && w->profiling != 2;
+    uint32_t group_first = 0, group_t0 = 0, group_n = 0; // the group tick t belongs to: its first serial, its first tick, its size
     for (uint32_t t = 0; t < ticks; ++t) {
         if (!phys && !w->maybe_dirty && !(flags & BGE_TICK_NORMAL_MATRICES)) {
             // TransformSystem::Update with nothing dirty: a no-op scan — only the kernel launches are skipped.  The
@@ -2043,6 +2063,17 @@ int tick_impl(bge_world* w, uint32_t ticks, float dt, const float gravity[3], ui
         p.nt_out = nt_out ? 1u : 0u;
         p.no_repose = sub.no_repose ? 1u : 0u;
         p.flag_word = flag_word ? 1u : 0u;
+        if (fusable && fuse_T > 1u && t == group_t0 + group_n) {
+            group_t0 = t;
+            group_n = bge::FuseClock::group_size(t, ticks, fuse_T);
+            bool wrapped = false;
+            group_first = w->fuse.begin_group(group_n, &wrapped);
+            if (wrapped) HIP_TRY(hipMemsetAsync(w->adv.p, 0, w->adv.bytes, w->stream));
+        }
+        // (a group of one tick has nothing to fuse: it goes out as every tick did, and no word is loaded)
+        const bool fused = fusable && fuse_T > 1u && group_n > 1u;
+        p.serial = fused ? group_first + (t - group_t0) : 0u;
+        p.n_left = fused ? group_n - (t - group_t0) : 1u;
         // (a tick without the translation-row path may write pos or world from any of its kernels, and moves the rows epoch)
         if (!rows_path) HIP_TRY(w->ensure_row3_current());
         if (rows_path) p.rs_epoch = w->epochs.rows;

@@ -202,7 +202,16 @@ BGE_API int bge_world_set_velocities(bge_world* world, uint64_t first, uint64_t 
  * (the reference uses (0, config.gravity, 0), PhysicsSystem.cpp:130).
  */
 BGE_API int bge_world_tick(bge_world* world, float dt, const float gravity[3], uint32_t flags);
-/* Enqueue `ticks` identical ticks back to back (the catch-up loop of Application::Run, Application.cpp:96-101). */
+/*
+ * Enqueue `ticks` identical ticks back to back (the catch-up loop of Application::Run, Application.cpp:96-101).
+ * Nothing can observe the state between the ticks of one call, and the library uses that: in a flat scene (one pass, no frozen
+ * root) ticked with PHYSICS | TRANSFORMS alone, the ticks go out in groups of BGE_FUSE_TICKS launches (environment, read per
+ * call; default 8; 1 = off), and a wave of 64 bodies whose tick is known to be lane-local arithmetic runs the ticks that remain of
+ * its group in one launch.  The intermediate ticks of a call are then never materialised in memory for those bodies; after the
+ * call every array holds what `ticks` single calls would have left, bit for bit.  There is still one launch per tick on the
+ * stream, groups never span calls, and an event pair per tick (bge_world_profile_enable(2)) switches the grouping off.
+ * If a launch of the call fails, bodies may be left at different ticks: the world is not usable after a failed tick call.
+ */
 BGE_API int bge_world_tick_many(bge_world* world, uint32_t ticks, float dt, const float gravity[3], uint32_t flags);
 /*
  * PhysicsSystem::StepSimulation (src/physics/PhysicsSystem.cpp:848-875) = Bullet's

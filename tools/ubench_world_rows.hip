@@ -13,6 +13,10 @@
 //   g  as f with all three components stored (st_vel): the layout alone, without the skipped stores
 //   h  as f without the per-lane flags load: one 16-B per-wave record through a wave-uniform address stands in for it
 //   i  as h without the row-3 store: the translation row stays in the position array, no matrix line is dirtied
+//   j  as i for n_ticks ticks in one launch: loads once, n_ticks updates in registers (each with the sleep-threshold ballot),
+//      stores pos, vel.y and the per-wave word adv = serial + n_ticks - 1 ("memory holds the state after tick adv")
+//   k  a follow-up launch of a group that (j) began: the wave loads its record and adv, finds adv >= serial and returns
+//      sequences "(j), then T - 1 x (k)" for T in {2, 4, 8} are timed per launch (= per tick) between runs of T x (i)
 // Each kernel runs `reps` times back to back between two events after a warm-up; one JSON line per (kernel, store
 // policy, size).  Built by tools/ubench_world_rows.sh; no part of the product library.
 #include <hip/hip_runtime.h>
@@ -238,6 +242,46 @@ __global__ void __launch_bounds__(kBlock, 8) k_flat_norow_wave(Soa s, const uint
     }
 }
 
+// (j) / (k) share one body, as the two kinds of launch share one kernel in the product: record, then adv against the launch's
+// serial (wave-uniform, nothing stored), then n_ticks updates in registers.  A wave that fails a ballot has stored nothing; the
+// product would go on into its single-tick path, here it returns (sleep_lin is a run-time 0: no lane ever fails).
+__device__ __forceinline__ void fused_body(const Soa& s, const uint4* __restrict__ words, uint32_t* __restrict__ adv, uint32_t epoch, uint32_t serial,
+                                           uint32_t n_ticks, float dt, float sleep_lin)
+{
+    const uint32_t slot = blockIdx.x * kBlock + threadIdx.x;
+    const uint32_t wave = blockIdx.x * 4u + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint4 w = words[wave];
+    if (adv[wave] >= serial) return;
+    if (((w.x ^ epoch) | (w.w ^ epoch)) != 0u) return;
+    if (!(w.z & 1u)) return;
+    F3 pos = ld3(s.pos, slot);
+    const F3 old = ld_vel(s.vel, slot);
+    asm volatile("" : "+v"(pos.x), "+v"(pos.y), "+v"(pos.z));
+    F3 vel = old;
+    for (uint32_t t = 0; t < n_ticks; ++t) {
+        vel.y = vel.y + -9.81f * dt;
+        if (__ballot(!(fabsf(vel.y) >= sleep_lin)) != 0ull) return;
+        pos.x = pos.x + vel.x * dt;
+        pos.y = pos.y + vel.y * dt;
+        pos.z = pos.z + vel.z * dt;
+    }
+    st_vel_if(s.vel, slot, vel, vel_xz_changed(vel, old), vel_y_changed(vel, old));
+    st3(s.pos, slot, pos);
+    if (n_ticks > 1u && (threadIdx.x & 63u) == 0u) adv[wave] = serial + n_ticks - 1u;
+}
+__global__ void __launch_bounds__(kBlock, 8)
+k_flat_fused(Soa s, const uint4* __restrict__ words, uint32_t* __restrict__ adv, uint32_t epoch, uint32_t serial, uint32_t n_ticks, float dt, float sleep_lin)
+{
+    fused_body(s, words, adv, epoch, serial, n_ticks, dt, sleep_lin);
+}
+__global__ void __launch_bounds__(kBlock, 8)
+k_flat_follow(Soa s, const uint4* __restrict__ words, uint32_t* __restrict__ adv, uint32_t epoch, uint32_t serial, uint32_t n_ticks, float dt, float sleep_lin)
+{
+    fused_body(s, words, adv, epoch, serial, n_ticks, dt, sleep_lin);
+}
+
+constexpr uint32_t kEpoch = 7; // what words 0 and 3 of every record of (h) hold, and what its launches pass
+
 template <typename F> float time_us(F launch, int warm, int reps)
 {
     hipEvent_t a, b;
@@ -264,7 +308,48 @@ void report(const char* kernel, bool nt, uint32_t n, float us, double bytes_per_
     std::fflush(stdout);
 }
 
-constexpr uint32_t kEpoch = 7; // what words 0 and 3 of every record of (h) hold, and what its launches pass
+
+// "(j), then T - 1 x (k)": launch i of a group carries serial s + i and n_left = T - i, as the product's launches would
+struct FusedSeq {
+    Soa s;
+    const uint4* words;
+    uint32_t* adv;
+    uint32_t n, T, serial = 1, at = 0;
+    float sleep_lin;
+    void operator()()
+    {
+        const dim3 g(n / kBlock), blk(kBlock);
+        if (at == 0)
+            k_flat_fused<<<g, blk>>>(s, words, adv, kEpoch, serial, T, 1.0f / 60.0f, sleep_lin);
+        else
+            k_flat_follow<<<g, blk>>>(s, words, adv, kEpoch, serial, T - at, 1.0f / 60.0f, sleep_lin);
+        ++serial;
+        at = (at + 1u) % T;
+    }
+};
+
+// (i), T = 2, 4, 8, three times over, and a fourth (i): the spread of the (i) lines is the yardstick.  Warm-up and reps are whole
+// groups (multiples of 8); the serials go on rising from run to run, adv is never reset.
+void run_fused(uint32_t n, int reps, Soa s, const uint4* words, uint32_t* adv, float sleep_lin)
+{
+    const int warm = 24;
+    reps = (reps + 7) / 8 * 8;
+    const dim3 blk(kBlock), g_slot(n / kBlock);
+    uint32_t serial = 1;
+    for (int round = 0; round < 4; ++round) {
+        report("i_flat_norow_wave", false, n, time_us([&] { k_flat_norow_wave<<<g_slot, blk>>>(s, words, kEpoch, n, 1.0f / 60.0f); }, warm, reps), 40.25);
+        if (round == 3) break;
+        for (uint32_t T : {2u, 4u, 8u}) {
+            FusedSeq seq{s, words, adv, n, T, serial, 0u, sleep_lin};
+            char name[32];
+            std::snprintf(name, sizeof name, "jk_fused_T%u", T);
+            report(name, false, n, time_us([&] { seq(); }, warm, reps), 40.3125 / T);
+            serial = seq.serial;
+        }
+    }
+    CK(hipGetLastError());
+    CK(hipDeviceSynchronize());
+}
 
 template <bool NT> void run_size(uint32_t n, int reps, Soa s, const uint4* words, float zero)
 {
@@ -303,13 +388,15 @@ template <bool NT> void run_size(uint32_t n, int reps, Soa s, const uint4* words
 } // namespace
 
 // usage: ubench_world_rows [slots ...]   (default 1048576 16777216; rounded up to whole 256-slot blocks)
-//        env UBENCH_REPS: timed launches per kernel (default 200); UBENCH_GXZ: x and z gravity of kernel (g) (default 0)
+//        env UBENCH_REPS: timed launches per kernel (default 200); UBENCH_GXZ: x and z gravity of kernel (g) (default 0);
+//        UBENCH_FUSED_ONLY: time (i), (j), (k) alone; UBENCH_SLEEP_LIN: the sleep threshold of (j) (default 0: every ballot passes)
 int main(int argc, char** argv)
 {
     std::vector<uint32_t> sizes;
     for (int i = 1; i < argc; ++i) sizes.push_back(static_cast<uint32_t>(std::strtoul(argv[i], nullptr, 10)));
     if (sizes.empty()) sizes = {1u << 20, 1u << 24};
     const float zero = std::getenv("UBENCH_GXZ") ? static_cast<float>(std::atof(std::getenv("UBENCH_GXZ"))) : 0.0f; // (g)'s x / z gravity
+    const bool fused_only = std::getenv("UBENCH_FUSED_ONLY") != nullptr; // kernels (i), (j), (k) alone
     const int reps = std::getenv("UBENCH_REPS") ? std::atoi(std::getenv("UBENCH_REPS")) : 200;
     for (uint32_t n0 : sizes) {
         const uint32_t n = (n0 + kBlock - 1) / kBlock * kBlock;
@@ -334,8 +421,16 @@ int main(int argc, char** argv)
         std::vector<uint4> wr(n / 64u, uint4{kEpoch, 0u, 1u, kEpoch});
         CK(hipMalloc(&words, 16ull * wr.size()));
         CK(hipMemcpy(words, wr.data(), 16ull * wr.size(), hipMemcpyHostToDevice));
-        run_size<false>(n, reps, s, words, zero);
-        run_size<true>(n, reps, s, words, zero);
+        uint32_t* adv = nullptr; // (j) / (k): one word per wave
+        CK(hipMalloc(&adv, 4ull * wr.size()));
+        CK(hipMemset(adv, 0, 4ull * wr.size()));
+        const float sleep_lin = std::getenv("UBENCH_SLEEP_LIN") ? static_cast<float>(std::atof(std::getenv("UBENCH_SLEEP_LIN"))) : 0.0f;
+        if (!fused_only) {
+            run_size<false>(n, reps, s, words, zero);
+            run_size<true>(n, reps, s, words, zero);
+        }
+        run_fused(n, reps, s, words, adv, sleep_lin);
+        CK(hipFree(adv));
         CK(hipFree(words));
         CK(hipFree(s.flags));
         CK(hipFree(s.pos));

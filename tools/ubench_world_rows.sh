@@ -5,7 +5,8 @@
 # 2. rocprofv3 --kernel-trace --stats                                                      -> stats/
 # 3. rocprofv3 --pmc FETCH_SIZE, then --pmc WRITE_SIZE, each a run of its own              -> pmc_FETCH_SIZE/, pmc_WRITE_SIZE/
 # then a per-kernel digest of all three (tools/ubench_world_rows_digest.py), which also prints the gates of kernel (h) against (f)
-# and of kernel (i) against (h).
+# of kernel (i) against (h), and of the sequences "(j), then T - 1 x (k)" against (i).
+#   UBENCH_FUSED_ONLY=1 bash tools/ubench_world_rows.sh [OUT_DIR]   runs (i), (j) and (k) alone
 set -o pipefail
 R=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$(realpath -m "${1:-$R/build/ubench_world_rows_out}")
