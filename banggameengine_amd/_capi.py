@@ -117,6 +117,9 @@ SYMBOLS = {
     "bge_world_characters_update": (C.c_int, [_vp, _f, _u32]),
     "bge_world_characters_download": (C.c_int, [_vp, _u64, _u64, _vp]),
     "bge_world_characters_state_device": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_u64)]),
+    "bge_world_characters_ride": (C.c_int, [_vp, _u32]),
+    "bge_world_characters_rides": (C.c_int, [_vp, _u64, _u64, _vp]),
+    "bge_world_characters_rides_device": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_u64)]),
     "bge_world_characters_watch_triggers": (C.c_int, [_vp, _u64, _vp, _vp, _u32, _u64]),
     "bge_world_characters_trigger_events": (C.c_int, [_vp, _vp, _u64, C.POINTER(_u64)]),
     "bge_world_characters_trigger_events_device": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_u64)]),

@@ -34,6 +34,7 @@
 #include "bge_recover.hpp"
 #include "bge_character.hpp"
 #include "bge_chartrig.hpp"
+#include "bge_ride.hpp"
 #include "bge_query.hpp"
 
 namespace {
@@ -398,6 +399,10 @@ struct bge_world {
     // recovery and the step move and get back, and the step's scratch
     DevBuf char_desc, char_input, char_state, char_recover_in, char_recover_out, char_step_in, char_step_out, char_scratch;
     uint64_t n_characters = 0;
+    // character platform riding (bge_ride.hip): the resident bge_character_ride records of the set while riding is on
+    DevBuf char_ride;
+    bool ride_on = false;
+    uint32_t ride_flags = 0;
     // character trigger events (bge_chartrig.hip): the per-character filters, the two [triggers][ceil(n / 64)] bitmaps
     // (ct_bits[ct_rem] = remembered, the other = remembered before the last update call), the per-(ghost, word) counts / offsets, the
     // per-ghost totals, bases and {trigger, entity} of the last call, the event list and its count
@@ -498,7 +503,7 @@ struct bge_world {
         for (DevBuf* b : std::initializer_list<DevBuf*>{&flags, &parent, &tile_hdr, &slot_of_entity, &entity_of_slot, &root_slots, &root_index, &root_worlds, &counter, &stage,
                           &stage2, &mass_palette, &normal, &filter_table, &grav_palette, &bp_partials, &obstacle_slots, &obstacle_gen, &obstacles, &obstacle_grid, &box_list, &box_count, &frozen, &rs_word, &adv, &trig_slot, &trig_entity, &trig_he, &trig_group,
                           &trig_mask, &trig_active, &trig_aabb, &trig_pairs, &trig_count, &trig_lists, &ground_list, &ground_count, &trig_tab[0], &trig_tab[1],
-                          &trig_delta_dev, &trig_keys_dev, &trig_pose, &query_in, &query_out, &query_keys, &query_all, &query_all_count, &query_ghosts, &move_in, &move_out, &move_state, &move_casts, &move_hits, &step_in, &step_out, &step_state, &step_casts, &step_hits, &recover_in, &recover_out, &recover_state, &recover_queries, &recover_hits, &char_desc, &char_input, &char_state, &char_recover_in, &char_recover_out, &char_step_in, &char_step_out, &char_scratch, &ct_group, &ct_mask, &ct_bits[0], &ct_bits[1], &ct_counts, &ct_row_total, &ct_row_base, &ct_ghost_rec, &ct_events, &ct_count, &ct_src_row, &dbg_block_sum, &dbg_block_off,
+                          &trig_delta_dev, &trig_keys_dev, &trig_pose, &query_in, &query_out, &query_keys, &query_all, &query_all_count, &query_ghosts, &move_in, &move_out, &move_state, &move_casts, &move_hits, &step_in, &step_out, &step_state, &step_casts, &step_hits, &recover_in, &recover_out, &recover_state, &recover_queries, &recover_hits, &char_desc, &char_input, &char_state, &char_recover_in, &char_recover_out, &char_step_in, &char_step_out, &char_scratch, &char_ride, &ct_group, &ct_mask, &ct_bits[0], &ct_bits[1], &ct_counts, &ct_row_total, &ct_row_base, &ct_ghost_rec, &ct_events, &ct_count, &ct_src_row, &dbg_block_sum, &dbg_block_off,
                           &dbg_lines, &dbg_total, &bounds, &cull_ballots, &cull_block_sum, &cull_block_off, &cull_out, &cull_total, &draw_keys,
                           &batch_sort, &batch_hist, &batch_out}) {
             b->release();
@@ -1337,6 +1342,15 @@ void bge_world_destroy(bge_world* w)
     delete w;
 }
 
+// Character platform riding: the anchors on entities [first, first + count) are cleared, on the stream (bge_world_set_topology: all
+// of them; bge_world_upload_bodies: an entity index that gets a new body carries nobody by the difference of two unrelated poses)
+static int ride_forget(bge_world* w, uint64_t first, uint64_t count)
+{
+    if (!w->ride_on || w->n_characters == 0) return BGE_OK;
+    HIP_TRY(bge::launch_char_ride_forget(w->stream, w->char_ride.p, static_cast<uint32_t>(w->n_characters), first, count));
+    return BGE_OK;
+}
+
 int bge_world_set_topology(bge_world* w, uint64_t n, const uint32_t* parent, const uint8_t* has_transform)
 try {
     if (!w) return fail(BGE_ERR_INVALID, "world is NULL");
@@ -1603,7 +1617,7 @@ try {
     w->triggers_device_stale = true; // slots moved
     w->global_of_slot_stale = true;
     w->pairs_from_slab = false;
-    return BGE_OK;
+    return ride_forget(w, 0, ~0ull); // (slots moved and entity indices may mean other entities: nobody rides across this)
 }
 BGE_CATCH_ALL("bge_world_set_topology")
 
@@ -1753,6 +1767,27 @@ static int upload_bodies(bge_world* w, uint64_t first, uint64_t count, const uin
         if (changed) {
             HIP_TRY(hipStreamSynchronize(w->stream));
             HIP_TRY(hipMemcpy(w->tile_hdr.p, w->flat.tile_hdr.data(), static_cast<size_t>(w->flat.n_tiles_total) * 4, hipMemcpyHostToDevice));
+        }
+    }
+    if (w->ride_on) {
+        // character platform riding: nobody keeps an anchor on an entity whose body is replaced.  The indexed form forgets run by
+        // run of consecutive indices; a list of more than kRuns runs is taken as its span.
+        constexpr size_t kRuns = 16;
+        std::vector<std::pair<uint64_t, uint64_t>> runs; // first, count
+        if (!index) {
+            runs.emplace_back(first, count);
+        } else {
+            std::vector<uint32_t> sorted(index, index + count);
+            std::sort(sorted.begin(), sorted.end());
+            for (uint32_t e : sorted) {
+                if (!runs.empty() && e < runs.back().first + runs.back().second) continue; // (listed twice)
+                if (!runs.empty() && e == runs.back().first + runs.back().second) runs.back().second += 1;
+                else runs.emplace_back(e, 1);
+            }
+            if (runs.size() > kRuns) runs.assign(1, {sorted.front(), uint64_t(sorted.back()) - sorted.front() + 1u});
+        }
+        for (const auto& run : runs) {
+            if (int rc = ride_forget(w, run.first, run.second)) return rc;
         }
     }
     const size_t bytes = words.size() * 4;
@@ -3673,6 +3708,9 @@ try {
     HIP_TRY(hipStreamSynchronize(w->stream)); // (an update of the old set may still be running on its buffers)
     w->n_characters = 0;
     chartrig_off(w); // (the watch belongs to the set: its filters and bitmaps are per character)
+    w->ride_on = false; // (and so do the ride records)
+    w->ride_flags = 0;
+    w->char_ride.release();
     if (n == 0) {
         for (DevBuf* b : {&w->char_desc, &w->char_input, &w->char_state, &w->char_recover_in, &w->char_recover_out, &w->char_step_in, &w->char_step_out,
                           &w->char_scratch}) {
@@ -3785,12 +3823,29 @@ try {
     c.scratch = w->char_scratch.as<uint2>();
     c.dt = dt;
     c.n = static_cast<uint32_t>(n);
+    bge::RideParams r{};
+    if (w->ride_on) {
+        r.state = w->char_state.p;
+        r.ride = w->char_ride.p;
+        r.n = c.n;
+        r.dynamic = (w->ride_flags & BGE_CHAR_RIDE_DYNAMIC) ? 1u : 0u;
+        r.n_entities = w->flat.n_entities;
+        r.n_slots = q.n_slots;
+        r.flags = q.flags;
+        r.pos = q.pos;
+        r.quat = q.quat;
+        r.slot_of_entity = q.slot_of_entity;
+        HIP_TRY(bge::launch_char_carry(w->stream, r));
+    }
     for (uint32_t k = 0; k < steps; ++k) {
         HIP_TRY(bge::launch_char_begin(w->stream, c, k == 0 ? 1u : 0u));
         if (int rc = recover_enqueue(w, qr, n, w->char_recover_in.p, w->char_recover_out.p)) return rc;
         HIP_TRY(bge::launch_char_move(w->stream, c));
         if (int rc = step_enqueue(w, q, n, w->char_step_in.p, w->char_step_out.p)) return rc;
         HIP_TRY(bge::launch_char_finish(w->stream, c));
+    }
+    if (w->ride_on) {
+        HIP_TRY(bge::launch_char_anchor(w->stream, r));
     }
     if (w->ct_on) {
         if (int rc = chartrig_enqueue(w, q.n_ghosts)) return rc;
@@ -3821,6 +3876,70 @@ try {
     return BGE_OK;
 }
 BGE_CATCH_ALL("bge_world_characters_state_device")
+
+// ---------------------------------------------------------------- character platform riding (bge_ride.hip)
+static_assert(sizeof(bge_character_ride) == 64, "bge_character_ride is 64 bytes (include/bge_world.h)");
+
+int bge_world_characters_ride(bge_world* w, uint32_t flags)
+try {
+    if (!w) return fail(BGE_ERR_INVALID, "world is NULL");
+    if (flags & ~uint32_t(BGE_CHAR_RIDE_ON | BGE_CHAR_RIDE_DYNAMIC)) return fail(BGE_ERR_INVALID, "flags = %#x: unknown bits", flags);
+    if ((flags & BGE_CHAR_RIDE_DYNAMIC) && !(flags & BGE_CHAR_RIDE_ON)) return fail(BGE_ERR_INVALID, "BGE_CHAR_RIDE_DYNAMIC without BGE_CHAR_RIDE_ON");
+    DeviceGuard guard(w->device);
+    if (flags == 0u) {
+        if (w->ride_on) {
+            HIP_TRY(hipStreamSynchronize(w->stream)); // (an update may still be writing the records)
+        }
+        w->ride_on = false;
+        w->ride_flags = 0;
+        w->char_ride.release();
+        return BGE_OK;
+    }
+    const uint64_t n = w->n_characters;
+    if (n == 0) return fail(BGE_ERR_INVALID, "there is no character set to switch riding on for");
+    if (!w->ride_on) {
+        // no anchor: entity = BGE_RAY_NO_ENTITY, turn = (0, 0, 0, 1), every other word 0
+        std::vector<bge_character_ride> fresh(n);
+        for (bge_character_ride& r : fresh) {
+            r = bge_character_ride{};
+            r.entity = BGE_RAY_NO_ENTITY;
+            r.turn[3] = 1.0f;
+        }
+        HIP_TRY(w->char_ride.ensure(n * sizeof(bge_character_ride)));
+        HIP_TRY(hipMemcpyAsync(w->char_ride.p, fresh.data(), n * sizeof(bge_character_ride), hipMemcpyHostToDevice, w->stream));
+        HIP_TRY(hipStreamSynchronize(w->stream)); // (the copy reads this function's memory)
+        w->ride_on = true;
+    }
+    w->ride_flags = flags;
+    return BGE_OK;
+}
+BGE_CATCH_ALL("bge_world_characters_ride")
+
+int bge_world_characters_rides(bge_world* w, uint64_t first, uint64_t count, bge_character_ride* out)
+try {
+    if (!w) return fail(BGE_ERR_INVALID, "world is NULL");
+    if (int rc = check_character_range(w, first, count)) return rc;
+    DeviceGuard guard(w->device);
+    if (count == 0) {
+        HIP_TRY(hipStreamSynchronize(w->stream));
+        return BGE_OK;
+    }
+    if (!w->ride_on) return fail(BGE_ERR_INVALID, "character platform riding is off");
+    if (!out) return fail(BGE_ERR_INVALID, "out is NULL");
+    HIP_TRY(hipMemcpyAsync(out, w->char_ride.as<bge_character_ride>() + first, count * sizeof(bge_character_ride), hipMemcpyDeviceToHost, w->stream));
+    HIP_TRY(hipStreamSynchronize(w->stream));
+    return BGE_OK;
+}
+BGE_CATCH_ALL("bge_world_characters_rides")
+
+int bge_world_characters_rides_device(bge_world* w, void** rides, uint64_t* n)
+try {
+    if (!w || !rides || !n) return fail(BGE_ERR_INVALID, "NULL argument");
+    *rides = w->ride_on ? w->char_ride.p : nullptr;
+    *n = w->ride_on ? w->n_characters : 0;
+    return BGE_OK;
+}
+BGE_CATCH_ALL("bge_world_characters_rides_device")
 
 // ---------------------------------------------------------------- character trigger events (bge_chartrig.hip)
 static_assert(sizeof(bge_character_trigger_event) == 12, "bge_character_trigger_event is 12 bytes (include/bge_world.h)");

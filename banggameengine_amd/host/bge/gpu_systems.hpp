@@ -160,6 +160,16 @@ template <class Vec3> struct GpuCharacterState {
     uint32_t steps = 0;
 };
 
+// What GetCharacterRide returns (extension: include/bge_world.h "Character platform riding"): what the last UpdateCharacters' carry
+// did to the character, as of the last SyncCharacters
+template <class Vec3> struct GpuCharacterRide {
+    bool carried = false;  // the platform moved and the character was moved with it
+    bool lost = false;     // the platform left the world (or stopped being rideable) under the character
+    uint32_t platform = 0; // EntityId of the body the character stood on when the call ended; kInvalidEntity (0) if none
+    Vec3 carriedBy{};      // what the carry added to the position
+    float turn[4] = {0.0f, 0.0f, 0.0f, 1.0f}; // xyzw: the platform's rotation since the call before, for the caller's facing
+};
+
 struct GpuTriggerEvent {
     enum class Type { Enter, Stay, Exit };
     Type type = Type::Enter;
@@ -792,6 +802,8 @@ public:
         chars_stale_ = char_inputs_stale_ = false;
         char_trig_watching_ = char_trig_pending_ = false; // (creating the set turns the device's watch off)
         char_trigger_events_.clear();
+        char_ride_applied_ = 0u; // (and riding)
+        char_rides_.clear();
         if (ok() && bge_world_characters_create(world_, 0, nullptr) != BGE_OK) Log("bge_world_characters_create");
     }
     // EXTENSION: trigger events for the characters (include/bge_world.h "Character trigger events"), off by default: every
@@ -805,6 +817,30 @@ public:
     }
     // the list of the last UpdateCharacters, as of the last SyncCharacters, in the device's order
     const std::vector<GpuTriggerEvent>& CharacterTriggerEvents() const { return char_trigger_events_; }
+    // EXTENSION: characters ride moving platforms (include/bge_world.h "Character platform riding"), off by default: every
+    // UpdateCharacters begins by moving each grounded character with the Static or Kinematic body it stood on (with dynamicBodies
+    // a Dynamic one too).  Applied by the next UpdateCharacters; re-creating the set loses no anchor worth keeping, since
+    // re-created characters are not grounded.
+    void SetCharacterPlatformRiding(bool on, bool dynamicBodies = false)
+    {
+        char_ride_want_ = 0u;
+        if (on) char_ride_want_ = static_cast<uint32_t>(BGE_CHAR_RIDE_ON) | (dynamicBodies ? static_cast<uint32_t>(BGE_CHAR_RIDE_DYNAMIC) : 0u);
+        if (!on) char_rides_.clear();
+    }
+    // carried, turn and the platform of the last UpdateCharacters, as of the last SyncCharacters; false while riding is off
+    template <class Vec3> bool GetCharacterRide(Id entity, GpuCharacterRide<Vec3>& out) const
+    {
+        auto it = char_index_.find(entity);
+        if (it == char_index_.end() || it->second >= char_rides_.size()) return false;
+        const bge_character_ride& r = char_rides_[it->second];
+        out = GpuCharacterRide<Vec3>{};
+        out.carried = (r.flags & BGE_CHAR_RIDE_CARRIED) != 0u;
+        out.lost = (r.flags & BGE_CHAR_RIDE_LOST) != 0u;
+        out.platform = r.entity != BGE_RAY_NO_ENTITY && r.entity < ids_.size() ? ids_[r.entity] : Id{0};
+        out.carriedBy.x = r.carried[0], out.carriedBy.y = r.carried[1], out.carriedBy.z = r.carried[2];
+        for (int k = 0; k < 4; ++k) out.turn[k] = r.turn[k];
+        return true;
+    }
     size_t CharacterCount() const { return char_ids_.size(); }
     bool SetCharacterWalk(Id entity, float dx, float dz)
     {
@@ -859,6 +895,11 @@ public:
             chars_stale_ = false;
             char_inputs_stale_ = true;
             char_trig_watching_ = false;
+            char_ride_applied_ = 0u; // (creating the set switched riding off)
+        }
+        if (char_ride_want_ != char_ride_applied_) {
+            if (bge_world_characters_ride(world_, char_ride_want_) != BGE_OK) return Log("bge_world_characters_ride");
+            char_ride_applied_ = char_ride_want_;
         }
         if (char_trig_on_ != char_trig_watching_) {
             if (bge_world_characters_watch_triggers(world_, char_trig_on_ ? char_descs_.size() : 0, nullptr, nullptr, BGE_CHAR_TRIGGER_STAY_EVENTS, 0) !=
@@ -893,6 +934,11 @@ public:
             if (!t) continue;
             std::memcpy(static_cast<void*>(&t->position), char_states_[i].position, 12);
             t->MarkDirty();
+        }
+        char_rides_.resize(char_ride_applied_ ? char_ids_.size() : 0);
+        if (!char_rides_.empty() && bge_world_characters_rides(world_, 0, char_rides_.size(), char_rides_.data()) != BGE_OK) {
+            char_rides_.clear();
+            return Log("bge_world_characters_rides");
         }
         return FetchCharacterTriggerEvents(scene);
     }
@@ -1483,6 +1529,9 @@ private:
     std::vector<uint32_t> char_overlaps_; // (trigger entity, character) pairs carried over a re-creation of the set
     std::vector<bge_character_trigger_event> raw_char_events_;
     std::vector<GpuTriggerEvent> char_trigger_events_;
+    // character platform riding: the flags wanted, the flags the device has, the records as last synced
+    uint32_t char_ride_want_ = 0u, char_ride_applied_ = 0u;
+    std::vector<bge_character_ride> char_rides_;
 
     template <class Vec3> static bge_sphere_cast MakeCast(const Vec3& o, const Vec3& d, float maxDistance, float radius, uint32_t layerMask)
     {
@@ -1756,6 +1805,7 @@ public:
     {
         if (!lastScene_) return false;
         GpuMirrors<SceneT>::Of(*lastScene_).SetCharacterTriggerEvents(characterTriggerEvents_);
+        GpuMirrors<SceneT>::Of(*lastScene_).SetCharacterPlatformRiding(characterRiding_, characterRidingDynamic_);
         return GpuMirrors<SceneT>::Of(*lastScene_).UpdateCharacters(dt, steps);
     }
     bool SyncCharacters(SceneT& scene) { return GpuMirrors<SceneT>::Of(scene).SyncCharacters(scene); }
@@ -1771,6 +1821,21 @@ public:
     {
         static const std::vector<GpuTriggerEvent> none;
         return lastScene_ ? GpuMirrors<SceneT>::Of(*lastScene_).CharacterTriggerEvents() : none;
+    }
+    // EXTENSION: characters ride moving platforms (include/bge_world.h "Character platform riding"), off by default.  With it on,
+    // a character that stands on a Static or Kinematic body (with dynamicBodies on a Dynamic one too) is moved with that body at the
+    // start of every UpdateCharacters; a game that moves platforms through their Transforms need not keep Bullet for that.  The
+    // carry is a teleport (no sweep) and leaves no velocity behind when the character steps off.
+    void SetCharacterPlatformRiding(bool on, bool dynamicBodies = false)
+    {
+        characterRiding_ = on;
+        characterRidingDynamic_ = on && dynamicBodies;
+        if (lastScene_) GpuMirrors<SceneT>::Of(*lastScene_).SetCharacterPlatformRiding(characterRiding_, characterRidingDynamic_);
+    }
+    // what the last UpdateCharacters' carry did and the platform stood on, as of the last SyncCharacters
+    template <class Vec3> bool GetCharacterRide(typename GpuSceneMirror<SceneT>::Id entity, GpuCharacterRide<Vec3>& out) const
+    {
+        return lastScene_ && GpuMirrors<SceneT>::Of(*lastScene_).GetCharacterRide(entity, out);
     }
     // as of the last SyncCharacters
     bool CharacterOnGround(typename GpuSceneMirror<SceneT>::Id entity) const
@@ -1909,6 +1974,7 @@ private:
     bool groundPlane_ = true;
     SceneT* lastScene_ = nullptr; // the scene whose world the ray queries read
     bool characterTriggerEvents_ = false; // SetCharacterTriggerEvents: handed to the scene's mirror by UpdateCharacters
+    bool characterRiding_ = false, characterRidingDynamic_ = false; // SetCharacterPlatformRiding: the same
     bool debugDrawEnabled_ = false;
     bge_debug_desc debugDesc_{static_cast<uint32_t>(sizeof(bge_debug_desc)), BGE_DEBUG_ALL, 0u, {0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f}};
     DebugLineBuffer debugLines_;

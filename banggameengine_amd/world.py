@@ -170,6 +170,12 @@ CHARACTER_STATE_DTYPE = np.dtype([("position", "<f4", (3,)), ("vertical_velocity
                                   ("ground_entity", "<u4"), ("ground_normal", "<f4", (3,)), ("hit_kind", "<u4"), ("hit_entity", "<u4"),
                                   ("hit_normal", "<f4", (3,)), ("step_rise", "<f4"), ("recovered", "<f4", (3,)), ("steps", "<u4")])
 assert CHARACTER_DESC_DTYPE.itemsize == 48 and CHARACTER_INPUT_DTYPE.itemsize == 16 and CHARACTER_STATE_DTYPE.itemsize == 80
+# character platform riding (bge_world_characters_ride ..): bge_character_ride_mode, bge_character_ride_flags and the record
+CHAR_RIDE_ON, CHAR_RIDE_DYNAMIC = 1, 2
+CHAR_RIDE_CARRIED, CHAR_RIDE_LOST = 1, 2
+CHARACTER_RIDE_DTYPE = np.dtype([("flags", "<u4"), ("entity", "<u4"), ("anchor_position", "<f4", (3,)), ("anchor_rotation", "<f4", (4,)),
+                                 ("carried", "<f4", (3,)), ("turn", "<f4", (4,))])
+assert CHARACTER_RIDE_DTYPE.itemsize == 64
 
 
 def make_characters(positions, radius=0.5, skin=0.01, step_height=0.35, min_ground_ny=0.7071068, probe_distance=0.1, gravity=9.81, jump_speed=5.0,
@@ -739,6 +745,29 @@ class World:
         """(device pointer, n) of the resident bge_character_state[n]; (0, 0) without characters."""
         ptr, n = C.c_void_p(), C.c_uint64()
         check(lib().bge_world_characters_state_device(self._h, C.byref(ptr), C.byref(n)))
+        return int(ptr.value or 0), int(n.value)
+
+    # -- character platform riding (include/bge_world.h "Character platform riding" states the rule)
+    def characters_ride(self, on=True, dynamic=False):
+        """Switches riding on (characters move with the Static or Kinematic body they stand on; with dynamic=True with a Dynamic
+        one too) or off.  Switching on while it is on changes only the flags and keeps the anchors."""
+        if dynamic and not on:
+            raise ValueError("dynamic=True needs on=True")
+        check(lib().bge_world_characters_ride(self._h, (CHAR_RIDE_ON if on else 0) | (CHAR_RIDE_DYNAMIC if dynamic else 0)))
+
+    def characters_rides(self, first=0, count=None):
+        """The ride records of characters first .. first + count (all of them by default) as a CHARACTER_RIDE_DTYPE array.
+        Synchronises the world's stream."""
+        if count is None:
+            count = self.characters_state_device()[1] - first
+        rides = np.zeros(max(count, 0), CHARACTER_RIDE_DTYPE)
+        check(lib().bge_world_characters_rides(self._h, first, count, _p(rides) if count > 0 else None))
+        return rides
+
+    def characters_rides_device(self):
+        """(device pointer, n) of the resident bge_character_ride[n]; (0, 0) while riding is off."""
+        ptr, n = C.c_void_p(), C.c_uint64()
+        check(lib().bge_world_characters_rides_device(self._h, C.byref(ptr), C.byref(n)))
         return int(ptr.value or 0), int(n.value)
 
     # -- character trigger events (include/bge_world.h "Character trigger events" states the rule and the order of the list)

@@ -815,9 +815,10 @@ BGE_API int bge_world_sphere_recover_device(bge_world* world, uint64_t n, const 
  *             The kerb of "Sphere step moves" (min_ground_ny cos 45 degrees, step_height 0.7): a character GROUNDED at
  *             (0, 0.51, 0) with walk (2, 0): walking, dy = 0, M is that example's result: position (2, 1.11, 0), ground_distance
  *             0.01, e = 0: flags GROUNDED | STEPPED, step_rise 0.7, ground_kind BODY, entity 0.
- *   Not done  capsule characters; pushing Dynamic bodies; riding moving platforms (a platform that moves INTO a character pushes
- *             it out through Recover, one that moves away or along does not carry it); writing into a Transform on the device
- *             (the adapter does that on the host).  Trigger volumes report characters through "Character trigger events" below,
+ *   Not done  capsule characters; pushing Dynamic bodies; writing into a Transform on the device (the adapter does that on the
+ *             host).  A platform that moves INTO a character pushes it out through Recover; one that moves away from or along
+ *             under a grounded character carries it only once "Character platform riding" below is switched on, and what remains
+ *             open there is a swept carry and inherited velocity.  Trigger volumes report characters through "Character trigger events" below,
  *             with what remains open there: the box is the sphere's, not a capsule's; the world's own bge_world_trigger_events
  *             still does not see characters; characters do not report each other.
  *   Characters are not bodies: no query sees them, they do not see each other, and no call here changes any other world state.
@@ -959,6 +960,82 @@ BGE_API int bge_world_characters_trigger_events_device(bge_world* world, void** 
 BGE_API int bge_world_characters_trigger_overlaps(bge_world* world, uint64_t cap, uint32_t* pairs2, uint64_t* total);
 BGE_API int bge_world_characters_set_trigger_overlaps(bge_world* world, uint64_t count, const uint32_t* pairs2);
 BGE_API int bge_world_trigger_boxes(bge_world* world, uint64_t count, const uint32_t* entity_index, float* aabb6, uint8_t* listed);
+
+/*
+ * Character platform riding: a character that stands on a body moves with it.  Each character remembers the body
+ * it stood on when the last bge_world_characters_update call ended and that body's pose (the anchor); the next call begins by
+ * putting the character where it was in that body's frame.  Opt-in: until bge_world_characters_ride switches it on, every other
+ * call does byte for byte what it did without this section.  The rule below is the specification.  All arithmetic is binary32, one
+ * rounding per operation, in the order written.
+ *   Pose      of a body: its position and its quaternion (xyzw) as the queries see them at that call: the position is what
+ *             bge_world_download_pose returns, the quaternion what bge_world_download_bodies returns.
+ *   Present   a body is present exactly when the queries' body pass would load it: its type is not BGE_BODY_NONE and it has not
+ *             been uploaded since the last physics tick.
+ *   Rideable  a present body is rideable when it is Static or Kinematic; with BGE_CHAR_RIDE_DYNAMIC a Dynamic body is rideable too.
+ *   Carry     once per bge_world_characters_update call, before its first step.  The stages run in order and the first that applies
+ *             decides:
+ *             1. flags = 0, carried = 0, turn = (0, 0, 0, 1).
+ *             2. If the character is not GROUNDED or entity == BGE_RAY_NO_ENTITY: nothing more.  (A warp clears GROUNDED, so a
+ *                warped character is never carried.)
+ *             3. If the anchor body is no longer present or no longer rideable: flags = BGE_CHAR_RIDE_LOST, the position stays.
+ *             4. If the body's current pose equals the anchor pose word for word (7 words): nothing more.  A world that did not move
+ *                stays byte-identical to one with riding off.
+ *             5. Otherwise, with p the character's position, (a_p, a_q) the anchor pose and (c_p, c_q) the current pose:
+ *                  l = rot(conj(a_q), p - a_p);  t = c_p + rot(c_q, l);  carried = t - p;  turn = mul(c_q, conj(a_q))
+ *                If every component of t is finite: position = t, flags = BGE_CHAR_RIDE_CARRIED; vertical_velocity and the state's
+ *                flags stay.  Otherwise flags = BGE_CHAR_RIDE_LOST, the position stays, carried stays 0 and turn the identity.
+ *             conj negates x, y and z.  rot(q, v) is
+ *                  tx = (q.y*v.z - q.z*v.y)*2;  ty = (q.z*v.x - q.x*v.z)*2;  tz = (q.x*v.y - q.y*v.x)*2;
+ *                  r.x = (v.x + q.w*tx) + (q.y*tz - q.z*ty);
+ *                  r.y = (v.y + q.w*ty) + (q.z*tx - q.x*tz);
+ *                  r.z = (v.z + q.w*tz) + (q.x*ty - q.y*tx)
+ *             and mul(p, q) is
+ *                  x = ((p.w*q.x + p.x*q.w) + p.y*q.z) - p.z*q.y
+ *                  y = ((p.w*q.y + p.y*q.w) + p.z*q.x) - p.x*q.z
+ *                  z = ((p.w*q.z + p.z*q.w) + p.x*q.y) - p.y*q.x
+ *                  w = ((p.w*q.w - p.x*q.x) - p.y*q.y) - p.z*q.z
+ *             The steps then run as in "Characters"; the first step's Recover resolves whatever the carry put the character into.
+ *   Anchor    once per call, after its last step and before the trigger events.  If the state is GROUNDED, ground_kind is
+ *             BGE_RAY_BODY and that body is rideable: entity = ground_entity and the anchor pose is that body's pose now.  Otherwise
+ *             entity = BGE_RAY_NO_ENTITY and the anchor words are 0.  (An INVALID last step leaves ground_kind MISS: no anchor.)
+ *   Hence     the plane and trigger ghosts are never ridden.  A character that jumped or walked off is not carried, and the platform
+ *             leaves without it.  The character keeps no horizontal velocity when it leaves a platform.  turn is for the caller's
+ *             facing: the device keeps none.
+ *   Example   a level box with its top at y = 1, a character of radius 0.5 and skin 0.01 GROUNDED on it at (1, 1.51, 0), anchor
+ *             pose ((0, 0.5, 0), identity).  The box moves to (0.25, 0.5, 0): l = (1, 1.01, 0), t = (1.25, 1.51, 0), carried =
+ *             (0.25, 0, 0), turn the identity.  The box instead turns by pi/8 about y, c_q = (0, 0.19509, 0, 0.98079): t =
+ *             (0.92388, 1.51, -0.38268), turn = c_q.
+ *   Forgetting  bge_world_characters_create switches riding off and drops the records.  bge_world_set_topology clears every anchor.
+ *             bge_world_upload_bodies over entities [first, first + count) clears the anchors whose entity lies in that range
+ *             (bge_world_upload_bodies_indexed: the entities of its list, run by run of consecutive indices; a list of more than
+ *             16 runs is taken as the span from its lowest to its highest index): an entity index that gets a new body must not
+ *             carry anyone by the difference between two unrelated poses.  Both clears are enqueued on the world's stream.
+ *   Not done  a swept carry: Carry is a teleport, so a carry longer than a wall is thick passes through the wall; inherited
+ *             velocity; capsule characters; pushing Dynamic bodies.
+ *   bge_world_characters_ride     flags = BGE_CHAR_RIDE_ON, optionally | BGE_CHAR_RIDE_DYNAMIC; 0 switches riding off and drops the
+ *                                 records.  Unknown bits, DYNAMIC without ON, and ON with no character set are BGE_ERR_INVALID.
+ *                                 Switching on allocates the records and clears them (no anchor); calling it again while riding is
+ *                                 on changes only the flags and keeps the anchors.  With riding on an update call makes two more
+ *                                 launches (not two more per step); nothing is read back.
+ *   bge_world_characters_rides    out[0 .. count) = the records of characters first .. first + count.  Synchronises the world's
+ *                                 stream.  A range outside the set is BGE_ERR_INVALID, and so is any count > 0 while riding is off.
+ *   bge_world_characters_rides_device  the resident bge_character_ride[n] (NULL and 0 while riding is off), valid until the next
+ *                                 bge_world_characters_ride(0) or bge_world_characters_create; reads must be ordered after the
+ *                                 world's stream.
+ */
+enum bge_character_ride_mode { BGE_CHAR_RIDE_ON = 1u, BGE_CHAR_RIDE_DYNAMIC = 2u };
+enum bge_character_ride_flags { BGE_CHAR_RIDE_CARRIED = 1u, BGE_CHAR_RIDE_LOST = 2u };
+typedef struct bge_character_ride {
+    uint32_t flags;           /* bge_character_ride_flags of the last update call */
+    uint32_t entity;          /* the anchor: the body stood on when the last call ended; BGE_RAY_NO_ENTITY if none */
+    float anchor_position[3]; /* that body's pose as that call saw it */
+    float anchor_rotation[4]; /* xyzw */
+    float carried[3];         /* what Carry added to the position in the last call; 0 if nothing */
+    float turn[4];            /* xyzw: the body's rotation since the anchor, cur * conj(anchor); (0, 0, 0, 1) if nothing */
+} bge_character_ride; /* 64 bytes, 4-byte aligned, moved word by word like every character record */
+BGE_API int bge_world_characters_ride(bge_world* world, uint32_t flags);
+BGE_API int bge_world_characters_rides(bge_world* world, uint64_t first, uint64_t count, bge_character_ride* out);
+BGE_API int bge_world_characters_rides_device(bge_world* world, void** rides, uint64_t* n);
 
 /*
  * The physics debug overlay: what PhysicsSystem::GetDebugLines hands to the renderer while the overlay is on
