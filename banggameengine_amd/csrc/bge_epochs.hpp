@@ -1,5 +1,5 @@
 // bge_epochs.hpp — the two epochs the tick kernel's per-wave words (WorldView::rs_word) are compared with, and the bookkeeping of
-// the deferred translation row (Row3State, below) and of fused ticks (FuseClock, below).  Host-only, no HIP: tests/test_rest_epoch_cpu.py and tests/test_row3_epoch_cpu.py
+// the deferred translation row (Row3State, below), of fused ticks (FuseClock, below) and of solo groups (SoloPlan, below).  Host-only, no HIP: tests/test_rest_epoch_cpu.py and tests/test_row3_epoch_cpu.py
 // compile this header on its own.
 //   rows  what word 0 must equal for the translation-row path (TickParams::rs_epoch)
 //   rest  what word 1 must equal for the rest path (TickParams::rest_epoch)
@@ -82,6 +82,25 @@ struct FuseClock {
     }
     // Ticks in the group that begins at tick t of a call of `ticks`, for groups of at most T (T >= 1): the last takes the remainder
     static uint32_t group_size(uint32_t t, uint32_t ticks, uint32_t T) { return ticks - t < T ? ticks - t : T; }
+};
+
+// Solo groups (DESIGN.md §4.1 "Solo groups"): in a scene whose every tile is flat (bge_flatten.hpp TileShape::all_flat) no wave reads
+// what another wave writes during a tick, so a wave can run the ticks of a group one after the other inside ONE launch, and the
+// host launches once per group and needs no answer from the device.  The groups are FuseClock's (same cut, same T); no serial is
+// handed out and WorldView::adv is not touched.
+//   wanted  the call goes out in solo groups: it is fusable, the scene is all-flat, and BGE_SOLO_GROUPS allows it
+//   plan    tick i (0-based) of a group of n: does it launch, and with which TickParams::n_solo.  The first tick of a group of
+//           n > 1 launches with n_solo = n and the others launch nothing; a group of one, and every tick of a call that is not in
+//           solo groups, launches as a plain tick (n_solo = 0: the ordinary kernel).
+struct SoloPlan {
+    bool launch;
+    uint32_t n_solo;
+    static bool wanted(bool fusable, bool all_flat, bool enabled) { return fusable && all_flat && enabled; }
+    static SoloPlan plan(bool solo, uint32_t i, uint32_t n)
+    {
+        if (!solo || n <= 1u) return SoloPlan{true, 0u};
+        return i == 0u ? SoloPlan{true, n} : SoloPlan{false, 0u};
+    }
 };
 
 } // namespace bge

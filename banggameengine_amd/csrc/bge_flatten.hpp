@@ -83,6 +83,29 @@ struct Flattened {
     std::vector<uint32_t> pass_of_entity;   // [n_entities] (kNone for no-transform / limbo)
 };
 
+// A flat tile, by the tick kernel's own test (bge_kernels.hip, flat_tile): wave-local, max level 0, no frozen root, no external
+// parent.  No wave of such a tile reads anything another wave writes during a tick.
+inline bool hdr_is_flat(uint32_t hdr) { return (hdr & (kHdrWaveLocal | kHdrFrozen | kHdrExt | kHdrLevelMask)) == kHdrWaveLocal; }
+
+// What the host knows of a scene's shape from the tile headers of one pass, tiles [begin, end).  Recomputed wherever a header
+// changes (layout with its kHdrFrozen bits, kHdrAllDynamic in bge_world_upload_bodies).
+//   all_flat              the pass has a tile and every tile is flat: a wave can run several ticks on its own (solo groups)
+//   any_flat_all_dynamic  some flat tile has kHdrAllDynamic: only such a tile can hold a vouched wave
+struct TileShape {
+    bool all_flat = false, any_flat_all_dynamic = false;
+    static TileShape of(const uint32_t* hdr, uint32_t begin, uint32_t end)
+    {
+        TileShape s;
+        s.all_flat = end > begin;
+        for (uint32_t t = begin; t < end; ++t) {
+            const bool flat = hdr_is_flat(hdr[t]);
+            s.all_flat = s.all_flat && flat;
+            s.any_flat_all_dynamic = s.any_flat_all_dynamic || (flat && (hdr[t] & kHdrAllDynamic) != 0u);
+        }
+        return s;
+    }
+};
+
 // parent[i] == kNone or >= n means "no parent".  has_transform may be null (all true).
 void flatten_topology(uint64_t n, const uint32_t* parent, const uint8_t* has_transform, Flattened& out);
 

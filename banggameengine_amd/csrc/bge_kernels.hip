@@ -31,6 +31,9 @@
 //   With TickParams::serial (fused ticks) a vouched wave runs the n_left ticks that remain of its group of launches
 //   in registers, stores once and says so in WorldView::adv; the group's later launches return at once for it.  k_tick<PHYS, XFORM>
 //   only; BGE_FUSE_TICKS=1 turns it off.
+//   With TickParams::n_solo (solo groups) ONE launch of the SOLO instantiation stands for a whole group of ticks of a
+//   scene whose every tile is flat: a vouched wave as above, every other wave tick after tick by the ordinary path inside the
+//   launch.  BGE_SOLO_GROUPS=0 turns it off.
 //   Waves whose bodies are all asleep (rest word, WorldView::rs_word word 1) read flags, the deactivation record and the contact
 //   word, 8..12 B per body, and store nothing.
 //   The world matrices leave through LDS so that every wave-level store instruction writes 1 KiB of
@@ -171,10 +174,50 @@ template <bool IS_MIN> __device__ __forceinline__ float wave_reduce_to_lane63(fl
 #ifndef BGE_XFORM_MIN_WAVES
 #define BGE_XFORM_MIN_WAVES 8 /* the variants with the transform part and nothing else heavy (the headline kernel).  While parent * local was formed on whole matrices (48 registers) they needed 72 VGPRs — at 64 they spilled 12 B per lane, 8 B per entity of scratch writes that rocprofv3 WRITE_SIZE showed — and ran at 7 waves per SIMD; with the product formed a row at a time (lds_mul_put) they need 55 / 48 */
 #endif
-template <bool PHYS, bool XFORM, bool AABB, bool NORMAL, bool BASIS>
+// The ticks of a vouched wave in registers (fused ticks, solo groups): n ticks, each with the single tick's expressions — applyGravity,
+// the slow-lane ballot, integrateTransforms — in their order.  false: a lane turned slow in one of them, and nothing is to be stored.
+__device__ __forceinline__ bool fuse_ticks(const float4 gf, const TickParams& p, uint32_t n, F3& vn, F3& xn)
+{
+    for (uint32_t i = 0; i < n; ++i) {
+        vn = F3{vn.x + (gf.x * gf.w) * p.dt, vn.y + (gf.y * gf.w) * p.dt, vn.z + (gf.z * gf.w) * p.dt};
+        if (__ballot(!(fabsf(vn.y) >= p.sleep_lin)) != 0ull) return false;
+        xn = F3{xn.x + vn.x * p.dt, xn.y + vn.y * p.dt, xn.z + vn.z * p.dt};
+    }
+    return true;
+}
+
+// Solo groups: between two ticks of ONE wave inside a solo launch (k_tick<..., SOLO>).  false: that was the launch's last tick.
+// The wave has just stored a tick's results and is about to read and overwrite them as the next launch would.  Its lanes are
+// different threads to the memory model, and some of those accesses cross lanes:
+//   * the full write-out stores matrix rows of OTHER lanes' slots (through LDS, 16 B per lane); on a pinned world
+//     (defer_row3 == 0) the next tick's translation-row store writes the same 16 bytes from the slot's own lane;
+//   * lane 0 stores the words of the wave's record, and the reload below reads them with lanes 0..3;
+//   * the write-out reads the wave's part of the LDS image that the next tick's lds_put overwrites.
+// A workgroup-scope fence orders all of them: on gfx950 it is the wait for the wave's outstanding memory operations and nothing
+// else — no cache write-back, no invalidate (the waves of a workgroup share one L1).  Nothing here waits for another wave: every
+// wave of a flat tile depends on its own memory only.
+// The record comes back through a VECTOR load (a lane-dependent address, then readlane): the scalar cache is not coherent with
+// the wave's own vector stores, so the wave-uniform load of the launch's first tick must not be repeated.
+__device__ __forceinline__ bool solo_next(const WorldView& w, uint32_t tile, uint32_t wave, uint32_t tid, uint32_t& remaining, uint4& rec)
+{
+    if (--remaining == 0u) return false;
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+    const uint32_t word = w.rs_word[4u * (tile * 4u + wave) + (tid & 3u)];
+    rec = make_uint4(__builtin_amdgcn_readlane(word, 0), __builtin_amdgcn_readlane(word, 1), __builtin_amdgcn_readlane(word, 2), __builtin_amdgcn_readlane(word, 3));
+    return true;
+}
+
+// SOLO (solo groups, TickParams::n_solo): an instantiation of its own for k_tick<PHYS, XFORM> — nothing else pays
+// for its loop.  The host vouches that every tile of the launch is flat, so the block-tile branch with its workgroup barriers is
+// compiled out, and every wave runs the n_solo ticks itself: fused in registers where it is vouched, else one tick after the other
+// by the ordinary path, with solo_next() in between.
+#ifndef BGE_SOLO_MIN_WAVES
+#define BGE_SOLO_MIN_WAVES 4 /* the SOLO variant: with the loop over the ticks around the body it needs 96 VGPRs; compiled for 6 waves per SIMD it spills 11 VGPRs, for 8 it spills 66 — scratch traffic in every tick, against a launch whose cost is shared by a whole group of ticks */
+#endif
+template <bool PHYS, bool XFORM, bool AABB, bool NORMAL, bool BASIS, bool SOLO = false>
 // 8 waves per SIMD (<= 64 VGPRs): the kernel waits on memory and, in block tiles, on barriers; occupancy hides both
 // (the NORMAL variant carries a 4x4 inverse: it gets 128 VGPRs instead of spilling)
-__global__ void __launch_bounds__(kTile, NORMAL ? 4 : (AABB ? BGE_AABB_MIN_WAVES : (BASIS ? BGE_BASIS_MIN_WAVES : (XFORM ? BGE_XFORM_MIN_WAVES : 8)))) k_tick(WorldView w, TickParams p)
+__global__ void __launch_bounds__(kTile, SOLO ? BGE_SOLO_MIN_WAVES : NORMAL ? 4 : (AABB ? BGE_AABB_MIN_WAVES : (BASIS ? BGE_BASIS_MIN_WAVES : (XFORM ? BGE_XFORM_MIN_WAVES : 8)))) k_tick(WorldView w, TickParams p)
 {
     __shared__ float4 lds[kTile * 4];
     // BASIS: Bullet's orientation step (getRotation -> exponential map -> safeNormalize -> setRotation: four square roots, ten
@@ -200,9 +243,11 @@ __global__ void __launch_bounds__(kTile, NORMAL ? 4 : (AABB ? BGE_AABB_MIN_WAVES
     uint32_t eq_at = kEqNone; // this lane's queue entry
 
     const uint32_t tile = p.tile_begin + blockIdx.x;
-    const uint32_t tid = threadIdx.x;
-    const uint32_t slot = tile * kTile + tid;
-    const uint32_t hdr = w.tile_hdr[tile];
+    uint32_t tid = threadIdx.x; // (neither changes; SOLO hides both from the optimiser once per tick, below)
+    uint32_t slot = tile * kTile + tid;
+    static_assert(!SOLO || (PHYS && XFORM && !AABB && !NORMAL && !BASIS), "solo groups exist for k_tick<PHYS, XFORM> alone");
+    // (SOLO: the host vouches that the tile is flat — bge_flatten.hpp hdr_is_flat — and the compiler may know it)
+    const uint32_t hdr = SOLO ? ((w.tile_hdr[tile] & ~(kHdrFrozen | kHdrExt | kHdrLevelMask)) | kHdrWaveLocal) : w.tile_hdr[tile];
     const uint32_t count = (hdr >> kHdrCountShift) & kHdrCountMask;
     const uint32_t max_level = hdr & kHdrLevelMask;
 
@@ -214,7 +259,7 @@ __global__ void __launch_bounds__(kTile, NORMAL ? 4 : (AABB ? BGE_AABB_MIN_WAVES
     constexpr bool kRowsPath = XFORM && !AABB && !NORMAL && !BASIS;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     // The wave's record {rows word, rest word, flag value, flag epoch} (WorldView::rs_word) in one wave-uniform 16-B load.
-    const uint4 rec = (kRowsPath && (p.rs_epoch | p.rest_epoch) != 0u) ? reinterpret_cast<const uint4*>(w.rs_word)[tile * 4u + wave] : make_uint4(0u, 0u, 0u, 0u);
+    uint4 rec = (kRowsPath && (p.rs_epoch | p.rest_epoch) != 0u) ? reinterpret_cast<const uint4*>(w.rs_word)[tile * 4u + wave] : make_uint4(0u, 0u, 0u, 0u);
     // Fused ticks (WorldView::adv, TickParams::serial / n_left; DESIGN.md §4.1 "Fused ticks"): the wave's state in memory is already
     // the state after the tick with serial adv — an earlier launch of this group ran the ticks up to it in registers — so a launch
     // whose serial is not beyond it has nothing to do.  Wave-uniform, nothing stored; only a flat wave-local tile can have set the
@@ -227,6 +272,39 @@ __global__ void __launch_bounds__(kTile, NORMAL ? 4 : (AABB ? BGE_AABB_MIN_WAVES
     if (kFuse && p.serial != 0u) {
         if (w.adv[tile * 4u + wave] >= p.serial && (hdr & kHdrWaveLocal) != 0u) return;
     }
+    // Solo groups: the ticks this launch still owes the wave, and whether the fused block below is worth a try (not in the first
+    // tick by the ordinary path: the first attempt has just declined).
+    [[maybe_unused]] uint32_t remaining = SOLO ? p.n_solo : 1u;
+    [[maybe_unused]] bool solo_retry = false;
+    if constexpr (SOLO) {
+        // First attempt: the vouched test and the fused block of the ordinary code below, for all n_solo ticks, BEFORE any store of
+        // the launch — so that header, record and palette entry come through scalar loads, as in a group's first launch (inside
+        // the loop, behind the wave's own stores, the same loads are vector loads).  The headline's path: one store, and out.
+        if (p.rs_epoch != 0u && rec.x == p.rs_epoch && !(p.rest_epoch != 0u && rec.y == p.rest_epoch) && p.flag_word != 0u && rec.w == p.rs_epoch &&
+            (hdr & kHdrAllDynamic) && p.cinfo_in == nullptr) {
+            const float4 gf = w.grav_palette[rec.z >> kMassShift];
+            if (gf.w != 0.0f) {
+                F3 x0 = ld3(w.pos, slot);
+                const F3 v = ld_vel(w.vel, slot);
+                asm volatile("" : "+v"(x0.x), "+v"(x0.y), "+v"(x0.z)); // (as below: both loads leave together)
+                F3 vn = v, xn = x0;
+                // (Expected, and with a mark of its own behind the stores: left to itself the compiler shares these stores with the fused
+                //  block inside the loop, in one exit block laid out behind the loop, and the twelve values then count as live across
+                //  all of it — spills on this very path.)
+                if (__builtin_expect(fuse_ticks(gf, p, remaining, vn, xn), 1)) {
+                    st_vel_if(w.vel, slot, vn, vel_xz_changed(vn, v), vel_y_changed(vn, v));
+                    st3(w.pos, slot, xn);
+                    if (p.defer_row3 == 0u) reinterpret_cast<float4*>(w.world)[4ull * slot + 3u] = make_float4(xn.x, xn.y, xn.z, 1.0f);
+                    asm volatile("; solo group: fused at the first attempt");
+                    return;
+                }
+            }
+        }
+    }
+solo_tick:; // (SOLO alone jumps here: the next tick of the launch, `rec` reloaded by solo_next)
+    // (Opaque per tick: otherwise every address a tick forms from the lane's slot is hoisted out of the loop over the ticks and
+    //  stays live across it — the variant then wants more than 128 VGPRs and spills on the first attempt's way out.)
+    if constexpr (SOLO) asm volatile("" : "+v"(slot), "+v"(tid));
     const uint32_t rs_old = p.rs_epoch != 0u ? rec.x : 0u;
     // (header: wave-local, max level 0, no frozen root, no external parent)
     const bool flat_tile = kRowsPath && (hdr & (kHdrWaveLocal | kHdrFrozen | kHdrExt | kHdrLevelMask)) == kHdrWaveLocal;
@@ -262,6 +340,8 @@ __global__ void __launch_bounds__(kTile, NORMAL ? 4 : (AABB ? BGE_AABB_MIN_WAVES
         } else {
             moved = PHYS && type_r != 0u; // an orphaned body is stepped: never on this path
         }
+        // (SOLO: the wave leaves the launch with ticks still owed.  Nothing but the wave itself writes its memory between its ticks
+        //  and this exit stores nothing, so every tick that remains would read the same words and leave by the same exit.)
         if (__ballot(moved) == 0ull) return;
     } else {
         // Vouched wave (WorldView::rs_word words 2 and 3, DESIGN.md §4.1 "flag word"): flag epoch == p.rs_epoch means that every one
@@ -285,7 +365,7 @@ __global__ void __launch_bounds__(kTile, NORMAL ? 4 : (AABB ? BGE_AABB_MIN_WAVES
                 // single tick's expressions and its ballot, and touches memory once.  It decides before any store: if a lane turns slow
                 // in any of the ticks, nothing is stored and the wave goes on as a launch with n_left = 1 does (below); the launches
                 // that follow in the group give it the same chance again with what is left.
-                if (kFuse && p.serial != 0u && p.n_left > 1u) {
+                if (kFuse && p.serial != 0u && p.n_left > 1u && !SOLO) {
                     F3 vn = v, xn = x0;
                     bool all_fast = true;
                     for (uint32_t i = 0; i < p.n_left; ++i) {
@@ -304,6 +384,19 @@ __global__ void __launch_bounds__(kTile, NORMAL ? 4 : (AABB ? BGE_AABB_MIN_WAVES
                         return;
                     }
                 }
+                // Solo groups: the same for the ticks the launch still owes the wave (fuse_ticks is this very loop), and no word to set —
+                // the wave's launch ends with it.
+                if constexpr (SOLO) {
+                    if (solo_retry && remaining > 1u) {
+                        F3 vn = v, xn = x0;
+                        if (fuse_ticks(gf, p, remaining, vn, xn)) {
+                            st_vel_if(w.vel, slot, vn, vel_xz_changed(vn, v), vel_y_changed(vn, v));
+                            st3(w.pos, slot, xn);
+                            if (p.defer_row3 == 0u) reinterpret_cast<float4*>(w.world)[4ull * slot + 3u] = make_float4(xn.x, xn.y, xn.z, 1.0f);
+                            return;
+                        }
+                    }
+                }
                 // (the expressions of applyGravity and integrateTransforms below, in their order)
                 const F3 v1{v.x + (gf.x * gf.w) * p.dt, v.y + (gf.y * gf.w) * p.dt, v.z + (gf.z * gf.w) * p.dt};
                 if (__ballot(!(fabsf(v1.y) >= p.sleep_lin)) == 0ull) {
@@ -312,6 +405,12 @@ __global__ void __launch_bounds__(kTile, NORMAL ? 4 : (AABB ? BGE_AABB_MIN_WAVES
                     st3(w.pos, slot, x1);
                     // (deferred: the row is (x1, 1) of the position just stored; readers compose it, k_row3_sync stores it — DESIGN.md §4.1)
                     if (p.defer_row3 == 0u) reinterpret_cast<float4*>(w.world)[4ull * slot + 3u] = make_float4(x1.x, x1.y, x1.z, 1.0f);
+                    if constexpr (SOLO) {
+                        if (solo_next(w, tile, wave, tid, remaining, rec)) {
+                            solo_retry = true;
+                            goto solo_tick;
+                        }
+                    }
                     return;
                 }
             }
@@ -808,6 +907,12 @@ __global__ void __launch_bounds__(kTile, NORMAL ? 4 : (AABB ? BGE_AABB_MIN_WAVES
     }
 
     if (f != f0) w.flags[slot] = f;
+    if constexpr (SOLO) {
+        if (solo_next(w, tile, wave, tid, remaining, rec)) {
+            solo_retry = true;
+            goto solo_tick;
+        }
+    }
 }
 
 // PhysicsSystem::Update with a stepSimulation that runs no sub-step (Bullet's accumulator, src/physics/PhysicsSystem.cpp:855-863:
@@ -1224,6 +1329,12 @@ hipError_t launch_tick(hipStream_t stream, const WorldView& w, const TickParams&
     const bool phys = (flags & 1u) != 0, xform = (flags & 2u) != 0, aabb = (flags & (4u | 32u)) != 0, normal = (flags & 16u) != 0;
     const dim3 grid(n_tiles), block(kTile);
     const bool basis = phys && (flags & 64u) != 0;
+    if (p.n_solo > 1u) {
+        // a solo group: the variant exists for the physics + transform tick alone, and a launch that asks for another is an error
+        if (!(phys && xform) || aabb || normal || basis || p.serial != 0u || p.n_left != 1u) return hipErrorInvalidValue;
+        hipLaunchKernelGGL((k_tick<true, true, false, false, false, true>), grid, block, 0, stream, w, p);
+        return hipGetLastError();
+    }
 #define BGE_LAUNCH(P, X, A, N)                                                                      \
     do {                                                                                            \
         if (basis) hipLaunchKernelGGL((k_tick<P, X, A, N, P>), grid, block, 0, stream, w, p);       \

@@ -239,6 +239,10 @@ struct TickParams {
                         // serials; a wave whose WorldView::adv is not below it returns at once, and a vouched wave runs n_left ticks in
                         // registers and sets adv = serial + n_left - 1.  0: off, adv is neither loaded nor compared nor written
     uint32_t n_left;    // with serial != 0: the ticks from this launch to the end of its group, this one included (>= 1)
+    uint32_t n_solo;    // solo groups (bge_epochs.hpp SoloPlan): > 1: this ONE launch stands for n_solo consecutive ticks; the host vouches
+                        // that every tile of the launch is flat, and launch_tick picks the solo variant of k_tick<PHYS, XFORM>, in which
+                        // every wave runs the ticks itself, one after the other.  serial = 0 and n_left = 1 with it.  0 or 1: a plain tick.
+                        // BGE_SOLO_GROUPS=0 keeps it 0
 };
 
 // flags: bit0 physics, bit1 transforms, bit2 / bit5 aabb, bit4 normal matrices (bge_tick_flags)

@@ -201,6 +201,11 @@ struct bge_world {
     std::vector<uint32_t> parent_entity; // entity-level parents (Scene::m_parents) as of the last set_topology
     DevBuf frozen;                       // WorldView::frozen (allocated with the first frozen root)
     bool any_frozen = false;
+    bge::TileShape shape;                // of the first pass's tile headers; refresh_shape() wherever a header changes
+    void refresh_shape()
+    {
+        shape = flat.pass_tile_begin.size() < 2 ? bge::TileShape{} : bge::TileShape::of(flat.tile_hdr.data(), flat.pass_tile_begin[0], flat.pass_tile_begin[1]);
+    }
     std::vector<uint8_t> body_type_host; // bge_body_type per entity index as last uploaded (BGE_BODY_NONE = no body)
     std::vector<uint8_t> orphan_host;    // 1: the entity lost its Transform while it had a body; the body kept its slot (kValid clear)
     // A body exists in the reference's world from the first PhysicsSystem::Update that sees its components AND a Transform
@@ -667,6 +672,7 @@ int make_store(bge_world* w, SlotBuf& a, bool synced = false)
 namespace {
 constexpr uint32_t kTriggerPairCap = 1u << 20;
 constexpr uint32_t kFuseTicksDefault = 8; // ticks per fused group of a bge_world_tick_many call (BGE_FUSE_TICKS; DESIGN.md §4.1 "Fused ticks": measured)
+constexpr uint32_t kSoloTicksDefault = 64; // ticks per solo group, where BGE_FUSE_TICKS is unset (DESIGN.md §4.1 "Solo groups": measured, the largest size tried)
 constexpr double kNtThresholdBytes = 300.0e6; // measured crossover between 2 M (plain wins) and 4 M slots (nt wins)
 
 // device mirrors of the trigger set (slots follow the current topology)
@@ -1607,6 +1613,7 @@ try {
     if (int rc = w->draw_keys.follow_topology(n, w->flat.n_entities, w->stream)) return rc;
     w->any_frozen = any_frozen;
     w->flat = std::move(nf);
+    w->refresh_shape();
     w->orphan_host.swap(orphan);
     w->body_type_host.resize(n, BGE_BODY_NONE); // surviving indices keep their body, new ones have none
     for (uint64_t i = 0; i < n; ++i) {
@@ -1765,6 +1772,7 @@ static int upload_bodies(bge_world* w, uint64_t first, uint64_t count, const uin
             }
         }
         if (changed) {
+            w->refresh_shape();
             HIP_TRY(hipStreamSynchronize(w->stream));
             HIP_TRY(hipMemcpy(w->tile_hdr.p, w->flat.tile_hdr.data(), static_cast<size_t>(w->flat.n_tiles_total) * 4, hipMemcpyHostToDevice));
         }
@@ -2076,8 +2084,19 @@ int tick_impl(bge_world* w, uint32_t ticks, float dt, const float gravity[3], ui
     // If a launch fails in the middle of a group, some waves are ahead of others: the error is returned as ever, and the world is
     // not usable after a failed tick call (include/bge_world.h).
     uint32_t fuse_T = kFuseTicksDefault;
-    if (const char* e = std::getenv("BGE_FUSE_TICKS")) fuse_T = static_cast<uint32_t>(std::max(1, std::atoi(e)));
-    const bool fusable = phys && rows_path && flag_word && w->flat.pass_tile_begin.size() - 1 == 1 && !w->any_frozen && w->profiling != 2;
+    const char* const fuse_env = std::getenv("BGE_FUSE_TICKS");
+    if (fuse_env) fuse_T = static_cast<uint32_t>(std::max(1, std::atoi(fuse_env)));
+    // (only a flat all-Dynamic tile can hold a vouched wave: without one, no launch loads a word that can never be set)
+    const bool fusable = phys && rows_path && flag_word && w->flat.pass_tile_begin.size() - 1 == 1 && !w->any_frozen && w->profiling != 2 && w->shape.any_flat_all_dynamic;
+    // Solo groups (bge_epochs.hpp SoloPlan, TickParams::n_solo): where every tile is flat, the first tick of a group launches ONE
+    // kernel in which every wave runs the group's ticks itself — fused in registers where it is vouched, one after the other by the
+    // ordinary path where it is not — and the group's other ticks launch nothing.  They still do all of this loop's bookkeeping.
+    // No serial, no adv.  BGE_SOLO_GROUPS=0 turns it off (A/B runs): round 9's scheme, one launch per tick.  Every fusable scene
+    // that is not all-flat keeps that scheme.
+    bool solo_env = true;
+    if (const char* e = std::getenv("BGE_SOLO_GROUPS")) solo_env = std::atoi(e) != 0;
+    const bool solo = bge::SoloPlan::wanted(fusable, w->shape.all_flat, solo_env);
+    if (solo && !fuse_env) fuse_T = kSoloTicksDefault; // (a solo group costs one launch whatever its size: its default is its own)
     uint32_t group_first = 0, group_t0 = 0, group_n = 0; // the group tick t belongs to: its first serial, its first tick, its size
     for (uint32_t t = 0; t < ticks; ++t) {
         if (!phys && !w->maybe_dirty && !(flags & BGE_TICK_NORMAL_MATRICES)) {
@@ -2102,13 +2121,15 @@ int tick_impl(bge_world* w, uint32_t ticks, float dt, const float gravity[3], ui
             group_t0 = t;
             group_n = bge::FuseClock::group_size(t, ticks, fuse_T);
             bool wrapped = false;
-            group_first = w->fuse.begin_group(group_n, &wrapped);
+            if (!solo) group_first = w->fuse.begin_group(group_n, &wrapped); // (a solo group carries no serial)
             if (wrapped) HIP_TRY(hipMemsetAsync(w->adv.p, 0, w->adv.bytes, w->stream));
         }
         // (a group of one tick has nothing to fuse: it goes out as every tick did, and no word is loaded)
-        const bool fused = fusable && fuse_T > 1u && group_n > 1u;
+        const bool fused = fusable && fuse_T > 1u && group_n > 1u && !solo;
         p.serial = fused ? group_first + (t - group_t0) : 0u;
         p.n_left = fused ? group_n - (t - group_t0) : 1u;
+        const bge::SoloPlan plan = bge::SoloPlan::plan(solo && fuse_T > 1u, t - group_t0, group_n);
+        p.n_solo = plan.n_solo;
         // (a tick without the translation-row path may write pos or world from any of its kernels, and moves the rows epoch)
         if (!rows_path) HIP_TRY(w->ensure_row3_current());
         if (rows_path) p.rs_epoch = w->epochs.rows;
@@ -2165,7 +2186,7 @@ int tick_impl(bge_world* w, uint32_t ticks, float dt, const float gravity[3], ui
             }
             HIP_TRY(hipEventRecord(w->prof_events[w->prof_used], w->stream));
         }
-        for (size_t pass = 0; pass < n_passes; ++pass) {
+        for (size_t pass = 0; pass < n_passes && plan.launch; ++pass) { // (a later tick of a solo group: its work is in the group's launch)
             p.tile_begin = w->flat.pass_tile_begin[pass];
             const uint32_t n_tiles = w->flat.pass_tile_begin[pass + 1] - p.tile_begin;
             HIP_TRY(bge::launch_tick(w->stream, w->view, p, n_tiles, flags));

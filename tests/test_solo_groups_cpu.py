@@ -1,0 +1,64 @@
+"""The host side of solo groups (DESIGN.md §4.1 "Solo groups"), without a GPU.
+
+* A stand-alone C++ program (tests/cpp/solo_groups.cpp), built with ASan + UBSan, drives the tile summary (csrc/bge_flatten.hpp
+  TileShape: all flat, one chain tile, one frozen tile, one tile with an external parent, no tile, no all-Dynamic tile) and the
+  schedule (csrc/bge_epochs.hpp SoloPlan on FuseClock's groups: K in 1..9, 17, 1000, T in 1, 2, 3, 8, 32; every tick covered exactly
+  once, a group of one launched as a plain tick, the switch off giving round 9's plan).
+* bge_world.cpp takes both from those headers and states neither inline; a launch with n_solo > 1 picks the SOLO instantiation of
+  k_tick<PHYS, XFORM> and nothing else does."""
+import os
+import re
+import subprocess
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "banggameengine_amd", "csrc")
+
+
+def test_solo_groups_program(tmp_path):
+    exe = str(tmp_path / "solo_groups")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                           "-I", CSRC, "-o", exe, os.path.join(ROOT, "tests", "cpp", "solo_groups.cpp")])
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "solo_groups ok" in r.stdout
+
+
+def _tick_impl(src):
+    m = re.search(r"^int tick_impl\([^;{]*\)\s*\{(.*?)^\}", src, re.S | re.M)
+    assert m
+    return m.group(1)
+
+
+def test_tick_impl_takes_shape_and_schedule_from_the_headers():
+    src = open(os.path.join(CSRC, "bge_world.cpp")).read()
+    tick = _tick_impl(src)
+    # the shape is computed in one place and refreshed wherever a header changes: layout (kHdrFrozen with it) and kHdrAllDynamic
+    assert src.count("bge::TileShape::of(") == 1 and "TileShape::of(" not in tick
+    assert src.count("refresh_shape();") >= 2
+    # tick_impl: solo = SoloPlan::wanted(fusable, all_flat, switch); the plan decides n_solo and whether the tick launches
+    m = re.search(r"const bool fusable = ([^;]*);", tick)
+    assert m and "w->shape.any_flat_all_dynamic" in [t.strip() for t in m.group(1).split("&&")]
+    assert re.search(r"const bool solo = bge::SoloPlan::wanted\(fusable, w->shape\.all_flat, solo_env\);", tick)
+    assert 'std::getenv("BGE_SOLO_GROUPS")' in tick  # read per call
+    assert tick.count("bge::SoloPlan::plan(") == 1
+    assert len(re.findall(r"\.n_solo\s*=[^=]", src)) == 1 and "p.n_solo = plan.n_solo;" in tick
+    assert re.search(r"for \(size_t pass = 0; pass < n_passes && plan\.launch; \+\+pass\)", tick)
+    # a solo group carries no serial, and a fused launch is never a solo one
+    assert "if (!solo) group_first = w->fuse.begin_group(group_n, &wrapped);" in tick
+    m = re.search(r"const bool fused = ([^;]*);", tick)
+    assert m and "!solo" in [t.strip() for t in m.group(1).split("&&")]
+
+
+def test_only_a_solo_launch_runs_the_solo_instantiation():
+    text = open(os.path.join(CSRC, "bge_kernels.hip")).read()
+    assert "template <bool PHYS, bool XFORM, bool AABB, bool NORMAL, bool BASIS, bool SOLO = false>" in text
+    assert 'static_assert(!SOLO || (PHYS && XFORM && !AABB && !NORMAL && !BASIS)' in text
+    launches = re.findall(r"k_tick<([^>]*)>\)", text)
+    solo = [l for l in launches if len(l.split(",")) == 6]
+    assert solo == ["true, true, false, false, false, true"], launches
+    m = re.search(r"if \(p\.n_solo > 1u\) \{(.*?)\n    \}", text, re.S)
+    assert m and "k_tick<true, true, false, false, false, true>" in m.group(1) and "return hipErrorInvalidValue;" in m.group(1)
+    # between two ticks of a wave: a workgroup-scope fence and nothing wider, no barrier
+    m = re.search(r"__device__ __forceinline__ bool solo_next\(.*?\n\}", text, re.S)
+    assert m and '__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup")' in m.group(0)
+    assert "__syncthreads" not in m.group(0) and '"agent"' not in m.group(0)

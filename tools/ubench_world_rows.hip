@@ -17,6 +17,8 @@
 //      stores pos, vel.y and the per-wave word adv = serial + n_ticks - 1 ("memory holds the state after tick adv")
 //   k  a follow-up launch of a group that (j) began: the wave loads its record and adv, finds adv >= serial and returns
 //      sequences "(j), then T - 1 x (k)" for T in {2, 4, 8} are timed per launch (= per tick) between runs of T x (i)
+//      solo sequences "(j) alone with n_ticks = T, once per T ticks" for T in {8, 16, 32, 64} (solo groups, DESIGN.md §4.1: no
+//      follow-up launch at all), timed per TICK, alternated three times with "(j), then 7 x (k)" (UBENCH_SOLO_ONLY)
 // Each kernel runs `reps` times back to back between two events after a warm-up; one JSON line per (kernel, store
 // policy, size).  Built by tools/ubench_world_rows.sh; no part of the product library.
 #include <hip/hip_runtime.h>
@@ -351,6 +353,36 @@ void run_fused(uint32_t n, int reps, Soa s, const uint4* words, uint32_t* adv, f
     CK(hipDeviceSynchronize());
 }
 
+// Solo groups: "(j) alone with n_ticks = T, once per T ticks" against round 9's "(j), then 7 x (k)", three times over and a fourth
+// round-9 run: the spread of the four jk_fused_T8 lines is the yardstick.  One launch of a solo sequence stands for T ticks, so its
+// line is the time per launch divided by T; `reps` launches of either kind are timed (whole groups of 8 for the round-9 sequence).
+void run_solo(uint32_t n, int reps, Soa s, const uint4* words, uint32_t* adv, float sleep_lin)
+{
+    const int warm = 24;
+    reps = (reps + 7) / 8 * 8;
+    const dim3 blk(kBlock), g_slot(n / kBlock);
+    uint32_t serial = 1;
+    for (int round = 0; round < 4; ++round) {
+        {
+            FusedSeq seq{s, words, adv, n, 8u, serial, 0u, sleep_lin};
+            report("jk_fused_T8", false, n, time_us([&] { seq(); }, warm, reps), 40.3125 / 8);
+            serial = seq.serial;
+        }
+        if (round == 3) break;
+        for (uint32_t T : {8u, 16u, 32u, 64u}) {
+            char name[32];
+            std::snprintf(name, sizeof name, "j_solo_T%u", T);
+            const float us = time_us([&] {
+                k_flat_fused<<<g_slot, blk>>>(s, words, adv, kEpoch, serial, T, 1.0f / 60.0f, sleep_lin);
+                serial += T;
+            }, warm, reps);
+            report(name, false, n, us / static_cast<float>(T), 40.3125 / T);
+        }
+    }
+    CK(hipGetLastError());
+    CK(hipDeviceSynchronize());
+}
+
 template <bool NT> void run_size(uint32_t n, int reps, Soa s, const uint4* words, float zero)
 {
     const int warm = 20;
@@ -389,7 +421,7 @@ template <bool NT> void run_size(uint32_t n, int reps, Soa s, const uint4* words
 
 // usage: ubench_world_rows [slots ...]   (default 1048576 16777216; rounded up to whole 256-slot blocks)
 //        env UBENCH_REPS: timed launches per kernel (default 200); UBENCH_GXZ: x and z gravity of kernel (g) (default 0);
-//        UBENCH_FUSED_ONLY: time (i), (j), (k) alone; UBENCH_SLEEP_LIN: the sleep threshold of (j) (default 0: every ballot passes)
+//        UBENCH_FUSED_ONLY: time (i), (j), (k) alone; UBENCH_SOLO_ONLY: the solo sequences against "(j), then 7 x (k)" alone; UBENCH_SLEEP_LIN: the sleep threshold of (j) (default 0: every ballot passes)
 int main(int argc, char** argv)
 {
     std::vector<uint32_t> sizes;
@@ -425,11 +457,15 @@ int main(int argc, char** argv)
         CK(hipMalloc(&adv, 4ull * wr.size()));
         CK(hipMemset(adv, 0, 4ull * wr.size()));
         const float sleep_lin = std::getenv("UBENCH_SLEEP_LIN") ? static_cast<float>(std::atof(std::getenv("UBENCH_SLEEP_LIN"))) : 0.0f;
-        if (!fused_only) {
-            run_size<false>(n, reps, s, words, zero);
-            run_size<true>(n, reps, s, words, zero);
+        if (std::getenv("UBENCH_SOLO_ONLY")) {
+            run_solo(n, reps, s, words, adv, sleep_lin);
+        } else {
+            if (!fused_only) {
+                run_size<false>(n, reps, s, words, zero);
+                run_size<true>(n, reps, s, words, zero);
+            }
+            run_fused(n, reps, s, words, adv, sleep_lin);
         }
-        run_fused(n, reps, s, words, adv, sleep_lin);
         CK(hipFree(adv));
         CK(hipFree(words));
         CK(hipFree(s.flags));
