@@ -43,6 +43,7 @@
 
 #include "bge_device_math.hpp"
 #include "bge_flatten.hpp"
+#include "bge_fuse_math.hpp"
 #include "bge_kernels.hpp"
 
 namespace bge {
@@ -176,14 +177,27 @@ template <bool IS_MIN> __device__ __forceinline__ float wave_reduce_to_lane63(fl
 #endif
 // The ticks of a vouched wave in registers (fused ticks, solo groups): n ticks, each with the single tick's expressions — applyGravity,
 // the slow-lane ballot, integrateTransforms — in their order.  false: a lane turned slow in one of them, and nothing is to be stored.
+// The arithmetic is bge_fuse_math.hpp's (fuse::fuse_ticks; fuse::fuse_ticks_exact is that very loop, and what a wave falls back
+// to): x and z velocity are a fixed point from the second tick on wherever gravity has no x or z part, and v.y is
+// monotone, so the loop carries four adds and a product per tick and the ballot is decided from v.y's first and last value.
+// The wave here is the hardware's: a lane value is a float, "any lane" a ballot.
+struct WaveLanes {
+    static __device__ __forceinline__ bool any(bool m) { return __ballot(m) != 0ull; }
+    static __device__ __forceinline__ float abs(float v) { return fabsf(v); }
+    static __device__ __forceinline__ bool same_bits(float a, float b) { return __float_as_uint(a) == __float_as_uint(b); }
+};
 __device__ __forceinline__ bool fuse_ticks(const float4 gf, const TickParams& p, uint32_t n, F3& vn, F3& xn)
 {
-    for (uint32_t i = 0; i < n; ++i) {
-        vn = F3{vn.x + (gf.x * gf.w) * p.dt, vn.y + (gf.y * gf.w) * p.dt, vn.z + (gf.z * gf.w) * p.dt};
-        if (__ballot(!(fabsf(vn.y) >= p.sleep_lin)) != 0ull) return false;
-        xn = F3{xn.x + vn.x * p.dt, xn.y + vn.y * p.dt, xn.z + vn.z * p.dt};
-    }
-    return true;
+    const fuse::Step c{(gf.x * gf.w) * p.dt, (gf.y * gf.w) * p.dt, (gf.z * gf.w) * p.dt, p.dt, p.sleep_lin};
+    return fuse::fuse_ticks<WaveLanes>(c, n, vn, xn);
+}
+// The exact loop alone, for SOLO's retry inside its loop over the ticks: the reduced loop there keeps two more lane values live
+// across the whole tick body, 98 VGPRs where the variant has 96 — an occupancy step (5 -> 4 waves per SIMD) for every wave of the
+// launch, to save instructions for the rare wave whose first attempt declined (DESIGN.md §4.1 "Lean fusion").
+__device__ __forceinline__ bool fuse_ticks_exact(const float4 gf, const TickParams& p, uint32_t n, F3& vn, F3& xn)
+{
+    const fuse::Step c{(gf.x * gf.w) * p.dt, (gf.y * gf.w) * p.dt, (gf.z * gf.w) * p.dt, p.dt, p.sleep_lin};
+    return fuse::fuse_ticks_exact<WaveLanes>(c, n, vn, xn);
 }
 
 // Solo groups: between two ticks of ONE wave inside a solo launch (k_tick<..., SOLO>).  false: that was the launch's last tick.
@@ -367,6 +381,10 @@ solo_tick:; // (SOLO alone jumps here: the next tick of the launch, `rec` reload
                 // that follow in the group give it the same chance again with what is left.
                 if (kFuse && p.serial != 0u && p.n_left > 1u && !SOLO) {
                     F3 vn = v, xn = x0;
+                    // (The exact loop, written out as round 9 left it and not taken from bge_fuse_math.hpp: this kernel also runs every call
+                    //  of ONE tick and every hierarchy scene.  With the reduced loop here its ISA was no longer the parent's and a call of one
+                    //  tick measured 2 % slower, depth-4 chains 0.9 %; the exact loop through the header changes the ISA as well.  As it
+                    //  stands the kernel is the parent's, instruction for instruction.  DESIGN.md §4.1 "Lean fusion".)
                     bool all_fast = true;
                     for (uint32_t i = 0; i < p.n_left; ++i) {
                         vn = F3{vn.x + (gf.x * gf.w) * p.dt, vn.y + (gf.y * gf.w) * p.dt, vn.z + (gf.z * gf.w) * p.dt};
@@ -384,12 +402,12 @@ solo_tick:; // (SOLO alone jumps here: the next tick of the launch, `rec` reload
                         return;
                     }
                 }
-                // Solo groups: the same for the ticks the launch still owes the wave (fuse_ticks is this very loop), and no word to set —
+                // Solo groups: the same for the ticks the launch still owes the wave (by the exact loop: see fuse_ticks_exact), and no word to set —
                 // the wave's launch ends with it.
                 if constexpr (SOLO) {
                     if (solo_retry && remaining > 1u) {
                         F3 vn = v, xn = x0;
-                        if (fuse_ticks(gf, p, remaining, vn, xn)) {
+                        if (fuse_ticks_exact(gf, p, remaining, vn, xn)) {
                             st_vel_if(w.vel, slot, vn, vel_xz_changed(vn, v), vel_y_changed(vn, v));
                             st3(w.pos, slot, xn);
                             if (p.defer_row3 == 0u) reinterpret_cast<float4*>(w.world)[4ull * slot + 3u] = make_float4(xn.x, xn.y, xn.z, 1.0f);

@@ -672,7 +672,7 @@ int make_store(bge_world* w, SlotBuf& a, bool synced = false)
 namespace {
 constexpr uint32_t kTriggerPairCap = 1u << 20;
 constexpr uint32_t kFuseTicksDefault = 8; // ticks per fused group of a bge_world_tick_many call (BGE_FUSE_TICKS; DESIGN.md §4.1 "Fused ticks": measured)
-constexpr uint32_t kSoloTicksDefault = 64; // ticks per solo group, where BGE_FUSE_TICKS is unset (DESIGN.md §4.1 "Solo groups": measured, the largest size tried)
+constexpr uint32_t kSoloTicksDefault = 512; // ticks per solo group, where BGE_FUSE_TICKS is unset (DESIGN.md §4.1 "Lean fusion": measured again with the reduced loop — the smallest of 64 .. 1024 whose median lies within the parent's spread of the best)
 constexpr double kNtThresholdBytes = 300.0e6; // measured crossover between 2 M (plain wins) and 4 M slots (nt wins)
 
 // device mirrors of the trigger set (slots follow the current topology)

@@ -212,7 +212,7 @@ BGE_API int bge_world_tick(bge_world* world, float dt, const float gravity[3], u
  * stream, groups never span calls, and an event pair per tick (bge_world_profile_enable(2)) switches the grouping off.
  * Solo groups: where EVERY tile of the scene is flat (no hierarchy at all, no frozen root), a group is ONE launch in which every
  * wave runs the group's ticks itself, one after the other, and the group's other ticks launch nothing; they still count as ticks
- * everywhere (bge_world_profile_read, the bodies' birth rule).  The default group is then 64 ticks (BGE_FUSE_TICKS sets it for both
+ * everywhere (bge_world_profile_read, the bodies' birth rule).  The default group is then 512 ticks (BGE_FUSE_TICKS sets it for both
  * schemes).  BGE_SOLO_GROUPS=0 (environment, read per call; default on) keeps one launch per tick.
  * If a launch of the call fails, bodies may be left at different ticks: the world is not usable after a failed tick call.
  */

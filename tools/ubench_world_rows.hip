@@ -19,6 +19,10 @@
 //      sequences "(j), then T - 1 x (k)" for T in {2, 4, 8} are timed per launch (= per tick) between runs of T x (i)
 //      solo sequences "(j) alone with n_ticks = T, once per T ticks" for T in {8, 16, 32, 64} (solo groups, DESIGN.md §4.1: no
 //      follow-up launch at all), timed per TICK, alternated three times with "(j), then 7 x (k)" (UBENCH_SOLO_ONLY)
+//   l  as j with the reduced loop of csrc/bge_fuse_math.hpp (fuse::fuse_ticks: x and z velocity a fixed point, the ballot decided
+//      from v.y's first and last value), in two forms: (l) is the product's function (the compiler packs the adds and unrolls), (l1) keeps the v.y
+//      add a single instruction.  "(l) alone with n_ticks = T, once per T ticks" against the same with (j) for T in {64, 256, 1024}, timed per
+//      LAUNCH and per tick, alternated three times (UBENCH_LEAN_ONLY)
 // Each kernel runs `reps` times back to back between two events after a warm-up; one JSON line per (kernel, store
 // policy, size).  Built by tools/ubench_world_rows.sh; no part of the product library.
 #include <hip/hip_runtime.h>
@@ -29,6 +33,7 @@
 #include <vector>
 
 #include "../banggameengine_amd/csrc/bge_device_math.hpp"
+#include "../banggameengine_amd/csrc/bge_fuse_math.hpp"
 
 using namespace bge::dev;
 
@@ -282,6 +287,59 @@ k_flat_follow(Soa s, const uint4* __restrict__ words, uint32_t* __restrict__ adv
     fused_body(s, words, adv, epoch, serial, n_ticks, dt, sleep_lin);
 }
 
+// (l) / (l1): (j)'s body around the reduced loop.  (l) is fuse::fuse_ticks itself, the product's function: the compiler packs the
+// adds (v_pk_add_f32, v_mul_f32, v_pk_add_f32 per tick) and unrolls by four.  (l1) is the same loop written out with the v.y add
+// behind an empty asm, which keeps it a single instruction (v_add_f32, v_mul_f32, v_add_f32 and one v_pk_add_f32 for x and z) and
+// which the unroller does not duplicate.
+struct UWave {
+    static __device__ __forceinline__ bool any(bool m) { return __ballot(m) != 0ull; }
+    static __device__ __forceinline__ float abs(float v) { return fabsf(v); }
+    static __device__ __forceinline__ bool same_bits(float a, float b) { return __float_as_uint(a) == __float_as_uint(b); }
+};
+__device__ __forceinline__ bool lean_plain_add(const bge::fuse::Step& c, uint32_t n, F3& vn, F3& xn)
+{
+    if (n == 0u) return true;
+    const F3 v1{vn.x + c.cx, vn.y + c.cy, vn.z + c.cz};
+    if (UWave::any(!(fabsf(v1.y) >= c.sleep_lin))) return false;
+    if (!UWave::any(!(UWave::same_bits(v1.x + c.cx, v1.x) && UWave::same_bits(v1.z + c.cz, v1.z)))) {
+        const float dx = v1.x * c.dt, dz = v1.z * c.dt;
+        float vy = v1.y;
+        F3 x{xn.x + dx, xn.y + vy * c.dt, xn.z + dz};
+        for (uint32_t i = 1; i < n; ++i) {
+            vy = vy + c.cy;
+            asm("" : "+v"(vy));
+            x = F3{x.x + dx, x.y + vy * c.dt, x.z + dz};
+        }
+        const float s = c.sleep_lin;
+        if (!UWave::any(!((v1.y >= s && vy >= s) || (v1.y <= -s && vy <= -s)))) {
+            vn = F3{v1.x, vy, v1.z};
+            xn = x;
+            return true;
+        }
+    }
+    return bge::fuse::fuse_ticks_exact<UWave>(c, n, vn, xn);
+}
+template <bool PLAIN_ADD>
+__global__ void __launch_bounds__(kBlock, 8)
+k_flat_lean(Soa s, const uint4* __restrict__ words, uint32_t* __restrict__ adv, uint32_t epoch, uint32_t serial, uint32_t n_ticks, float dt, float sleep_lin)
+{
+    const uint32_t slot = blockIdx.x * kBlock + threadIdx.x;
+    const uint32_t wave = blockIdx.x * 4u + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint4 w = words[wave];
+    if (adv[wave] >= serial) return;
+    if (((w.x ^ epoch) | (w.w ^ epoch)) != 0u) return;
+    if (!(w.z & 1u)) return;
+    F3 pos = ld3(s.pos, slot);
+    const F3 old = ld_vel(s.vel, slot);
+    asm volatile("" : "+v"(pos.x), "+v"(pos.y), "+v"(pos.z));
+    F3 vel = old;
+    const bge::fuse::Step c{0.0f, -9.81f * dt, 0.0f, dt, sleep_lin};
+    if (!(PLAIN_ADD ? lean_plain_add(c, n_ticks, vel, pos) : bge::fuse::fuse_ticks<UWave>(c, n_ticks, vel, pos))) return;
+    st_vel_if(s.vel, slot, vel, vel_xz_changed(vel, old), vel_y_changed(vel, old));
+    st3(s.pos, slot, pos);
+    if (n_ticks > 1u && (threadIdx.x & 63u) == 0u) adv[wave] = serial + n_ticks - 1u;
+}
+
 constexpr uint32_t kEpoch = 7; // what words 0 and 3 of every record of (h) hold, and what its launches pass
 
 template <typename F> float time_us(F launch, int warm, int reps)
@@ -383,6 +441,37 @@ void run_solo(uint32_t n, int reps, Soa s, const uint4* words, uint32_t* adv, fl
     CK(hipDeviceSynchronize());
 }
 
+// The reduced loop: (j), (l), (l1), each "alone with n_ticks = T, once per T ticks", for T = 64, 256, 1024, three times over.  One line
+// per run: us per LAUNCH, and the same per tick.  The spread of the three (j) lines of a T is the yardstick for that T.
+void run_lean(uint32_t n, int reps, Soa s, const uint4* words, uint32_t* adv, float sleep_lin)
+{
+    const int warm = 24;
+    const dim3 blk(kBlock), g_slot(n / kBlock);
+    uint32_t serial = 1;
+    auto line = [&](const char* kernel, uint32_t T, float us) {
+        std::printf("{\"kernel\": \"%s\", \"T\": %u, \"slots\": %u, \"us_per_launch\": %.3f, \"us_per_tick\": %.4f}\n", kernel, T, n, us, us / static_cast<float>(T));
+        std::fflush(stdout);
+    };
+    for (int round = 0; round < 3; ++round) {
+        for (uint32_t T : {64u, 256u, 1024u}) {
+            line("j_solo", T, time_us([&] {
+                     k_flat_fused<<<g_slot, blk>>>(s, words, adv, kEpoch, serial, T, 1.0f / 60.0f, sleep_lin);
+                     serial += T;
+                 }, warm, reps));
+            line("l_lean", T, time_us([&] {
+                     k_flat_lean<false><<<g_slot, blk>>>(s, words, adv, kEpoch, serial, T, 1.0f / 60.0f, sleep_lin);
+                     serial += T;
+                 }, warm, reps));
+            line("l1_lean_plain_add", T, time_us([&] {
+                     k_flat_lean<true><<<g_slot, blk>>>(s, words, adv, kEpoch, serial, T, 1.0f / 60.0f, sleep_lin);
+                     serial += T;
+                 }, warm, reps));
+        }
+    }
+    CK(hipGetLastError());
+    CK(hipDeviceSynchronize());
+}
+
 template <bool NT> void run_size(uint32_t n, int reps, Soa s, const uint4* words, float zero)
 {
     const int warm = 20;
@@ -421,7 +510,8 @@ template <bool NT> void run_size(uint32_t n, int reps, Soa s, const uint4* words
 
 // usage: ubench_world_rows [slots ...]   (default 1048576 16777216; rounded up to whole 256-slot blocks)
 //        env UBENCH_REPS: timed launches per kernel (default 200); UBENCH_GXZ: x and z gravity of kernel (g) (default 0);
-//        UBENCH_FUSED_ONLY: time (i), (j), (k) alone; UBENCH_SOLO_ONLY: the solo sequences against "(j), then 7 x (k)" alone; UBENCH_SLEEP_LIN: the sleep threshold of (j) (default 0: every ballot passes)
+//        UBENCH_FUSED_ONLY: time (i), (j), (k) alone; UBENCH_SOLO_ONLY: the solo sequences against "(j), then 7 x (k)" alone; UBENCH_SLEEP_LIN: the sleep threshold of (j) (default 0: every ballot passes);
+//        UBENCH_LEAN_ONLY: (j) against (l) and (l1) alone
 int main(int argc, char** argv)
 {
     std::vector<uint32_t> sizes;
@@ -457,7 +547,9 @@ int main(int argc, char** argv)
         CK(hipMalloc(&adv, 4ull * wr.size()));
         CK(hipMemset(adv, 0, 4ull * wr.size()));
         const float sleep_lin = std::getenv("UBENCH_SLEEP_LIN") ? static_cast<float>(std::atof(std::getenv("UBENCH_SLEEP_LIN"))) : 0.0f;
-        if (std::getenv("UBENCH_SOLO_ONLY")) {
+        if (std::getenv("UBENCH_LEAN_ONLY")) {
+            run_lean(n, reps, s, words, adv, sleep_lin);
+        } else if (std::getenv("UBENCH_SOLO_ONLY")) {
             run_solo(n, reps, s, words, adv, sleep_lin);
         } else {
             if (!fused_only) {
