@@ -12,3 +12,10 @@ import numpy as np
 
 F_REL, F_ABS, P_REL, N_ABS, N_SCALE = 1e-5, 1e-6, 2e-5, 1e-4, 2e-6
 NEVER_INSIDE_MARGIN = np.float32(1e-3)  # by how much a mover that started clear may end inside something
+
+# Histogram of the sharded broadphase (bge_world_axis_histogram, refmodel/slabs.hist_sandwich).  The device forms the bin of a min
+# corner x as t = (x - lo) * (1 / ((hi - lo) / bins)) in five binary32 roundings (hi - lo, the division by bins, the reciprocal,
+# x - lo, the product), each relative 2^-24 = u, on quantities no larger than hi - lo once carried back to x: the bin edge the
+# device sees lies within 5 u (hi - lo) of the exact one.  The sandwich allows d = HIST_EDGE_ULPS u (hi - lo), the next power of
+# two above that bound; the factor follows from this count, not from what a device returned.
+HIST_EDGE_ULPS = 8

@@ -17,21 +17,9 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 from banggameengine_amd import sharding, synth  # noqa: E402
 from helpers import build_oracle, run_oracle  # noqa: E402
+from refmodel.slabs import brute_pairs as _brute_pairs  # noqa: E402
 
 NONE = 0xFFFFFFFF
-
-
-def _brute_pairs(aabb, gid, group, mask, static):
-    """All pairs of the broadphase specification (oracle/broadphase_ref.h) among the given records, as global ids."""
-    out = []
-    n = len(aabb)
-    for i in range(n):
-        a = aabb[i]
-        ov = (a[:3] <= aabb[i + 1:, 3:]).all(axis=1) & (a[3:] >= aabb[i + 1:, :3]).all(axis=1)
-        ok = ov & ((group[i] & mask[i + 1:]) != 0) & ((group[i + 1:] & mask[i]) != 0) & ~(static[i] & static[i + 1:])
-        for j in np.flatnonzero(ok) + i + 1:
-            out.append((i, j))
-    return np.array(out, np.int64).reshape(-1, 2)
 
 
 def _scene(n=2500, side=14.0, seed=21):
