@@ -23,7 +23,7 @@ namespace {
 //   k_island_union / k_island_members   union-find over the pairs (findUnions unites every pair of the cache); the bodies that are
 //                       in a pair, keyed root slot << 32 | entity, and whether their island holds an ACTIVE_TAG body   (sorted by hipcub)
 //   k_island_flags      bodies of islands that stay awake get kCiIsland; k_island_own collides their own pairs (plane, obstacles)
-//   k_island_solve      one thread per island (iteration state in LDS where it fits; islands of 5 .. 16 bodies in a second launch);
+//   k_island_solve      one thread per island (iteration state in LDS where it fits; islands of up to 16 bodies beyond an LDS column in a second launch);
 //   k_island_solve_big  a workgroup per island of more than IslandParams::big_points contact points, Bullet's row order kept by levels
 // then k_ground_select / k_ground / k_contact_boxes for the one-body islands and k_tick for everybody, as always.
 struct IslBody {
@@ -929,8 +929,9 @@ __global__ void __launch_bounds__(64) k_island_rows(WorldView w, GroundParams g,
                                static_cast<IslRowCold*>(ip.rows_cold), ip.row_first[lo], j);
 }
 
-// MID = false: the grid walks the sorted body list, an island's first body solves it — or hands it on: to the mid list (5 .. kIslMidBodies bodies:
-// k_island_solve<.., true>, launched next, keeps their bodies' delta velocities in LDS) or to the big list (k_island_solve_big).
+// MID = false: the grid walks the sorted body list, an island's first body solves it — or hands it on: to the mid list (up to kIslMidBodies
+// bodies that do not fit an LDS column, be it by their number or by more than kIslLdsPoints points: k_island_solve<.., true>, launched next,
+// keeps their bodies' delta velocities in LDS) or to the big list (k_island_solve_big).
 template <bool BASIS, bool MID>
 __global__ void __launch_bounds__(64) k_island_solve(WorldView w, GroundParams g, IslandParams ip)
 {
@@ -1045,7 +1046,7 @@ __global__ void __launch_bounds__(64) k_island_solve(WorldView w, GroundParams g
             frictionRow[r].applied = L.row(r, 2);
         }
     } else if (MID) {
-        // (5 .. kIslMidBodies bodies, up to IslandParams::big_points contact points — a tower, a small pile: the bodies' delta velocities
+        // (up to kIslMidBodies bodies on up to IslandParams::big_points contact points — a tower, a small pile, four boxes in a row: the bodies' delta velocities
         //  in LDS, a row's own scalars in the row; rows one ahead, a resolved row writes back the one word that changed)
         const IslLocal L{s_isl + (threadIdx.x & 63u), first};
         for (uint32_t i = first; i < end; ++i) {
@@ -1450,7 +1451,10 @@ hipError_t launch_island_solve(hipStream_t stream, const WorldView& w, const Gro
     const dim3 grid((ip.n_bodies + 63u) / 64u), block(64);
     size_t scan_bytes = ip.scan_tmp_bytes;
     const dim3 row_grid((ip.row_cap / 2u + 64u) / 64u); // (a thread for every row the arrays can hold; those past the last row leave at once)
-    const dim3 mid_grid((ip.n_bodies / (kIslLdsBodies + 1u) + 64u) / 64u); // (an island on the mid list has more than kIslLdsBodies bodies)
+    // (a thread for every island the mid list can hold.  Not n_bodies / (kIslLdsBodies + 1): an island of up to kIslLdsBodies bodies is on
+    //  the list too when it has more than kIslLdsPoints points — four boxes side by side on the plane — and so is a one-body island of
+    //  k_island_orphans that rests on the plane and an obstacle.  One body an island is the worst case: the first launch's grid)
+    const dim3 mid_grid = grid;
     if (bullet_basis) {
         hipLaunchKernelGGL(k_island_own<true>, grid, block, 0, stream, w, g, ip);
         hipLaunchKernelGGL(k_island_bodies<true>, grid, block, 0, stream, w, g, ip);

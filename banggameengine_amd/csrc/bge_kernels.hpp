@@ -180,7 +180,7 @@ struct IslandParams {
     uint32_t iterations;            // 10 (btContactSolverInfo::m_numIterations)
     // islands too big for one thread's LDS column: k_island_solve lists them, k_island_solve_big takes a workgroup to each
     uint32_t* big_list;             // [n_bodies][2] first body, end (counts[4] of them; counts[5] is the workgroups' ticket)
-    uint32_t* mid_list;             // [n_bodies][2] likewise, islands of 5 .. 16 bodies (counts[7] of them): k_island_solve<.., true>
+    uint32_t* mid_list;             // [n_bodies][2] likewise, islands of up to 16 bodies beyond an LDS column (counts[7] of them): k_island_solve<.., true>
     uint32_t* row_count;            // [n_bodies] contact points body i brings into its island's row list (k_island_bodies; 0 off the path)
     uint32_t* row_first;            // [n_bodies] exclusive sum of row_count: the island's rows are rows row_first[first] .. of the two arrays
     void* scan_tmp;                 // hipcub's temporary storage for that sum (island_scan_bytes)

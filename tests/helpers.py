@@ -47,6 +47,16 @@ def build_oracle(wl, orient_mode=po.ORIENT_IDEAL, aabbs=False, has_transform=Non
     return ref
 
 
+def build_island_oracle(case, basis=False):
+    """The oracle's scene of a case of refmodel/island_cases.py: plane and obstacle contacts as the case says, Dynamic boxes
+    against each other on."""
+    ref = build_oracle(case.wl, orient_mode=po.ORIENT_BASIS if basis else po.ORIENT_IDEAL, has_transform=case.has_transform, size=case.size, mass=case.mass)
+    ref.SetGroundPlane(case.plane)
+    ref.SetStaticContacts(case.static)
+    ref.SetDynamicContacts(True)
+    return ref
+
+
 def run_oracle(ref, wl, ticks, seed_velocity=True, physics=True, angvel=None):
     for k in range(ticks):
         if physics:
@@ -63,3 +73,43 @@ def run_world(world, wl, ticks, seed_velocity=True, flags=3, angvel=None):
         if k == 0 and seed_velocity and (flags & 1):
             world.set_velocities(wl.vel, angvel)
     return world
+
+
+def compare_dynamic_world(w, ref, tick, dyn, plane, static):
+    """A world with Dynamic-against-Dynamic contacts against the oracle after a tick, bit for bit: activation states, the pair cache
+    (which pairs, their points, their impulses), velocities, position, quaternion, rotationEuler, the timers of awake bodies, and of
+    every third Dynamic body the plane manifold (plane) and the obstacle manifolds (static).  Returns (states, pair header)."""
+    rb, gb = ref.bulk_bodies(), w.download_bodies()
+    ex = rb["exists"]
+    pos, euler = w.download_pose()
+    rpos, reuler = ref.bulk_pose()
+    st, tm = w.download_activation()
+    rst, rtm = ref.bulk_activation()
+    assert np.array_equal(st[ex], rst[ex].astype(np.uint8)), f"tick {tick}: activation states differ at {np.flatnonzero(st[ex] != rst[ex])[:8]}"
+    hdr, pts = w.download_dynamic_pairs()
+    rhdr, rpts = ref.DynamicPairs()
+    rhdr = rhdr.copy()
+    rhdr[:, :2] -= 1                                                          # entity id -> index
+    assert hdr.shape == rhdr.shape and np.array_equal(hdr, rhdr), f"tick {tick}: pair cache {hdr.tolist()[:6]} vs oracle {rhdr.tolist()[:6]}"
+    assert_bits_equal(pts, rpts, f"tick {tick}: points of the pair manifolds")
+    assert_bits_equal(gb["linvel"][dyn], rb["linvel"][dyn], f"tick {tick}: linear velocity")
+    assert_bits_equal(gb["angvel"][dyn], rb["angvel"][dyn], f"tick {tick}: angular velocity")
+    assert_bits_equal(pos, rpos, f"tick {tick}: position")
+    assert_bits_equal(gb["quat"][ex], rb["quat"][ex], f"tick {tick}: quaternion")
+    assert_bits_equal(euler, reuler, f"tick {tick}: rotationEuler")
+    assert_bits_equal(tm[ex & (rst == 1)], rtm[ex & (rst == 1)], f"tick {tick}: deactivation timers")
+    if plane:
+        cn, cpts = w.download_contacts()
+        for e in np.flatnonzero(dyn)[::3]:
+            rn, rpts2 = ref.GroundContacts(int(e) + 1)
+            assert cn[e] == rn, f"tick {tick}: body {e} has {cn[e]} plane contacts, oracle {rn}"
+            assert_bits_equal(cpts[e, :rn], rpts2, f"tick {tick}: plane contact points of body {e}")
+    if static:
+        nb, bh, bp = w.download_box_contacts()
+        for e in np.flatnonzero(dyn)[::3]:
+            want = ref.BoxContacts(int(e) + 1)
+            assert nb[e] == len(want), f"tick {tick}: body {e} has {nb[e]} box manifolds, oracle {len(want)}"
+            for k, (other, rows) in enumerate(want):
+                assert bh[e, k, 0] == other - 1 and bh[e, k, 1] == len(rows)
+                assert_bits_equal(bp[e, k, :len(rows)], rows, f"tick {tick}: body {e} manifold {k} points")
+    return st, hdr

@@ -12,6 +12,7 @@ from banggameengine_amd import synth
 from oracle import pyoracle as po
 
 from helpers import DT, assert_bits_equal, bits, build_oracle, matrix_rel_err, parent_i32, run_oracle, run_world
+from helpers import compare_dynamic_world as _compare_dynamic_world
 
 pytestmark = pytest.mark.gpu
 
@@ -1238,43 +1239,6 @@ def test_many_static_boxes_through_the_obstacle_grid_match_oracle_bitwise(grid, 
         final_pos, _ = w.download_pose()
     assert most == 4, most                                                   # a plank held the four lowest of its candidates
     assert (final_pos[dyn, 1] > 0.5).sum() > 600                             # the blocks caught most of the rain
-
-
-def _compare_dynamic_world(w, ref, tick, dyn, plane, static):
-    rb, gb = ref.bulk_bodies(), w.download_bodies()
-    ex = rb["exists"]
-    pos, euler = w.download_pose()
-    rpos, reuler = ref.bulk_pose()
-    st, tm = w.download_activation()
-    rst, rtm = ref.bulk_activation()
-    assert np.array_equal(st[ex], rst[ex].astype(np.uint8)), f"tick {tick}: activation states differ at {np.flatnonzero(st[ex] != rst[ex])[:8]}"
-    hdr, pts = w.download_dynamic_pairs()
-    rhdr, rpts = ref.DynamicPairs()
-    rhdr = rhdr.copy()
-    rhdr[:, :2] -= 1                                                          # entity id -> index
-    assert hdr.shape == rhdr.shape and np.array_equal(hdr, rhdr), f"tick {tick}: pair cache {hdr.tolist()[:6]} vs oracle {rhdr.tolist()[:6]}"
-    assert_bits_equal(pts, rpts, f"tick {tick}: points of the pair manifolds")
-    assert_bits_equal(gb["linvel"][dyn], rb["linvel"][dyn], f"tick {tick}: linear velocity")
-    assert_bits_equal(gb["angvel"][dyn], rb["angvel"][dyn], f"tick {tick}: angular velocity")
-    assert_bits_equal(pos, rpos, f"tick {tick}: position")
-    assert_bits_equal(gb["quat"][ex], rb["quat"][ex], f"tick {tick}: quaternion")
-    assert_bits_equal(euler, reuler, f"tick {tick}: rotationEuler")
-    assert_bits_equal(tm[ex & (rst == 1)], rtm[ex & (rst == 1)], f"tick {tick}: deactivation timers")
-    if plane:
-        cn, cpts = w.download_contacts()
-        for e in np.flatnonzero(dyn)[::3]:
-            rn, rpts2 = ref.GroundContacts(int(e) + 1)
-            assert cn[e] == rn, f"tick {tick}: body {e} has {cn[e]} plane contacts, oracle {rn}"
-            assert_bits_equal(cpts[e, :rn], rpts2, f"tick {tick}: plane contact points of body {e}")
-    if static:
-        nb, bh, bp = w.download_box_contacts()
-        for e in np.flatnonzero(dyn)[::3]:
-            want = ref.BoxContacts(int(e) + 1)
-            assert nb[e] == len(want), f"tick {tick}: body {e} has {nb[e]} box manifolds, oracle {len(want)}"
-            for k, (other, rows) in enumerate(want):
-                assert bh[e, k, 0] == other - 1 and bh[e, k, 1] == len(rows)
-                assert_bits_equal(bp[e, k, :len(rows)], rows, f"tick {tick}: body {e} manifold {k} points")
-    return st, hdr
 
 
 @pytest.mark.parametrize("basis,plane,static,big", [(False, True, False, 128), (True, True, True, 128), (False, False, True, 128), (True, True, True, 16), (False, True, False, 0)],
