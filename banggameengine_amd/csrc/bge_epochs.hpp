@@ -1,6 +1,7 @@
 // bge_epochs.hpp — the two epochs the tick kernel's per-wave words (WorldView::rs_word) are compared with, and the bookkeeping of
 // the deferred translation row (Row3State, below), of fused ticks (FuseClock, below) and of solo groups (SoloPlan, below).  Host-only, no HIP: tests/test_rest_epoch_cpu.py and tests/test_row3_epoch_cpu.py
-// compile this header on its own.
+// compile this header on its own.  Which tick takes which path, defers, fuses or goes out in solo groups is decided from these pieces
+// in bge_tick_plan.hpp (TickPlan, TickGroups).
 //   rows  what word 0 must equal for the translation-row path (TickParams::rs_epoch)
 //   rest  what word 1 must equal for the rest path (TickParams::rest_epoch)
 // A bump invalidates every word of its kind at once.  The rules:

@@ -45,6 +45,7 @@
 #include "bge_flatten.hpp"
 #include "bge_fuse_math.hpp"
 #include "bge_kernels.hpp"
+#include "bge_tick_plan.hpp"
 
 namespace bge {
 
@@ -270,7 +271,7 @@ __global__ void __launch_bounds__(kTile, SOLO ? BGE_SOLO_MIN_WAVES : NORMAL ? 4 
     // epoch on every call that could).  Unless a lane re-poses or spins in this tick, rows 0..2 would come out bit for bit as
     // they are stored: the wave skips the euler / scale loads and bx_mtx_srt and stores the translation row alone (DESIGN.md
     // §4.1: 68 instead of 140 B per flat body).  The word is loaded as a scalar next to the tile header.
-    constexpr bool kRowsPath = XFORM && !AABB && !NORMAL && !BASIS;
+    constexpr bool kRowsPath = tick_variant_has_rows_path(XFORM, AABB, NORMAL, BASIS);
     const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     // The wave's record {rows word, rest word, flag value, flag epoch} (WorldView::rs_word) in one wave-uniform 16-B load.
     uint4 rec = (kRowsPath && (p.rs_epoch | p.rest_epoch) != 0u) ? reinterpret_cast<const uint4*>(w.rs_word)[tile * 4u + wave] : make_uint4(0u, 0u, 0u, 0u);
@@ -1341,15 +1342,17 @@ inline dim3 grid_for(uint64_t n, uint32_t block) { return dim3(static_cast<uint3
 } // namespace
 
 // ------------------------------------------------------------------ launch wrappers
+static_assert(kTickPhysics == BGE_TICK_PHYSICS && kTickTransforms == BGE_TICK_TRANSFORMS && kTickAabb == (BGE_TICK_BROADPHASE | BGE_TICK_AABBS) &&
+              kTickNormal == BGE_TICK_NORMAL_MATRICES && kTickBasis == BGE_TICK_BULLET_BASIS, "bge_kernels.hpp names the bits of bge_tick_flags");
 hipError_t launch_tick(hipStream_t stream, const WorldView& w, const TickParams& p, uint32_t n_tiles, uint32_t flags)
 {
     if (n_tiles == 0) return hipSuccess;
-    const bool phys = (flags & 1u) != 0, xform = (flags & 2u) != 0, aabb = (flags & (4u | 32u)) != 0, normal = (flags & 16u) != 0;
+    const bool phys = (flags & kTickPhysics) != 0, xform = (flags & kTickTransforms) != 0, aabb = (flags & kTickAabb) != 0, normal = (flags & kTickNormal) != 0;
     const dim3 grid(n_tiles), block(kTile);
-    const bool basis = phys && (flags & 64u) != 0;
+    const bool basis = phys && (flags & kTickBasis) != 0;
     if (p.n_solo > 1u) {
         // a solo group: the variant exists for the physics + transform tick alone, and a launch that asks for another is an error
-        if (!(phys && xform) || aabb || normal || basis || p.serial != 0u || p.n_left != 1u) return hipErrorInvalidValue;
+        if (!phys || !tick_variant_has_rows_path(xform, aabb, normal, basis) || p.serial != 0u || p.n_left != 1u) return hipErrorInvalidValue;
         hipLaunchKernelGGL((k_tick<true, true, false, false, false, true>), grid, block, 0, stream, w, p);
         return hipGetLastError();
     }

@@ -245,7 +245,8 @@ struct TickParams {
                         // BGE_SOLO_GROUPS=0 keeps it 0
 };
 
-// flags: bit0 physics, bit1 transforms, bit2 / bit5 aabb, bit4 normal matrices (bge_tick_flags)
+// flags: bit0 physics, bit1 transforms, bit2 / bit5 aabb, bit4 normal matrices, bit6 Bullet basis (bge_tick_flags)
+constexpr uint32_t kTickPhysics = 1u, kTickTransforms = 2u, kTickAabb = 4u | 32u, kTickNormal = 16u, kTickBasis = 64u;
 hipError_t launch_tick(hipStream_t stream, const WorldView& w, const TickParams& p, uint32_t n_tiles, uint32_t flags);
 
 // Stores the deferred translation rows: in every wave whose rows word equals `epoch`, valid slots get row 3 = (pos, 1)

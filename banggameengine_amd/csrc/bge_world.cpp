@@ -28,6 +28,7 @@
 #include "bge_debug.hpp"
 #include "bge_flatten.hpp"
 #include "bge_epochs.hpp"
+#include "bge_tick_plan.hpp"
 #include "bge_kernels.hpp"
 #include "bge_move.hpp"
 #include "bge_step.hpp"
@@ -671,9 +672,6 @@ int make_store(bge_world* w, SlotBuf& a, bool synced = false)
 
 namespace {
 constexpr uint32_t kTriggerPairCap = 1u << 20;
-constexpr uint32_t kFuseTicksDefault = 8; // ticks per fused group of a bge_world_tick_many call (BGE_FUSE_TICKS; DESIGN.md §4.1 "Fused ticks": measured)
-constexpr uint32_t kSoloTicksDefault = 512; // ticks per solo group, where BGE_FUSE_TICKS is unset (DESIGN.md §4.1 "Lean fusion": measured again with the reduced loop — the smallest of 64 .. 1024 whose median lies within the parent's spread of the best)
-constexpr double kNtThresholdBytes = 300.0e6; // measured crossover between 2 M (plain wins) and 4 M slots (nt wins)
 
 // device mirrors of the trigger set (slots follow the current topology)
 int sync_triggers_to_device(bge_world* w)
@@ -1926,6 +1924,27 @@ int contact_substep(bge_world* w, bge::TickParams& p, float dt, const float grav
     return BGE_OK;
 }
 
+// The trigger ghosts' boxes from the Transforms as they are before the step
+int pose_ghosts(bge_world* w)
+{
+    ensure_triggers(w);
+    if (w->triggers_device_stale) {
+        if (int rc = sync_triggers_to_device(w)) return rc;
+    }
+    HIP_TRY(bge::launch_trigger_aabb(w->stream, static_cast<uint32_t>(w->triggers.size()), w->trigger_view(), w->view));
+    for (bge_world::Trigger& tg : w->triggers) tg.posed = tg.posed || (tg.runtime_active && !tg.frozen);
+    return BGE_OK;
+}
+
+// Is a one-shot volume in the world?
+bool any_one_shot(const bge_world* w)
+{
+    for (const bge_world::Trigger& t : w->triggers) {
+        if (t.one_shot && t.runtime_active) return true;
+    }
+    return false;
+}
+
 // The tick's broadphase after the tick kernel, and the trigger volumes' overlaps with the new boxes
 int broadphase_and_triggers(bge_world* w, bool with_triggers)
 {
@@ -1968,10 +1987,8 @@ int broadphase_and_triggers(bge_world* w, bool with_triggers)
         // The short way needs last tick's table to hold exactly the host's sets and no one-shot volume in the world (one that
         // fires leaves the world in the middle of ProcessTriggerEvents' loop and takes itself out of the later ghosts' lists:
         // that order dependence stays on the host)
-        bool short_way = w->trig_device_diff && w->trig_mirror_valid;
-        for (const bge_world::Trigger& t : w->triggers) short_way = short_way && !(t.one_shot && t.runtime_active);
         int how = 1;
-        if (short_way) {
+        if (w->trig_device_diff && w->trig_mirror_valid && !any_one_shot(w)) {
             how = process_trigger_pairs_fast(w);
             if (how < 0) return how;
         }
@@ -1979,9 +1996,7 @@ int broadphase_and_triggers(bge_world* w, bool with_triggers)
             if (int rc2 = process_trigger_pairs(w)) return rc2;
             ++w->trig_slow_ticks;
             w->trig_mirror_valid = false;
-            bool one_shot = false;
-            for (const bge_world::Trigger& t : w->triggers) one_shot = one_shot || (t.one_shot && t.runtime_active);
-            if (w->trig_device_diff && !one_shot) {
+            if (w->trig_device_diff && !any_one_shot(w)) {
                 if (int rc2 = rebuild_trigger_mirror(w)) return rc2;
             }
         }
@@ -2042,62 +2057,11 @@ int tick_impl(bge_world* w, uint32_t ticks, float dt, const float gravity[3], ui
             w->prof_events.push_back(e);
         }
     }
-    // Output stores: non-temporal once the tick's working set (~140 B per slot, 204 B with normal matrices) no longer
-    // fits the 256 MiB Infinity Cache; BGE_NT_STORES=0/1 overrides (experiments)
-    bool nt_out = static_cast<double>(w->flat.n_slots) * ((flags & BGE_TICK_NORMAL_MATRICES) ? 204.0 : 140.0) > kNtThresholdBytes;
-    if (const char* e = std::getenv("BGE_NT_STORES")) nt_out = std::atoi(e) != 0;
-    // Translation-row fast path of the tick kernel (WorldView::rs_word): only in the variants it exists in (transforms, with or
-    // without the default physics step, nothing else), and only where no other kernel of the tick writes euler, scale, world
-    // or quat (ground plane, obstacles, Dynamic contacts).  Only while the working set fits the Infinity Cache, unless the
-    // tick defers the row (below): beyond it a 16-B store into every 64-B matrix costs more than the whole matrix
-    // (tools/ubench_world_rows.hip: 16 M slots, 2.7x).
-    // BGE_WORLD_ROWS=0 turns it off (A/B runs); a tick without it moves the epoch on, so that no word outlives what it vouched for.
-    const bool contacts = phys && (w->ground_plane || w->static_contacts || w->dynamic_contacts);
-    // Deferred translation row (bge_epochs.hpp Row3State): translation-row waves do not store row 3 either; the readers that run every
-    // frame compose it, everything else stores it first (bge_world::ensure_row3_current).  BGE_DEFER_ROW3=0 turns it off (A/B runs).
-    // A deferring tick writes no partial matrix line, so the Infinity Cache limit above does not apply to it (the first, full-path
-    // ticks keep their non-temporal stores).
-    bool defer_env = true;
-    if (const char* e = std::getenv("BGE_DEFER_ROW3")) defer_env = std::atoi(e) != 0;
-    const bool can_defer = w->row3.may_defer(true, w->flat.pass_tile_begin.size() - 1, w->any_frozen, defer_env);
-    bool rows_path = xform && !contacts && (!nt_out || can_defer) &&
-                     !(flags & (BGE_TICK_AABBS | BGE_TICK_BROADPHASE | BGE_TICK_NORMAL_MATRICES | BGE_TICK_BULLET_BASIS | BGE_TICK_GATHER_ROOTS));
-    if (const char* e = std::getenv("BGE_WORLD_ROWS")) rows_path = rows_path && std::atoi(e) != 0;
-    const bool defer_row3 = rows_path && can_defer;
-    // Vouched waves of the translation-row path (WorldView::rs_word, words 2 and 3): a wave whose 64 flag words are known to be one
-    // clean value skips the flags read.  The words are kept whether or not the block runs; BGE_FLAG_WORD=0 turns the block off (A/B runs).
-    bool flag_word = rows_path;
-    if (const char* e = std::getenv("BGE_FLAG_WORD")) flag_word = flag_word && std::atoi(e) != 0;
-    // Rest path of the tick kernel (WorldView::rs_word, word 1): waves whose bodies are all asleep read 12 B per body and store
-    // nothing.  In the same variants as the translation-row path — but ON with the ground plane, obstacles and Dynamic contacts,
-    // where a scene at rest spends its life: every kernel of the contact stage either leaves a sleeping body alone or marks its
-    // flags, deactivation record or contact word.  It stores nothing, so the non-temporal regime needs no
-    // exclusion.  BGE_REST_PATH=0 turns it off (A/B runs); a tick without it moves its epoch on.
-    bool rest_path = xform && !(flags & (BGE_TICK_AABBS | BGE_TICK_BROADPHASE | BGE_TICK_NORMAL_MATRICES | BGE_TICK_BULLET_BASIS | BGE_TICK_GATHER_ROOTS));
-    if (const char* e = std::getenv("BGE_REST_PATH")) rest_path = rest_path && std::atoi(e) != 0;
-    // Fused ticks (bge_epochs.hpp FuseClock, TickParams::serial): the ticks of this call go out in groups of at most fuse_T launches, and
-    // a vouched wave runs the ticks that remain of its group in the first launch that finds it vouched; the group's later launches
-    // return at once for it.  Only the physics + transform tick on the translation-row path with the flag word, only in a scene of
-    // one pass without a frozen root (Row3State::may_defer's conditions without `pinned`: in any other scene a child of a later pass
-    // reads a flat root's matrix inside the tick, and that must be the matrix of that very tick), and not with an event pair per
-    // tick, which wants launches of equal meaning.  BGE_FUSE_TICKS=T sets the group size; 1 is off (A/B runs).  Groups never span calls.
-    // If a launch fails in the middle of a group, some waves are ahead of others: the error is returned as ever, and the world is
-    // not usable after a failed tick call (include/bge_world.h).
-    uint32_t fuse_T = kFuseTicksDefault;
-    const char* const fuse_env = std::getenv("BGE_FUSE_TICKS");
-    if (fuse_env) fuse_T = static_cast<uint32_t>(std::max(1, std::atoi(fuse_env)));
-    // (only a flat all-Dynamic tile can hold a vouched wave: without one, no launch loads a word that can never be set)
-    const bool fusable = phys && rows_path && flag_word && w->flat.pass_tile_begin.size() - 1 == 1 && !w->any_frozen && w->profiling != 2 && w->shape.any_flat_all_dynamic;
-    // Solo groups (bge_epochs.hpp SoloPlan, TickParams::n_solo): where every tile is flat, the first tick of a group launches ONE
-    // kernel in which every wave runs the group's ticks itself — fused in registers where it is vouched, one after the other by the
-    // ordinary path where it is not — and the group's other ticks launch nothing.  They still do all of this loop's bookkeeping.
-    // No serial, no adv.  BGE_SOLO_GROUPS=0 turns it off (A/B runs): round 9's scheme, one launch per tick.  Every fusable scene
-    // that is not all-flat keeps that scheme.
-    bool solo_env = true;
-    if (const char* e = std::getenv("BGE_SOLO_GROUPS")) solo_env = std::atoi(e) != 0;
-    const bool solo = bge::SoloPlan::wanted(fusable, w->shape.all_flat, solo_env);
-    if (solo && !fuse_env) fuse_T = kSoloTicksDefault; // (a solo group costs one launch whatever its size: its default is its own)
-    uint32_t group_first = 0, group_t0 = 0, group_n = 0; // the group tick t belongs to: its first serial, its first tick, its size
+    const size_t n_passes = w->flat.pass_tile_begin.size() - 1;
+    const bge::TickScene scene{w->flat.n_slots, n_passes, w->any_frozen, w->ground_plane || w->static_contacts || w->dynamic_contacts,
+                               w->shape.all_flat, w->shape.any_flat_all_dynamic, w->profiling};
+    const bge::TickPlan plan = bge::TickPlan::of(flags, scene, bge::TickKnobs::from_env(), w->row3);
+    bge::TickGroups groups(plan, ticks);
     for (uint32_t t = 0; t < ticks; ++t) {
         if (!phys && !w->maybe_dirty && !(flags & BGE_TICK_NORMAL_MATRICES)) {
             // TransformSystem::Update with nothing dirty: a no-op scan — only the kernel launches are skipped.  The
@@ -2114,42 +2078,28 @@ int tick_impl(bge_world* w, uint32_t ticks, float dt, const float gravity[3], ui
         p.gx = gravity ? gravity[0] : 0.0f;
         p.gy = gravity ? gravity[1] : 0.0f;
         p.gz = gravity ? gravity[2] : 0.0f;
-        p.nt_out = nt_out ? 1u : 0u;
+        p.nt_out = plan.nt_out ? 1u : 0u;
         p.no_repose = sub.no_repose ? 1u : 0u;
-        p.flag_word = flag_word ? 1u : 0u;
-        if (fusable && fuse_T > 1u && t == group_t0 + group_n) {
-            group_t0 = t;
-            group_n = bge::FuseClock::group_size(t, ticks, fuse_T);
-            bool wrapped = false;
-            if (!solo) group_first = w->fuse.begin_group(group_n, &wrapped); // (a solo group carries no serial)
-            if (wrapped) HIP_TRY(hipMemsetAsync(w->adv.p, 0, w->adv.bytes, w->stream));
-        }
-        // (a group of one tick has nothing to fuse: it goes out as every tick did, and no word is loaded)
-        const bool fused = fusable && fuse_T > 1u && group_n > 1u && !solo;
-        p.serial = fused ? group_first + (t - group_t0) : 0u;
-        p.n_left = fused ? group_n - (t - group_t0) : 1u;
-        const bge::SoloPlan plan = bge::SoloPlan::plan(solo && fuse_T > 1u, t - group_t0, group_n);
-        p.n_solo = plan.n_solo;
+        p.flag_word = plan.flag_word ? 1u : 0u;
+        const bge::TickGroups::Tick group = groups.next(t, w->fuse);
+        if (group.clear_adv) HIP_TRY(hipMemsetAsync(w->adv.p, 0, w->adv.bytes, w->stream));
+        p.serial = group.serial;
+        p.n_left = group.n_left;
+        p.n_solo = group.n_solo;
         // (a tick without the translation-row path may write pos or world from any of its kernels, and moves the rows epoch)
-        if (!rows_path) HIP_TRY(w->ensure_row3_current());
-        if (rows_path) p.rs_epoch = w->epochs.rows;
+        if (!plan.rows_path) HIP_TRY(w->ensure_row3_current());
+        if (plan.rows_path) p.rs_epoch = w->epochs.rows;
         else if (w->epochs.tick_without_rows()) w->words_clear();
-        if (defer_row3) {
+        if (plan.defer_row3) {
             p.defer_row3 = 1u;
             w->row3.deferred(w->epochs.rows);
         }
-        if (rest_path) p.rest_epoch = w->epochs.rest;
+        if (plan.rest_path) p.rest_epoch = w->epochs.rest;
         else if (w->epochs.tick_without_rest()) w->words_clear();
         w->fill_sleep(p);
         const bool with_triggers = (flags & BGE_TICK_BROADPHASE) && !w->triggers.empty();
         if (with_triggers && !sub.ghosts_posed) {
-            ensure_triggers(w);
-            if (w->triggers_device_stale) {
-                if (int rc = sync_triggers_to_device(w)) return rc;
-            }
-            // ghost boxes from the Transforms as they are before the step
-            HIP_TRY(bge::launch_trigger_aabb(w->stream, static_cast<uint32_t>(w->triggers.size()), w->trigger_view(), w->view));
-            for (bge_world::Trigger& tg : w->triggers) tg.posed = tg.posed || (tg.runtime_active && !tg.frozen);
+            if (int rc = pose_ghosts(w)) return rc;
         }
         if (flags & BGE_TICK_BROADPHASE) {
             // the broadphase takes its grid from per-wave partials the tick kernel writes beside the AABBs
@@ -2160,10 +2110,9 @@ int tick_impl(bge_world* w, uint32_t ticks, float dt, const float gravity[3], ui
             }
             p.bp_partial = w->bp_partials.as<float4>();
         }
-        if (contacts) {
+        if (plan.contacts) {
             if (int rc = contact_substep(w, p, dt, gravity, flags, sub)) return rc;
         }
-        const size_t n_passes = w->flat.pass_tile_begin.size() - 1;
         // BGE_TICK_GATHER_ROOTS with a transform pass: the roots write the all-gather's send buffer themselves
         const bool fused_gather = (flags & BGE_TICK_GATHER_ROOTS) && xform;
         if (flags & BGE_TICK_GATHER_ROOTS) {
@@ -2186,7 +2135,7 @@ int tick_impl(bge_world* w, uint32_t ticks, float dt, const float gravity[3], ui
             }
             HIP_TRY(hipEventRecord(w->prof_events[w->prof_used], w->stream));
         }
-        for (size_t pass = 0; pass < n_passes && plan.launch; ++pass) { // (a later tick of a solo group: its work is in the group's launch)
+        for (size_t pass = 0; pass < n_passes && group.launch; ++pass) { // (a later tick of a solo group: its work is in the group's launch)
             p.tile_begin = w->flat.pass_tile_begin[pass];
             const uint32_t n_tiles = w->flat.pass_tile_begin[pass + 1] - p.tile_begin;
             HIP_TRY(bge::launch_tick(w->stream, w->view, p, n_tiles, flags));
@@ -2246,12 +2195,7 @@ try {
         if (!w->has_topology) return fail(BGE_ERR_STATE, "bge_world_set_topology has not been called");
         // EnsureTrigger / SyncTriggersToPhysics pose the ghosts from the Transforms as they are BEFORE stepSimulation
         DeviceGuard guard(w->device);
-        ensure_triggers(w);
-        if (w->triggers_device_stale) {
-            if (int rc = sync_triggers_to_device(w)) return rc;
-        }
-        HIP_TRY(bge::launch_trigger_aabb(w->stream, static_cast<uint32_t>(w->triggers.size()), w->trigger_view(), w->view));
-        for (bge_world::Trigger& tg : w->triggers) tg.posed = tg.posed || (tg.runtime_active && !tg.frozen);
+        if (int rc = pose_ghosts(w)) return rc;
         sub.ghosts_posed = true;
     }
     if (run == 0) {

@@ -3,7 +3,8 @@
 * A stand-alone C++ program (tests/cpp/fuse_clock.cpp) replays tick_impl's group loop on bge::FuseClock: the split of K ticks into
   groups of at most T for K in 1..9, 17, 1000 and T in 1, 2, 3, 4, 8, serials that only rise across groups and calls, and the wrap
   that asks for the zeroing of the words.
-* bge_world.cpp keeps that state in the struct and nowhere else, and a launch carries a serial only where the tick is fusable."""
+* bge_world.cpp keeps that state in the struct and nowhere else; what a launch carries comes from csrc/bge_tick_plan.hpp TickGroups,
+  which tests/test_tick_plan_cpu.py runs."""
 import os
 import re
 import subprocess
@@ -29,30 +30,21 @@ def _tick_impl(src):
 
 def test_a_launch_carries_a_serial_only_where_the_tick_is_fusable():
     src = open(os.path.join(CSRC, "bge_world.cpp")).read()
+    plan = open(os.path.join(CSRC, "bge_tick_plan.hpp")).read()
     assert "bge::FuseClock fuse;" in src
     tick = _tick_impl(src)
-    # one place hands serials out, and only tick_impl touches the clock or writes the two parameters
-    assert src.count("fuse.begin_group(") == 1 and tick.count("fuse.begin_group(") == 1
-    assert len(re.findall(r"\bfuse\.next\b", src)) == 0
-    assert len(re.findall(r"\.serial\s*=[^=]", src)) == 1 and len(re.findall(r"\.n_left\s*=[^=]", src)) == 1
-    # the fusable condition: the physics + transform tick on the translation-row path with the flag word, one pass, no frozen root,
-    # no event pair per tick
-    m = re.search(r"const bool fusable = ([^;]*);", tick)
-    assert m
-    cond = m.group(1)
-    for term in ("phys", "rows_path", "flag_word", "w->flat.pass_tile_begin.size() - 1 == 1", "!w->any_frozen", "w->profiling != 2"):
-        assert term in [t.strip() for t in cond.split("&&")], (term, cond)
-    # serial is `fused ? ... : 0u`, and `fused` implies `fusable`; TickParams starts zeroed
-    m = re.search(r"const bool fused = ([^;]*);", tick)
-    assert m and m.group(1).split("&&")[0].strip() == "fusable"
-    assert re.search(r"p\.serial = fused \? [^:;]* : 0u;", tick) and re.search(r"p\.n_left = fused \? [^:;]* : 1u;", tick)
+    # one place hands serials out (TickGroups::next), only tick_impl gives it the clock, and only tick_impl writes the two parameters
+    assert plan.count(".begin_group(") == 1 and "begin_group(" not in src
+    assert len(re.findall(r"\bfuse\b", src)) == 2 and tick.count("groups.next(t, w->fuse)") == 1
+    assert len(re.findall(r"\b(fuse|clock)\.next\b", src + plan)) == 0
+    assert len(re.findall(r"\.serial\s*=[^=]", src + plan)) == 1 and len(re.findall(r"\.n_left\s*=[^=]", src + plan)) == 1
+    assert "p.serial = group.serial;" in tick and "p.n_left = group.n_left;" in tick
+    # which launches carry a serial (fusable, not solo, a group of more than one) is run, not read: tests/cpp/tick_plan.cpp.
+    # TickParams starts zeroed
     assert "bge::TickParams p{};" in tick
-    # the clock moves only for a fusable tick, and the zeroing it asks for is ordered on the world's stream before the launches
-    m = re.search(r"if \(([^{]*)\) \{\s*group_t0 = t;(.*?)\n        \}", tick, re.S)
-    assert m and m.group(1).split("&&")[0].strip() == "fusable"
-    body = m.group(2)
-    assert "if (wrapped) HIP_TRY(hipMemsetAsync(w->adv.p, 0, w->adv.bytes, w->stream));" in body
-    assert tick.find("fuse.begin_group(") < tick.find("launch_tick(")
+    # the zeroing the clock asks for is ordered on the world's stream, after the group began and before the launches
+    memset = "if (group.clear_adv) HIP_TRY(hipMemsetAsync(w->adv.p, 0, w->adv.bytes, w->stream));"
+    assert -1 < tick.find("groups.next(t, w->fuse)") < tick.find(memset) < tick.find("launch_tick(")
     # the words are zeroed with every layout
     assert "hipMemsetAsync(w->adv.p, 0, T * 16, w->stream)" in src
 

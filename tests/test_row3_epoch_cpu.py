@@ -51,9 +51,10 @@ def test_the_store_comes_before_everything_that_would_break_the_rule():
     fn = _functions(src)
     # a tick without the translation-row path: before its epoch bump (and so before all of its kernels)
     tick = fn["tick_impl"]
-    assert _before(tick, "if (!rows_path) HIP_TRY(w->ensure_row3_current());", "epochs.tick_without_rows()")
+    assert _before(tick, "if (!plan.rows_path) HIP_TRY(w->ensure_row3_current());", "epochs.tick_without_rows()")
     assert _before(tick, "epochs.tick_without_rows()", "contact_substep(") and _before(tick, "epochs.tick_without_rows()", "launch_tick(")
-    assert _before(tick, "row3.may_defer(true,", "row3.deferred(w->epochs.rows)") and "defer_row3 = rows_path && can_defer" in tick
+    # (which tick defers — a translation-row tick that may — is run, not read: tests/cpp/tick_plan.cpp)
+    assert _before(tick, "bge::TickPlan::of(flags, scene, bge::TickKnobs::from_env(), w->row3)", "if (plan.defer_row3) {") and _before(tick, "if (plan.defer_row3) {", "row3.deferred(w->epochs.rows)")
     # calls that write pos, or move stored matrices, before their epochs_edit()
     assert _before(fn["upload_trs"], "ensure_row3_current()", "upload_rows(")
     assert _before(fn["bge_world_set_topology"], "ensure_row3_current()", "launch_gather_rows(")

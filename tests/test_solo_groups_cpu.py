@@ -4,7 +4,7 @@
   TileShape: all flat, one chain tile, one frozen tile, one tile with an external parent, no tile, no all-Dynamic tile) and the
   schedule (csrc/bge_epochs.hpp SoloPlan on FuseClock's groups: K in 1..9, 17, 1000, T in 1, 2, 3, 8, 32; every tick covered exactly
   once, a group of one launched as a plain tick, the switch off giving round 9's plan).
-* bge_world.cpp takes both from those headers and states neither inline; a launch with n_solo > 1 picks the SOLO instantiation of
+* bge_world.cpp takes both from those headers (through csrc/bge_tick_plan.hpp) and states neither inline; a launch with n_solo > 1 picks the SOLO instantiation of
   k_tick<PHYS, XFORM> and nothing else does."""
 import os
 import re
@@ -35,18 +35,15 @@ def test_tick_impl_takes_shape_and_schedule_from_the_headers():
     # the shape is computed in one place and refreshed wherever a header changes: layout (kHdrFrozen with it) and kHdrAllDynamic
     assert src.count("bge::TileShape::of(") == 1 and "TileShape::of(" not in tick
     assert src.count("refresh_shape();") >= 2
-    # tick_impl: solo = SoloPlan::wanted(fusable, all_flat, switch); the plan decides n_solo and whether the tick launches
-    m = re.search(r"const bool fusable = ([^;]*);", tick)
-    assert m and "w->shape.any_flat_all_dynamic" in [t.strip() for t in m.group(1).split("&&")]
-    assert re.search(r"const bool solo = bge::SoloPlan::wanted\(fusable, w->shape\.all_flat, solo_env\);", tick)
-    assert 'std::getenv("BGE_SOLO_GROUPS")' in tick  # read per call
-    assert tick.count("bge::SoloPlan::plan(") == 1
-    assert len(re.findall(r"\.n_solo\s*=[^=]", src)) == 1 and "p.n_solo = plan.n_solo;" in tick
-    assert re.search(r"for \(size_t pass = 0; pass < n_passes && plan\.launch; \+\+pass\)", tick)
-    # a solo group carries no serial, and a fused launch is never a solo one
-    assert "if (!solo) group_first = w->fuse.begin_group(group_n, &wrapped);" in tick
-    m = re.search(r"const bool fused = ([^;]*);", tick)
-    assert m and "!solo" in [t.strip() for t in m.group(1).split("&&")]
+    # tick_impl takes the plan (TickPlan::of) and each tick's n_solo and launch (TickGroups::next) from csrc/bge_tick_plan.hpp,
+    # whose values tests/cpp/tick_plan.cpp checks; the switches are read once per call, by TickKnobs::from_env alone
+    plan = open(os.path.join(CSRC, "bge_tick_plan.hpp")).read()
+    assert "getenv" not in tick and tick.count("bge::TickKnobs::from_env()") == 1 and src.count("TickKnobs::from_env()") == 1
+    assert tick.count("bge::TickPlan::of(") == 1 and "SoloPlan::" not in src and plan.count("SoloPlan::plan(") == 1
+    assert len(re.findall(r"\.n_solo\s*=[^=]", src + plan)) == 1 and "p.n_solo = group.n_solo;" in tick
+    assert re.search(r"for \(size_t pass = 0; pass < n_passes && group\.launch; \+\+pass\)", tick)
+    # a solo group carries no serial
+    assert "if (!solo_) first_ = clock.begin_group(n_, &wrapped);" in plan
 
 
 def test_only_a_solo_launch_runs_the_solo_instantiation():
