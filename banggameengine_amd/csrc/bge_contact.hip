@@ -72,10 +72,17 @@ __global__ void __launch_bounds__(1024) k_obstacle_grid(GroundParams g)
     while (n < static_cast<int>(kObstacleGridAxis) && static_cast<uint32_t>(n * n) < K) n *= 2;
     const bool any = mnx <= mxx && mnz <= mxz && mxx - mnx < INFINITY && mxz - mnz < INFINITY;
     const float ux = any && mxx > mnx ? static_cast<float>(n) / (mxx - mnx) : 0.0f, uz = any && mxz > mnz ? static_cast<float>(n) / (mxz - mnz) : 0.0f;
-    // pass 1: counts (an obstacle that covers more than 64 cells goes on the wide list instead)
+    // pass 1: counts (an obstacle that covers more than 64 cells goes on the wide list instead).  A LIVE obstacle that cannot be put
+    // on the grid — the common bounds have no finite span (two obstacles 3.6e38 apart, an AABB that holds an infinity), or its own box
+    // is not ordered — makes the grid invalid: the callers then walk all obstacles, as they do without a grid.  (An empty but valid
+    // grid would hide every obstacle from them.)  A scene without a live obstacle keeps its empty, valid grid.
     for (uint32_t k = tid; k < K; k += 1024u) {
         const ObstacleRec& o = g.obstacles[k];
-        if (!any || !o.live || !(o.aabb[0] <= o.aabb[3]) || !(o.aabb[2] <= o.aabb[5])) continue;
+        if (!o.live) continue;
+        if (!any || !(o.aabb[0] <= o.aabb[3]) || !(o.aabb[2] <= o.aabb[5])) {
+            s_bad = 1u;
+            continue;
+        }
         const int x0 = obs_cell(o.aabb[0], mnx, ux, n), x1 = obs_cell(o.aabb[3], mnx, ux, n), z0 = obs_cell(o.aabb[2], mnz, uz, n), z1 = obs_cell(o.aabb[5], mnz, uz, n);
         if ((x1 - x0 + 1) * (z1 - z0 + 1) > 64) {
             const uint32_t at = atomicAdd(&s_wide, 1u);
@@ -187,8 +194,10 @@ __global__ void __launch_bounds__(256) k_ground_select(WorldView w, GroundParams
     // Static / Kinematic box colliders on: a Dynamic BOX that holds manifolds with boxes, or whose reach (conservative: the L1 norm
     // of its half extents bounds its AABB at any orientation, plus this step's motion, plus Bullet's 0.02) touches an obstacle's
     // fed AABB, goes to k_contact_boxes — which decides the pairs exactly and handles the plane for that body too
+    // (g.box_list is null while the obstacle contacts are off: bge_world_set_static_contacts(0) ended every pair and cleared kCiBoxes,
+    //  so nothing may be routed to a list that does not exist)
     bool boxes = false;
-    if (g.n_obstacles != 0u || (ci0 & kCiBoxes)) {
+    if (g.box_list != nullptr && (g.n_obstacles != 0u || (ci0 & kCiBoxes))) {
         if (awake && !(ci0 & kCiCapsule)) {
             boxes = (ci0 & kCiBoxes) != 0;
             if (!boxes) {
@@ -345,7 +354,30 @@ __global__ void __launch_bounds__(64) k_contact_boxes(WorldView w, GroundParams 
     }
 }
 
+// bge_world_set_static_contacts(0): every pair with an obstacle ends.  A body that holds manifold rows (awake or asleep) gives them
+// up — the rows free, kCiBoxes cleared — and nothing else of it changes: a sleeping body stays asleep where it is.
+__global__ void __launch_bounds__(256) k_end_obstacle_pairs(WorldView w, uint64_t n_slots)
+{
+    const uint64_t slot = blockIdx.x * static_cast<uint64_t>(blockDim.x) + threadIdx.x;
+    if (slot >= n_slots) return;
+    const uint32_t ci = w.cinfo[slot];
+    if (!(ci & kCiBoxes)) return;
+    uint32_t* rows = w.bmanifold + slot * (kBoxManifolds * kBoxManifoldWords);
+    for (uint32_t e = 0; e < kBoxManifolds; ++e) {
+        rows[e * kBoxManifoldWords] = kBoxNone;
+        rows[e * kBoxManifoldWords + 1] = 0u;
+    }
+    w.cinfo[slot] = ci & ~kCiBoxes;
+}
+
 } // namespace
+
+hipError_t launch_end_obstacle_pairs(hipStream_t stream, const WorldView& w, uint64_t n_slots)
+{
+    if (n_slots == 0 || !w.bmanifold || !w.cinfo) return hipSuccess;
+    hipLaunchKernelGGL(k_end_obstacle_pairs, dim3(static_cast<uint32_t>((n_slots + 255) / 256)), dim3(256), 0, stream, w, n_slots);
+    return hipGetLastError();
+}
 
 hipError_t launch_ground(hipStream_t stream, const WorldView& w, const GroundParams& g, bool bullet_basis)
 {

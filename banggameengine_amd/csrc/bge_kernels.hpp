@@ -260,6 +260,7 @@ hipError_t launch_pose_only(hipStream_t stream, const WorldView& w, uint64_t n_s
 // launched before launch_tick of the same sub-step.
 // the phases of a sub-step with Dynamic-against-Dynamic contacts (the host reads counts[] back between them: the sorts need them)
 hipError_t launch_obstacles(hipStream_t stream, const WorldView& w, const GroundParams& g);
+hipError_t launch_end_obstacle_pairs(hipStream_t stream, const WorldView& w, uint64_t n_slots); // bge_world_set_static_contacts(0)
 hipError_t launch_island_begin(hipStream_t stream, const WorldView& w, const GroundParams& g, const IslandParams& ip, bool bullet_basis);
 hipError_t launch_island_pair_keys(hipStream_t stream, const WorldView& w, const IslandParams& ip);
 hipError_t island_sort_keys(hipStream_t stream, void* tmp, size_t& tmp_bytes, const uint64_t* in, uint64_t* out, uint32_t n);

@@ -1236,7 +1236,7 @@ int island_substep(bge_world* w, bge::GroundParams& gp, uint64_t n_slots, bool b
     ip.body_slot = w->isl_body_slot.as<uint32_t>();
     ip.n_bodies = n_bodies;
     // every point the manifolds can hold: 4 on the plane + 4 x 4 on obstacles per body (where those are on), 4 per pair; two rows a point
-    const uint64_t own_points = (w->ground_plane ? 4ull : 0ull) + (w->static_contacts_ever ? 4ull * bge::kBoxManifolds : 0ull); // (rows of obstacle manifolds outlive the switch)
+    const uint64_t own_points = (w->ground_plane ? 4ull : 0ull) + (w->static_contacts_ever ? 4ull * bge::kBoxManifolds : 0ull); // (a capacity: switching off ends every obstacle pair, so the rows are only needed while on)
     const uint64_t row_cap = 2ull * (own_points * n_bodies + 4ull * n_pairs) + 2;
     HIP_TRY(w->isl_solver_bodies.ensure(static_cast<size_t>(n_bodies) * bge::kIslBodyBytes));
     HIP_TRY(w->isl_rows.ensure(static_cast<size_t>(row_cap) * bge::kIslRowBytes + static_cast<size_t>(row_cap / 2 + 1) * bge::kIslRowColdBytes));
@@ -2255,6 +2255,12 @@ try {
     DeviceGuard guard(w->device);
     const bool on = enabled != 0;
     if (int rc = on ? make_store(w, w->bmanifold) : BGE_OK) return rc;
+    if (!on && w->static_contacts && w->has_topology && w->bmanifold.p && w->bmanifold.bytes >= w->bmanifold.bytes_for(w->slot_rows())) {
+        // switching off ends every pair with an obstacle here and now: no body keeps a manifold row or kCiBoxes (contact_substep hands
+        // the kernels no obstacle list and no box list while the switch is off, so nothing may still ask for them)
+        HIP_TRY(hipStreamSynchronize(w->stream));
+        HIP_TRY(bge::launch_end_obstacle_pairs(w->stream, w->view, w->slot_rows()));
+    }
     w->static_contacts = on;
     w->static_contacts_ever = w->static_contacts_ever || on;
     w->obstacles_stale = true;

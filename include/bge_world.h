@@ -313,7 +313,11 @@ BGE_API int bge_world_download_contacts(bge_world* world, uint64_t first, uint64
  *       Not built: capsules against boxes (GJK / EPA); Dynamic against Dynamic is bge_world_set_dynamic_contacts.  A body holds at most 4 such manifolds (lowest
  *       entity indices); the Dynamic body is always the pair's body A — Bullet orders a pair by proxy creation, which the
  *       reference leaves to an unordered_map's iteration order (oracle/boxbox_ref.h states every such choice).
- *   bge_world_upload_restitution   RigidBody::restitution per entity (default 0, src/ecs/PhysicsComponents.h:33).
+ *       Switching OFF (1 -> 0) ends every pair with an obstacle at the call: afterwards no body holds a box manifold —
+ *       bge_world_download_box_contacts reports 0 manifolds for every body at once, sleeping ones included — a tick is safe,
+ *       a sleeping body stays asleep where it is (nothing else of any body changes), and a later switch to 1 starts from empty
+ *       manifolds.  The call waits for the world's stream.
+ *   bge_world_upload_restitution  RigidBody::restitution per entity (default 0, src/ecs/PhysicsComponents.h:33).
  *   bge_world_download_box_contacts  per queried entity: n_manifolds[i] in 0..4, header8 = 4 x (other entity index or
  *       0xffffffff, points 0..4) in ascending entity index, points192 = 4 manifolds x 4 points x (localA.xyz, localB.xyz,
  *       normalWorldOnB.xyz, distance, appliedImpulse, appliedImpulseLateral1).  Any of the three may be NULL.

@@ -213,7 +213,7 @@ int orc_get_ground_contacts(void* h, uint32_t id, float* out32)
     return m.n;
 }
 // Dynamic boxes against the scene's Static / Kinematic box colliders (boxbox_ref.h)
-void orc_set_static_contacts(void* h, int enabled) { S(h)->physics.staticContacts = enabled != 0; }
+void orc_set_static_contacts(void* h, int enabled) { S(h)->physics.SetStaticContacts(enabled != 0); }
 void orc_set_restitution(void* h, uint32_t id, float restitution)
 {
     if (RefRigidBody* b = S(h)->scene.GetRigidBody(id)) b->restitution = restitution;

@@ -208,6 +208,20 @@ public:
         uint32_t genA = 0, genB = 0;
     };
 
+    // Switching the obstacle contacts off ends every pair with an obstacle at the call: no body holds a box manifold afterwards (a
+    // sleeping one neither — it stays asleep where it is), and switching on again starts from empty manifolds.  (Without this
+    // StepFreeBody would go on solving manifolds that CollideWithBoxes no longer refreshes.)
+    void SetStaticContacts(bool on)
+    {
+        if (staticContacts && !on) {
+            for (auto& kv : runtime_) {
+                kv.second.boxes.clear();
+                kv.second.boxGeneration.clear();
+            }
+        }
+        staticContacts = on;
+    }
+
     std::unordered_map<EntityId, RefBodyRuntime>& Runtimes() { return runtime_; }
     const std::map<std::pair<EntityId, EntityId>, DynPair>& DynamicPairs() const { return dynPairs_; }
     std::unordered_map<EntityId, RefTriggerRuntime>& TriggerRuntimes() { return triggerRuntime_; }

@@ -75,6 +75,51 @@ def run_world(world, wl, ticks, seed_velocity=True, flags=3, angvel=None):
     return world
 
 
+def build_obstacle_oracle(case, basis=False):
+    """The oracle's scene of a case of refmodel/obstacle_cases.py: plane as the case says, obstacle contacts on, Dynamic boxes against
+    each other off (every body is an island of its own: k_ground_select / k_contact_boxes do all the work)."""
+    ref = build_oracle(case.wl, orient_mode=po.ORIENT_BASIS if basis else po.ORIENT_IDEAL, has_transform=case.has_transform, size=case.size, mass=case.mass)
+    ref.SetGroundPlane(case.plane)
+    ref.SetStaticContacts(case.static)
+    if case.sub_steps:
+        ref.SetAccumulator(True, DT, 4)
+    return ref
+
+
+def compare_obstacle_world(w, ref, tick, dyn, plane, bodies=None):
+    """A world of Dynamic boxes on Static / Kinematic boxes against the oracle after a tick, bit for bit: activation states, the
+    timers of awake bodies, position, rotationEuler, quaternion, both velocities, and of EVERY Dynamic body (dyn: a mask; bodies:
+    the entity indices to take instead, for a world of many thousands) the plane manifold and every box manifold — partner, point count,
+    points, impulses; rows beyond a body's manifolds must be free.  Returns the manifolds per body (n,)."""
+    rb, gb = ref.bulk_bodies(), w.download_bodies()
+    ex = rb["exists"]
+    pos, euler = w.download_pose()
+    rpos, reuler = ref.bulk_pose()
+    st, tm = w.download_activation()
+    rst, rtm = ref.bulk_activation()
+    assert np.array_equal(st[ex], rst[ex].astype(np.uint8)), f"tick {tick}: activation states differ at {np.flatnonzero(ex)[st[ex] != rst[ex]][:8]}"
+    assert_bits_equal(gb["linvel"][dyn], rb["linvel"][dyn], f"tick {tick}: linear velocity")
+    assert_bits_equal(gb["angvel"][dyn], rb["angvel"][dyn], f"tick {tick}: angular velocity")
+    assert_bits_equal(pos, rpos, f"tick {tick}: position")
+    assert_bits_equal(gb["quat"][ex], rb["quat"][ex], f"tick {tick}: quaternion")
+    assert_bits_equal(euler, reuler, f"tick {tick}: rotationEuler")
+    assert_bits_equal(tm[ex & (rst == 1)], rtm[ex & (rst == 1)], f"tick {tick}: deactivation timers")
+    nb, bh, bp = w.download_box_contacts()
+    cn, cpts = w.download_contacts() if plane else (None, None)
+    for e in (np.flatnonzero(dyn) if bodies is None else bodies):
+        want = ref.BoxContacts(int(e) + 1)
+        assert nb[e] == len(want), f"tick {tick}: body {e} has {nb[e]} box manifolds {bh[e].tolist()}, oracle {[(o - 1, len(r)) for o, r in want]}"
+        for k, (other, rows) in enumerate(want):
+            assert bh[e, k, 0] == other - 1 and bh[e, k, 1] == len(rows), f"tick {tick}: body {e} manifold {k}: {bh[e, k]} vs oracle ({other - 1}, {len(rows)})"
+            assert_bits_equal(bp[e, k, :len(rows)], rows, f"tick {tick}: body {e} manifold {k} points")
+        assert (bh[e, len(want):, 0] == NO_PARENT).all() and (bh[e, len(want):, 1] == 0).all(), f"tick {tick}: body {e} reports rows beyond its manifolds"
+        if plane:
+            rn, rpts2 = ref.GroundContacts(int(e) + 1)
+            assert cn[e] == rn, f"tick {tick}: body {e} has {cn[e]} plane contacts, oracle {rn}"
+            assert_bits_equal(cpts[e, :rn], rpts2, f"tick {tick}: plane contact points of body {e}")
+    return nb
+
+
 def compare_dynamic_world(w, ref, tick, dyn, plane, static):
     """A world with Dynamic-against-Dynamic contacts against the oracle after a tick, bit for bit: activation states, the pair cache
     (which pairs, their points, their impulses), velocities, position, quaternion, rotationEuler, the timers of awake bodies, and of

@@ -1148,16 +1148,18 @@ def test_dynamic_boxes_on_static_boxes_match_oracle_bitwise(basis, plane):
     assert slept > 100, slept
 
 
-@pytest.mark.parametrize("grid", [True, False], ids=["grid", "all-pairs"])
-def test_many_static_boxes_through_the_obstacle_grid_match_oracle_bitwise(grid, monkeypatch):
+@pytest.mark.parametrize("grid,basis", [(True, False), (False, False), (True, True), (False, True)],
+                         ids=["grid", "all-pairs", "grid-bullet_basis", "all-pairs-bullet_basis"])
+def test_many_static_boxes_through_the_obstacle_grid_match_oracle_bitwise(grid, basis, monkeypatch):
     """with more than 64 Static / Kinematic boxes the candidate test of a body walks an x-z grid over the obstacles' fed
     AABBs (bge_contact.hip k_obstacle_grid) instead of all of them.  400 blocks of mixed footprint on a jittered 20 x 20 layout —
     neighbours overlap, so that a body can see more than four candidates and the four lowest entities must be the ones kept — plus
     one slab under a quarter of the field and one long wall (both cover more than 64 cells: the wide list), one block far outside
     (stretches the bounds), one Kinematic block that is teleported across the field on the way.  800 Dynamic boxes rain on it.  Pose,
     velocities, every box manifold with its points, activation — bit for bit against the oracle, with the grid and with
-    BGE_OBSTACLE_GRID=0 (every body tests every obstacle)."""
+    BGE_OBSTACLE_GRID=0 (every body tests every obstacle), in both orientation schemes."""
     monkeypatch.setenv("BGE_OBSTACLE_GRID", "1" if grid else "0")
+    flags = B.TICK_ALL | (B.TICK_BULLET_BASIS if basis else 0)
     rng = np.random.default_rng(77)
     n_obs, n_dyn = 404, 800
     n = n_obs + n_dyn
@@ -1190,7 +1192,7 @@ def test_many_static_boxes_through_the_obstacle_grid_match_oracle_bitwise(grid, 
     mass[d] = rng.choice([0.3, 1.0, 5.0], n_dyn)
     friction = rng.choice([0.3, 0.5, 1.0], n).astype(np.float32)
     wl.body_type = body_type
-    ref = build_oracle(wl, orient_mode=po.ORIENT_IDEAL, size=size, mass=mass)
+    ref = build_oracle(wl, orient_mode=po.ORIENT_BASIS if basis else po.ORIENT_IDEAL, size=size, mass=mass)
     for i in range(n):
         ref.SetFriction(i + 1, float(friction[i]))
     ref.SetGroundPlane(True)
@@ -1214,7 +1216,7 @@ def test_many_static_boxes_through_the_obstacle_grid_match_oracle_bitwise(grid, 
                 w.upload_trs(pos=home, first=402)
             ref.PhysicsSystemUpdate(DT)
             ref.TransformSystemUpdate()
-            w.tick(dt=DT, flags=B.TICK_ALL)
+            w.tick(dt=DT, flags=flags)
             if tick % 6 and tick > 6 and not (118 <= tick <= 124):
                 continue
             rb, gb = ref.bulk_bodies(), w.download_bodies()
