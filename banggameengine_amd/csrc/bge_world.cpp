@@ -36,6 +36,7 @@
 #include "bge_character.hpp"
 #include "bge_chartrig.hpp"
 #include "bge_ride.hpp"
+#include "bge_crowd.hpp"
 #include "bge_query.hpp"
 
 namespace {
@@ -409,6 +410,16 @@ struct bge_world {
     DevBuf char_ride;
     bool ride_on = false;
     uint32_t ride_flags = 0;
+    // crowd separation (bge_crowd.hip): staging for the host entry point, the snapshot records, the grid path's per-sphere
+    // {bucket, rank}, bucket counts / offsets, scan storage and r_max word; the resident bge_crowd_hit records and filters of the
+    // character set while its crowd is on
+    DevBuf crowd_in, crowd_out, crowd_rec_a, crowd_rec_b, crowd_cell, crowd_count, crowd_start, crowd_scan, crowd_rmax;
+    uint32_t crowd_scan_table = 0; // the table size crowd_scan is sized for
+    size_t crowd_scan_bytes = 0;
+    DevBuf char_crowd_hits, char_crowd_group, char_crowd_mask;
+    bool char_crowd_on = false;
+    float char_crowd_max_push = 0.0f;
+    float char_r_max = 0.0f; // the largest desc.radius of the set
     // character trigger events (bge_chartrig.hip): the per-character filters, the two [triggers][ceil(n / 64)] bitmaps
     // (ct_bits[ct_rem] = remembered, the other = remembered before the last update call), the per-(ghost, word) counts / offsets, the
     // per-ghost totals, bases and {trigger, entity} of the last call, the event list and its count
@@ -509,7 +520,7 @@ struct bge_world {
         for (DevBuf* b : std::initializer_list<DevBuf*>{&flags, &parent, &tile_hdr, &slot_of_entity, &entity_of_slot, &root_slots, &root_index, &root_worlds, &counter, &stage,
                           &stage2, &mass_palette, &normal, &filter_table, &grav_palette, &bp_partials, &obstacle_slots, &obstacle_gen, &obstacles, &obstacle_grid, &box_list, &box_count, &frozen, &rs_word, &adv, &trig_slot, &trig_entity, &trig_he, &trig_group,
                           &trig_mask, &trig_active, &trig_aabb, &trig_pairs, &trig_count, &trig_lists, &ground_list, &ground_count, &trig_tab[0], &trig_tab[1],
-                          &trig_delta_dev, &trig_keys_dev, &trig_pose, &query_in, &query_out, &query_keys, &query_all, &query_all_count, &query_ghosts, &move_in, &move_out, &move_state, &move_casts, &move_hits, &step_in, &step_out, &step_state, &step_casts, &step_hits, &recover_in, &recover_out, &recover_state, &recover_queries, &recover_hits, &char_desc, &char_input, &char_state, &char_recover_in, &char_recover_out, &char_step_in, &char_step_out, &char_scratch, &char_ride, &ct_group, &ct_mask, &ct_bits[0], &ct_bits[1], &ct_counts, &ct_row_total, &ct_row_base, &ct_ghost_rec, &ct_events, &ct_count, &ct_src_row, &dbg_block_sum, &dbg_block_off,
+                          &trig_delta_dev, &trig_keys_dev, &trig_pose, &query_in, &query_out, &query_keys, &query_all, &query_all_count, &query_ghosts, &move_in, &move_out, &move_state, &move_casts, &move_hits, &step_in, &step_out, &step_state, &step_casts, &step_hits, &recover_in, &recover_out, &recover_state, &recover_queries, &recover_hits, &char_desc, &char_input, &char_state, &char_recover_in, &char_recover_out, &char_step_in, &char_step_out, &char_scratch, &char_ride, &crowd_in, &crowd_out, &crowd_rec_a, &crowd_rec_b, &crowd_cell, &crowd_count, &crowd_start, &crowd_scan, &crowd_rmax, &char_crowd_hits, &char_crowd_group, &char_crowd_mask, &ct_group, &ct_mask, &ct_bits[0], &ct_bits[1], &ct_counts, &ct_row_total, &ct_row_base, &ct_ghost_rec, &ct_events, &ct_count, &ct_src_row, &dbg_block_sum, &dbg_block_off,
                           &dbg_lines, &dbg_total, &bounds, &cull_ballots, &cull_block_sum, &cull_block_off, &cull_out, &cull_total, &draw_keys,
                           &batch_sort, &batch_hist, &batch_out}) {
             b->release();
@@ -3637,6 +3648,13 @@ static_assert(sizeof(bge_character_state) == 80, "bge_character_state is 80 byte
 
 namespace {
 
+void char_crowd_off(bge_world* w)
+{
+    w->char_crowd_on = false;
+    w->char_crowd_max_push = 0.0f;
+    for (DevBuf* b : {&w->char_crowd_hits, &w->char_crowd_group, &w->char_crowd_mask}) b->release();
+}
+
 int check_character_range(const bge_world* w, uint64_t first, uint64_t count)
 {
     if (first > w->n_characters || count > w->n_characters - first) {
@@ -3682,6 +3700,9 @@ try {
     w->ride_on = false; // (and so do the ride records)
     w->ride_flags = 0;
     w->char_ride.release();
+    char_crowd_off(w); // (and the crowd's filters and hit records)
+    w->char_r_max = 0.0f;
+    for (uint64_t i = 0; i < n; ++i) w->char_r_max = std::max(w->char_r_max, descs[i].radius);
     if (n == 0) {
         for (DevBuf* b : {&w->char_desc, &w->char_input, &w->char_state, &w->char_recover_in, &w->char_recover_out, &w->char_step_in, &w->char_step_out,
                           &w->char_scratch}) {
@@ -3771,6 +3792,82 @@ try {
 }
 BGE_CATCH_ALL("bge_world_characters_warp")
 
+
+// ---------------------------------------------------------------- crowd separation (bge_crowd.hip)
+static_assert(sizeof(bge_crowd_sphere) == 24, "bge_crowd_sphere is 24 bytes (include/bge_world.h)");
+static_assert(sizeof(bge_crowd_hit) == 32, "bge_crowd_hit is 32 bytes (include/bge_world.h)");
+
+namespace {
+
+constexpr uint64_t kCrowdGridMinDefault = 256; // the smallest measured size, and the grid path is ahead there
+
+// Sizes the temporaries for n spheres (both paths: BGE_CROWD_GRID_MIN is read per call) and names them in p
+int crowd_reserve(bge_world* w, uint64_t n, bge::CrowdParams& p)
+{
+    const uint32_t table = bge::crowd_table_size(n);
+    if (w->crowd_scan_table != table) {
+        w->crowd_scan_bytes = bge::crowd_scan_bytes(table);
+        w->crowd_scan_table = table;
+    }
+    HIP_TRY(w->crowd_rec_a.ensure(n * 16));
+    HIP_TRY(w->crowd_rec_b.ensure(n * 16));
+    HIP_TRY(w->crowd_cell.ensure(n * 8));
+    HIP_TRY(w->crowd_count.ensure(size_t(table) * 4));
+    HIP_TRY(w->crowd_start.ensure(size_t(table) * 4));
+    HIP_TRY(w->crowd_scan.ensure(std::max<size_t>(w->crowd_scan_bytes, 16)));
+    HIP_TRY(w->crowd_rmax.ensure(4));
+    p.rec_a = w->crowd_rec_a.p;
+    p.rec_b = w->crowd_rec_b.p;
+    p.cell = w->crowd_cell.as<uint32_t>();
+    p.count = w->crowd_count.as<uint32_t>();
+    p.start = w->crowd_start.as<uint32_t>();
+    p.scan_tmp = w->crowd_scan.p;
+    p.scan_bytes = w->crowd_scan_bytes;
+    p.table = table;
+    uint64_t grid_min = kCrowdGridMinDefault;
+    if (const char* e = std::getenv("BGE_CROWD_GRID_MIN")) grid_min = std::strtoull(e, nullptr, 10);
+    p.grid = n >= grid_min ? 1u : 0u;
+    return BGE_OK;
+}
+
+int crowd_check_max_push(float max_push)
+{
+    if (!(std::isfinite(max_push) && max_push >= 0.0f)) return fail(BGE_ERR_INVALID, "max_push = %g: must be finite and >= 0", (double)max_push);
+    return BGE_OK;
+}
+
+int crowd_query_enqueue(bge_world* w, uint64_t n, const void* spheres, float max_push, void* hits)
+{
+    bge::CrowdParams p{};
+    if (int rc = crowd_reserve(w, n, p)) return rc;
+    const uint32_t* s = static_cast<const uint32_t*>(spheres);
+    p.src = bge::CrowdSource{s, s + 3, s + 4, s + 5, 6u, 6u, 6u, 6u};
+    p.n = static_cast<uint32_t>(n);
+    p.max_push = max_push;
+    p.hits = hits;
+    p.r_max_device = w->crowd_rmax.as<uint32_t>();
+    HIP_TRY(bge::launch_crowd(w->stream, p));
+    return BGE_OK;
+}
+
+// Separate of one step: the character set as the batch, the push applied to state.position
+int char_crowd_params(bge_world* w, bge::CrowdParams& p)
+{
+    const uint64_t n = w->n_characters;
+    if (int rc = crowd_reserve(w, n, p)) return rc; // (sized by bge_world_characters_crowd: nothing is allocated here)
+    uint32_t* state = w->char_state.as<uint32_t>();
+    p.src = bge::CrowdSource{state, w->char_desc.as<uint32_t>() + 3, w->char_crowd_group.as<uint32_t>(), w->char_crowd_mask.as<uint32_t>(),
+                             20u, 12u, 1u, 1u};
+    p.n = static_cast<uint32_t>(n);
+    p.max_push = w->char_crowd_max_push;
+    p.hits = w->char_crowd_hits.p;
+    p.apply_position = state;
+    p.r_max_host = w->char_r_max;
+    return BGE_OK;
+}
+
+} // namespace
+
 int bge_world_characters_update(bge_world* w, float dt, uint32_t steps)
 try {
     if (!w) return fail(BGE_ERR_INVALID, "world is NULL");
@@ -3808,7 +3905,14 @@ try {
         r.slot_of_entity = q.slot_of_entity;
         HIP_TRY(bge::launch_char_carry(w->stream, r));
     }
+    bge::CrowdParams cp{};
+    if (w->char_crowd_on) {
+        if (int rc = char_crowd_params(w, cp)) return rc;
+    }
     for (uint32_t k = 0; k < steps; ++k) {
+        if (w->char_crowd_on) {
+            HIP_TRY(bge::launch_crowd(w->stream, cp)); // Separate
+        }
         HIP_TRY(bge::launch_char_begin(w->stream, c, k == 0 ? 1u : 0u));
         if (int rc = recover_enqueue(w, qr, n, w->char_recover_in.p, w->char_recover_out.p)) return rc;
         HIP_TRY(bge::launch_char_move(w->stream, c));
@@ -3911,6 +4015,103 @@ try {
     return BGE_OK;
 }
 BGE_CATCH_ALL("bge_world_characters_rides_device")
+
+
+// ---------------------------------------------------------------- crowd separation: the entry points (bge_crowd.hip)
+int bge_world_crowd_query(bge_world* w, uint64_t n, const bge_crowd_sphere* spheres, float max_push, bge_crowd_hit* hits)
+try {
+    if (!w) return fail(BGE_ERR_INVALID, "world is NULL");
+    if (int rc = crowd_check_max_push(max_push)) return rc;
+    if (n == 0) return BGE_OK;
+    if (!spheres || !hits) return fail(BGE_ERR_INVALID, "NULL argument");
+    if (n > 0x3fffffffull) return fail(BGE_ERR_INVALID, "n = %llu: at most 2^30 - 1 spheres", (unsigned long long)n);
+    DeviceGuard guard(w->device);
+    HIP_TRY(w->crowd_in.ensure(n * sizeof(bge_crowd_sphere)));
+    HIP_TRY(w->crowd_out.ensure(n * sizeof(bge_crowd_hit)));
+    HIP_TRY(hipMemcpyAsync(w->crowd_in.p, spheres, n * sizeof(bge_crowd_sphere), hipMemcpyHostToDevice, w->stream));
+    if (int rc = crowd_query_enqueue(w, n, w->crowd_in.p, max_push, w->crowd_out.p)) return rc;
+    HIP_TRY(hipMemcpyAsync(hits, w->crowd_out.p, n * sizeof(bge_crowd_hit), hipMemcpyDeviceToHost, w->stream));
+    HIP_TRY(hipStreamSynchronize(w->stream));
+    return BGE_OK;
+}
+BGE_CATCH_ALL("bge_world_crowd_query")
+
+int bge_world_crowd_query_device(bge_world* w, uint64_t n, const void* spheres_device, float max_push, void* hits_device)
+try {
+    if (!w) return fail(BGE_ERR_INVALID, "world is NULL");
+    if (int rc = crowd_check_max_push(max_push)) return rc;
+    if (n == 0) return BGE_OK;
+    if (!spheres_device || !hits_device) return fail(BGE_ERR_INVALID, "NULL argument");
+    if ((reinterpret_cast<uintptr_t>(spheres_device) | reinterpret_cast<uintptr_t>(hits_device)) & 3u) {
+        return fail(BGE_ERR_INVALID, "spheres_device and hits_device must be 4-byte aligned");
+    }
+    if (n > 0x3fffffffull) return fail(BGE_ERR_INVALID, "n = %llu: at most 2^30 - 1 spheres", (unsigned long long)n);
+    DeviceGuard guard(w->device);
+    return crowd_query_enqueue(w, n, spheres_device, max_push, hits_device);
+}
+BGE_CATCH_ALL("bge_world_crowd_query_device")
+
+int bge_world_characters_crowd(bge_world* w, uint32_t flags, float max_push, uint64_t n, const uint32_t* group, const uint32_t* mask)
+try {
+    if (!w) return fail(BGE_ERR_INVALID, "world is NULL");
+    if (flags & ~uint32_t(BGE_CHAR_CROWD_ON)) return fail(BGE_ERR_INVALID, "flags = %#x: unknown bits", flags);
+    DeviceGuard guard(w->device);
+    if (flags == 0u) {
+        if (w->char_crowd_on) {
+            HIP_TRY(hipStreamSynchronize(w->stream)); // (an update may still be writing the records)
+        }
+        char_crowd_off(w);
+        return BGE_OK;
+    }
+    if (int rc = crowd_check_max_push(max_push)) return rc;
+    if (w->n_characters == 0) return fail(BGE_ERR_INVALID, "there is no character set to switch the crowd on for");
+    if (n != w->n_characters) {
+        return fail(BGE_ERR_INVALID, "n = %llu, the set holds %llu characters", (unsigned long long)n, (unsigned long long)w->n_characters);
+    }
+    HIP_TRY(hipStreamSynchronize(w->stream)); // (an update may still be reading the filters)
+    bge::CrowdParams sized{};
+    if (int rc = crowd_reserve(w, n, sized)) return rc;
+    HIP_TRY(w->char_crowd_group.ensure(n * 4));
+    HIP_TRY(w->char_crowd_mask.ensure(n * 4));
+    const std::vector<uint32_t> ones(group ? 0 : n, 1u), all(mask ? 0 : n, 0xffffffffu);
+    HIP_TRY(hipMemcpyAsync(w->char_crowd_group.p, group ? group : ones.data(), n * 4, hipMemcpyHostToDevice, w->stream));
+    HIP_TRY(hipMemcpyAsync(w->char_crowd_mask.p, mask ? mask : all.data(), n * 4, hipMemcpyHostToDevice, w->stream));
+    if (!w->char_crowd_on) {
+        HIP_TRY(w->char_crowd_hits.ensure(n * sizeof(bge_crowd_hit)));
+        HIP_TRY(hipMemsetAsync(w->char_crowd_hits.p, 0, n * sizeof(bge_crowd_hit), w->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(w->stream)); // (the copies read the caller's and this function's memory)
+    w->char_crowd_on = true;
+    w->char_crowd_max_push = max_push;
+    return BGE_OK;
+}
+BGE_CATCH_ALL("bge_world_characters_crowd")
+
+int bge_world_characters_crowd_hits(bge_world* w, uint64_t first, uint64_t count, bge_crowd_hit* out)
+try {
+    if (!w) return fail(BGE_ERR_INVALID, "world is NULL");
+    if (int rc = check_character_range(w, first, count)) return rc;
+    DeviceGuard guard(w->device);
+    if (count == 0) {
+        HIP_TRY(hipStreamSynchronize(w->stream));
+        return BGE_OK;
+    }
+    if (!w->char_crowd_on) return fail(BGE_ERR_INVALID, "the character crowd is off");
+    if (!out) return fail(BGE_ERR_INVALID, "out is NULL");
+    HIP_TRY(hipMemcpyAsync(out, w->char_crowd_hits.as<bge_crowd_hit>() + first, count * sizeof(bge_crowd_hit), hipMemcpyDeviceToHost, w->stream));
+    HIP_TRY(hipStreamSynchronize(w->stream));
+    return BGE_OK;
+}
+BGE_CATCH_ALL("bge_world_characters_crowd_hits")
+
+int bge_world_characters_crowd_hits_device(bge_world* w, void** hits, uint64_t* n)
+try {
+    if (!w || !hits || !n) return fail(BGE_ERR_INVALID, "NULL argument");
+    *hits = w->char_crowd_on ? w->char_crowd_hits.p : nullptr;
+    *n = w->char_crowd_on ? w->n_characters : 0;
+    return BGE_OK;
+}
+BGE_CATCH_ALL("bge_world_characters_crowd_hits_device")
 
 // ---------------------------------------------------------------- character trigger events (bge_chartrig.hip)
 static_assert(sizeof(bge_character_trigger_event) == 12, "bge_character_trigger_event is 12 bytes (include/bge_world.h)");

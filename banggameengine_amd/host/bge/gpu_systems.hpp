@@ -170,6 +170,17 @@ template <class Vec3> struct GpuCharacterRide {
     float turn[4] = {0.0f, 0.0f, 0.0f, 1.0f}; // xyzw: the platform's rotation since the call before, for the caller's facing
 };
 
+// What GetCharacterCrowd returns (extension: include/bge_world.h "Crowd separation"): what the last step of the last
+// UpdateCharacters found around the character, as of the last SyncCharacters
+template <class Vec3> struct GpuCharacterCrowd {
+    bool pushed = false;   // another character overlapped this one and it was pushed away from the deepest
+    bool clamped = false;  // the push was cut to maxPush
+    uint32_t other = 0;    // EntityId of that character; kInvalidEntity (0) if none
+    uint32_t overlaps = 0; // how many characters overlapped this one
+    float depth = 0.0f;    // by how much `other` did
+    Vec3 push{};           // what the step added to the position (level: y is 0)
+};
+
 struct GpuTriggerEvent {
     enum class Type { Enter, Stay, Exit };
     Type type = Type::Enter;
@@ -804,6 +815,8 @@ public:
         char_trigger_events_.clear();
         char_ride_applied_ = 0u; // (and riding)
         char_rides_.clear();
+        char_crowd_applied_ = false; // (and the crowd)
+        char_crowd_hits_.clear();
         if (ok() && bge_world_characters_create(world_, 0, nullptr) != BGE_OK) Log("bge_world_characters_create");
     }
     // EXTENSION: trigger events for the characters (include/bge_world.h "Character trigger events"), off by default: every
@@ -839,6 +852,31 @@ public:
         out.platform = r.entity != BGE_RAY_NO_ENTITY && r.entity < ids_.size() ? ids_[r.entity] : Id{0};
         out.carriedBy.x = r.carried[0], out.carriedBy.y = r.carried[1], out.carriedBy.z = r.carried[2];
         for (int k = 0; k < 4; ++k) out.turn[k] = r.turn[k];
+        return true;
+    }
+    // EXTENSION: characters push each other apart (include/bge_world.h "Crowd separation"), off by default: every step of
+    // UpdateCharacters begins by moving each character away from the character that overlaps it deepest, by half the overlap and
+    // at most maxPush (0 = no limit).  Every character is of group 1 and sees all.  Applied by the next UpdateCharacters, and
+    // again whenever AddCharacter re-creates the set.
+    void SetCharacterCrowd(bool on, float maxPush = 0.0f)
+    {
+        char_crowd_want_ = on;
+        char_crowd_max_push_ = on ? maxPush : 0.0f;
+        if (!on) char_crowd_hits_.clear();
+    }
+    // what the last step of the last UpdateCharacters found, as of the last SyncCharacters; false while the crowd is off
+    template <class Vec3> bool GetCharacterCrowd(Id entity, GpuCharacterCrowd<Vec3>& out) const
+    {
+        auto it = char_index_.find(entity);
+        if (it == char_index_.end() || it->second >= char_crowd_hits_.size()) return false;
+        const bge_crowd_hit& h = char_crowd_hits_[it->second];
+        out = GpuCharacterCrowd<Vec3>{};
+        out.pushed = (h.flags & BGE_CROWD_PUSHED) != 0u;
+        out.clamped = (h.flags & BGE_CROWD_CLAMPED) != 0u;
+        out.other = h.other != BGE_RAY_NO_ENTITY && h.other < char_ids_.size() ? char_ids_[h.other] : Id{0};
+        out.overlaps = h.n_overlaps;
+        out.depth = h.depth;
+        out.push.x = h.push[0], out.push.y = h.push[1], out.push.z = h.push[2];
         return true;
     }
     size_t CharacterCount() const { return char_ids_.size(); }
@@ -896,6 +934,15 @@ public:
             char_inputs_stale_ = true;
             char_trig_watching_ = false;
             char_ride_applied_ = 0u; // (creating the set switched riding off)
+            char_crowd_applied_ = false; // (and the crowd)
+        }
+        if (char_crowd_want_ != char_crowd_applied_ || (char_crowd_want_ && char_crowd_max_push_ != char_crowd_applied_push_)) {
+            if (bge_world_characters_crowd(world_, char_crowd_want_ ? static_cast<uint32_t>(BGE_CHAR_CROWD_ON) : 0u, char_crowd_max_push_,
+                                           char_crowd_want_ ? char_descs_.size() : 0, nullptr, nullptr) != BGE_OK) {
+                return Log("bge_world_characters_crowd");
+            }
+            char_crowd_applied_ = char_crowd_want_;
+            char_crowd_applied_push_ = char_crowd_max_push_;
         }
         if (char_ride_want_ != char_ride_applied_) {
             if (bge_world_characters_ride(world_, char_ride_want_) != BGE_OK) return Log("bge_world_characters_ride");
@@ -939,6 +986,11 @@ public:
         if (!char_rides_.empty() && bge_world_characters_rides(world_, 0, char_rides_.size(), char_rides_.data()) != BGE_OK) {
             char_rides_.clear();
             return Log("bge_world_characters_rides");
+        }
+        char_crowd_hits_.resize(char_crowd_applied_ ? char_ids_.size() : 0);
+        if (!char_crowd_hits_.empty() && bge_world_characters_crowd_hits(world_, 0, char_crowd_hits_.size(), char_crowd_hits_.data()) != BGE_OK) {
+            char_crowd_hits_.clear();
+            return Log("bge_world_characters_crowd_hits");
         }
         return FetchCharacterTriggerEvents(scene);
     }
@@ -1532,6 +1584,9 @@ private:
     // character platform riding: the flags wanted, the flags the device has, the records as last synced
     uint32_t char_ride_want_ = 0u, char_ride_applied_ = 0u;
     std::vector<bge_character_ride> char_rides_;
+    bool char_crowd_want_ = false, char_crowd_applied_ = false;
+    float char_crowd_max_push_ = 0.0f, char_crowd_applied_push_ = 0.0f;
+    std::vector<bge_crowd_hit> char_crowd_hits_;
 
     template <class Vec3> static bge_sphere_cast MakeCast(const Vec3& o, const Vec3& d, float maxDistance, float radius, uint32_t layerMask)
     {
@@ -1806,6 +1861,7 @@ public:
         if (!lastScene_) return false;
         GpuMirrors<SceneT>::Of(*lastScene_).SetCharacterTriggerEvents(characterTriggerEvents_);
         GpuMirrors<SceneT>::Of(*lastScene_).SetCharacterPlatformRiding(characterRiding_, characterRidingDynamic_);
+        GpuMirrors<SceneT>::Of(*lastScene_).SetCharacterCrowd(characterCrowd_, characterCrowdMaxPush_);
         return GpuMirrors<SceneT>::Of(*lastScene_).UpdateCharacters(dt, steps);
     }
     bool SyncCharacters(SceneT& scene) { return GpuMirrors<SceneT>::Of(scene).SyncCharacters(scene); }
@@ -1836,6 +1892,21 @@ public:
     template <class Vec3> bool GetCharacterRide(typename GpuSceneMirror<SceneT>::Id entity, GpuCharacterRide<Vec3>& out) const
     {
         return lastScene_ && GpuMirrors<SceneT>::Of(*lastScene_).GetCharacterRide(entity, out);
+    }
+    // EXTENSION: characters push each other apart (include/bge_world.h "Crowd separation"), off by default.  In the reference the
+    // character ghosts block each other's sweeps; here every step begins by parting overlapping characters by half their overlap
+    // (at most maxPush per step; 0 = no limit), level, away from the deepest neighbour.  A push, not a cast: two characters may
+    // overlap by what one step walked.
+    void SetCharacterCrowd(bool on, float maxPush = 0.0f)
+    {
+        characterCrowd_ = on;
+        characterCrowdMaxPush_ = on ? maxPush : 0.0f;
+        if (lastScene_) GpuMirrors<SceneT>::Of(*lastScene_).SetCharacterCrowd(characterCrowd_, characterCrowdMaxPush_);
+    }
+    // what the last step of the last UpdateCharacters found around the character, as of the last SyncCharacters
+    template <class Vec3> bool GetCharacterCrowd(typename GpuSceneMirror<SceneT>::Id entity, GpuCharacterCrowd<Vec3>& out) const
+    {
+        return lastScene_ && GpuMirrors<SceneT>::Of(*lastScene_).GetCharacterCrowd(entity, out);
     }
     // as of the last SyncCharacters
     bool CharacterOnGround(typename GpuSceneMirror<SceneT>::Id entity) const
@@ -1975,6 +2046,8 @@ private:
     SceneT* lastScene_ = nullptr; // the scene whose world the ray queries read
     bool characterTriggerEvents_ = false; // SetCharacterTriggerEvents: handed to the scene's mirror by UpdateCharacters
     bool characterRiding_ = false, characterRidingDynamic_ = false; // SetCharacterPlatformRiding: the same
+    bool characterCrowd_ = false;                                   // SetCharacterCrowd: the same
+    float characterCrowdMaxPush_ = 0.0f;
     bool debugDrawEnabled_ = false;
     bge_debug_desc debugDesc_{static_cast<uint32_t>(sizeof(bge_debug_desc)), BGE_DEBUG_ALL, 0u, {0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f}};
     DebugLineBuffer debugLines_;

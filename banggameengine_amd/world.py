@@ -176,6 +176,24 @@ CHAR_RIDE_CARRIED, CHAR_RIDE_LOST = 1, 2
 CHARACTER_RIDE_DTYPE = np.dtype([("flags", "<u4"), ("entity", "<u4"), ("anchor_position", "<f4", (3,)), ("anchor_rotation", "<f4", (4,)),
                                  ("carried", "<f4", (3,)), ("turn", "<f4", (4,))])
 assert CHARACTER_RIDE_DTYPE.itemsize == 64
+# crowd separation (bge_world_crowd_query*, bge_world_characters_crowd ..): bge_crowd_flags, bge_character_crowd_mode and the records
+CROWD_INVALID, CROWD_PUSHED, CROWD_CLAMPED = 1, 2, 4
+CHAR_CROWD_ON = 1
+CROWD_SPHERE_DTYPE = np.dtype([("center", "<f4", (3,)), ("radius", "<f4"), ("group", "<u4"), ("mask", "<u4")])
+CROWD_HIT_DTYPE = np.dtype([("flags", "<u4"), ("other", "<u4"), ("n_overlaps", "<u4"), ("depth", "<f4"), ("push", "<f4", (3,)),
+                            ("reserved", "<u4")])
+assert CROWD_SPHERE_DTYPE.itemsize == 24 and CROWD_HIT_DTYPE.itemsize == 32
+
+
+def make_crowd_spheres(centers, radius=0.5, group=1, mask=0xFFFFFFFF):
+    """bge_crowd_sphere records: centers (n, 3); every other argument a scalar or one value per sphere."""
+    c = np.ascontiguousarray(centers, np.float32).reshape(-1, 3)
+    spheres = np.zeros(len(c), CROWD_SPHERE_DTYPE)
+    spheres["center"] = c
+    spheres["radius"] = np.broadcast_to(np.asarray(radius, np.float32), (len(c),))
+    spheres["group"] = np.broadcast_to(np.asarray(group, np.uint64).astype(np.uint32), (len(c),))
+    spheres["mask"] = np.broadcast_to(np.asarray(mask, np.uint64).astype(np.uint32), (len(c),))
+    return spheres
 
 
 def make_characters(positions, radius=0.5, skin=0.01, step_height=0.35, min_ground_ny=0.7071068, probe_distance=0.1, gravity=9.81, jump_speed=5.0,
@@ -768,6 +786,51 @@ class World:
         """(device pointer, n) of the resident bge_character_ride[n]; (0, 0) while riding is off."""
         ptr, n = C.c_void_p(), C.c_uint64()
         check(lib().bge_world_characters_rides_device(self._h, C.byref(ptr), C.byref(n)))
+        return int(ptr.value or 0), int(n.value)
+
+    # -- crowd separation (include/bge_world.h "Crowd separation" states the rule)
+    def crowd_query(self, spheres, max_push=0.0):
+        """Every sphere of the batch against every other: spheres is a CROWD_SPHERE_DTYPE array (make_crowd_spheres()); a
+        CROWD_HIT_DTYPE array comes back (flags, the deepest overlapping sphere, the number of overlaps, its depth, the level push
+        away from it).  max_push > 0 limits the push.  Uses nothing of the world but its stream."""
+        spheres = np.ascontiguousarray(spheres, CROWD_SPHERE_DTYPE)
+        hits = np.zeros(len(spheres), CROWD_HIT_DTYPE)
+        check(lib().bge_world_crowd_query(self._h, len(spheres), _p(spheres) if len(spheres) else None, float(max_push),
+                                          _p(hits) if len(spheres) else None))
+        return hits
+
+    def crowd_query_device(self, spheres, hits, max_push=0.0):
+        """The same between device tensors: spheres holds n bge_crowd_sphere records (24 bytes each, e.g. a uint8 tensor made from
+        make_crowd_spheres()), hits room for n bge_crowd_hit records (32 bytes each).  Enqueued on the world's stream without
+        synchronisation, as raycast_device()."""
+        n = _device_records(spheres, hits, "spheres", "hits", 24, 32)
+        check(lib().bge_world_crowd_query_device(self._h, n, C.c_void_p(spheres.data_ptr()), float(max_push), C.c_void_p(hits.data_ptr())))
+
+    def characters_crowd(self, on=True, max_push=0.0, group=None, mask=None):
+        """Switches crowd separation on (every step of characters_update() begins by pushing overlapping characters apart) or off.
+        group, mask: one value per character or a scalar (default 1 and 0xffffffff).  Calling it again replaces them and max_push."""
+        if not on:
+            check(lib().bge_world_characters_crowd(self._h, 0, 0.0, 0, None, None))
+            return
+        n = self.characters_state_device()[1]
+        pick = lambda a: None if a is None else np.ascontiguousarray(np.broadcast_to(np.asarray(a, np.uint64).astype(np.uint32), (n,)))
+        g, m = pick(group), pick(mask)
+        check(lib().bge_world_characters_crowd(self._h, CHAR_CROWD_ON, float(max_push), n, None if g is None else _p(g),
+                                               None if m is None else _p(m)))
+
+    def characters_crowd_hits(self, first=0, count=None):
+        """The crowd records of characters first .. first + count (all of them by default) as the last update call's last step
+        left them: a CROWD_HIT_DTYPE array.  Synchronises the world's stream."""
+        if count is None:
+            count = self.characters_state_device()[1] - first
+        hits = np.zeros(max(count, 0), CROWD_HIT_DTYPE)
+        check(lib().bge_world_characters_crowd_hits(self._h, first, count, _p(hits) if count > 0 else None))
+        return hits
+
+    def characters_crowd_hits_device(self):
+        """(device pointer, n) of the resident bge_crowd_hit[n]; (0, 0) while the crowd is off."""
+        ptr, n = C.c_void_p(), C.c_uint64()
+        check(lib().bge_world_characters_crowd_hits_device(self._h, C.byref(ptr), C.byref(n)))
         return int(ptr.value or 0), int(n.value)
 
     # -- character trigger events (include/bge_world.h "Character trigger events" states the rule and the order of the list)

@@ -829,7 +829,8 @@ BGE_API int bge_world_sphere_recover_device(bge_world* world, uint64_t n, const 
  *             open there is a swept carry and inherited velocity.  Trigger volumes report characters through "Character trigger events" below,
  *             with what remains open there: the box is the sphere's, not a capsule's; the world's own bge_world_trigger_events
  *             still does not see characters; characters do not report each other.
- *   Characters are not bodies: no query sees them, they do not see each other, and no call here changes any other world state.
+ *   Characters are not bodies: no query sees them, they see each other only through "Crowd separation" below once it is switched on
+ *   (a push; they do not block each other's sweeps), and no call here changes any other world state.
  *   bge_world_characters_create   replaces the set with n characters made from descs; n = 0 removes it (descs may then be NULL).
  *                                 Every desc is checked on the host: every float finite, radius >= 0, skin > 0, step_height >= 0,
  *                                 probe_distance >= 0, gravity >= 0, jump_speed >= 0, fall_speed > 0, layer_mask != 0; a bad desc is
@@ -1044,6 +1045,93 @@ typedef struct bge_character_ride {
 BGE_API int bge_world_characters_ride(bge_world* world, uint32_t flags);
 BGE_API int bge_world_characters_rides(bge_world* world, uint64_t first, uint64_t count, bge_character_ride* out);
 BGE_API int bge_world_characters_rides_device(bge_world* world, void** rides, uint64_t* n);
+
+/*
+ * Crowd separation: spheres of a batch push each other apart, and so do the device's characters once switched on (DESIGN.md
+ * 4.23).  In the reference every character's ghost is in the Bullet world with group 2 and mask all, so the sweeps of
+ * btKinematicCharacterController see the other characters and characters block each other; here the characters part by a level
+ * push at the head of every step.  The rule below is the specification.  All arithmetic is binary32, one rounding per operation,
+ * left to right, as in "Sphere moves"; sqrtf and / are the correctly rounded ones.
+ *   Crowd query  a stateless query over a batch of n spheres against EACH OTHER: of the world it uses only the stream and the device.
+ *   Valid     a sphere is valid iff its four floats are finite and radius >= 0.  An invalid sphere gets flags = BGE_CROWD_INVALID,
+ *             other = BGE_RAY_NO_ENTITY and every other word 0, and it is not there for the others.
+ *   Pair      for i != j, both valid: a candidate iff (group_i & mask_j) != 0 && (group_j & mask_i) != 0.  Then
+ *                  d[k] = c_i[k] - c_j[k];  d2 = (d.x*d.x + d.y*d.y) + d.z*d.z;  R = r_i + r_j;  depth = R - sqrtf(d2)
+ *             and the pair overlaps iff depth > 0.  Both ends compute the same depth, bit for bit.
+ *   Answer    for i: n_overlaps = the number of overlapping j; other = the j of the LARGEST depth, ties to the lowest j (the rule of
+ *             bge_world_sphere_penetration); depth = that depth.  With no overlap: flags 0, other = BGE_RAY_NO_ENTITY, the rest 0.
+ *   Push      is level, so a crowd never climbs onto itself.  With d taken against `other`:
+ *                  hl2 = d.x*d.x + d.z*d.z
+ *                  if hl2 > 1e-12f:  hl = sqrtf(hl2);  m = (d.x / hl, 0, d.z / hl)
+ *                  otherwise         m = (i < other ? 1 : -1, 0, 0)      coincident or stacked centres part by index
+ *                  t = depth * 0.5f;  if max_push > 0 && t > max_push:  t = max_push and BGE_CROWD_CLAMPED is set
+ *                  push = (m.x*t, +0, m.z*t) and BGE_CROWD_PUSHED is set
+ *   Hence     the answer depends on nothing but the batch: not on the search structure and not on the order in which candidates
+ *             are met.  Every field is a maximum with a stated tie or an integer count.  The same call gives the same bytes every
+ *             time.
+ *   Example   spheres of radius 0.5 at (0, 0, 0) and (0.6, 0, 0): d2 = 0.36, depth = 1 - 0.6 = 0.4, t = 0.2; sphere 0 gets other 1,
+ *             push (-0.2, 0, 0), sphere 1 gets other 0, push (0.2, 0, 0); applied, the centres are 1 apart: touching.
+ *   bge_world_crowd_query         hits[0 .. n) for spheres[0 .. n) (host memory).  max_push must be finite and >= 0, otherwise
+ *                                 BGE_ERR_INVALID; 0 means no limit.  n = 0 is a no-op; NULL with n > 0 is BGE_ERR_INVALID; n is at
+ *                                 most 2^30 - 1.  Synchronises the world's stream.  Changes no world state and works before
+ *                                 bge_world_set_topology.
+ *   bge_world_crowd_query_device  the same from and to device pointers, 4-byte aligned (a misaligned pointer is BGE_ERR_INVALID);
+ *                                 enqueued on the world's stream, no synchronisation, nothing read back.
+ *   BGE_CROWD_GRID_MIN            (environment, read per call; default 256) batches of fewer spheres are answered by all pairs, larger
+ *                                 ones through a hashed grid.  Both give the same bytes.
+ * Characters.  Opt-in: until bge_world_characters_crowd switches it on, every call does byte for byte what it does without this
+ * section.
+ *   Separate  with the crowd on, every step of bge_world_characters_update begins with the stage Separate, before Recover: the crowd
+ *             query over {state.position, desc.radius, group, mask} of ALL characters as they stand (in the first step that is
+ *             after the riding Carry).  A BGE_CHAR_INVALID character still stands where it is and takes part.
+ *   Apply     for a character whose hit is PUSHED: position.x = position.x + push.x, position.z = position.z + push.z, and nothing
+ *             else of the state changes.  A character that is not PUSHED is not touched at all: a set in which nobody overlaps gives
+ *             the same bytes as with the crowd off, a -0 coordinate included.  The step then runs as in "Characters" from that
+ *             position.
+ *   Ordering  Separate comes first, so the step's own Recover and Move have the last word: a character pushed into a wall is pushed
+ *             out of it in the same step, and after an update call no character is inside the world; two may still overlap each
+ *             other by what the last step walked.  Ride anchors and trigger events see the positions the last step left, as before.
+ *   Records   the hit records kept are those of the call's last step.
+ *   bge_world_characters_crowd    flags = BGE_CHAR_CROWD_ON, or 0 = off (which drops the records; n, group and mask are then
+ *                                 ignored).  With ON, n must equal the set's size; group and mask are per character, NULL means
+ *                                 group 1 and mask 0xffffffff.  Unknown flag bits, a max_push that is not finite and >= 0, a wrong n
+ *                                 and ON without a set are BGE_ERR_INVALID.  Calling it again replaces the filters and max_push.  All
+ *                                 arrays are allocated here: an update call allocates nothing and reads nothing back.  Synchronises
+ *                                 the world's stream.
+ *   bge_world_characters_crowd_hits  out[0 .. count) = the records of characters first .. first + count as the last update call's
+ *                                 last step left them (all words 0 before the first update).  Synchronises the world's stream.  A
+ *                                 range outside the set is BGE_ERR_INVALID, and so is any count > 0 while the crowd is off.
+ *   bge_world_characters_crowd_hits_device  the resident bge_crowd_hit[n] (NULL and 0 while the crowd is off), valid until the next
+ *                                 bge_world_characters_crowd(0) or bge_world_characters_create; reads must be ordered after the
+ *                                 world's stream.
+ *   bge_world_characters_create   switches the crowd off and drops the records.  bge_world_characters_warp does nothing special.
+ *   Not done  characters do not block each other's SWEEPS: this is a push, not a cast, so two characters may overlap by what one
+ *             step walked; vertical stacking (the push is level: a character standing on another is parted sideways); more than
+ *             the deepest neighbour per step (a character between several others moves away from the deepest only, and the steps
+ *             after it deal with the rest).
+ */
+typedef struct bge_crowd_sphere {
+    float center[3];
+    float radius;
+    uint32_t group;
+    uint32_t mask;
+} bge_crowd_sphere; /* 24 bytes */
+enum bge_crowd_flags { BGE_CROWD_INVALID = 1u, BGE_CROWD_PUSHED = 2u, BGE_CROWD_CLAMPED = 4u };
+enum bge_character_crowd_mode { BGE_CHAR_CROWD_ON = 1u };
+typedef struct bge_crowd_hit {
+    uint32_t flags;      /* bge_crowd_flags */
+    uint32_t other;      /* index of the deepest overlapping sphere; BGE_RAY_NO_ENTITY if none */
+    uint32_t n_overlaps; /* how many spheres of the batch overlap this one */
+    float depth;         /* of `other`; 0 if none */
+    float push[3];       /* push[1] is always +0 */
+    uint32_t reserved;   /* 0 */
+} bge_crowd_hit; /* 32 bytes, 4-byte aligned, moved word by word */
+BGE_API int bge_world_crowd_query(bge_world* world, uint64_t n, const bge_crowd_sphere* spheres, float max_push, bge_crowd_hit* hits);
+BGE_API int bge_world_crowd_query_device(bge_world* world, uint64_t n, const void* spheres_device, float max_push, void* hits_device);
+BGE_API int bge_world_characters_crowd(bge_world* world, uint32_t flags, float max_push, uint64_t n, const uint32_t* group,
+                                       const uint32_t* mask);
+BGE_API int bge_world_characters_crowd_hits(bge_world* world, uint64_t first, uint64_t count, bge_crowd_hit* out);
+BGE_API int bge_world_characters_crowd_hits_device(bge_world* world, void** hits, uint64_t* n);
 
 /*
  * The physics debug overlay: what PhysicsSystem::GetDebugLines hands to the renderer while the overlay is on
