@@ -19,13 +19,21 @@
 //                  normal of the winner recomputed with the same device functions, and the bge_ray_hit (bge_penetration_hit)
 //                  written.  The key goes back to all ones.
 //   k_query_all_finish<Q>  one thread per query: appends the ghosts' and the plane's hits to the list.
+//   k_qindex_search<Q, ALL>  the body pass through the query index (bge_qindex.hpp; include/bge_world.h "Query index"; DESIGN.md
+//                  4.24), when the call built one: one wave per query over the cells its extent touches and the wide list, the
+//                  same cull and exact test per visited body.  Queries that go far are listed, and k_query_bodies<Q, ALL, true>
+//                  runs the all-bodies pass over that list alone.
 // Each (Q, ALL) is a kernel of its own; nothing inside the loops asks for the kind at run time.
 #include <hip/hip_runtime.h>
+
+#include <type_traits>
 
 #include "../../include/bge_world.h"
 #include "bge_flatten.hpp"
 #include "bge_kernels.hpp"
+#include "bge_qindex_math.hpp"
 #include "bge_query.hpp"
+#include "bge_query_body.hpp"
 #include "bge_ray_device.hpp"
 #include "bge_sphere_device.hpp"
 
@@ -42,7 +50,6 @@ __device__ __forceinline__ bool finite3(const F3& v)
 {
     return __builtin_isfinite(v.x) && __builtin_isfinite(v.y) && __builtin_isfinite(v.z);
 }
-__device__ __forceinline__ float abs_sum(const F3& v) { return __builtin_fabsf(v.x) + __builtin_fabsf(v.y) + __builtin_fabsf(v.z); }
 
 // The key of a hit of value f >= 0 by the object `code`: the smaller key wins.  Q::kLargest: the larger value wins instead (the
 // bits complemented; an object code is never all ones, so no key of a hit is the all-ones "no hit").
@@ -72,14 +79,6 @@ __device__ __forceinline__ float key_value(unsigned long long key)
 //                             the largest value wins instead of the smallest
 //   again(pr, ...), again_plane(pr, n)   the winner's test once more for its record: the normal, and a value handed to point()
 //   point(pr, f, v, n, on_plane), write(o, pr, kind, entity, f, at, n)   the contact point of the winner, and its 10-word record
-
-// The body of a lane as the cull needs it; cand = false when it is not in the world or no query can see it
-struct BodyLane {
-    bool cand, capsule;
-    F3 c, dims;
-    uint32_t grp;
-    float rb; // bounding radius with the rounding of the cull's arithmetic on top
-};
 
 // Words 0..6 of a bge_ray or a bge_sphere_cast: the segment from + delta * f.  Returns whether it is one that can hit anything.
 __device__ __forceinline__ bool segment_prep(const uint32_t* w, F3& from, F3& delta, float& max_distance, float& len2)
@@ -124,6 +123,17 @@ struct SegmentEntry {
     float4 a, d; // from.xyz, 1 / |delta|^2; delta.xyz, layer mask bits (0: the query sees nothing)
 };
 
+// The box of the segment from .. from + delta, for the query index (include/bge_world.h "Query index": the extent)
+__device__ __forceinline__ void segment_box(const F3& from, const F3& delta, float lo[3], float hi[3])
+{
+    const float a[3] = {from.x, from.y, from.z}, b[3] = {from.x + delta.x, from.y + delta.y, from.z + delta.z};
+    for (int i = 0; i < 3; ++i) {
+        lo[i] = __builtin_fminf(a[i], b[i]);
+        hi[i] = __builtin_fmaxf(a[i], b[i]);
+        if (!(a[i] == a[i]) || !(b[i] == b[i])) lo[i] = hi[i] = __builtin_nanf(""); // (fmin / fmax drop a NaN: keep it, the query is far)
+    }
+}
+
 struct RayQuery { // bge_ray, 8 words
     static constexpr bool kClosest = true, kList = true, kLargest = false;
     struct Prep {
@@ -163,6 +173,12 @@ struct RayQuery { // bge_ray, 8 words
     static __device__ __forceinline__ Extra extra(const Shared& sh, uint32_t k) { return sh.slack[k]; }
 
     static __device__ __forceinline__ bool cull(const Entry& e, Extra slack, const BodyLane& b) { return segment_near(e.a, e.d, b.c, b.rb + slack); }
+    // what the query index needs: the box of the segment, and what cull() adds to rb
+    static __device__ __forceinline__ float extent(const Prep& p, float lo[3], float hi[3])
+    {
+        segment_box(p.from, p.delta, lo, hi);
+        return p.slack;
+    }
     static __device__ __forceinline__ float exact(const Entry& e, Extra, const BodyLane& b, const Q4& q, F3& n)
     {
         return ray_shape(F3{e.a.x, e.a.y, e.a.z}, F3{e.d.x, e.d.y, e.d.z}, b.c, q, b.capsule, b.dims, n);
@@ -230,6 +246,11 @@ struct SphereCastQuery { // bge_sphere_cast, 10 words
     static __device__ __forceinline__ bool cull(const Entry& e, Extra sr, const BodyLane& b)
     {
         return segment_near(e.a, e.d, b.c, b.rb + sr.y * 1.0001f + sr.x);
+    }
+    static __device__ __forceinline__ float extent(const Prep& p, float lo[3], float hi[3])
+    {
+        segment_box(p.from, p.delta, lo, hi);
+        return p.radius * 1.0001f + p.slack;
     }
     static __device__ __forceinline__ float exact(const Entry& e, Extra sr, const BodyLane& b, const Q4& q, F3& n)
     {
@@ -302,6 +323,14 @@ struct SphereOverlapQuery { // bge_sphere, 5 words: every object whose distance 
         const float rr = b.rb + e.a.w * 1.0001f + e.ms.y;
         return ex * ex + ey * ey + ez * ez <= rr * rr;
     }
+    // (the point form: the box is the centre)
+    static __device__ __forceinline__ float extent(const Prep& p, float lo[3], float hi[3])
+    {
+        lo[0] = hi[0] = p.c.x;
+        lo[1] = hi[1] = p.c.y;
+        lo[2] = hi[2] = p.c.z;
+        return p.radius * 1.0001f + p.slack;
+    }
     static __device__ __forceinline__ float exact(const Entry& e, Extra, const BodyLane& b, const Q4& q, F3&)
     {
         const float dist = point_shape_distance(F3{e.a.x, e.a.y, e.a.z}, b.c, q, b.capsule, b.dims);
@@ -359,25 +388,6 @@ struct SpherePenetrationQuery : SphereOverlapQuery {
 };
 
 // ---------------------------------------------------------------- the body pass
-__device__ __forceinline__ BodyLane load_body(const QueryParams& p, uint64_t s)
-{
-    BodyLane b{false, false, F3{0.0f, 0.0f, 0.0f}, F3{0.0f, 0.0f, 0.0f}, 0u, 0.0f};
-    if (s >= p.n_slots) return b;
-    const uint32_t f = p.flags[s];
-    // in Bullet's world: a body of any type, not uploaded since the last physics tick (EnsureRigidBody creates it then)
-    if ((f & kTypeMask) == 0u || (f & kBDirty)) return b;
-    b.grp = p.group[s];
-    b.cand = b.grp != 0u && p.mask[s] != 0u;
-    if (!b.cand) return b;
-    b.c = ld3(p.pos, static_cast<uint32_t>(s));
-    const float4 cs = p.cshape[s];
-    b.dims = F3{cs.x, cs.y, cs.z};
-    b.capsule = (p.cinfo[s] & kCiCapsule) != 0u;
-    const float rad = b.capsule ? cs.x + cs.y : __builtin_sqrtf(cs.x * cs.x + cs.y * cs.y + cs.z * cs.z);
-    b.rb = rad * 1.0001f + 1e-5f * abs_sum(b.c) + 1e-6f;
-    return b;
-}
-
 __device__ __forceinline__ void write_rec(const QueryParams& p, uint32_t at, uint32_t query, uint32_t code, float f, const F3& n)
 {
     if (at >= p.all_cap) return; // (counted, not written: the host grows the list and runs the batch again)
@@ -409,22 +419,46 @@ __device__ __forceinline__ void append_one(const QueryParams& p, uint32_t query,
     write_rec(p, atomicAdd(p.all_count, 1u), query, code, f, n);
 }
 
-template <class Q, bool ALL>
-__global__ void __launch_bounds__(256) k_query_bodies(QueryParams p)
+// the queries of a far pass' chunk (a function's own LDS: the other instantiations have none of it)
+__device__ __forceinline__ uint32_t* far_chunk()
+{
+    __shared__ uint32_t q[kChunk];
+    return q;
+}
+
+// FAR: the batch is the far list of the query index (p.qi.far_list, its length on the device); the same pass otherwise
+template <class Q, bool ALL, bool FAR = false>
+__global__ void __launch_bounds__(256) k_query_bodies(std::conditional_t<FAR, QueryCall, QueryParams> p)
 {
     static_assert(ALL || Q::kClosest, "a list-only query has no closest-hit pass");
     __shared__ typename Q::Shared sh;
     const uint32_t tid = threadIdx.x;
+    uint32_t n_queries = p.n_queries;
+    uint32_t* qid = nullptr;
+    if constexpr (FAR) {
+        n_queries = p.qi.words[kQiFarCount];
+        if (n_queries == 0u) return; // (uniform)
+        if (n_queries > p.n_queries) n_queries = p.n_queries;
+        qid = far_chunk();
+    }
     for (uint64_t base = blockIdx.x * 256ull; base < p.n_slots; base += gridDim.x * 256ull) {
         const uint64_t s = base + tid;
         const BodyLane b = load_body(p, s);
         if (__syncthreads_or(b.cand) == 0) continue; // (uniform: a workgroup without candidates skips the queries)
         bool have_q = false;
         Q4 q{0.0f, 0.0f, 0.0f, 1.0f};
-        for (uint32_t r0 = 0; r0 < p.n_queries; r0 += kChunk) {
-            const uint32_t nr = p.n_queries - r0 < kChunk ? p.n_queries - r0 : kChunk;
+        for (uint32_t r0 = 0; r0 < n_queries; r0 += kChunk) {
+            const uint32_t nr = n_queries - r0 < kChunk ? n_queries - r0 : kChunk;
             __syncthreads();
-            if (tid < nr) Q::stage(sh, tid, Q::prep(p.records, r0 + tid));
+            if constexpr (FAR) {
+                if (tid < nr) {
+                    const uint32_t r = p.qi.far_list[r0 + tid];
+                    qid[tid] = r;
+                    Q::stage(sh, tid, Q::prep(p.records, r));
+                }
+            } else {
+                if (tid < nr) Q::stage(sh, tid, Q::prep(p.records, r0 + tid));
+            }
             __syncthreads();
             for (uint32_t k = 0; k < nr; ++k) {
                 const typename Q::Entry e = Q::entry(sh, k);
@@ -442,7 +476,8 @@ __global__ void __launch_bounds__(256) k_query_bodies(QueryParams p)
                         const float f = Q::exact(e, x, b, q, n);
                         if (f >= 0.0f) {
                             if constexpr (!ALL) {
-                                atomicMin(p.keys + r0 + k, query_key<Q>(f, p.entity_of_slot[s] & kQueryEntityMask));
+                                if constexpr (FAR) atomicMin(p.keys + qid[k], query_key<Q>(f, p.entity_of_slot[s] & kQueryEntityMask));
+                                else atomicMin(p.keys + r0 + k, query_key<Q>(f, p.entity_of_slot[s] & kQueryEntityMask));
                             } else {
                                 hit = true;
                                 fh = f;
@@ -451,9 +486,102 @@ __global__ void __launch_bounds__(256) k_query_bodies(QueryParams p)
                         }
                     }
                 }
-                if constexpr (ALL) append_wave(p, hit, r0 + k, hit ? p.entity_of_slot[s] & kQueryEntityMask : 0u, fh, nh);
+                if constexpr (ALL) append_wave(p, hit, FAR ? qid[k] : r0 + k, hit ? p.entity_of_slot[s] & kQueryEntityMask : 0u, fh, nh);
             }
         }
+    }
+}
+
+// ---------------------------------------------------------------- the body pass through the query index
+// One wave per query, four per workgroup.  The wave decides its query's cells (bge_qindex_math.hpp range(): uniform), walks the
+// bucket of each and then the wide list with lanes striding over the records, and puts every record it accepts through the
+// description's own cull and exact: the arithmetic of a visited body is k_query_bodies', operation for operation.  A record is
+// accepted only on the visit of its OWN cell (its key bits): a bucket two visited cells share, or a hash collision, tests nobody
+// twice.  A far query's index goes on the far list; k_query_bodies<Q, ALL, true> takes it from there.
+constexpr uint32_t kSearchWaves = 4;
+
+template <class Q, bool ALL>
+__global__ void __launch_bounds__(64 * kSearchWaves) k_qindex_search(QueryCall p)
+{
+    static_assert(ALL || Q::kClosest, "a list-only query has no closest-hit pass");
+    __shared__ typename Q::Shared sh; // (slots 0 .. 3: each lane reads back what it staged itself, no barrier)
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const uint32_t r = blockIdx.x * kSearchWaves + wave;
+    if (r >= p.n_queries) return; // (uniform per wave; no workgroup barrier below)
+    const QIndexView& qi = p.qi;
+    const typename Q::Prep pr = Q::prep(p.records, r);
+    Q::stage(sh, wave, pr);
+    const typename Q::Entry e = Q::entry(sh, wave);
+    const typename Q::Extra x = Q::extra(sh, wave);
+    float lo[3], hi[3];
+    const float growth = Q::extent(pr, lo, hi);
+    const qindex::Range rg = qindex::range(lo, hi, growth, qi.h, qi.max_cells);
+    if (rg.far) {
+        if (lane == 0u) {
+            qi.far_list[atomicAdd(qi.words + kQiFarCount, 1u)] = r; // (< n_queries: one append per query)
+            atomicAdd(qi.words + kQiRoutedFar, 1u);
+        }
+        return;
+    }
+    if (lane == 0u) atomicAdd(qi.words + kQiRoutedIndex, 1u);
+    const uint32_t qmask = Q::mask(e);
+    if (qmask == 0u) return; // (sees nothing)
+
+    unsigned long long best = ~0ull;
+    // record idx of this lane (live: there is one); keyed: only a record of the cell with these key bits
+    auto visit = [&](uint32_t idx, bool live, bool keyed, uint32_t key) {
+        bool hit = false;
+        float fh = 0.0f;
+        F3 nh{0.0f, 0.0f, 0.0f};
+        uint32_t code = 0u;
+        if (live) {
+            const uint4 c = qi.rec_c[idx];
+            if ((!keyed || c.z == key) && (c.y & qmask) != 0u) {
+                const float4 ra = qi.rec_a[idx], rb = qi.rec_b[idx];
+                const BodyLane b{true, __float_as_uint(rb.w) != 0u, F3{ra.x, ra.y, ra.z}, F3{rb.x, rb.y, rb.z}, c.y, ra.w};
+                if (Q::cull(e, x, b)) {
+                    const Q4 q = ld4(p.quat, c.x);
+                    F3 n{0.0f, 0.0f, 0.0f};
+                    const float f = Q::exact(e, x, b, q, n);
+                    if (f >= 0.0f) {
+                        if constexpr (!ALL) {
+                            const unsigned long long k = query_key<Q>(f, c.w);
+                            best = k < best ? k : best;
+                        } else {
+                            hit = true;
+                            code = c.w;
+                            fh = f;
+                            nh = n;
+                        }
+                    }
+                }
+            }
+        }
+        if constexpr (ALL) append_wave(p, hit, r, code, fh, nh);
+    };
+
+    for (int cz = rg.lo[2]; cz <= rg.hi[2]; ++cz) {
+        for (int cy = rg.lo[1]; cy <= rg.hi[1]; ++cy) {
+            for (int cx = rg.lo[0]; cx <= rg.hi[0]; ++cx) {
+                const uint32_t bucket = qindex::bucket(cx, cy, cz, qi.table);
+                const uint32_t key = qindex::key(cx, cy, cz);
+                const uint32_t first = qi.start[bucket];
+                const uint32_t end = min(first + qi.count[bucket], qi.n_rec);
+                for (uint32_t k0 = first; k0 < end; k0 += 64u) visit(k0 + lane, k0 + lane < end, true, key);
+            }
+        }
+    }
+    const uint32_t n_wide = min(qi.words[kQiWide], qi.n_rec);
+    for (uint32_t k0 = 0; k0 < n_wide; k0 += 64u) visit(qi.n_rec - 1u - min(k0 + lane, n_wide - 1u), k0 + lane < n_wide, false, 0u);
+
+    if constexpr (!ALL) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const uint32_t l = __shfl_xor(static_cast<uint32_t>(best), off, 64), h = __shfl_xor(static_cast<uint32_t>(best >> 32), off, 64);
+            const unsigned long long o = static_cast<unsigned long long>(h) << 32 | l;
+            best = o < best ? o : best;
+        }
+        if (lane == 0u && best != ~0ull) atomicMin(p.keys + r, best);
     }
 }
 
@@ -556,22 +684,38 @@ __global__ void __launch_bounds__(64) k_query_all_finish(QueryParams p)
     }
 }
 
+// the body pass of a batch: through the index and then over its far list, or over every body
+template <class Q, bool ALL>
+hipError_t launch_bodies(hipStream_t stream, const QueryCall& p)
+{
+    if (p.n_slots == 0) return hipSuccess;
+    const uint64_t blocks = (p.n_slots + 255) / 256;
+    const dim3 body_grid(static_cast<uint32_t>(blocks < kMaxBlocks ? blocks : kMaxBlocks));
+    if (!p.qi.on) {
+        hipLaunchKernelGGL((k_query_bodies<Q, ALL>), body_grid, dim3(256), 0, stream, static_cast<const QueryParams&>(p));
+        return hipSuccess;
+    }
+    if (hipError_t e = hipMemsetAsync(p.qi.words + kQiFarCount, 0, sizeof(uint32_t), stream)) return e;
+    hipLaunchKernelGGL((k_qindex_search<Q, ALL>), dim3((p.n_queries + kSearchWaves - 1u) / kSearchWaves), dim3(64 * kSearchWaves), 0, stream, p);
+    hipLaunchKernelGGL((k_query_bodies<Q, ALL, true>), body_grid, dim3(256), 0, stream, p);
+    return hipSuccess;
+}
+
 template <class Q>
-hipError_t launch(hipStream_t stream, const QueryParams& p, bool all)
+hipError_t launch(hipStream_t stream, const QueryCall& p, bool all)
 {
     if (p.n_queries == 0) return hipSuccess;
-    const uint64_t blocks = (p.n_slots + 255) / 256;
-    const dim3 body_grid(static_cast<uint32_t>(blocks < kMaxBlocks ? blocks : kMaxBlocks)), finish_grid((p.n_queries + 63u) / 64u);
+    const dim3 finish_grid((p.n_queries + 63u) / 64u);
     if (all) {
         if constexpr (Q::kList) {
-            if (p.n_slots) hipLaunchKernelGGL((k_query_bodies<Q, true>), body_grid, dim3(256), 0, stream, p);
-            hipLaunchKernelGGL(k_query_all_finish<Q>, finish_grid, dim3(64), 0, stream, p);
+            if (hipError_t e = launch_bodies<Q, true>(stream, p)) return e;
+            hipLaunchKernelGGL(k_query_all_finish<Q>, finish_grid, dim3(64), 0, stream, static_cast<const QueryParams&>(p));
         } else {
             return hipErrorInvalidValue;
         }
     } else if constexpr (Q::kClosest) {
-        if (p.n_slots) hipLaunchKernelGGL((k_query_bodies<Q, false>), body_grid, dim3(256), 0, stream, p);
-        hipLaunchKernelGGL(k_query_finish<Q>, finish_grid, dim3(64), 0, stream, p);
+        if (hipError_t e = launch_bodies<Q, false>(stream, p)) return e;
+        hipLaunchKernelGGL(k_query_finish<Q>, finish_grid, dim3(64), 0, stream, static_cast<const QueryParams&>(p));
     } else {
         return hipErrorInvalidValue;
     }
@@ -580,7 +724,7 @@ hipError_t launch(hipStream_t stream, const QueryParams& p, bool all)
 
 } // namespace
 
-hipError_t launch_query(hipStream_t stream, QueryKind kind, const QueryParams& p, bool all)
+hipError_t launch_query(hipStream_t stream, QueryKind kind, const QueryCall& p, bool all)
 {
     switch (kind) {
     case QueryKind::Ray: return launch<RayQuery>(stream, p, all);

@@ -8,6 +8,8 @@
 
 #include <cstdint>
 
+#include "bge_qindex.hpp"
+
 namespace bge {
 
 // A trigger ghost the queries and the debug overlay can see (the host lists the ghosts that are in the world and posed; few per
@@ -63,10 +65,17 @@ struct QueryParams {
     uint32_t all_cap;
 };
 
-// The body pass, then one thread per query (ghosts, plane).  all = false: the closest hit of each query into p.hits (rays and
+// What a launch takes: the parameters, and the query index of this call (bge_qindex.hpp); qi.on = 0: every body is tested against
+// every query.  The passes that do not read the index are handed the QueryParams alone.
+struct QueryCall : QueryParams {
+    QIndexView qi;
+};
+
+// The body pass, then one thread per query (ghosts, plane).  With p.qi.on the body pass is the index's: one wave per query over the
+// cells its extent touches and the wide list, then the all-bodies pass over the queries that went far (same tests, same bytes).  all = false: the closest hit of each query into p.hits (rays and
 // sphere casts; for a penetration the deepest; an overlap has no closest hit: hipErrorInvalidValue).  all = true: every (query,
 // object) hit is appended to p.all behind p.all_count (zeroed before the call by the caller); an overlap's records carry the
 // distance and no normal; a penetration has no list (the overlap is its list): hipErrorInvalidValue.
-hipError_t launch_query(hipStream_t stream, QueryKind kind, const QueryParams& p, bool all);
+hipError_t launch_query(hipStream_t stream, QueryKind kind, const QueryCall& p, bool all);
 
 } // namespace bge

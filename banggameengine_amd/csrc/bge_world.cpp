@@ -37,6 +37,8 @@
 #include "bge_chartrig.hpp"
 #include "bge_ride.hpp"
 #include "bge_crowd.hpp"
+#include "bge_qindex.hpp"
+#include "bge_qindex_math.hpp"
 #include "bge_query.hpp"
 
 namespace {
@@ -394,6 +396,16 @@ struct bge_world {
     // list, and the ghosts the queries see (rebuilt from `triggers` per query, uploaded when it changed)
     DevBuf query_in, query_out, query_keys, query_all, query_all_count, query_ghosts;
     uint64_t query_keys_n = 0;
+    // the query index (bge_qindex.hip; include/bge_world.h "Query index"): the desc in force, the buffers of a build (grow-only),
+    // and what the last call that queried did
+    bge_query_index_desc qi_desc{0u, 0.0f, 0u, 0u, BGE_QUERY_INDEX_MIN_WORK_DEFAULT};
+    DevBuf qi_count, qi_start, qi_cell, qi_rec_a, qi_rec_b, qi_rec_c, qi_scan, qi_words, qi_far;
+    uint32_t qi_scan_table = 0;
+    size_t qi_scan_bytes = 0;
+    bool qi_last_built = false;
+    float qi_last_edge = 0.0f;
+    uint32_t qi_last_table = 0;
+    uint64_t qi_builds = 0;
     uint32_t query_all_cap = 0;
     std::vector<bge::QueryGhost> query_ghosts_host, query_ghosts_dev;
     // sphere moves (bge_move.hip): staging for the host entry point, the per-mover state, and the cast / hit records of the passes
@@ -520,7 +532,7 @@ struct bge_world {
         for (DevBuf* b : std::initializer_list<DevBuf*>{&flags, &parent, &tile_hdr, &slot_of_entity, &entity_of_slot, &root_slots, &root_index, &root_worlds, &counter, &stage,
                           &stage2, &mass_palette, &normal, &filter_table, &grav_palette, &bp_partials, &obstacle_slots, &obstacle_gen, &obstacles, &obstacle_grid, &box_list, &box_count, &frozen, &rs_word, &adv, &trig_slot, &trig_entity, &trig_he, &trig_group,
                           &trig_mask, &trig_active, &trig_aabb, &trig_pairs, &trig_count, &trig_lists, &ground_list, &ground_count, &trig_tab[0], &trig_tab[1],
-                          &trig_delta_dev, &trig_keys_dev, &trig_pose, &query_in, &query_out, &query_keys, &query_all, &query_all_count, &query_ghosts, &move_in, &move_out, &move_state, &move_casts, &move_hits, &step_in, &step_out, &step_state, &step_casts, &step_hits, &recover_in, &recover_out, &recover_state, &recover_queries, &recover_hits, &char_desc, &char_input, &char_state, &char_recover_in, &char_recover_out, &char_step_in, &char_step_out, &char_scratch, &char_ride, &crowd_in, &crowd_out, &crowd_rec_a, &crowd_rec_b, &crowd_cell, &crowd_count, &crowd_start, &crowd_scan, &crowd_rmax, &char_crowd_hits, &char_crowd_group, &char_crowd_mask, &ct_group, &ct_mask, &ct_bits[0], &ct_bits[1], &ct_counts, &ct_row_total, &ct_row_base, &ct_ghost_rec, &ct_events, &ct_count, &ct_src_row, &dbg_block_sum, &dbg_block_off,
+                          &trig_delta_dev, &trig_keys_dev, &trig_pose, &query_in, &query_out, &query_keys, &query_all, &query_all_count, &query_ghosts, &qi_count, &qi_start, &qi_cell, &qi_rec_a, &qi_rec_b, &qi_rec_c, &qi_scan, &qi_words, &qi_far, &move_in, &move_out, &move_state, &move_casts, &move_hits, &step_in, &step_out, &step_state, &step_casts, &step_hits, &recover_in, &recover_out, &recover_state, &recover_queries, &recover_hits, &char_desc, &char_input, &char_state, &char_recover_in, &char_recover_out, &char_step_in, &char_step_out, &char_scratch, &char_ride, &crowd_in, &crowd_out, &crowd_rec_a, &crowd_rec_b, &crowd_cell, &crowd_count, &crowd_start, &crowd_scan, &crowd_rmax, &char_crowd_hits, &char_crowd_group, &char_crowd_mask, &ct_group, &ct_mask, &ct_bits[0], &ct_bits[1], &ct_counts, &ct_row_total, &ct_row_base, &ct_ghost_rec, &ct_events, &ct_count, &ct_src_row, &dbg_block_sum, &dbg_block_off,
                           &dbg_lines, &dbg_total, &bounds, &cull_ballots, &cull_block_sum, &cull_block_off, &cull_out, &cull_total, &draw_keys,
                           &batch_sort, &batch_hist, &batch_out}) {
             b->release();
@@ -1326,6 +1338,8 @@ try {
     if (const char* e = std::getenv("BGE_TRIGGER_GRID_MIN")) w->trigger_grid_min = static_cast<uint32_t>(std::strtoul(e, nullptr, 10));
     if (const char* e = std::getenv("BGE_TRIGGER_DEVICE_DIFF")) w->trig_device_diff = std::strtoul(e, nullptr, 10) != 0;
     if (const char* e = std::getenv("BGE_OBSTACLE_GRID")) w->obstacle_grid_on = std::strtoul(e, nullptr, 10) != 0;
+    if (const char* e = std::getenv("BGE_QUERY_INDEX")) w->qi_desc.mode = std::strtoul(e, nullptr, 10) != 0 ? 1u : 0u;
+    if (const char* e = std::getenv("BGE_QUERY_INDEX_MIN_WORK")) w->qi_desc.min_work = std::strtoull(e, nullptr, 10);
     DeviceGuard guard(device);
     if (desc && desc->stream) {
         w->stream = static_cast<hipStream_t>(desc->stream);
@@ -3124,6 +3138,48 @@ try {
 }
 BGE_CATCH_ALL("bge_world_trigger_query_stats")
 
+// ---------------------------------------------------------------- the query index: the entry points (bge_qindex.hip)
+static_assert(sizeof(bge_query_index_desc) == 24, "bge_query_index_desc is 24 bytes (include/bge_world.h)");
+static_assert(sizeof(bge_query_index_stats) == 64, "bge_query_index_stats is 64 bytes (include/bge_world.h)");
+
+int bge_world_set_query_index(bge_world* w, const bge_query_index_desc* desc)
+try {
+    if (!w) return fail(BGE_ERR_INVALID, "NULL world");
+    if (!desc) {
+        w->qi_desc.mode = 0u;
+        return BGE_OK;
+    }
+    if (desc->mode > 1u) return fail(BGE_ERR_INVALID, "bge_query_index_desc.mode = %u: 0 (off) or 1 (on)", desc->mode);
+    if (!std::isfinite(desc->cell_edge) || desc->cell_edge < 0.0f) {
+        return fail(BGE_ERR_INVALID, "bge_query_index_desc.cell_edge = %g: finite and >= 0 (0 = chosen by the library)", double(desc->cell_edge));
+    }
+    if (desc->reserved != 0u) return fail(BGE_ERR_INVALID, "bge_query_index_desc.reserved = %u: must be 0", desc->reserved);
+    w->qi_desc = *desc;
+    return BGE_OK;
+}
+BGE_CATCH_ALL("bge_world_set_query_index")
+
+int bge_world_query_index_stats(bge_world* w, bge_query_index_stats* out)
+try {
+    if (!w || !out) return fail(BGE_ERR_INVALID, "NULL argument");
+    *out = bge_query_index_stats{};
+    out->builds = w->qi_builds;
+    if (!w->qi_last_built) return BGE_OK;
+    DeviceGuard guard(w->device);
+    uint32_t words[bge::kQiWords] = {};
+    HIP_TRY(hipMemcpyAsync(words, w->qi_words.p, sizeof(words), hipMemcpyDeviceToHost, w->stream));
+    HIP_TRY(hipStreamSynchronize(w->stream));
+    out->built = 1u;
+    out->table_size = w->qi_last_table;
+    out->cell_edge = w->qi_last_edge;
+    out->bodies_indexed = words[bge::kQiIndexed];
+    out->bodies_wide = words[bge::kQiWide];
+    out->queries_indexed = words[bge::kQiRoutedIndex];
+    out->queries_far = words[bge::kQiRoutedFar];
+    return BGE_OK;
+}
+BGE_CATCH_ALL("bge_world_query_index_stats")
+
 // ---------------------------------------------------------------- queries: rays, sphere casts, sphere overlaps (bge_query.hip)
 static_assert(sizeof(bge_ray) == 32, "bge_ray is 32 bytes (include/bge_world.h)");
 static_assert(sizeof(bge_ray_hit) == 40, "bge_ray_hit is 40 bytes (include/bge_world.h)");
@@ -3181,8 +3237,62 @@ int sync_query_ghosts(bge_world* w)
     return BGE_OK;
 }
 
-// What every query needs: the ghosts the queries see, the per-query keys, the body arrays.
-int query_prepare(bge_world* w, uint64_t n, bge::QueryParams& p)
+// Builds the query index for a call of n queries (include/bge_world.h "Query index": once per public call, all its passes share
+// it) and names it in p.qi; or leaves p.qi.on = 0: the index is off, the batch is below min_work, or there is no slot.  Buffers
+// are sized here, before the first launch of the call.
+int query_index_prepare(bge_world* w, uint64_t n, bge::QueryCall& p)
+{
+    w->qi_last_built = false;
+    const bge_query_index_desc& d = w->qi_desc;
+    const uint64_t slots = p.n_slots;
+    if (d.mode == 0u || n == 0 || slots == 0 || slots > 0x7fffffffull) return BGE_OK;
+    if (n * slots < d.min_work) return BGE_OK; // (n < 2^31, slots < 2^31)
+    const uint32_t table = bge::qindex_table_size(slots);
+    if (w->qi_scan_table != table) {
+        w->qi_scan_bytes = bge::qindex_scan_bytes(table);
+        w->qi_scan_table = table;
+    }
+    HIP_TRY(w->qi_count.ensure(size_t(table) * 4));
+    HIP_TRY(w->qi_start.ensure(size_t(table) * 4));
+    HIP_TRY(w->qi_cell.ensure(slots * 8));
+    HIP_TRY(w->qi_rec_a.ensure(slots * 16));
+    HIP_TRY(w->qi_rec_b.ensure(slots * 16));
+    HIP_TRY(w->qi_rec_c.ensure(slots * 16));
+    HIP_TRY(w->qi_scan.ensure(std::max<size_t>(w->qi_scan_bytes, 16)));
+    HIP_TRY(w->qi_words.ensure(bge::kQiWords * 4));
+    HIP_TRY(w->qi_far.ensure(n * 4));
+    bge::QIndexView& v = p.qi;
+    v.on = 1u;
+    v.table = table;
+    v.h = bge::qindex::edge(d.cell_edge);
+    v.max_cells = d.max_cells ? d.max_cells : bge::qindex::kMaxCellsDefault;
+    v.n_rec = static_cast<uint32_t>(slots);
+    v.start = w->qi_start.as<uint32_t>();
+    v.count = w->qi_count.as<uint32_t>();
+    v.rec_a = w->qi_rec_a.as<float4>();
+    v.rec_b = w->qi_rec_b.as<float4>();
+    v.rec_c = w->qi_rec_c.as<uint4>();
+    v.words = w->qi_words.as<uint32_t>();
+    v.far_list = w->qi_far.as<uint32_t>();
+    bge::QIndexBuild b{};
+    b.count = w->qi_count.as<uint32_t>();
+    b.start = w->qi_start.as<uint32_t>();
+    b.cell = w->qi_cell.as<uint32_t>();
+    b.rec_a = w->qi_rec_a.as<float4>();
+    b.rec_b = w->qi_rec_b.as<float4>();
+    b.rec_c = w->qi_rec_c.as<uint4>();
+    b.scan_tmp = w->qi_scan.p;
+    b.scan_bytes = w->qi_scan_bytes;
+    HIP_TRY(bge::launch_qindex_build(w->stream, p, b));
+    w->qi_last_built = true;
+    w->qi_last_edge = v.h;
+    w->qi_last_table = table;
+    w->qi_builds += 1;
+    return BGE_OK;
+}
+
+// What every query needs: the ghosts the queries see, the per-query keys, the body arrays, the query index when it is on.
+int query_prepare(bge_world* w, uint64_t n, bge::QueryCall& p)
 {
     if (!w->has_topology) return fail(BGE_ERR_STATE, "bge_world_set_topology has not been called");
     if (n > 0x7fffffffull) return fail(BGE_ERR_INVALID, "n_rays = %llu: at most 2^31 - 1 rays per batch", (unsigned long long)n);
@@ -3195,7 +3305,7 @@ int query_prepare(bge_world* w, uint64_t n, bge::QueryParams& p)
         HIP_TRY(hipMemsetAsync(w->query_keys.p, 0xff, n * 8, w->stream));
         w->query_keys_n = n;
     }
-    p = bge::QueryParams{};
+    p = bge::QueryCall{};
     p.n_queries = static_cast<uint32_t>(n);
     p.n_slots = w->flat.n_slots;
     p.flags = w->view.flags;
@@ -3212,11 +3322,11 @@ int query_prepare(bge_world* w, uint64_t n, bge::QueryParams& p)
     p.ghost_pose = w->trig_pose.as<float>();
     p.plane = w->ground_plane ? 1u : 0u;
     p.keys = w->query_keys.as<unsigned long long>();
-    return BGE_OK;
+    return query_index_prepare(w, n, p);
 }
 
 // the batch's query records (bge_ray, bge_sphere_cast, bge_sphere) into the staging buffer
-int query_upload(bge_world* w, uint64_t bytes, const void* records, bge::QueryParams& p)
+int query_upload(bge_world* w, uint64_t bytes, const void* records, bge::QueryCall& p)
 {
     HIP_TRY(w->query_in.ensure(bytes));
     HIP_TRY(hipMemcpyAsync(w->query_in.p, records, bytes, hipMemcpyHostToDevice, w->stream));
@@ -3227,7 +3337,7 @@ int query_upload(bge_world* w, uint64_t bytes, const void* records, bge::QueryPa
 // Runs an all-hits launch and brings its list back sorted by query, then by (f, object code) or, for the overlap, by object code
 // alone: a total order, so the result does not depend on the order of the appends.  The list's capacity grows to what a batch
 // found: a second run of the same batch fits.
-int query_collect(bge_world* w, bge::QueryKind kind, bge::QueryParams& p, std::vector<bge::QueryRec>& rec)
+int query_collect(bge_world* w, bge::QueryKind kind, bge::QueryCall& p, std::vector<bge::QueryRec>& rec)
 {
     HIP_TRY(w->query_all_count.ensure(4));
     p.all_count = w->query_all_count.as<uint32_t>();
@@ -3287,7 +3397,7 @@ int query_closest(bge_world* w, bge::QueryKind kind, uint64_t n, size_t record_b
     if (n == 0) return BGE_OK;
     if (!records || !hits) return fail(BGE_ERR_INVALID, "NULL argument");
     DeviceGuard guard(w->device);
-    bge::QueryParams p;
+    bge::QueryCall p;
     if (int rc = query_prepare(w, n, p)) return rc;
     if (int rc = query_upload(w, n * record_bytes, records, p)) return rc;
     HIP_TRY(w->query_out.ensure(n * sizeof(bge_ray_hit)));
@@ -3305,7 +3415,7 @@ int query_closest_device(bge_world* w, bge::QueryKind kind, uint64_t n, const vo
     if (n == 0) return BGE_OK;
     if (!records_device || !hits_device) return fail(BGE_ERR_INVALID, "NULL argument");
     DeviceGuard guard(w->device);
-    bge::QueryParams p;
+    bge::QueryCall p;
     if (int rc = query_prepare(w, n, p)) return rc;
     p.records = records_device;
     p.hits = hits_device;
@@ -3316,7 +3426,7 @@ int query_closest_device(bge_world* w, bge::QueryKind kind, uint64_t n, const vo
 // A batch of sphere moves between device buffers (include/bge_world.h "Sphere moves"): begin, BGE_MOVE_SLIDES rounds of a
 // closest-hit sphere-cast pass and a step, the probe's pass, finish — all enqueued, nothing read in between.  q comes from
 // query_prepare(w, n, q), which holds the checks of the batch (topology, n, entity range) for both entry points.
-int move_enqueue(bge_world* w, bge::QueryParams q, uint64_t n, const void* moves_device, void* results_device)
+int move_enqueue(bge_world* w, bge::QueryCall q, uint64_t n, const void* moves_device, void* results_device)
 {
     HIP_TRY(w->move_state.ensure(n * bge::kMoveStateBytes));
     HIP_TRY(w->move_casts.ensure(n * sizeof(bge_sphere_cast)));
@@ -3344,7 +3454,7 @@ int move_enqueue(bge_world* w, bge::QueryParams q, uint64_t n, const void* moves
 // begin, then BGE_MOVE_SLIDES passes over both lanes (2n casts: the plain slide at i, the step at n + i), two passes over the step's
 // half alone (its last Forward round, its Down cast), the selection, the probe's pass over the first half, finish — all enqueued,
 // nothing read in between.  q comes from query_prepare(w, 2 * n, q).  The scratch is the step mover's own.
-int step_enqueue(bge_world* w, bge::QueryParams q, uint64_t n, const void* moves_device, void* results_device)
+int step_enqueue(bge_world* w, bge::QueryCall q, uint64_t n, const void* moves_device, void* results_device)
 {
     HIP_TRY(w->step_state.ensure(n * bge::kStepStateBytes));
     HIP_TRY(w->step_casts.ensure(2 * n * sizeof(bge_sphere_cast)));
@@ -3356,7 +3466,7 @@ int step_enqueue(bge_world* w, bge::QueryParams q, uint64_t n, const void* moves
     m.casts = w->step_casts.p;
     m.hits = w->step_hits.p;
     m.n = static_cast<uint32_t>(n);
-    bge::QueryParams both = q, step_half = q, plain_half = q;
+    bge::QueryCall both = q, step_half = q, plain_half = q;
     both.records = plain_half.records = w->step_casts.p;
     both.hits = plain_half.hits = w->step_hits.p;
     step_half.records = static_cast<const char*>(w->step_casts.p) + n * sizeof(bge_sphere_cast);
@@ -3375,7 +3485,7 @@ int step_enqueue(bge_world* w, bge::QueryParams q, uint64_t n, const void* moves
 // A batch of sphere recoveries between device buffers (include/bge_world.h "Sphere penetration and recovery"): begin,
 // BGE_RECOVER_ROUNDS rounds of a penetration pass and a step, the final check's pass, finish — all enqueued, nothing read in
 // between.  q comes from query_prepare(w, n, q).  The scratch is the recovery's own, not the mover's.
-int recover_enqueue(bge_world* w, bge::QueryParams q, uint64_t n, const void* records_device, void* results_device)
+int recover_enqueue(bge_world* w, bge::QueryCall q, uint64_t n, const void* records_device, void* results_device)
 {
     HIP_TRY(w->recover_state.ensure(n * bge::kRecoverStateBytes));
     HIP_TRY(w->recover_queries.ensure(n * sizeof(bge_sphere)));
@@ -3419,7 +3529,7 @@ int query_list(bge_world* w, const QueryList& q, uint64_t n, const void* records
     }
     if (!records) return fail(BGE_ERR_INVALID, "%s is NULL", q.records_name);
     DeviceGuard guard(w->device);
-    bge::QueryParams p;
+    bge::QueryCall p;
     if (int rc = query_prepare(w, n, p)) return rc;
     if (int rc = query_upload(w, n * q.record_bytes, records, p)) return rc;
     std::vector<bge::QueryRec> rec;
@@ -3523,7 +3633,7 @@ try {
     if (n == 0) return BGE_OK;
     if (!moves || !results) return fail(BGE_ERR_INVALID, "NULL argument");
     DeviceGuard guard(w->device);
-    bge::QueryParams q;
+    bge::QueryCall q;
     if (int rc = query_prepare(w, n, q)) return rc; // (before the staging is sized: it refuses a batch that is too large)
     HIP_TRY(w->move_in.ensure(n * sizeof(bge_sphere_move)));
     HIP_TRY(w->move_out.ensure(n * sizeof(bge_sphere_move_result)));
@@ -3544,7 +3654,7 @@ try {
         return fail(BGE_ERR_INVALID, "moves_device and results_device must be 4-byte aligned");
     }
     DeviceGuard guard(w->device);
-    bge::QueryParams q;
+    bge::QueryCall q;
     if (int rc = query_prepare(w, n, q)) return rc;
     return move_enqueue(w, q, n, moves_device, results_device);
 }
@@ -3557,7 +3667,7 @@ try {
     if (!moves || !results) return fail(BGE_ERR_INVALID, "NULL argument");
     if (n > 0x3fffffffull) return fail(BGE_ERR_INVALID, "n = %llu: a step move asks 2 n casts per pass, at most 2^31 - 1", (unsigned long long)n);
     DeviceGuard guard(w->device);
-    bge::QueryParams q;
+    bge::QueryCall q;
     if (int rc = query_prepare(w, 2 * n, q)) return rc; // (before the staging is sized: it refuses a batch that is too large)
     HIP_TRY(w->step_in.ensure(n * sizeof(bge_sphere_step_move)));
     HIP_TRY(w->step_out.ensure(n * sizeof(bge_sphere_step_result)));
@@ -3579,7 +3689,7 @@ try {
     }
     if (n > 0x3fffffffull) return fail(BGE_ERR_INVALID, "n = %llu: a step move asks 2 n casts per pass, at most 2^31 - 1", (unsigned long long)n);
     DeviceGuard guard(w->device);
-    bge::QueryParams q;
+    bge::QueryCall q;
     if (int rc = query_prepare(w, 2 * n, q)) return rc;
     return step_enqueue(w, q, n, moves_device, results_device);
 }
@@ -3614,7 +3724,7 @@ try {
     if (n == 0) return BGE_OK;
     if (!records || !results) return fail(BGE_ERR_INVALID, "NULL argument");
     DeviceGuard guard(w->device);
-    bge::QueryParams q;
+    bge::QueryCall q;
     if (int rc = query_prepare(w, n, q)) return rc; // (before the staging is sized: it refuses a batch that is too large)
     HIP_TRY(w->recover_in.ensure(n * sizeof(bge_sphere_recover)));
     HIP_TRY(w->recover_out.ensure(n * sizeof(bge_sphere_recover_result)));
@@ -3635,7 +3745,7 @@ try {
         return fail(BGE_ERR_INVALID, "records_device and results_device must be 4-byte aligned");
     }
     DeviceGuard guard(w->device);
-    bge::QueryParams q;
+    bge::QueryCall q;
     if (int rc = query_prepare(w, n, q)) return rc;
     return recover_enqueue(w, q, n, records_device, results_device);
 }
@@ -3876,9 +3986,9 @@ try {
     const uint64_t n = w->n_characters;
     if (n == 0) return BGE_OK;
     DeviceGuard guard(w->device);
-    bge::QueryParams q;
+    bge::QueryCall q;
     if (int rc = query_prepare(w, 2 * n, q)) return rc; // (the step move's 2 n casts per pass; the recovery asks n of them)
-    bge::QueryParams qr = q;
+    bge::QueryCall qr = q;
     qr.n_queries = static_cast<uint32_t>(n);
     bge::CharacterParams c{};
     c.desc = w->char_desc.p;

@@ -879,6 +879,21 @@ public:
         out.push.x = h.push[0], out.push.y = h.push[1], out.push.z = h.push[2];
         return true;
     }
+    // EXTENSION: the query index (include/bge_world.h "Query index"), off by default: every query, move, recovery and character
+    // step visits only the bodies near it instead of all of them; every answer keeps its bytes.  cellEdge = 0: the library's.
+    bool SetQueryIndex(bool on, float cellEdge = 0.0f)
+    {
+        bge_query_index_desc d{};
+        d.mode = on ? 1u : 0u;
+        d.cell_edge = cellEdge;
+        d.min_work = BGE_QUERY_INDEX_MIN_WORK_DEFAULT;
+        return bge_world_set_query_index(world_, &d) == BGE_OK || Log("bge_world_set_query_index");
+    }
+    // what the last call that queried did with it (synchronises the world's stream)
+    bool GetQueryIndexStats(bge_query_index_stats& out) const
+    {
+        return bge_world_query_index_stats(world_, &out) == BGE_OK || Log("bge_world_query_index_stats");
+    }
     size_t CharacterCount() const { return char_ids_.size(); }
     bool SetCharacterWalk(Id entity, float dx, float dz)
     {
@@ -1908,6 +1923,21 @@ public:
     {
         return lastScene_ && GpuMirrors<SceneT>::Of(*lastScene_).GetCharacterCrowd(entity, out);
     }
+    // EXTENSION: the query index (include/bge_world.h "Query index"), off by default.  With it on, Raycast .. UpdateCharacters
+    // visit only the bodies near each query instead of every body; every answer keeps its bytes.  cellEdge = 0: the library's
+    // choice.  Handed to the scene's mirror here and by every Update.
+    void SetQueryIndex(bool on, float cellEdge = 0.0f)
+    {
+        queryIndexSet_ = true;
+        queryIndex_ = on;
+        queryIndexEdge_ = on ? cellEdge : 0.0f;
+        if (lastScene_) GpuMirrors<SceneT>::Of(*lastScene_).SetQueryIndex(queryIndex_, queryIndexEdge_);
+    }
+    // what the last call that queried did with the index (synchronises the world's stream)
+    bool GetQueryIndexStats(bge_query_index_stats& out) const
+    {
+        return lastScene_ && GpuMirrors<SceneT>::Of(*lastScene_).GetQueryIndexStats(out);
+    }
     // as of the last SyncCharacters
     bool CharacterOnGround(typename GpuSceneMirror<SceneT>::Id entity) const
     {
@@ -2017,6 +2047,7 @@ private:
     {
         auto& m = GpuMirrors<SceneT>::Of(scene);
         lastScene_ = &scene;
+        if (queryIndexSet_) m.SetQueryIndex(queryIndex_, queryIndexEdge_); // (until SetQueryIndex is called the world keeps its default: off)
         m.gravity[0] = 0.0f;
         m.gravity[1] = config_.gravity; // m_world->setGravity(btVector3(0, m_config.gravity, 0)), PhysicsSystem.cpp:130, 292
         m.gravity[2] = 0.0f;
@@ -2048,6 +2079,8 @@ private:
     bool characterRiding_ = false, characterRidingDynamic_ = false; // SetCharacterPlatformRiding: the same
     bool characterCrowd_ = false;                                   // SetCharacterCrowd: the same
     float characterCrowdMaxPush_ = 0.0f;
+    bool queryIndexSet_ = false, queryIndex_ = false; // SetQueryIndex: handed to the scene's mirror by Step
+    float queryIndexEdge_ = 0.0f;
     bool debugDrawEnabled_ = false;
     bge_debug_desc debugDesc_{static_cast<uint32_t>(sizeof(bge_debug_desc)), BGE_DEBUG_ALL, 0u, {0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f}};
     DebugLineBuffer debugLines_;

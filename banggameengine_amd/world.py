@@ -183,6 +183,13 @@ CROWD_SPHERE_DTYPE = np.dtype([("center", "<f4", (3,)), ("radius", "<f4"), ("gro
 CROWD_HIT_DTYPE = np.dtype([("flags", "<u4"), ("other", "<u4"), ("n_overlaps", "<u4"), ("depth", "<f4"), ("push", "<f4", (3,)),
                             ("reserved", "<u4")])
 assert CROWD_SPHERE_DTYPE.itemsize == 24 and CROWD_HIT_DTYPE.itemsize == 32
+# the query index (bge_world_set_query_index, bge_world_query_index_stats): bge_query_index_desc, bge_query_index_stats
+QUERY_INDEX_MIN_WORK_DEFAULT = 1 << 30
+QUERY_INDEX_DESC_DTYPE = np.dtype([("mode", "<u4"), ("cell_edge", "<f4"), ("max_cells", "<u4"), ("reserved", "<u4"), ("min_work", "<u8")])
+QUERY_INDEX_STATS_DTYPE = np.dtype([("built", "<u4"), ("table_size", "<u4"), ("bodies_indexed", "<u8"), ("bodies_wide", "<u8"),
+                                    ("queries_indexed", "<u8"), ("queries_far", "<u8"), ("cell_edge", "<f4"), ("reserved", "<u4"),
+                                    ("builds", "<u8"), ("reserved2", "<u8")])
+assert QUERY_INDEX_DESC_DTYPE.itemsize == 24 and QUERY_INDEX_STATS_DTYPE.itemsize == 64
 
 
 def make_crowd_spheres(centers, radius=0.5, group=1, mask=0xFFFFFFFF):
@@ -832,6 +839,26 @@ class World:
         ptr, n = C.c_void_p(), C.c_uint64()
         check(lib().bge_world_characters_crowd_hits_device(self._h, C.byref(ptr), C.byref(n)))
         return int(ptr.value or 0), int(n.value)
+
+    # -- the query index (include/bge_world.h "Query index" states the rule)
+    def set_query_index(self, on=True, cell_edge=0.0, max_cells=0, min_work=None):
+        """Switches the query index on or off: with it, the body pass of every query (and of the moves, recoveries and character
+        steps made of them) visits only the bodies near the query instead of all of them.  Every answer keeps its bytes.
+        cell_edge = 0 and max_cells = 0: chosen by the library; min_work: calls with n_queries * n_slots below it take the
+        all-bodies pass (None: the library's default, 0: every call goes through the index)."""
+        d = np.zeros(1, QUERY_INDEX_DESC_DTYPE)
+        d["mode"] = 1 if on else 0
+        d["cell_edge"] = cell_edge
+        d["max_cells"] = max_cells
+        d["min_work"] = QUERY_INDEX_MIN_WORK_DEFAULT if min_work is None else int(min_work)
+        check(lib().bge_world_set_query_index(self._h, _p(d)))
+
+    def query_index_stats(self):
+        """What the last call that queried did with the index: a dict of the fields of bge_query_index_stats (built, table_size,
+        bodies_indexed, bodies_wide, queries_indexed, queries_far, cell_edge, builds).  Synchronises the world's stream."""
+        s = np.zeros(1, QUERY_INDEX_STATS_DTYPE)
+        check(lib().bge_world_query_index_stats(self._h, _p(s)))
+        return {k: (float(s[k][0]) if k == "cell_edge" else int(s[k][0])) for k in s.dtype.names if not k.startswith("reserved")}
 
     # -- character trigger events (include/bge_world.h "Character trigger events" states the rule and the order of the list)
     def characters_watch_triggers(self, group=None, mask=None, stay=True, event_capacity=0):

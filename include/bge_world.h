@@ -1134,6 +1134,74 @@ BGE_API int bge_world_characters_crowd_hits(bge_world* world, uint64_t first, ui
 BGE_API int bge_world_characters_crowd_hits_device(bge_world* world, void** hits, uint64_t* n);
 
 /*
+ * Query index.  Opt-in; off by default, and while it is off every call enqueues exactly what it enqueues without this section.
+ * Every ray, sphere cast, overlap and penetration query — and so every move, step move, recovery and character step, which are
+ * made of them — tests bodies against queries in one body pass.  Without the index that pass tests EVERY body against EVERY
+ * query.  With it, a spatial hash of the bodies' cull spheres at their current poses is built on the device at the head of the
+ * call, and a query's body pass visits only the cells its extent touches.  The index only chooses WHICH bodies a query looks at:
+ * every body it looks at goes through the same cull and the same exact test, operation for operation, a closest hit is a minimum
+ * with a stated tie and a list is sorted by a total order, so every answer is THE SAME BYTES as with the index off.  Ghosts and
+ * the ground plane are not indexed (they are handled per query as before).  The rule below is the specification; h is the cell
+ * edge in force, cell(x) = clamp(floor(x / h), -2^20, 2^20) per axis, computed in float.
+ *   1 Members     exactly the bodies the queries can see at all: a body of any type that is in the world (not uploaded since the
+ *                 last physics tick, not removed) with group != 0 and mask != 0.  A member's cull sphere has the body's position
+ *                 c as centre and rb = rad * 1.0001 + 1e-5 * (|c.x| + |c.y| + |c.z|) + 1e-6 as radius (rad: capsule radius +
+ *                 half height; box |half extents with margin|), each operation rounded to float — the queries' own expression.
+ *   2 Wide list   a member whose rb is not finite or exceeds h / 2 is on the wide list; every other member is in the cell of c.
+ *                 Every indexed query tests the whole wide list.  A large ground box is such a body; so is one at 1e30.  A
+ *                 non-finite pose needs no special case: its cull fails as it does without the index.
+ *   3 Far queries the extent of a query is the box of its segment (ray, sphere cast: origin and origin + direction * max_distance)
+ *                 or its centre (overlap, penetration: the point form), and its growth what its cull adds to rb: slack for a
+ *                 ray, radius * 1.0001 + slack for the others, slack the kind's own 1e-5 * (sum of magnitudes) term.  With
+ *                 reach = (h / 2 + growth) * 1.0625 the query visits the cells cell(lo - reach) .. cell(hi + reach) per axis.  It
+ *                 goes FAR instead when that is more than max_cells cells, or more than 1024 on one axis (a member's record
+ *                 carries the low 10 bits of its cell per axis, which is what tells visited cells apart), or when lo - reach,
+ *                 hi + reach or reach is not finite, or reach > 1e18.  Far queries run the all-bodies pass, over the far
+ *                 queries alone.  A long diagonal ray is therefore far; a 3-D line walk through the cells is not built.
+ *   4 Coverage    for every (query, member) pair the cull passes, the member is visited: in its own cell, or on the wide list,
+ *                 or because the query is far (DESIGN.md 4.24 has the argument for the margin 1.0625 over float rounding).
+ *   5 No double visits  a member is accepted only on the visit of its own cell, by the key bits in its record: a bucket shared by
+ *                 two visited cells, or a hash collision, puts no object twice into a list of all hits.
+ *   6 Freshness   the index is built once per public call that queries, before its first pass, from the poses of that moment,
+ *                 and all passes of the call share it (the passes of one bge_world_characters_update, the slides of a move, the
+ *                 casts of a step move).  Nothing is kept across calls.  No query call synchronises or reads anything back for it.
+ *   bge_world_set_query_index    desc = NULL or mode = 0: off.  mode = 1: on, with cell_edge (0 = chosen by the library: 4.0),
+ *                 max_cells (0 = default: 256) and min_work: a call of n queries against a world of n_slots slots builds and uses
+ *                 the index when n * n_slots >= min_work (for a move, step move and character update n is the casts of one
+ *                 pass) and takes the all-bodies pass otherwise; 0 = every call.  BGE_QUERY_INDEX_MIN_WORK_DEFAULT (2^30: about
+ *                 1,000 queries against a million slots, the measured crossover of DESIGN.md 4.24) is the library's choice.  mode > 1, a negative or non-finite cell_edge or reserved != 0 is BGE_ERR_INVALID and
+ *                 changes nothing.  An edge below 1e-18 counts as 1e-18.
+ *   bge_world_query_index_stats  what the last call that queried did: whether it built the index, members in cells and on the
+ *                 wide list, queries that walked cells and queries that went far (summed over the passes of that call; a list
+ *                 that outgrew its capacity runs its pass twice), the cell edge and table size, and builds since the world's
+ *                 creation.  Synchronises the stream once and reads a few words.
+ * The environment gives the default desc of a NEW world, read once in bge_world_create: BGE_QUERY_INDEX=1 (mode = 1) and
+ * BGE_QUERY_INDEX_MIN_WORK=<n>.  They change no result.
+ */
+#define BGE_QUERY_INDEX_MIN_WORK_DEFAULT ((uint64_t)1 << 30)
+typedef struct bge_query_index_desc {
+    uint32_t mode;      /* 0 off, 1 on */
+    float cell_edge;    /* 0 = chosen by the library */
+    uint32_t max_cells; /* most cells one query may visit; 0 = default */
+    uint32_t reserved;  /* 0 */
+    uint64_t min_work;  /* n_queries * n_slots below it: the all-bodies pass */
+} bge_query_index_desc; /* 24 bytes */
+typedef struct bge_query_index_stats {
+    uint32_t built;           /* 1: the last call that queried built and used the index */
+    uint32_t table_size;      /* buckets */
+    uint64_t bodies_indexed;  /* members in cells */
+    uint64_t bodies_wide;     /* members on the wide list */
+    uint64_t queries_indexed; /* queries that walked their cells */
+    uint64_t queries_far;     /* queries that took the all-bodies pass */
+    float cell_edge;
+    uint32_t reserved;
+    uint64_t builds;          /* since bge_world_create */
+    uint64_t reserved2;
+} bge_query_index_stats; /* 64 bytes */
+BGE_API int bge_world_set_query_index(bge_world* world, const bge_query_index_desc* desc);
+BGE_API int bge_world_query_index_stats(bge_world* world, bge_query_index_stats* out);
+
+/*
  * The physics debug overlay: what PhysicsSystem::GetDebugLines hands to the renderer while the overlay is on
  * (src/physics/PhysicsSystem.cpp:857-873, 1148-1175; src/physics/BulletDebugDrawer.cpp) — every collision object's shape as
  * wireframe lines in one colour, then one short red line per contact point — made on the device from the state the last tick
