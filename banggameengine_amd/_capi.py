@@ -125,6 +125,11 @@ SYMBOLS = {
     "bge_world_characters_crowd": (C.c_int, [_vp, _u32, C.c_float, _u64, _vp, _vp]),
     "bge_world_characters_crowd_hits": (C.c_int, [_vp, _u64, _u64, _vp]),
     "bge_world_characters_crowd_hits_device": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_u64)]),
+    "bge_world_apply_impulses": (C.c_int, [_vp, _u64, _vp, _vp]),
+    "bge_world_apply_impulses_device": (C.c_int, [_vp, _u64, _vp, _vp]),
+    "bge_world_characters_push": (C.c_int, [_vp, _vp]),
+    "bge_world_characters_push_records": (C.c_int, [_vp, _u64, _u64, _vp]),
+    "bge_world_characters_push_records_device": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_u64)]),
     "bge_world_set_query_index": (C.c_int, [_vp, _vp]),
     "bge_world_query_index_stats": (C.c_int, [_vp, _vp]),
     "bge_world_characters_watch_triggers": (C.c_int, [_vp, _u64, _vp, _vp, _u32, _u64]),

@@ -37,6 +37,8 @@
 #include "bge_chartrig.hpp"
 #include "bge_ride.hpp"
 #include "bge_crowd.hpp"
+#include "bge_impulse.hpp"
+#include "bge_impulse_math.hpp"
 #include "bge_qindex.hpp"
 #include "bge_qindex_math.hpp"
 #include "bge_query.hpp"
@@ -432,6 +434,14 @@ struct bge_world {
     bool char_crowd_on = false;
     float char_crowd_max_push = 0.0f;
     float char_r_max = 0.0f; // the largest desc.radius of the set
+    // impulses (bge_impulse.hip): staging for the host entry point, the (slot, record index) pairs before and after the sort and
+    // hipcub's storage (grow-only, sized for imp_cap records); the resident push records of the character set while push is on
+    DevBuf imp_in, imp_status, imp_keys[2], imp_vals[2], imp_sort;
+    uint64_t imp_cap = 0, imp_sort_n = 0; // records the pair arrays hold; the n imp_sort_need was asked for
+    size_t imp_sort_need = 0;
+    DevBuf char_push_records;
+    bool char_push_on = false;
+    bge_character_push_desc char_push_desc{0u, 0.0f, 0.0f, 0u};
     // character trigger events (bge_chartrig.hip): the per-character filters, the two [triggers][ceil(n / 64)] bitmaps
     // (ct_bits[ct_rem] = remembered, the other = remembered before the last update call), the per-(ghost, word) counts / offsets, the
     // per-ghost totals, bases and {trigger, entity} of the last call, the event list and its count
@@ -532,7 +542,7 @@ struct bge_world {
         for (DevBuf* b : std::initializer_list<DevBuf*>{&flags, &parent, &tile_hdr, &slot_of_entity, &entity_of_slot, &root_slots, &root_index, &root_worlds, &counter, &stage,
                           &stage2, &mass_palette, &normal, &filter_table, &grav_palette, &bp_partials, &obstacle_slots, &obstacle_gen, &obstacles, &obstacle_grid, &box_list, &box_count, &frozen, &rs_word, &adv, &trig_slot, &trig_entity, &trig_he, &trig_group,
                           &trig_mask, &trig_active, &trig_aabb, &trig_pairs, &trig_count, &trig_lists, &ground_list, &ground_count, &trig_tab[0], &trig_tab[1],
-                          &trig_delta_dev, &trig_keys_dev, &trig_pose, &query_in, &query_out, &query_keys, &query_all, &query_all_count, &query_ghosts, &qi_count, &qi_start, &qi_cell, &qi_rec_a, &qi_rec_b, &qi_rec_c, &qi_scan, &qi_words, &qi_far, &move_in, &move_out, &move_state, &move_casts, &move_hits, &step_in, &step_out, &step_state, &step_casts, &step_hits, &recover_in, &recover_out, &recover_state, &recover_queries, &recover_hits, &char_desc, &char_input, &char_state, &char_recover_in, &char_recover_out, &char_step_in, &char_step_out, &char_scratch, &char_ride, &crowd_in, &crowd_out, &crowd_rec_a, &crowd_rec_b, &crowd_cell, &crowd_count, &crowd_start, &crowd_scan, &crowd_rmax, &char_crowd_hits, &char_crowd_group, &char_crowd_mask, &ct_group, &ct_mask, &ct_bits[0], &ct_bits[1], &ct_counts, &ct_row_total, &ct_row_base, &ct_ghost_rec, &ct_events, &ct_count, &ct_src_row, &dbg_block_sum, &dbg_block_off,
+                          &trig_delta_dev, &trig_keys_dev, &trig_pose, &query_in, &query_out, &query_keys, &query_all, &query_all_count, &query_ghosts, &qi_count, &qi_start, &qi_cell, &qi_rec_a, &qi_rec_b, &qi_rec_c, &qi_scan, &qi_words, &qi_far, &move_in, &move_out, &move_state, &move_casts, &move_hits, &step_in, &step_out, &step_state, &step_casts, &step_hits, &recover_in, &recover_out, &recover_state, &recover_queries, &recover_hits, &char_desc, &char_input, &char_state, &char_recover_in, &char_recover_out, &char_step_in, &char_step_out, &char_scratch, &char_ride, &crowd_in, &crowd_out, &crowd_rec_a, &crowd_rec_b, &crowd_cell, &crowd_count, &crowd_start, &crowd_scan, &crowd_rmax, &char_crowd_hits, &char_crowd_group, &char_crowd_mask, &imp_in, &imp_status, &imp_keys[0], &imp_keys[1], &imp_vals[0], &imp_vals[1], &imp_sort, &char_push_records, &ct_group, &ct_mask, &ct_bits[0], &ct_bits[1], &ct_counts, &ct_row_total, &ct_row_base, &ct_ghost_rec, &ct_events, &ct_count, &ct_src_row, &dbg_block_sum, &dbg_block_off,
                           &dbg_lines, &dbg_total, &bounds, &cull_ballots, &cull_block_sum, &cull_block_off, &cull_out, &cull_total, &draw_keys,
                           &batch_sort, &batch_hist, &batch_out}) {
             b->release();
@@ -3765,6 +3775,13 @@ void char_crowd_off(bge_world* w)
     for (DevBuf* b : {&w->char_crowd_hits, &w->char_crowd_group, &w->char_crowd_mask}) b->release();
 }
 
+void char_push_off(bge_world* w)
+{
+    w->char_push_on = false;
+    w->char_push_desc = bge_character_push_desc{0u, 0.0f, 0.0f, 0u};
+    w->char_push_records.release();
+}
+
 int check_character_range(const bge_world* w, uint64_t first, uint64_t count)
 {
     if (first > w->n_characters || count > w->n_characters - first) {
@@ -3811,6 +3828,7 @@ try {
     w->ride_flags = 0;
     w->char_ride.release();
     char_crowd_off(w); // (and the crowd's filters and hit records)
+    char_push_off(w);  // (and the push records)
     w->char_r_max = 0.0f;
     for (uint64_t i = 0; i < n; ++i) w->char_r_max = std::max(w->char_r_max, descs[i].radius);
     if (n == 0) {
@@ -3976,6 +3994,53 @@ int char_crowd_params(bge_world* w, bge::CrowdParams& p)
     return BGE_OK;
 }
 
+// ---- impulses (bge_impulse.hip)
+static_assert(sizeof(bge_impulse) == 32, "bge_impulse is 32 bytes (include/bge_world.h)");
+static_assert(sizeof(bge_character_push_desc) == 16, "bge_character_push_desc is 16 bytes (include/bge_world.h)");
+
+// Sizes the sort's arrays for n records (grow-only: a call of no more records than one before allocates nothing) and names them in p
+int impulse_reserve(bge_world* w, uint64_t n, bge::ImpulseParams& p)
+{
+    if (n > w->imp_cap) {
+        const size_t bytes = bge::impulse::word_array_bytes(n);
+        for (DevBuf* b : {&w->imp_keys[0], &w->imp_keys[1], &w->imp_vals[0], &w->imp_vals[1]}) HIP_TRY(b->ensure(bytes));
+        w->imp_cap = n;
+    }
+    if (n != w->imp_sort_n) {
+        w->imp_sort_need = bge::impulse_sort_bytes(static_cast<uint32_t>(n));
+        w->imp_sort_n = n;
+    }
+    HIP_TRY(w->imp_sort.ensure(std::max<size_t>(w->imp_sort_need, 16)));
+    p.keys_in = w->imp_keys[0].as<uint32_t>();
+    p.keys_out = w->imp_keys[1].as<uint32_t>();
+    p.vals_in = w->imp_vals[0].as<uint32_t>();
+    p.vals_out = w->imp_vals[1].as<uint32_t>();
+    p.sort_tmp = w->imp_sort.p;
+    p.sort_bytes = w->imp_sort.bytes;
+    return BGE_OK;
+}
+
+// Valid, Apply and Wake of n records that lie in device memory; the caller has moved the epochs on (epochs_edit)
+int impulses_enqueue(bge_world* w, uint64_t n, const void* records, void* status)
+{
+    bge::ImpulseParams p{};
+    if (int rc = impulse_reserve(w, n, p)) return rc;
+    p.records = static_cast<const uint32_t*>(records);
+    p.status = static_cast<uint32_t*>(status);
+    p.n = static_cast<uint32_t>(n);
+    p.n_entities = w->flat.n_entities;
+    p.slot_of_entity = w->slot_of_entity.as<uint32_t>();
+    HIP_TRY(bge::launch_impulses(w->stream, p, w->view));
+    return BGE_OK;
+}
+
+int impulses_check(const bge_world* w, uint64_t n)
+{
+    if (!w->has_topology) return fail(BGE_ERR_STATE, "bge_world_set_topology has not been called");
+    if (!bge::impulse::count_ok(n)) return fail(BGE_ERR_INVALID, "n = %llu: at most 2^30 - 1 impulse records", (unsigned long long)n);
+    return BGE_OK;
+}
+
 } // namespace
 
 int bge_world_characters_update(bge_world* w, float dt, uint32_t steps)
@@ -3986,6 +4051,9 @@ try {
     const uint64_t n = w->n_characters;
     if (n == 0) return BGE_OK;
     DeviceGuard guard(w->device);
+    // Push writes velocities, flags and deactivation records: the tick's per-wave words go, as for bge_world_set_velocities, and a
+    // deferred translation row is made current BEFORE query_prepare captures how the queries read row 3
+    if (w->char_push_on) w->epochs_edit();
     bge::QueryCall q;
     if (int rc = query_prepare(w, 2 * n, q)) return rc; // (the step move's 2 n casts per pass; the recovery asks n of them)
     bge::QueryCall qr = q;
@@ -4019,6 +4087,18 @@ try {
     if (w->char_crowd_on) {
         if (int rc = char_crowd_params(w, cp)) return rc;
     }
+    bge::CharPushParams pp{};
+    if (w->char_push_on) {
+        pp.state = w->char_state.as<uint32_t>();
+        pp.records = w->char_push_records.as<uint32_t>();
+        pp.n = c.n;
+        pp.n_entities = w->flat.n_entities;
+        pp.slot_of_entity = w->slot_of_entity.as<uint32_t>();
+        pp.force = w->char_push_desc.force;
+        pp.dt = dt;
+        pp.max_normal_y = w->char_push_desc.max_normal_y;
+        pp.body_mask = w->char_push_desc.body_mask;
+    }
     for (uint32_t k = 0; k < steps; ++k) {
         if (w->char_crowd_on) {
             HIP_TRY(bge::launch_crowd(w->stream, cp)); // Separate
@@ -4028,6 +4108,10 @@ try {
         HIP_TRY(bge::launch_char_move(w->stream, c));
         if (int rc = step_enqueue(w, q, n, w->char_step_in.p, w->char_step_out.p)) return rc;
         HIP_TRY(bge::launch_char_finish(w->stream, c));
+        if (w->char_push_on) {
+            HIP_TRY(bge::launch_char_push(w->stream, pp, w->view)); // Push
+            if (int rc = impulses_enqueue(w, n, w->char_push_records.p, nullptr)) return rc; // (sized by bge_world_characters_push)
+        }
     }
     if (w->ride_on) {
         HIP_TRY(bge::launch_char_anchor(w->stream, r));
@@ -4222,6 +4306,110 @@ try {
     return BGE_OK;
 }
 BGE_CATCH_ALL("bge_world_characters_crowd_hits_device")
+
+// ---------------------------------------------------------------- impulses and the characters' push: the entry points (bge_impulse.hip)
+int bge_world_apply_impulses(bge_world* w, uint64_t n, const bge_impulse* records, uint32_t* status)
+try {
+    if (!w) return fail(BGE_ERR_INVALID, "world is NULL");
+    if (n == 0) return BGE_OK;
+    if (!records) return fail(BGE_ERR_INVALID, "records is NULL");
+    if (int rc = impulses_check(w, n)) return rc;
+    DeviceGuard guard(w->device);
+    HIP_TRY(w->imp_in.ensure(bge::impulse::record_bytes(n)));
+    if (status) HIP_TRY(w->imp_status.ensure(bge::impulse::word_array_bytes(n)));
+    HIP_TRY(hipMemcpyAsync(w->imp_in.p, records, bge::impulse::record_bytes(n), hipMemcpyHostToDevice, w->stream));
+    w->epochs_edit();
+    // from here on a copy from or to the caller's memory may be in flight: no return before the stream has passed it
+    int rc = impulses_enqueue(w, n, w->imp_in.p, status ? w->imp_status.p : nullptr);
+    hipError_t copied = hipSuccess;
+    if (rc == BGE_OK && status) copied = hipMemcpyAsync(status, w->imp_status.p, bge::impulse::word_array_bytes(n), hipMemcpyDeviceToHost, w->stream);
+    const hipError_t synced = hipStreamSynchronize(w->stream);
+    if (rc != BGE_OK) return rc;
+    HIP_TRY(copied);
+    HIP_TRY(synced);
+    return BGE_OK;
+}
+BGE_CATCH_ALL("bge_world_apply_impulses")
+
+int bge_world_apply_impulses_device(bge_world* w, uint64_t n, const void* records_device, void* status_device)
+try {
+    if (!w) return fail(BGE_ERR_INVALID, "world is NULL");
+    if (n == 0) return BGE_OK;
+    if (!records_device) return fail(BGE_ERR_INVALID, "records_device is NULL");
+    if ((reinterpret_cast<uintptr_t>(records_device) | reinterpret_cast<uintptr_t>(status_device)) & 3u) {
+        return fail(BGE_ERR_INVALID, "records_device and status_device must be 4-byte aligned");
+    }
+    if (int rc = impulses_check(w, n)) return rc;
+    DeviceGuard guard(w->device);
+    w->epochs_edit();
+    return impulses_enqueue(w, n, records_device, status_device);
+}
+BGE_CATCH_ALL("bge_world_apply_impulses_device")
+
+int bge_world_characters_push(bge_world* w, const bge_character_push_desc* desc)
+try {
+    if (!w || !desc) return fail(BGE_ERR_INVALID, "NULL argument");
+    if (desc->flags & ~uint32_t(BGE_CHAR_PUSH_ON)) return fail(BGE_ERR_INVALID, "bge_character_push_desc::flags = %#x: unknown bits", desc->flags);
+    DeviceGuard guard(w->device);
+    if (desc->flags == 0u) {
+        if (w->char_push_on) {
+            HIP_TRY(hipStreamSynchronize(w->stream)); // (an update may still be writing the records)
+        }
+        char_push_off(w);
+        return BGE_OK;
+    }
+    switch (bge::impulse::push_desc_error(desc->flags, desc->force, desc->max_normal_y)) {
+    case 0: break;
+    case 2: return fail(BGE_ERR_INVALID, "bge_character_push_desc::force = %g: must be finite and >= 0", (double)desc->force);
+    default: return fail(BGE_ERR_INVALID, "bge_character_push_desc::max_normal_y = %g: must be finite and in [0, 1)", (double)desc->max_normal_y);
+    }
+    const uint64_t n = w->n_characters;
+    if (n == 0) return fail(BGE_ERR_INVALID, "there is no character set to switch push on for");
+    HIP_TRY(hipStreamSynchronize(w->stream)); // (an update may still be running with the old desc's buffers)
+    bge::ImpulseParams sized{};
+    if (int rc = impulse_reserve(w, n, sized)) return rc;
+    if (!w->char_push_on) {
+        // no push yet: entity = BGE_RAY_NO_ENTITY, every other word 0
+        std::vector<bge_impulse> fresh(n);
+        for (bge_impulse& r : fresh) {
+            r = bge_impulse{};
+            r.entity = BGE_RAY_NO_ENTITY;
+        }
+        HIP_TRY(w->char_push_records.ensure(n * sizeof(bge_impulse)));
+        HIP_TRY(hipMemcpyAsync(w->char_push_records.p, fresh.data(), n * sizeof(bge_impulse), hipMemcpyHostToDevice, w->stream));
+        HIP_TRY(hipStreamSynchronize(w->stream)); // (the copy reads this function's memory)
+    }
+    w->char_push_on = true;
+    w->char_push_desc = *desc;
+    return BGE_OK;
+}
+BGE_CATCH_ALL("bge_world_characters_push")
+
+int bge_world_characters_push_records(bge_world* w, uint64_t first, uint64_t count, bge_impulse* out)
+try {
+    if (!w) return fail(BGE_ERR_INVALID, "world is NULL");
+    if (int rc = check_character_range(w, first, count)) return rc;
+    DeviceGuard guard(w->device);
+    if (count == 0) {
+        HIP_TRY(hipStreamSynchronize(w->stream));
+        return BGE_OK;
+    }
+    if (!w->char_push_on) return fail(BGE_ERR_INVALID, "the character push is off");
+    if (!out) return fail(BGE_ERR_INVALID, "out is NULL");
+    HIP_TRY(hipMemcpyAsync(out, w->char_push_records.as<bge_impulse>() + first, count * sizeof(bge_impulse), hipMemcpyDeviceToHost, w->stream));
+    HIP_TRY(hipStreamSynchronize(w->stream));
+    return BGE_OK;
+}
+BGE_CATCH_ALL("bge_world_characters_push_records")
+
+int bge_world_characters_push_records_device(bge_world* w, void** records, uint64_t* n)
+try {
+    if (!w || !records || !n) return fail(BGE_ERR_INVALID, "NULL argument");
+    *records = w->char_push_on ? w->char_push_records.p : nullptr;
+    *n = w->char_push_on ? w->n_characters : 0;
+    return BGE_OK;
+}
+BGE_CATCH_ALL("bge_world_characters_push_records_device")
 
 // ---------------------------------------------------------------- character trigger events (bge_chartrig.hip)
 static_assert(sizeof(bge_character_trigger_event) == 12, "bge_character_trigger_event is 12 bytes (include/bge_world.h)");

@@ -409,6 +409,7 @@ public:
     bool UpdatePhysics(SceneT& scene, double dt)
     {
         if (!ok() || !RefreshTopology(scene) || !UploadBodies(scene) || !UploadDirtyTransforms(scene)) return false;
+        if (!FlushImpulses()) return false; // (what ApplyImpulse .. queued since the last Update, before the step)
         uint32_t flags = BGE_TICK_PHYSICS;
         if (bullet_basis) flags |= BGE_TICK_BULLET_BASIS;
         bool triggers = false;
@@ -879,6 +880,27 @@ public:
         out.push.x = h.push[0], out.push.y = h.push[1], out.push.z = h.push[2];
         return true;
     }
+    // EXTENSION: characters push the Dynamic bodies they walk into (include/bge_world.h "Character push"), off by default: every
+    // step of UpdateCharacters ends by giving the body hit an impulse of force * dt, level, away from the character.  Applied by
+    // the next UpdateCharacters, and again whenever AddCharacter re-creates the set.
+    void SetCharacterPush(bool on, float force = 0.0f, float maxNormalY = 0.5f)
+    {
+        char_push_want_ = bge_character_push_desc{on ? static_cast<uint32_t>(BGE_CHAR_PUSH_ON) : 0u, on ? force : 0.0f, on ? maxNormalY : 0.0f,
+                                                  on ? 0xffffffffu : 0u};
+    }
+    // EXTENSION: impulses on Dynamic bodies (include/bge_world.h "Impulses"): Bullet's applyImpulse / applyCentralImpulse /
+    // applyTorqueImpulse + activate().  Queued here, in call order, and applied as one batch at the head of the next UpdatePhysics,
+    // after that frame's uploads and before its step.  An entity that has no Dynamic body by then is skipped.
+    void QueueImpulse(Id entity, uint32_t flags, const float impulse[3], const float point[3])
+    {
+        bge_impulse r{};
+        r.flags = flags;
+        std::memcpy(r.impulse, impulse, 12);
+        std::memcpy(r.point, point, 12);
+        impulse_ids_.push_back(entity);
+        impulses_.push_back(r);
+    }
+    size_t QueuedImpulses() const { return impulses_.size(); }
     // EXTENSION: the query index (include/bge_world.h "Query index"), off by default: every query, move, recovery and character
     // step visits only the bodies near it instead of all of them; every answer keeps its bytes.  cellEdge = 0: the library's.
     bool SetQueryIndex(bool on, float cellEdge = 0.0f)
@@ -950,6 +972,7 @@ public:
             char_trig_watching_ = false;
             char_ride_applied_ = 0u; // (creating the set switched riding off)
             char_crowd_applied_ = false; // (and the crowd)
+            char_push_applied_ = bge_character_push_desc{0u, 0.0f, 0.0f, 0u}; // (and push)
         }
         if (char_crowd_want_ != char_crowd_applied_ || (char_crowd_want_ && char_crowd_max_push_ != char_crowd_applied_push_)) {
             if (bge_world_characters_crowd(world_, char_crowd_want_ ? static_cast<uint32_t>(BGE_CHAR_CROWD_ON) : 0u, char_crowd_max_push_,
@@ -958,6 +981,10 @@ public:
             }
             char_crowd_applied_ = char_crowd_want_;
             char_crowd_applied_push_ = char_crowd_max_push_;
+        }
+        if (std::memcmp(&char_push_want_, &char_push_applied_, sizeof char_push_want_) != 0) {
+            if (bge_world_characters_push(world_, &char_push_want_) != BGE_OK) return Log("bge_world_characters_push");
+            char_push_applied_ = char_push_want_;
         }
         if (char_ride_want_ != char_ride_applied_) {
             if (bge_world_characters_ride(world_, char_ride_want_) != BGE_OK) return Log("bge_world_characters_ride");
@@ -1602,6 +1629,30 @@ private:
     bool char_crowd_want_ = false, char_crowd_applied_ = false;
     float char_crowd_max_push_ = 0.0f, char_crowd_applied_push_ = 0.0f;
     std::vector<bge_crowd_hit> char_crowd_hits_;
+    // character push: the desc wanted and the desc the device has (all zeros = off)
+    bge_character_push_desc char_push_want_{0u, 0.0f, 0.0f, 0u}, char_push_applied_{0u, 0.0f, 0.0f, 0u};
+    // impulses queued since the last UpdatePhysics, in call order, and whom they are for
+    std::vector<Id> impulse_ids_;
+    std::vector<bge_impulse> impulses_;
+
+    // the queue as one batch; an entity the mirror does not know gets BGE_RAY_NO_ENTITY, which no world carries
+    bool FlushImpulses()
+    {
+        if (impulses_.empty()) return true;
+        if (ids_.empty()) { // (an empty scene has no world to apply them to)
+            impulses_.clear();
+            impulse_ids_.clear();
+            return true;
+        }
+        for (size_t k = 0; k < impulses_.size(); ++k) {
+            auto it = index_of_.find(impulse_ids_[k]);
+            impulses_[k].entity = it == index_of_.end() ? BGE_RAY_NO_ENTITY : it->second;
+        }
+        const int rc = bge_world_apply_impulses(world_, impulses_.size(), impulses_.data(), nullptr);
+        impulses_.clear();
+        impulse_ids_.clear();
+        return rc == BGE_OK || Log("bge_world_apply_impulses");
+    }
 
     template <class Vec3> static bge_sphere_cast MakeCast(const Vec3& o, const Vec3& d, float maxDistance, float radius, uint32_t layerMask)
     {
@@ -1837,7 +1888,8 @@ public:
 
     // EXTENSION: sphere characters on the device (include/bge_world.h "Characters") in the place of the reference's
     // btKinematicCharacterController (PhysicsSystem.cpp:709-846).  The surface follows the reference's use of Bullet's controller;
-    // the shape is a sphere of the capsule's radius, and capsules, pushing Dynamic bodies and riding platforms are not done.
+    // the shape is a sphere of the capsule's radius, and capsules are not done; pushing Dynamic bodies and riding platforms are
+    // opt-in (SetCharacterPush, SetCharacterPlatformRiding below).
     // Per frame, after Update: SetCharacterWalk / CharacterJump from the input, UpdateCharacters(fixed step, the Update's
     // sub-steps), SyncCharacters.  They act on the scene of the last Update and return false before it.
     // AddCharacter: the position is the entity's Transform's; radius, step height, max slope, jump speed and gravity are the
@@ -1877,6 +1929,7 @@ public:
         GpuMirrors<SceneT>::Of(*lastScene_).SetCharacterTriggerEvents(characterTriggerEvents_);
         GpuMirrors<SceneT>::Of(*lastScene_).SetCharacterPlatformRiding(characterRiding_, characterRidingDynamic_);
         GpuMirrors<SceneT>::Of(*lastScene_).SetCharacterCrowd(characterCrowd_, characterCrowdMaxPush_);
+        GpuMirrors<SceneT>::Of(*lastScene_).SetCharacterPush(characterPush_, characterPushForce_, characterPushMaxNormalY_);
         return GpuMirrors<SceneT>::Of(*lastScene_).UpdateCharacters(dt, steps);
     }
     bool SyncCharacters(SceneT& scene) { return GpuMirrors<SceneT>::Of(scene).SyncCharacters(scene); }
@@ -1923,6 +1976,33 @@ public:
     {
         return lastScene_ && GpuMirrors<SceneT>::Of(*lastScene_).GetCharacterCrowd(entity, out);
     }
+    // EXTENSION: characters push the Dynamic bodies they walk into (include/bge_world.h "Character push"), off by default.  In the
+    // reference the character's ghost is a fixed body to the solver and a crate is pushed out of it; here the body a step's slide
+    // hit gets force * dt, level, away from the character, unless the hit is steeper than maxNormalY (a character standing on a
+    // crate does not push it).  No reaction on the character, no spin.
+    void SetCharacterPush(bool on, float force = 0.0f, float maxNormalY = 0.5f)
+    {
+        characterPush_ = on;
+        characterPushForce_ = on ? force : 0.0f;
+        characterPushMaxNormalY_ = maxNormalY;
+        if (lastScene_) GpuMirrors<SceneT>::Of(*lastScene_).SetCharacterPush(characterPush_, characterPushForce_, characterPushMaxNormalY_);
+    }
+    // EXTENSION: impulses (include/bge_world.h "Impulses"): btRigidBody::applyImpulse / applyCentralImpulse / applyTorqueImpulse,
+    // each with activate(), on the body of `entity` in the scene of the last Update.  Queued, and applied in call order as one batch
+    // at the head of the next Update, before its step; ActivateBody only wakes.  false before the first Update.
+    template <class Vec3> bool ApplyImpulse(typename GpuSceneMirror<SceneT>::Id entity, const Vec3& impulse, const Vec3& relPos)
+    {
+        return QueueImpulse(entity, BGE_IMPULSE_AT_POINT, impulse.x, impulse.y, impulse.z, relPos.x, relPos.y, relPos.z);
+    }
+    template <class Vec3> bool ApplyCentralImpulse(typename GpuSceneMirror<SceneT>::Id entity, const Vec3& impulse)
+    {
+        return QueueImpulse(entity, BGE_IMPULSE_CENTRAL, impulse.x, impulse.y, impulse.z, 0.0f, 0.0f, 0.0f);
+    }
+    template <class Vec3> bool ApplyTorqueImpulse(typename GpuSceneMirror<SceneT>::Id entity, const Vec3& torque)
+    {
+        return QueueImpulse(entity, BGE_IMPULSE_TORQUE, torque.x, torque.y, torque.z, 0.0f, 0.0f, 0.0f);
+    }
+    bool ActivateBody(typename GpuSceneMirror<SceneT>::Id entity) { return QueueImpulse(entity, BGE_IMPULSE_CENTRAL, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f); }
     // EXTENSION: the query index (include/bge_world.h "Query index"), off by default.  With it on, Raycast .. UpdateCharacters
     // visit only the bodies near each query instead of every body; every answer keeps its bytes.  cellEdge = 0: the library's
     // choice.  Handed to the scene's mirror here and by every Update.
@@ -2068,6 +2148,14 @@ private:
         if (debugDrawEnabled_) m.DebugLines(debugDesc_, debugLines_); // debugDrawWorld + CollectDebugLines, PhysicsSystem.cpp:866-870
     }
 
+    bool QueueImpulse(typename GpuSceneMirror<SceneT>::Id entity, uint32_t flags, float ix, float iy, float iz, float px, float py, float pz)
+    {
+        if (!lastScene_) return false;
+        const float impulse[3] = {ix, iy, iz}, point[3] = {px, py, pz};
+        GpuMirrors<SceneT>::Of(*lastScene_).QueueImpulse(entity, flags, impulse, point);
+        return true;
+    }
+
     std::filesystem::path configPath_;
     std::filesystem::file_time_type lastWriteTime_{};
     bool hasLastWriteTime_ = false;
@@ -2079,6 +2167,8 @@ private:
     bool characterRiding_ = false, characterRidingDynamic_ = false; // SetCharacterPlatformRiding: the same
     bool characterCrowd_ = false;                                   // SetCharacterCrowd: the same
     float characterCrowdMaxPush_ = 0.0f;
+    bool characterPush_ = false;                                    // SetCharacterPush: the same
+    float characterPushForce_ = 0.0f, characterPushMaxNormalY_ = 0.5f;
     bool queryIndexSet_ = false, queryIndex_ = false; // SetQueryIndex: handed to the scene's mirror by Step
     float queryIndexEdge_ = 0.0f;
     bool debugDrawEnabled_ = false;

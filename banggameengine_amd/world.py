@@ -183,6 +183,14 @@ CROWD_SPHERE_DTYPE = np.dtype([("center", "<f4", (3,)), ("radius", "<f4"), ("gro
 CROWD_HIT_DTYPE = np.dtype([("flags", "<u4"), ("other", "<u4"), ("n_overlaps", "<u4"), ("depth", "<f4"), ("push", "<f4", (3,)),
                             ("reserved", "<u4")])
 assert CROWD_SPHERE_DTYPE.itemsize == 24 and CROWD_HIT_DTYPE.itemsize == 32
+# impulses and the characters' push (bge_world_apply_impulses*, bge_world_characters_push ..): bge_impulse_flags, bge_impulse_status,
+# bge_character_push_mode and the records
+IMPULSE_AT_POINT, IMPULSE_CENTRAL, IMPULSE_TORQUE, IMPULSE_WORLD_POINT = 0, 1, 2, 4
+IMPULSE_APPLIED, IMPULSE_WOKE, IMPULSE_INVALID, IMPULSE_NO_BODY = 1, 2, 4, 8
+CHAR_PUSH_ON = 1
+IMPULSE_DTYPE = np.dtype([("entity", "<u4"), ("flags", "<u4"), ("impulse", "<f4", (3,)), ("point", "<f4", (3,))])
+CHARACTER_PUSH_DESC_DTYPE = np.dtype([("flags", "<u4"), ("force", "<f4"), ("max_normal_y", "<f4"), ("body_mask", "<u4")])
+assert IMPULSE_DTYPE.itemsize == 32 and CHARACTER_PUSH_DESC_DTYPE.itemsize == 16
 # the query index (bge_world_set_query_index, bge_world_query_index_stats): bge_query_index_desc, bge_query_index_stats
 QUERY_INDEX_MIN_WORK_DEFAULT = 1 << 30
 QUERY_INDEX_DESC_DTYPE = np.dtype([("mode", "<u4"), ("cell_edge", "<f4"), ("max_cells", "<u4"), ("reserved", "<u4"), ("min_work", "<u8")])
@@ -201,6 +209,23 @@ def make_crowd_spheres(centers, radius=0.5, group=1, mask=0xFFFFFFFF):
     spheres["group"] = np.broadcast_to(np.asarray(group, np.uint64).astype(np.uint32), (len(c),))
     spheres["mask"] = np.broadcast_to(np.asarray(mask, np.uint64).astype(np.uint32), (len(c),))
     return spheres
+
+
+def make_impulses(entity, impulse, point=None, kind=None, world_point=False):
+    """bge_impulse records: entity (n,), impulse (n, 3); point (n, 3) or None (zeros); kind and world_point a scalar or one value
+    per record.  kind = None: IMPULSE_AT_POINT where a point is given, IMPULSE_CENTRAL otherwise."""
+    if kind is None:
+        kind = IMPULSE_CENTRAL if point is None else IMPULSE_AT_POINT
+    e = np.atleast_1d(np.asarray(entity, np.uint64)).astype(np.uint32)
+    records = np.zeros(len(e), IMPULSE_DTYPE)
+    records["entity"] = e
+    records["impulse"] = np.ascontiguousarray(impulse, np.float32).reshape(-1, 3)
+    if point is not None:
+        records["point"] = np.ascontiguousarray(point, np.float32).reshape(-1, 3)
+    flags = np.broadcast_to(np.asarray(kind, np.uint32), (len(e),)).copy()
+    flags |= np.where(np.broadcast_to(np.asarray(world_point, bool), (len(e),)), IMPULSE_WORLD_POINT, 0).astype(np.uint32)
+    records["flags"] = flags
+    return records
 
 
 def make_characters(positions, radius=0.5, skin=0.01, step_height=0.35, min_ground_ny=0.7071068, probe_distance=0.1, gravity=9.81, jump_speed=5.0,
@@ -838,6 +863,53 @@ class World:
         """(device pointer, n) of the resident bge_crowd_hit[n]; (0, 0) while the crowd is off."""
         ptr, n = C.c_void_p(), C.c_uint64()
         check(lib().bge_world_characters_crowd_hits_device(self._h, C.byref(ptr), C.byref(n)))
+        return int(ptr.value or 0), int(n.value)
+
+    # -- impulses and the characters' push (include/bge_world.h "Impulses" and "Character push" state the rule)
+    def apply_impulses(self, entity, impulse=None, point=None, kind=None, world_point=False, want_status=False):
+        """Applies impulses to Dynamic bodies as Bullet's applyImpulse / applyCentralImpulse / applyTorqueImpulse + activate() would,
+        record after record: entity (n,), impulse (n, 3), point (n, 3) or None; kind = IMPULSE_AT_POINT / CENTRAL / TORQUE (None:
+        AT_POINT with a point, CENTRAL without).  entity may also be a ready IMPULSE_DTYPE array (make_impulses()), the other
+        arguments are then ignored.  want_status: the status word per record comes back (IMPULSE_APPLIED, ...)."""
+        if isinstance(entity, np.ndarray) and entity.dtype == IMPULSE_DTYPE:
+            records = np.ascontiguousarray(entity)
+        else:
+            records = make_impulses(entity, impulse, point, kind, world_point)
+        status = np.zeros(len(records), np.uint32) if want_status else None
+        check(lib().bge_world_apply_impulses(self._h, len(records), _p(records) if len(records) else None,
+                                             _p(status) if want_status and len(records) else None))
+        return status
+
+    def apply_impulses_device(self, records, status=None):
+        """The same between device tensors: records holds n bge_impulse records (32 bytes each, e.g. a uint8 tensor made from
+        make_impulses()), status (optional) room for n 32-bit words.  Enqueued on the world's stream without synchronisation, as
+        raycast_device()."""
+        n = _device_records(records, records if status is None else status, "records", "status", 32, 0 if status is None else 4)
+        check(lib().bge_world_apply_impulses_device(self._h, n, C.c_void_p(records.data_ptr()),
+                                                    None if status is None else C.c_void_p(status.data_ptr())))
+
+    def characters_push(self, on=True, force=0.0, max_normal_y=0.5, body_mask=0xFFFFFFFF):
+        """Switches the characters' push on (every step of characters_update() ends by pushing the Dynamic body the character
+        walked into with `force` newtons over the step, level, away from the character) or off.  Hits steeper than max_normal_y
+        (|hit_normal.y|) and bodies whose group misses body_mask are not pushed.  Calling it again replaces the settings."""
+        d = np.zeros(1, CHARACTER_PUSH_DESC_DTYPE)
+        if on:
+            d[0] = (CHAR_PUSH_ON, force, max_normal_y, body_mask)
+        check(lib().bge_world_characters_push(self._h, _p(d)))
+
+    def characters_push_records(self, first=0, count=None):
+        """The push records of characters first .. first + count (all of them by default) as the last update call's last step
+        left them: an IMPULSE_DTYPE array.  Synchronises the world's stream."""
+        if count is None:
+            count = self.characters_state_device()[1] - first
+        records = np.zeros(max(count, 0), IMPULSE_DTYPE)
+        check(lib().bge_world_characters_push_records(self._h, first, count, _p(records) if count > 0 else None))
+        return records
+
+    def characters_push_records_device(self):
+        """(device pointer, n) of the resident bge_impulse[n]; (0, 0) while push is off."""
+        ptr, n = C.c_void_p(), C.c_uint64()
+        check(lib().bge_world_characters_push_records_device(self._h, C.byref(ptr), C.byref(n)))
         return int(ptr.value or 0), int(n.value)
 
     # -- the query index (include/bge_world.h "Query index" states the rule)

@@ -272,7 +272,8 @@ BGE_API int bge_world_download_dirty(bge_world* world, uint64_t first, uint64_t 
 /* Deactivation ("sleeping") of free bodies, inside stepSimulation (src/physics/PhysicsSystem.cpp:863): a Dynamic body
  * whose |v| stays below 0.8 and |w| below 1.0 for more than 2 s goes WANTS_DEACTIVATION at the end of that step and
  * ISLAND_SLEEPING in the next one (a free body is an island of its own); asleep it takes no gravity, is not integrated,
- * and its velocities are zeroed every step.  Only body (re)creation wakes it (the reference never calls activate()).
+ * and its velocities are zeroed every step.  Body (re)creation wakes it, and so does an impulse ("Impulses" below: the extension's
+ * activate(); the reference never calls it).
  * state[i] receives a bge_activation; time[i] btCollisionObject::m_deactivationTime while the body is ACTIVE_TAG and 0
  * otherwise (Bullet keeps a stale value there that nothing reads).  Either pointer may be NULL. */
 BGE_API int bge_world_download_activation(bge_world* world, uint64_t first, uint64_t count, uint8_t* state, float* time);
@@ -823,14 +824,16 @@ BGE_API int bge_world_sphere_recover_device(bge_world* world, uint64_t n, const 
  *             The kerb of "Sphere step moves" (min_ground_ny cos 45 degrees, step_height 0.7): a character GROUNDED at
  *             (0, 0.51, 0) with walk (2, 0): walking, dy = 0, M is that example's result: position (2, 1.11, 0), ground_distance
  *             0.01, e = 0: flags GROUNDED | STEPPED, step_rise 0.7, ground_kind BODY, entity 0.
- *   Not done  capsule characters; pushing Dynamic bodies; writing into a Transform on the device (the adapter does that on the
- *             host).  A platform that moves INTO a character pushes it out through Recover; one that moves away from or along
+ *   Not done  capsule characters; writing into a Transform on the device (the adapter does that on the host).  Dynamic bodies are
+ *             pushed only once "Character push" below is switched on, and what remains open there is a reaction on the character
+ *             and a push at the contact point.  A platform that moves INTO a character pushes it out through Recover; one that moves away from or along
  *             under a grounded character carries it only once "Character platform riding" below is switched on, and what remains
  *             open there is a swept carry and inherited velocity.  Trigger volumes report characters through "Character trigger events" below,
  *             with what remains open there: the box is the sphere's, not a capsule's; the world's own bge_world_trigger_events
  *             still does not see characters; characters do not report each other.
  *   Characters are not bodies: no query sees them, they see each other only through "Crowd separation" below once it is switched on
- *   (a push; they do not block each other's sweeps), and no call here changes any other world state.
+ *   (a push; they do not block each other's sweeps), and no call here changes any other world state — except that, once
+ *   "Character push" below is switched on, an update call changes the velocities and the activation of the Dynamic bodies pushed.
  *   bge_world_characters_create   replaces the set with n characters made from descs; n = 0 removes it (descs may then be NULL).
  *                                 Every desc is checked on the host: every float finite, radius >= 0, skin > 0, step_height >= 0,
  *                                 probe_distance >= 0, gravity >= 0, jump_speed >= 0, fall_speed > 0, layer_mask != 0; a bad desc is
@@ -1132,6 +1135,120 @@ BGE_API int bge_world_characters_crowd(bge_world* world, uint32_t flags, float m
                                        const uint32_t* mask);
 BGE_API int bge_world_characters_crowd_hits(bge_world* world, uint64_t first, uint64_t count, bge_crowd_hit* out);
 BGE_API int bge_world_characters_crowd_hits_device(bge_world* world, void** hits, uint64_t* n);
+
+/*
+ * Impulses: a batch of impulse records applied to Dynamic bodies on the device.  An extension: the reference never
+ * calls them, but they are Bullet's btRigidBody::applyImpulse / applyCentralImpulse / applyTorqueImpulse, each followed by
+ * btCollisionObject::activate(), and the rule below is the specification.  All arithmetic is binary32, one rounding per operation,
+ * in the stated order.
+ *   Record    bge_impulse {entity, flags, impulse[3], point[3]}.  The low two bits of flags are the kind:
+ *               BGE_IMPULSE_AT_POINT (0)  point is Bullet's rel_pos: relative to the body's origin, in world axes
+ *               BGE_IMPULSE_CENTRAL  (1)  point is ignored
+ *               BGE_IMPULSE_TORQUE   (2)  impulse is a torque impulse, point is ignored
+ *             BGE_IMPULSE_WORLD_POINT (4), with AT_POINT only: point is a world position and r[k] = point[k] - origin[k], origin
+ *             being the body's position in memory.  Kind 3, WORLD_POINT with another kind and any other bit are unknown flags.
+ *   Valid     a record is valid iff its flags are known, every float its kind reads is finite (impulse; point too for AT_POINT),
+ *             entity < the world's entity count, and that entity carries a Dynamic body at the time of the call: it has a slot
+ *             and the slot's type is Dynamic (a body kept without a Transform counts; so does one whose RigidBody or Collider is
+ *             dirty — see Wake).  Every other record is skipped and changes nothing.
+ *   Apply     per body, its valid records in ASCENDING RECORD INDEX, as if Bullet's calls were made one after the other, on the
+ *             velocities in memory (v, w):
+ *               AT_POINT, CENTRAL   v[k] = v[k] + impulse[k] * inv_mass                                    k = x, y, z
+ *               AT_POINT            t = cross3(r, impulse);  w = w + mat_vec(invI_world, t)
+ *               TORQUE              t = impulse;             w = w + mat_vec(invI_world, t)
+ *             cross3(a, b) = (a.y*b.z - a.z*b.y, a.z*b.x - a.x*b.z, a.x*b.y - a.y*b.x); mat_vec row r = (m[r][0]*t.x + m[r][1]*t.y)
+ *             + m[r][2]*t.z; w = w + u adds component by component.  inv_mass is the value the tick uses (1 / mass as uploaded).
+ *             invI_world is the contact solver's, computed once per body and call from the pose in memory, so it does not change
+ *             between the records of a call.  Records of different bodies do not meet.
+ *   Inertia   mass = max(mass as uploaded, 0.01); inv_mass = 1 / mass.  Box: he = the collider's half extents with margin (for
+ *             sizes >= 0.4: (size - 0.04f) + 0.04f per axis), l = 2 * he, m12 = mass * 0.0833333358168602f,
+ *             I = (m12*(l.y*l.y + l.z*l.z), m12*(l.x*l.x + l.z*l.z), m12*(l.x*l.x + l.y*l.y)).  Capsule (radius r, half height
+ *             hh): l = 2 * (r, r + hh, r), sm = mass * 0.08333333f, I likewise with sm.  il[k] = I[k] != 0 ? 1 / I[k] : 0.
+ *             basis B = btMatrix3x3(q) of the stored quaternion q, the same under both orientation schemes:
+ *             d = ((q.x*q.x + q.y*q.y) + q.z*q.z) + q.w*q.w; s = 2 / d; xs, ys, zs = q.x*s, q.y*s, q.z*s; wx = q.w*xs ..; xx = q.x*xs ..;
+ *             B = [1 - (yy + zz), xy - wz, xz + wy; xy + wz, 1 - (xx + zz), yz - wx; xz - wy, yz + wx, 1 - (xx + yy)].
+ *             invI_world[r][c] = ((B[r][0]*il.x)*B[c][0] + (B[r][1]*il.y)*B[c][1]) + (B[r][2]*il.z)*B[c][2].
+ *   Wake      a body with at least one valid record is activated as activate() does it: its state becomes ACTIVE_TAG and
+ *             m_deactivationTime 0, whether it was asleep, wanted to sleep or was awake with a running timer.  A valid record
+ *             whose impulse is all zeros still wakes: that is the caller's activate().  Cached contacts (the plane's manifold,
+ *             the box manifolds, the pair cache of Dynamic-against-Dynamic contacts) are not touched: a woken body warm-starts
+ *             from what it held.  With Dynamic-against-Dynamic contacts on, the next tick finds an island that is no longer all
+ *             asleep: its other sleeping bodies go WANTS_DEACTIVATION with timer 0 (Bullet's buildIslands) and the island is
+ *             collided and solved again.  A body whose RigidBody or Collider is
+ *             dirty is re-created by the next tick with zero velocity, as after any upload: the impulse is lost with the old body.
+ *   Status    optional, one word per record: BGE_IMPULSE_APPLIED (1) on every valid record; BGE_IMPULSE_WOKE (2) in addition on
+ *             the lowest-index valid record of a body that was not ACTIVE_TAG with timer 0 before the call;
+ *             BGE_IMPULSE_INVALID (4) alone for unknown flags or a non-finite float (whatever the entity is); otherwise
+ *             BGE_IMPULSE_NO_BODY (8) alone for an entity out of range or without a Dynamic body.
+ *   Hence     the result is the same bytes every time, however many records name one body and however the batch is ordered
+ *             among different bodies: no sum is taken across records other than the one the order states.
+ *   Example   a 1 kg box of half extents 0.5 at rest at the origin, unrotated, ISLAND_SLEEPING.  I_local = (1/6, 1/6, 1/6),
+ *             invI_world = diag(6).  Record 0: AT_POINT, impulse (0, 0, 2), point (0.5, 0, 0): v = (0, 0, 2), t = (0, -1, 0),
+ *             w = (0, -6, 0).  Record 1 on the same body: CENTRAL, impulse (1, 0, 0): v = (1, 0, 2).  The body is ACTIVE_TAG with
+ *             timer 0; status = {APPLIED | WOKE, APPLIED}.
+ *   bge_world_apply_impulses         records[0 .. n) from host memory; status[0 .. n) or NULL.  n = 0 is a no-op; records NULL
+ *                                    with n > 0 is BGE_ERR_INVALID; n is at most 2^30 - 1.  Before bge_world_set_topology it
+ *                                    returns what bge_world_sphere_cast returns there.  Synchronises the world's stream.
+ *   bge_world_apply_impulses_device  the same from and to device pointers, 4-byte aligned (a misaligned pointer is
+ *                                    BGE_ERR_INVALID); status_device may be NULL.  Enqueued on the world's stream, no
+ *                                    synchronisation, nothing read back; the records must stay as they are until the stream has
+ *                                    passed the call.
+ */
+enum bge_impulse_flags { BGE_IMPULSE_AT_POINT = 0u, BGE_IMPULSE_CENTRAL = 1u, BGE_IMPULSE_TORQUE = 2u, BGE_IMPULSE_WORLD_POINT = 4u };
+enum bge_impulse_status { BGE_IMPULSE_APPLIED = 1u, BGE_IMPULSE_WOKE = 2u, BGE_IMPULSE_INVALID = 4u, BGE_IMPULSE_NO_BODY = 8u };
+typedef struct bge_impulse {
+    uint32_t entity;
+    uint32_t flags;   /* bge_impulse_flags */
+    float impulse[3]; /* N s; for BGE_IMPULSE_TORQUE a torque impulse, N m s */
+    float point[3];   /* AT_POINT: rel_pos, or a world position with BGE_IMPULSE_WORLD_POINT; otherwise ignored */
+} bge_impulse; /* 32 bytes, 4-byte aligned, moved word by word */
+BGE_API int bge_world_apply_impulses(bge_world* world, uint64_t n, const bge_impulse* records, uint32_t* status);
+BGE_API int bge_world_apply_impulses_device(bge_world* world, uint64_t n, const void* records_device, void* status_device);
+
+/*
+ * Character push: the device's characters shove the Dynamic bodies they walk into.  In the reference the
+ * character's ghost is a fixed body to the solver and a crate is pushed out of it; here the step's hit becomes an impulse record.
+ * Opt-in: until bge_world_characters_push switches it on, every call does byte for byte what it does without this section.
+ *   Push      with push on, every step of bge_world_characters_update ends with the stage Push, after State.  For character i the
+ *             record is empty (entity = BGE_RAY_NO_ENTITY, every other word 0) unless all of these hold for the state the step
+ *             left: the step was valid (no BGE_CHAR_INVALID); hit_kind == BGE_RAY_BODY; hit_entity carries a Dynamic body (as
+ *             "Impulses" Valid); that body's collision group & body_mask != 0; |hit_normal.y| <= max_normal_y.  Then, with
+ *             n = hit_normal:
+ *                  h = sqrtf(n.x*n.x + n.z*n.z);  d = (-n.x / h, 0, -n.z / h);  m = force * dt;  impulse = (d.x*m, d.y*m, d.z*m)
+ *             kind BGE_IMPULSE_CENTRAL, entity = hit_entity, point 0.  max_normal_y < 1 makes h > 0 for a unit normal; a record
+ *             whose impulse is not finite is skipped by Apply like any other.
+ *   Apply     the n records then go through "Impulses" Apply and Wake, record index = character index: two characters against
+ *             one crate in one step add in character order, and a pushed body wakes.  No status is kept.
+ *   Hence     bodies do not move between the steps of one update call, so every step of a call pushes; the push is central, so
+ *             it produces no spin; a character standing on a crate does not push it (its hit normal is vertical, and the ground
+ *             probe is not a hit); there is no reaction on the character.
+ *   Example   force 30, dt = 1/60, a character walking along +x into the face of a 1 kg crate: hit_normal = (-1, 0, 0), h = 1,
+ *             d = (1, 0, 0), m = 0.5: the crate's v.x grows by 0.5 in that step, and it is ACTIVE_TAG with timer 0.
+ *   Records   the push records kept are those of the call's last step.
+ *   bge_world_characters_push     desc->flags = BGE_CHAR_PUSH_ON, or 0 = off (which drops the records; the other members are then
+ *                                 ignored).  Unknown flag bits, a force that is not finite and >= 0, a max_normal_y that is not
+ *                                 finite and in [0, 1), a NULL desc and ON without a set are BGE_ERR_INVALID.  Calling it again
+ *                                 replaces the desc.  All arrays are allocated here: an update call allocates nothing and reads
+ *                                 nothing back.  Synchronises the world's stream.
+ *   bge_world_characters_push_records  out[0 .. count) = the records of characters first .. first + count as the last update
+ *                                 call's last step left them (empty before the first update).  Synchronises the world's stream.
+ *                                 A range outside the set is BGE_ERR_INVALID, and so is any count > 0 while push is off.
+ *   bge_world_characters_push_records_device  the resident bge_impulse[n] (NULL and 0 while push is off), valid until the next
+ *                                 bge_world_characters_push(off) or bge_world_characters_create; reads must be ordered after the
+ *                                 world's stream.
+ *   bge_world_characters_create   switches push off and drops the records.
+ *   Not done  a reaction on the character; a push at the contact point (spin); radial impulses; forces accumulated over a step.
+ */
+enum bge_character_push_mode { BGE_CHAR_PUSH_ON = 1u };
+typedef struct bge_character_push_desc {
+    uint32_t flags;     /* bge_character_push_mode */
+    float force;        /* newtons, finite, >= 0 */
+    float max_normal_y; /* finite, in [0, 1): steeper hits (|hit_normal.y| above it) do not push */
+    uint32_t body_mask; /* a body is pushed iff its collision group & body_mask != 0 */
+} bge_character_push_desc; /* 16 bytes */
+BGE_API int bge_world_characters_push(bge_world* world, const bge_character_push_desc* desc);
+BGE_API int bge_world_characters_push_records(bge_world* world, uint64_t first, uint64_t count, bge_impulse* out);
+BGE_API int bge_world_characters_push_records_device(bge_world* world, void** records, uint64_t* n);
 
 /*
  * Query index.  Opt-in; off by default, and while it is off every call enqueues exactly what it enqueues without this section.
