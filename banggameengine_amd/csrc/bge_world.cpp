@@ -947,7 +947,12 @@ int process_trigger_pairs_fast(bge_world* w)
     const uint32_t n_delta = host[0], n_pairs = host[3];
     w->trig_against_all = host[4];
     w->trig_through_grid = host[5];
-    if (n_pairs > kTriggerPairCap) return fail(BGE_ERR_OOM, "%u trigger overlaps in one tick exceed the buffer of %u", n_pairs, kTriggerPairCap);
+    if (n_pairs > kTriggerPairCap) {
+        // k_trigger_diff_cur has put this tick's keys into trig_tab[0] already: both tables are rebuilt from the host's sets, which
+        // this tick leaves as they were, before the next difference is taken (bge_world.h: a tick that fails this way)
+        w->trig_mirror_valid = false;
+        return fail(BGE_ERR_OOM, "%u trigger overlaps in one tick exceed the buffer of %u", n_pairs, kTriggerPairCap);
+    }
     if (host[2] || n_delta > kTrigDeltaCap || (static_cast<uint64_t>(host[1]) << 1) > (1ull << w->trig_tab_log2)) {
         w->trig_mirror_valid = false; // (both tables are rebuilt, larger, after the long way)
         if (w->trig_pairs_host.size() < 2 * static_cast<size_t>(n_pairs)) w->trig_pairs_host.resize(2 * static_cast<size_t>(n_pairs));

@@ -377,6 +377,9 @@ BGE_API int bge_world_pairs(bge_world* world, uint32_t* pairs2, uint64_t cap, ui
  *       it in the same tick no longer list it (:1062-1072).  The triggers are processed IN THE ORDER OF THE UPLOADED ARRAY
  *       (the reference walks a std::unordered_map — an order the language leaves open; the C++ adapter and the oracle use
  *       ascending EntityId).  With triggers present such a tick synchronises the stream (the events are for host code).
+ *       A tick may find at most 2^20 overlaps (trigger, body) and (trigger, trigger) together; one that finds more fails with
+ *       BGE_ERR_OOM and a message naming both numbers.  A tick that fails this way reports no events and leaves every
+ *       remembered set as it was before it; the next successful tick is diffed against those sets.
  *   bge_world_trigger_events returns (and clears) the events accumulated since the previous call.
  *   bge_world_trigger_active reports TriggerVolume::active per queried entity (0 after a one-shot fired, or no trigger).
  *   With more than 64 triggers (BGE_TRIGGER_GRID_MIN overrides the number) step (b) changes: a ghost whose box covers at

@@ -150,6 +150,18 @@ int orc_trigger_is_active(void* h, uint32_t id)
     const RefTriggerVolume* t = S(h)->scene.GetTriggerVolume(id);
     return t && t->active ? 1 : 0;
 }
+// the ghost's box as EnsureTrigger last posed it (min xyz, max xyz); 0 when the entity has no ghost in the world
+int orc_trigger_box(void* h, uint32_t id, float* out6)
+{
+    const auto& rts = S(h)->physics.TriggerRuntimes();
+    const auto it = rts.find(id);
+    if (it == rts.end() || !it->second.hasGhost || !it->second.active) return 0;
+    for (int a = 0; a < 3; ++a) {
+        out6[a] = it->second.aabbMin[a];
+        out6[3 + a] = it->second.aabbMax[a];
+    }
+    return 1;
+}
 // events of the last physics update as (type, trigger id, other id) triples; returns how many there are
 uint64_t orc_trigger_events(void* h, uint32_t* out3, uint64_t cap)
 {

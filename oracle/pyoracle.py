@@ -57,6 +57,8 @@ class _Lib:
         l.orc_bench_tick_soa.argtypes = [C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_double,
                                          C.c_int, C.POINTER(C.c_int), C.c_void_p]
         l.orc_trigger_events.restype = C.c_uint64
+        l.orc_trigger_box.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+        l.orc_trigger_box.restype = C.c_int
         l.orc_add_trigger.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_int]
         l.orc_physics_update.argtypes = [C.c_void_p, C.c_double]
         l.orc_set_accumulator.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_int]
@@ -260,6 +262,11 @@ class RefScene:
 
     def TriggerIsActive(self, eid):
         return bool(lib().orc_trigger_is_active(self.h, C.c_uint32(eid)))
+
+    def TriggerBox(self, eid):
+        """The ghost's box as EnsureTrigger last posed it (min xyz, max xyz), or None when the entity has no ghost in the world."""
+        out = np.empty(6, np.float32)
+        return out if lib().orc_trigger_box(self.h, C.c_uint32(eid), _vp(out)) else None
 
     def TriggerEvents(self):
         """(type, trigger id, other id) rows of the last PhysicsSystemUpdate, sorted; type 0 Enter, 1 Stay, 2 Exit."""
