@@ -87,6 +87,30 @@ inline Vec3 PlaneSpace1(const Vec3& n)
     return V(-n.y * k, n.x * k, 0.0f);
 }
 
+// What one CollideBoxBox call did, for the tests that must prove which branch a pose takes (tests/refmodel/boxbox_cases.py).  A sink is
+// optional everywhere (a null pointer by default) and only ever written: no result depends on it.
+struct BoxTrace {
+    enum Action { kNone = 0, kSkipped = 1, kReplaced = 2, kAppended = 3, kSortedIn = 4 };
+    enum Reason { kDistance = 1, kDrift = 2 };
+    int ran = 0;            // the detector was called
+    int code = 0, invertNormal = 0;
+    int lanr = -1, nrSign = 0, codeN = -1; // face codes: the incident axis, the sign of nr[lanr] (-1 / +1), the reference axis
+    int nClip = -1;         // points out of IntersectRectQuad2
+    int early8 = 0;         // ... left through its 8-point exit
+    int cnum = -1;          // points with dep >= 0
+    int culled = 0, cullI0 = -1; // culled: 1 CullPoints2 ran, 2 it ran and took its a = 1e18 branch
+    int edgeParallel = -1;  // edge codes: 1 where d <= 0.0001 was taken
+    int skipMask = 0;       // bit k: edge axis 7 + k was skipped because l <= epsilon
+    int nOut = 0;           // points the detector reported
+    int nBefore = 0;        // points in the manifold before the call
+    int action[4] = {0, 0, 0, 0}, index[4] = {-1, -1, -1, -1}, maxPen[4] = {-2, -2, -2, -2}; // per detector point
+    int nRemoved = 0, reason[4] = {0, 0, 0, 0}, wasLast[4] = {0, 0, 0, 0}, removedRow[4] = {-1, -1, -1, -1};
+    float in[30] = {};      // p1, R1 (rows), side1, p2, R2, side2 as the detector took them
+    float normalOnB[3] = {0, 0, 0};
+    float point[12] = {}, depth[4] = {0, 0, 0, 0};
+    float breaking = 0.0f;
+};
+
 namespace bb {
 
 // dMatrix3: 3 rows of 4 (the fourth column unused), element (i, j) at [4 i + j]
@@ -134,8 +158,15 @@ inline void LineClosestApproach(const Vec3& pa, const Vec3& ua, const Vec3& pb, 
     }
 }
 
+// the branch LineClosestApproach takes for these directions (the same expression; for the trace only)
+inline bool ParallelEdges(const float ua[3], const float ub[3])
+{
+    const float uaub = Dot(ua, 1, ub, 1);
+    return 1.0f - uaub * uaub <= 0.0001f;
+}
+
 // intersection of the rectangle (+-h[0], +-h[1]) with the quadrilateral p[0..7]; points as x, y pairs in ret; count 0..8
-inline int IntersectRectQuad2(const float h[2], const float p[8], float ret[16])
+inline int IntersectRectQuad2(const float h[2], const float p[8], float ret[16], int* early8 = nullptr)
 {
     int nq = 4, nr = 0;
     float buffer[16];
@@ -155,6 +186,7 @@ inline int IntersectRectQuad2(const float h[2], const float p[8], float ret[16])
                     nr++;
                     if (nr & 8) {
                         q = r;
+                        if (early8) *early8 = 1;
                         goto done;
                     }
                 }
@@ -166,6 +198,7 @@ inline int IntersectRectQuad2(const float h[2], const float p[8], float ret[16])
                     nr++;
                     if (nr & 8) {
                         q = r;
+                        if (early8) *early8 = 1;
                         goto done;
                     }
                 }
@@ -182,7 +215,7 @@ done:
 }
 
 // cullPoints2: m of the n points (2 n floats) that represent the polygon best; i0 is always the first
-inline void CullPoints2(int n, const float p[], int m, int i0, int iret[])
+inline void CullPoints2(int n, const float p[], int m, int i0, int iret[], int* areaGuard = nullptr)
 {
     constexpr float kPi = 3.14159265f; // M__PI of the file
     float a, cx, cy, q;
@@ -207,6 +240,7 @@ inline void CullPoints2(int n, const float p[], int m, int i0, int iret[])
             a = 0.3333333432674408f / (a + q); // (1.f / (3 * (a + q)) in the source: the reference's compiled code — MSVC /fp:fast — divides the constant 0x3eaaaaab)
         } else {
             a = 1.0e18f; // BT_LARGE_FLOAT
+            if (areaGuard) *areaGuard = 1;
         }
         cx = a * (cx + q * (p[n * 2 - 2] + p[0]));
         cy = a * (cy + q * (p[n * 2 - 1] + p[1]));
@@ -239,7 +273,8 @@ inline void CullPoints2(int n, const float p[], int m, int i0, int iret[])
 }
 
 // dBoxBox2 with maxc = 4; the contact points go to `out` as btBoxBoxDetector hands them to Result::addContactPoint
-inline int BoxBox2(const Vec3& p1v, const M34& R1m, const Vec3& side1, const Vec3& p2v, const M34& R2m, const Vec3& side2, Out& out)
+inline int BoxBox2(const Vec3& p1v, const M34& R1m, const Vec3& side1, const Vec3& p2v, const M34& R2m, const Vec3& side2, Out& out,
+                   BoxTrace* trace = nullptr)
 {
     const float fudge_factor = 1.05f;
     const float* R1 = R1m.m;
@@ -309,6 +344,8 @@ inline int BoxBox2(const Vec3& p1v, const M34& R1m, const Vec3& side1, const Vec
             invert_normal = ((expr1) < 0);                               \
             code = (cc);                                                 \
         }                                                                \
+    } else if (trace) {                                                  \
+        trace->skipMask |= 1 << ((cc) - 7);                              \
     }
     const float fudge2 = 1.0e-5f;
     Q11 += fudge2;
@@ -348,6 +385,10 @@ inline int BoxBox2(const Vec3& p1v, const M34& R1m, const Vec3& side1, const Vec
     }
     const float depth = -s;
     out.code = code;
+    if (trace) {
+        trace->code = code;
+        trace->invertNormal = invert_normal;
+    }
     const Vec3 minusNormal = V(-normal[0], -normal[1], -normal[2]);
 
     if (code > 6) {
@@ -368,6 +409,7 @@ inline int BoxBox2(const Vec3& p1v, const M34& R1m, const Vec3& side1, const Vec
         for (int i = 0; i < 3; ++i) ua[i] = R1[(code - 7) / 3 + i * 4];
         for (int i = 0; i < 3; ++i) ub[i] = R2[(code - 7) % 3 + i * 4];
         LineClosestApproach(V(pa[0], pa[1], pa[2]), V(ua[0], ua[1], ua[2]), V(pb[0], pb[1], pb[2]), V(ub[0], ub[1], ub[2]), &alpha, &beta);
+        if (trace) trace->edgeParallel = ParallelEdges(ua, ub) ? 1 : 0;
         for (int i = 0; i < 3; ++i) pa[i] += ua[i] * alpha;
         for (int i = 0; i < 3; ++i) pb[i] += ub[i] * beta;
         out.normalOnB[0] = minusNormal; // output.addContactPoint(-normal, pb, -*depth)
@@ -479,7 +521,15 @@ inline int BoxBox2(const Vec3& p1v, const M34& R1m, const Vec3& side1, const Vec
     rect[0] = Sa[code1];
     rect[1] = Sa[code2];
     float ret[16];
-    const int n = IntersectRectQuad2(rect, quad, ret);
+    int early8 = 0;
+    const int n = IntersectRectQuad2(rect, quad, ret, trace ? &early8 : nullptr);
+    if (trace) {
+        trace->lanr = lanr;
+        trace->nrSign = nr[lanr] < 0 ? -1 : 1;
+        trace->codeN = codeN;
+        trace->nClip = n;
+        trace->early8 = early8;
+    }
     if (n < 1) return 0;
     float point[3 * 8];
     float dep[8];
@@ -500,6 +550,7 @@ inline int BoxBox2(const Vec3& p1v, const M34& R1m, const Vec3& side1, const Vec
             cnum++;
         }
     }
+    if (trace) trace->cnum = cnum;
     if (cnum < 1) return 0;
     int maxc = 4;
     if (maxc > cnum) maxc = cnum;
@@ -527,7 +578,12 @@ inline int BoxBox2(const Vec3& p1v, const M34& R1m, const Vec3& side1, const Vec
             }
         }
         int iret[8];
-        CullPoints2(cnum, ret, maxc, i1, iret);
+        int areaGuard = 0;
+        CullPoints2(cnum, ret, maxc, i1, iret, trace ? &areaGuard : nullptr);
+        if (trace) {
+            trace->culled = 1 + areaGuard; // (2: the polygon's area was no more than epsilon, a = 1e18)
+            trace->cullI0 = i1;
+        }
         for (int j = 0; j < maxc; ++j) {
             float w[3];
             for (int i = 0; i < 3; ++i) w[i] = point[iret[j] * 3 + i] + pa[i];
@@ -549,7 +605,7 @@ inline int BoxBox2(const Vec3& p1v, const M34& R1m, const Vec3& side1, const Vec
 } // namespace bb
 
 // btPersistentManifold::sortCachedPoints for a box manifold (the same rule as contact_ref.h's SortCachedPoints)
-inline int SortCachedBoxPoints(const BoxManifold& m, const BoxPoint& pt)
+inline int SortCachedBoxPoints(const BoxManifold& m, const BoxPoint& pt, int* maxPenetrationOut = nullptr)
 {
     int maxPenetrationIndex = -1;
     float maxPenetration = pt.distance;
@@ -559,6 +615,7 @@ inline int SortCachedBoxPoints(const BoxManifold& m, const BoxPoint& pt)
             maxPenetration = m.p[i].distance;
         }
     }
+    if (maxPenetrationOut) *maxPenetrationOut = maxPenetrationIndex;
     float res[4] = {0.0f, 0.0f, 0.0f, 0.0f};
     const Vec3& p0 = m.p[0].localA;
     const Vec3& p1 = m.p[1].localA;
@@ -582,14 +639,41 @@ inline int SortCachedBoxPoints(const BoxManifold& m, const BoxPoint& pt)
 }
 
 // btBoxBoxCollisionAlgorithm::processCollision for body0 = the Dynamic box `a`, body1 = the Static / Kinematic box `b`
-inline void CollideBoxBox(BoxManifold& m, const BoxPose& a, const BoxPose& b)
+inline void CollideBoxBox(BoxManifold& m, const BoxPose& a, const BoxPose& b, BoxTrace* trace = nullptr)
 {
     bb::Out out;
-    bb::BoxBox2(a.origin, bb::FromBasis(a.basis), Scale(a.halfWithMargin, 2.0f), b.origin, bb::FromBasis(b.basis), Scale(b.halfWithMargin, 2.0f), out);
+    if (trace) {
+        *trace = BoxTrace{};
+        trace->ran = 1;
+        trace->nBefore = m.n;
+        trace->breaking = m.breaking;
+        const BoxPose* ps[2] = {&a, &b};
+        for (int k = 0; k < 2; ++k) {
+            float* o = trace->in + 15 * k;
+            o[0] = ps[k]->origin.x; o[1] = ps[k]->origin.y; o[2] = ps[k]->origin.z;
+            for (int r = 0; r < 3; ++r)
+                for (int c = 0; c < 3; ++c) o[3 + 3 * r + c] = ps[k]->basis.m[r][c];
+            o[12] = ps[k]->halfWithMargin.x * 2.0f; o[13] = ps[k]->halfWithMargin.y * 2.0f; o[14] = ps[k]->halfWithMargin.z * 2.0f;
+        }
+    }
+    bb::BoxBox2(a.origin, bb::FromBasis(a.basis), Scale(a.halfWithMargin, 2.0f), b.origin, bb::FromBasis(b.basis), Scale(b.halfWithMargin, 2.0f), out, trace);
+    if (trace) {
+        trace->nOut = out.n;
+        for (int k = 0; k < out.n; ++k) {
+            trace->point[3 * k] = out.point[k].x; trace->point[3 * k + 1] = out.point[k].y; trace->point[3 * k + 2] = out.point[k].z;
+            trace->depth[k] = out.depth[k];
+        }
+        if (out.n) {
+            trace->normalOnB[0] = out.normalOnB[0].x; trace->normalOnB[1] = out.normalOnB[0].y; trace->normalOnB[2] = out.normalOnB[0].z;
+        }
+    }
     for (int k = 0; k < out.n; ++k) {
         // btManifoldResult::addContactPoint(normalOnBInWorld, pointInWorld, depth)
         const float depth = out.depth[k];
-        if (depth > m.breaking) continue;
+        if (depth > m.breaking) {
+            if (trace) trace->action[k] = BoxTrace::kSkipped;
+            continue;
+        }
         const Vec3 normalOnB = out.normalOnB[k];
         const Vec3 pointInWorld = out.point[k];
         const Vec3 pointA = Add(pointInWorld, Scale(normalOnB, depth));
@@ -614,12 +698,23 @@ inline void CollideBoxBox(BoxManifold& m, const BoxPose& a, const BoxPose& b)
             np.appliedImpulse = m.p[nearest].appliedImpulse; // replaceContactPoint
             np.appliedImpulseLateral1 = m.p[nearest].appliedImpulseLateral1;
             m.p[nearest] = np;
+            if (trace) {
+                trace->action[k] = BoxTrace::kReplaced;
+                trace->index[k] = nearest;
+            }
         } else {
             int insert = m.n; // addManifoldPoint
-            if (insert == 4) {
-                insert = SortCachedBoxPoints(m, np);
+            int maxPen = -2;
+            const bool full = insert == 4;
+            if (full) {
+                insert = SortCachedBoxPoints(m, np, &maxPen);
             } else {
                 m.n++;
+            }
+            if (trace) {
+                trace->action[k] = full ? BoxTrace::kSortedIn : BoxTrace::kAppended;
+                trace->index[k] = insert; // (before the guard below: -1 would show that it can fire)
+                trace->maxPen[k] = maxPen;
             }
             if (insert < 0) insert = 0;
             m.p[insert] = np;
@@ -642,6 +737,12 @@ inline void CollideBoxBox(BoxManifold& m, const BoxPose& a, const BoxPose& b)
             remove = distance2d > m.breaking * m.breaking;
         }
         if (remove) {
+            if (trace && trace->nRemoved < 4) {
+                const int r = trace->nRemoved++;
+                trace->reason[r] = !(c.distance <= m.breaking) ? BoxTrace::kDistance : BoxTrace::kDrift;
+                trace->wasLast[r] = i == m.n - 1;
+                trace->removedRow[r] = i;
+            }
             const int last = m.n - 1;
             if (i != last) m.p[i] = m.p[last];
             m.p[last] = BoxPoint{};

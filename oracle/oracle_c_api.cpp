@@ -3,6 +3,7 @@
 // Flat C entry points over the CPU restatement so that tests/, __graft_entry__.smoke()
 // and bench.py's cpu_baseline leg can drive it through ctypes.  Nothing in the product
 // (banggameengine_amd/, include/) may link or load this library.
+#include <algorithm>
 #include <chrono>
 #include <cstdint>
 #include <cstring>
@@ -283,6 +284,76 @@ int orc_get_dynamic_pairs(void* h, int cap, uint32_t* hdr, float* out)
     }
     return static_cast<int>(pairs.size());
 }
+// ---- the trace of the box-box narrowphase (ct::BoxTrace) as 40 ints and 50 floats:
+// ints: ran, code, invertNormal, lanr, nrSign, codeN, nClip, early8, cnum, culled, cullI0, edgeParallel, skipMask, nOut, nBefore,
+//       action[4], index[4], maxPen[4], nRemoved, reason[4], wasLast[4], removedRow[4]
+// floats: p1, R1, side1, p2, R2, side2 (30), normalOnB (3), point[4] (12), depth[4], breaking
+static void PackTrace(const ct::BoxTrace& t, int32_t* i, float* f)
+{
+    const int head[15] = {t.ran, t.code, t.invertNormal, t.lanr, t.nrSign, t.codeN, t.nClip, t.early8, t.cnum, t.culled, t.cullI0, t.edgeParallel, t.skipMask, t.nOut, t.nBefore};
+    for (int k = 0; k < 15; ++k) i[k] = head[k];
+    for (int k = 0; k < 4; ++k) {
+        i[15 + k] = t.action[k];
+        i[19 + k] = t.index[k];
+        i[23 + k] = t.maxPen[k];
+        i[28 + k] = t.reason[k];
+        i[32 + k] = t.wasLast[k];
+        i[36 + k] = t.removedRow[k];
+    }
+    i[27] = t.nRemoved;
+    std::memcpy(f, t.in, sizeof(t.in));
+    std::memcpy(f + 30, t.normalOnB, sizeof(t.normalOnB));
+    std::memcpy(f + 33, t.point, sizeof(t.point));
+    std::memcpy(f + 45, t.depth, sizeof(t.depth));
+    f[49] = t.breaking;
+}
+void orc_set_box_trace(void* h, int enabled) { S(h)->physics.traceBoxes = enabled != 0; }
+// kind 0: the obstacle manifolds (key = Dynamic entity, obstacle entity), 1: the pairs of Dynamic boxes (lower, higher) of the last
+// physics update, ascending; returns how many there are and fills the first `cap`
+int orc_get_box_traces(void* h, int kind, int cap, uint32_t* key2, int32_t* ints40, float* floats50)
+{
+    const auto& tr = kind == 0 ? S(h)->physics.BoxTraces() : S(h)->physics.PairTraces();
+    int k = 0;
+    for (const auto& kv : tr) {
+        if (k >= cap) break;
+        key2[2 * k] = kv.first.first;
+        key2[2 * k + 1] = kv.first.second;
+        PackTrace(kv.second, ints40 + 40 * k, floats50 + 50 * k);
+        ++k;
+    }
+    return static_cast<int>(tr.size());
+}
+// CollideBoxBox on n pairs of boxes with empty manifolds, posed as EnsureRigidBody poses a body (position, rotationEuler, collider
+// size = half extents): the narrowphase alone, for the seeded searches of the tests.  Traces as above.
+void orc_boxbox_detect(uint64_t n, const float* posA, const float* eulerA, const float* sizeA, const float* posB, const float* eulerB,
+                       const float* sizeB, int32_t* ints40, float* floats50)
+{
+#if defined(_OPENMP)
+#pragma omp parallel for schedule(static)
+#endif
+    for (int64_t i = 0; i < static_cast<int64_t>(n); ++i) {
+        ct::BoxPose ps[2];
+        float breaking = 0.0f;
+        for (int k = 0; k < 2; ++k) {
+            const float* p = (k ? posB : posA) + 3 * i;
+            const float* e = (k ? eulerB : eulerA) + 3 * i;
+            const float* z = (k ? sizeB : sizeA) + 3 * i;
+            ps[k].origin = bt::Vec3{p[0], p[1], p[2]};
+            ps[k].basis = bt::MatFromQuat(bt::QuatFromTransformEuler(e[0], e[1], e[2]));
+            ct::Shape sh;
+            sh.dims = bt::BoxAabbHalfExtents(std::max(z[0], 0.01f), std::max(z[1], 0.01f), std::max(z[2], 0.01f));
+            ps[k].halfWithMargin = sh.dims;
+            const float b = ct::ContactBreakingThreshold(sh);
+            breaking = k ? std::min(breaking, b) : b;
+        }
+        ct::BoxManifold m;
+        m.breaking = breaking;
+        ct::BoxTrace t;
+        ct::CollideBoxBox(m, ps[0], ps[1], &t);
+        PackTrace(t, ints40 + 40 * i, floats50 + 50 * i);
+    }
+}
+
 uint64_t orc_count_dirty(void* h) { return S(h)->scene.CountDirtyTransforms(); }
 uint64_t orc_transform_count(void* h) { return S(h)->scene.GetTransformCount(); }
 

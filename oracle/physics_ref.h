@@ -203,6 +203,13 @@ public:
     // together and put to sleep together: island_ref.h and CollideDynamicPairs / StepIsland below).  Off by default.
     bool dynamicContacts = false;
 
+    // Optional trace of the box-box narrowphase (ct::BoxTrace): with traceBoxes on, every CollideBoxBox call of an Update leaves what it
+    // did under (Dynamic entity, obstacle entity) or (lower entity, higher entity).  Off by default; only ever written.
+    bool traceBoxes = false;
+    using TraceMap = std::map<std::pair<EntityId, EntityId>, ct::BoxTrace>;
+    const TraceMap& BoxTraces() const { return boxTraces_; }
+    const TraceMap& PairTraces() const { return pairTraces_; }
+
     struct DynPair {
         ct::BoxManifold m;
         uint32_t genA = 0, genB = 0;
@@ -230,6 +237,8 @@ public:
     // The rigid-body slice of PhysicsSystem::Update(scene, camera, input, dt).
     void Update(RefScene& scene, double dt)
     {
+        boxTraces_.clear();
+        pairTraces_.clear();
         // :1222-1246 prune
         std::vector<EntityId> gone;
         for (const auto& kv : runtime_) {
@@ -584,7 +593,7 @@ private:
                 }
                 if (a.activation != kIslandSleeping || b.activation != kIslandSleeping) {
                     const ct::BoxPose pa{a.origin, a.basis, a.shape.dims}, pb{b.origin, b.basis, b.shape.dims};
-                    ct::CollideBoxBox(e.m, pa, pb);
+                    ct::CollideBoxBox(e.m, pa, pb, traceBoxes ? &pairTraces_[{ea, eb}] : nullptr);
                 }
                 next[{ea, eb}] = e;
                 const EntityId ra = find(ea), rb = find(eb);
@@ -718,7 +727,7 @@ private:
                 m.restitution = rt.restitution * o.restitution;                             // ... calculateCombinedRestitution
             }
             const ct::BoxPose a{rt.origin, rt.basis, rt.shape.dims}, b{o.origin, o.basis, o.shape.dims};
-            ct::CollideBoxBox(m, a, b);
+            ct::CollideBoxBox(m, a, b, traceBoxes ? &boxTraces_[{self, ob.first}] : nullptr);
             next.push_back(m);
             nextGen.push_back(o.generation);
         }
@@ -856,6 +865,7 @@ private:
         }
     }
 
+    TraceMap boxTraces_, pairTraces_;
     std::unordered_map<EntityId, RefBodyRuntime> runtime_;
     std::map<std::pair<EntityId, EntityId>, DynPair> dynPairs_; // the pair cache of Dynamic boxes with its manifolds, (lower, higher) entity
     std::unordered_map<EntityId, RefTriggerRuntime> triggerRuntime_;

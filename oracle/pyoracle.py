@@ -76,6 +76,10 @@ class _Lib:
         l.orc_get_ground_contacts.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
         l.orc_get_ground_contacts.restype = C.c_int
         l.orc_set_physics_options.argtypes = [C.c_void_p, C.c_float, C.c_int, C.c_int]
+        l.orc_set_box_trace.argtypes = [C.c_void_p, C.c_int]
+        l.orc_get_box_traces.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        l.orc_get_box_traces.restype = C.c_int
+        l.orc_boxbox_detect.argtypes = [C.c_uint64] + [C.c_void_p] * 8
         l.orc_add_rigidbody.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_float, C.c_uint32, C.c_uint32]
 
 
@@ -187,6 +191,56 @@ def bench_tick_soa(shape, pos_box, bodies_on_roots_only, n, seed, warm, ticks, d
     sec = lib().orc_bench_tick_soa(shape, pos_box, int(bodies_on_roots_only), n, seed, warm, ticks, float(np.float32(dt)),
                                    threads, C.byref(used), _vp(world))
     return (sec, used.value, world) if want_world else (sec, used.value)
+
+
+# ----------------------------------------------------------------------------- the box-box narrowphase's trace
+ACT_NONE, ACT_SKIPPED, ACT_REPLACED, ACT_APPENDED, ACT_SORTED_IN = range(5)
+REMOVED_BY_DISTANCE, REMOVED_BY_DRIFT = 1, 2
+
+
+class BoxTraces:
+    """The traces of several CollideBoxBox calls as arrays, one row a call (ct::BoxTrace of oracle/boxbox_ref.h).
+    key (n, 2): entity ids (Dynamic, obstacle) or (lower, higher); zeros for orc_boxbox_detect.
+    Detector: ran, code, invert_normal; lanr, nr_sign, code_n, n_clip, early8, cnum, culled (1: CullPoints2 ran, 2: and took its
+    a = 1e18 branch), cull_i0 (face codes; -1 / 0 otherwise);
+    edge_parallel (edge codes: 1 where d <= 0.0001 was taken, else 0; -1 otherwise); skip_mask (bit k: edge axis 7 + k skipped because
+    l <= epsilon); n_out.  Cache: n_before; action / index / max_pen (n, 4) per detector point (ACT_*; the row replaced, appended to or
+    evicted; maxPenetrationIndex, -2 where sortCachedPoints did not run); n_removed, reason (REMOVED_BY_*), was_last, removed_row
+    (n, 4) in the order of removal.  Inputs as the detector took them: p1, p2 (n, 3), R1, R2 (n, 3, 3), half1, half2 (n, 3: half
+    extents with margin); its answer: normal_on_b (n, 3), point (n, 4, 3), depth (n, 4); breaking (n,)."""
+
+    def __init__(self, key, ints, floats):
+        i, f = ints, floats
+        self.key, self._ints, self._floats = key, ints, floats
+        (self.ran, self.code, self.invert_normal, self.lanr, self.nr_sign, self.code_n, self.n_clip, self.early8, self.cnum, self.culled,
+         self.cull_i0, self.edge_parallel, self.skip_mask, self.n_out, self.n_before) = (i[:, k] for k in range(15))
+        self.action, self.index, self.max_pen = i[:, 15:19], i[:, 19:23], i[:, 23:27]
+        self.n_removed, self.reason, self.was_last, self.removed_row = i[:, 27], i[:, 28:32], i[:, 32:36], i[:, 36:40]
+        self.p1, self.R1, self.half1 = f[:, 0:3], f[:, 3:12].reshape(-1, 3, 3), f[:, 12:15] * np.float32(0.5)
+        self.p2, self.R2, self.half2 = f[:, 15:18], f[:, 18:27].reshape(-1, 3, 3), f[:, 27:30] * np.float32(0.5)
+        self.normal_on_b, self.point, self.depth, self.breaking = f[:, 30:33], f[:, 33:45].reshape(-1, 4, 3), f[:, 45:49], f[:, 49]
+
+    def __len__(self):
+        return len(self.key)
+
+    def take(self, rows):
+        """The rows a mask or an index array selects."""
+        return BoxTraces(self.key[rows], self._ints[rows], self._floats[rows])
+
+    def row_of(self, a, b):
+        """The row of the call for entity ids (a, b), or None."""
+        hit = np.flatnonzero((self.key[:, 0] == a) & (self.key[:, 1] == b))
+        return int(hit[0]) if len(hit) else None
+
+
+def boxbox_detect(pos_a, euler_a, size_a, pos_b, euler_b, size_b):
+    """CollideBoxBox on n pairs of boxes with empty manifolds, posed as the oracle poses a body from position, rotationEuler and the
+    collider's size (half extents): BoxTraces of n rows."""
+    arrs = [np.ascontiguousarray(a, np.float32).reshape(-1, 3) for a in (pos_a, euler_a, size_a, pos_b, euler_b, size_b)]
+    n = len(arrs[0])
+    ints, floats = np.zeros((n, 40), np.int32), np.zeros((n, 50), np.float32)
+    lib().orc_boxbox_detect(C.c_uint64(n), *[_vp(a) for a in arrs], _vp(ints), _vp(floats))
+    return BoxTraces(np.zeros((n, 2), np.uint32), ints, floats)
 
 
 # ----------------------------------------------------------------------------- scene session
@@ -338,6 +392,29 @@ class RefScene:
         out = np.zeros((4, 4, 12), np.float32)
         n = lib().orc_get_box_contacts(self.h, eid, _vp(hdr), _vp(out))
         return [(int(hdr[k, 0]), out[k, :hdr[k, 1]].copy()) for k in range(min(n, 4))]
+
+    def SetBoxTrace(self, enabled=True):
+        """Every CollideBoxBox call of a physics update leaves a trace (BoxTrace / PairTrace).  Off by default; changes no result."""
+        lib().orc_set_box_trace(self.h, int(enabled))
+
+    def _traces(self, kind):
+        n = lib().orc_get_box_traces(self.h, kind, 0, None, None, None)
+        key, ints, floats = np.zeros((n, 2), np.uint32), np.zeros((n, 40), np.int32), np.zeros((n, 50), np.float32)
+        lib().orc_get_box_traces(self.h, kind, n, _vp(key), _vp(ints), _vp(floats))
+        return BoxTraces(key, ints, floats)
+
+    def BoxTrace(self, eid=None):
+        """BoxTraces of the last physics update's calls for obstacle manifolds, key = (Dynamic entity id, obstacle entity id),
+        ascending; of one Dynamic entity where eid is given."""
+        t = self._traces(0)
+        if eid is None:
+            return t
+        keep = t.key[:, 0] == eid
+        return t.take(keep)
+
+    def PairTrace(self):
+        """BoxTraces of the last physics update's calls for pairs of Dynamic boxes, key = (lower entity id, higher entity id)."""
+        return self._traces(1)
 
     def SetDynamicContacts(self, enabled=True):
         """Dynamic boxes collide with each other; bodies whose fed AABBs overlap form one simulation island (island_ref.h)."""

@@ -19,3 +19,10 @@ NEVER_INSIDE_MARGIN = np.float32(1e-3)  # by how much a mover that started clear
 # device sees lies within 5 u (hi - lo) of the exact one.  The sandwich allows d = HIST_EDGE_ULPS u (hi - lo), the next power of
 # two above that bound; the factor follows from this count, not from what a device returned.
 HIST_EDGE_ULPS = 8
+
+# The box-box narrowphase against its float64 model (refmodel/boxbox64): the largest deviation of the ORACLE's answers from the model over
+# the whole case set of refmodel/boxbox_cases, every figure taken relative to the pair's scale, is BOXBOX_MEASURED (DESIGN.md 6b has the
+# figure per check).  The margin of 4 is for the summation orders a compiler's fast-math mode may choose differently (the reference was
+# built with one); it comes from that argument, not from what a device returned.
+BOXBOX_MEASURED = 6.5e-7
+BOXBOX_REL = 4 * BOXBOX_MEASURED
