@@ -8,9 +8,9 @@ implementation: importing works without a GPU, creating a :class:`World` without
 """
 from ._capi import BgeError, lib, lib_path  # noqa: F401
 from .world import (DEBUG_ALL, DEBUG_CONTACTS, DEBUG_SHAPES, BODY_DYNAMIC, BODY_KINEMATIC, BODY_NONE, BODY_STATIC, NO_PARENT, SHAPE_BOX, SHAPE_CAPSULE,  # noqa: F401
-                    TICK_AABBS, TICK_ALL, TICK_BULLET_BASIS, TICK_BROADPHASE, TICK_GATHER_ROOTS, TICK_NORMAL_MATRICES, TICK_PHYSICS, TICK_TRANSFORMS, World, flatten_topology,
+                    TICK_AABBS, TICK_ALL, TICK_BULLET_BASIS, TICK_BROADPHASE, TICK_GATHER_ROOTS, TICK_NORMAL_MATRICES, TICK_PHYSICS, TICK_TRANSFORMS, World, device_memory, flatten_topology,
                     partition_subtrees)
 from .world import (PENETRATION_HIT_DTYPE, RECOVER_INVALID, RECOVER_MOVED, RECOVER_ROUNDS, RECOVER_STUCK, SPHERE_RECOVER_DTYPE,  # noqa: F401
                     SPHERE_RECOVER_RESULT_DTYPE, make_sphere_recovers)
 
-__all__ = ["World", "BgeError", "lib", "lib_path", "flatten_topology", "partition_subtrees"]
+__all__ = ["World", "BgeError", "lib", "lib_path", "device_memory", "flatten_topology", "partition_subtrees"]

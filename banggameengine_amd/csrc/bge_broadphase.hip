@@ -1719,19 +1719,6 @@ int Broadphase::fail(int code, const char* what, hipError_t e)
     return code;
 }
 
-void Broadphase::release()
-{
-    for (void** p : {&pairs_, &scan_stage_, &counters_, &cell_count_, &cell_start_, &scan_status_, &sort_matrix_,
-                     &sort_offsets_, &sort_status_, &coarse_, &sorted_slot_, &sorted_aabb_, &body_cell_,
-                     &large_list_}) {
-        if (*p) (void)hipFree(*p);
-        *p = nullptr;
-    }
-    n_slots_ = capacity_ = 0;
-    table_size_ = 0;
-    ran_ = false;
-}
-
 #define BP_TRY(expr)                                                       \
     do {                                                                   \
         const hipError_t e_ = (expr);                                      \
@@ -1744,23 +1731,27 @@ int Broadphase::configure(uint64_t n_slots, uint64_t pair_capacity)
         ran_ = false;
         return BGE_OK;
     }
-    release();
-    n_slots_ = n_slots;
-    capacity_ = pair_capacity;
+    // Nothing is configured until every allocation below has succeeded (the sizes are committed at the end): after a failure run()
+    // refuses, and the next configure() allocates again.  The buffers that do not grow are kept, and the last run() on the caller's
+    // stream may still use them: it ends before they are cleared on the null stream.
+    if (n_slots_) BP_TRY(hipDeviceSynchronize());
+    n_slots_ = capacity_ = 0;
+    table_size_ = 0;
+    ran_ = false;
     // table: at least 2 cells per possible body, multiple of the scan block
     uint64_t t = std::max<uint64_t>(2 * n_slots, 4096);
     t = (t + kScanBlock - 1) / kScanBlock * kScanBlock;
     if (t > 0x7ffff000ull) t = 0x7ffff000ull / kScanBlock * kScanBlock;
-    table_size_ = static_cast<uint32_t>(t);
+    const uint32_t table_size = static_cast<uint32_t>(t);
     // Allocation is lazy-free: a world that never runs the broadphase still pays for these buffers;
     // they total ~ (8 + 8 + 32 + 8 + 4) B per slot + 8 B per pair.
-    BP_TRY(hipMalloc(&pairs_, std::max<uint64_t>(capacity_, 1) * 8));
-    BP_TRY(hipMalloc(&scan_stage_, shard_capacity(capacity_) * kShards * 8)); // sharded staging of the pair list
-    BP_TRY(hipMalloc(&counters_, sizeof(Accum)));
-    BP_TRY(hipMalloc(&cell_count_, (static_cast<size_t>(table_size_) + 2 * kScanTile) * 4)); // whole scan tiles, zero-padded
-    BP_TRY(hipMalloc(&cell_start_, (static_cast<size_t>(table_size_) + 2 * kScanTile) * 4));
-    BP_TRY(hipMalloc(&scan_status_, (static_cast<size_t>(table_size_) / kScanBlock + 2) * 8));
-    BP_TRY(hipMemset(scan_status_, 0, (static_cast<size_t>(table_size_) / kScanBlock + 2) * 8));
+    BP_TRY(pairs_.ensure(std::max<uint64_t>(pair_capacity, 1) * 8));
+    BP_TRY(scan_stage_.ensure(shard_capacity(pair_capacity) * kShards * 8)); // sharded staging of the pair list
+    BP_TRY(counters_.ensure(sizeof(Accum)));
+    BP_TRY(cell_count_.ensure((static_cast<size_t>(table_size) + 2 * kScanTile) * 4)); // whole scan tiles, zero-padded
+    BP_TRY(cell_start_.ensure((static_cast<size_t>(table_size) + 2 * kScanTile) * 4));
+    BP_TRY(scan_status_.ensure((static_cast<size_t>(table_size) / kScanBlock + 2) * 8));
+    BP_TRY(hipMemset(scan_status_.p, 0, (static_cast<size_t>(table_size) / kScanBlock + 2) * 8));
     scan_epoch_ = 0;
     sort_groups_ = kSortGroups;
     if (const char* e = std::getenv("BGE_BP_SORT_GROUPS")) sort_groups_ = std::min<uint32_t>(kSortGroups, std::max(1, std::atoi(e))); // tests: several passes per workgroup at small n
@@ -1768,26 +1759,26 @@ int Broadphase::configure(uint64_t n_slots, uint64_t pair_capacity)
     if (const char* e = std::getenv("BGE_BP_FILTER")) small_palette_ = std::string(e) != "table"; // A/B and tests: keep the (group, mask) table
     if (const char* e = std::getenv("BGE_BP_COARSE")) transposed_coarse_ = std::string(e) != "scatter"; // A/B: per-thread scattered record writes
     if (const char* e = std::getenv("BGE_BP_RECORDS")) full_records_ = std::atoi(e) == 48;  // A/B: BGE_BP_RECORDS=48 keeps full records
-    BP_TRY(hipMalloc(&sorted_slot_, std::max<uint64_t>(n_slots, 1) * 4));  // body rank inside its cell
-    BP_TRY(hipMalloc(&sorted_aabb_, std::max<uint64_t>(n_slots, 1) * 48));
-    BP_TRY(hipMalloc(&body_cell_, std::max<uint64_t>(n_slots, 1) * 4));
-    BP_TRY(hipMalloc(&large_list_, std::max<uint64_t>(n_slots, 1) * 4));
-    BP_TRY(hipMemset(counters_, 0, sizeof(Accum)));
+    BP_TRY(sorted_slot_.ensure(std::max<uint64_t>(n_slots, 1) * 4));  // body rank inside its cell
+    BP_TRY(sorted_aabb_.ensure(std::max<uint64_t>(n_slots, 1) * 48));
+    BP_TRY(body_cell_.ensure(std::max<uint64_t>(n_slots, 1) * 4));
+    BP_TRY(large_list_.ensure(std::max<uint64_t>(n_slots, 1) * 4));
+    BP_TRY(hipMemset(counters_.p, 0, sizeof(Accum)));
     compacted_ = false;
     // LDS sort (k_sort_*): coarse buckets of 4096 cells (8192 for tables beyond 16 M cells); larger tables keep the
     // atomic counting sort
     sort_shift_ = 12;
-    while (sort_shift_ < 13 && (table_size_ >> sort_shift_) + 2 > kSortMaxBuckets) ++sort_shift_;
-    lds_sort_ = (table_size_ >> sort_shift_) + 2 <= kSortMaxBuckets;
+    while (sort_shift_ < 13 && (table_size >> sort_shift_) + 2 > kSortMaxBuckets) ++sort_shift_;
+    lds_sort_ = (table_size >> sort_shift_) + 2 <= kSortMaxBuckets;
     if (const char* e = std::getenv("BGE_BP_SORT")) lds_sort_ = lds_sort_ && std::string(e) != "atomic"; // A/B
     if (lds_sort_) {
-        sort_buckets_ = (table_size_ >> sort_shift_) + 2;
+        sort_buckets_ = (table_size >> sort_shift_) + 2;
         const size_t entries = static_cast<size_t>(sort_buckets_) * kSortGroups + 2 * kScanTile;
-        BP_TRY(hipMalloc(&sort_matrix_, entries * 4));
-        BP_TRY(hipMalloc(&sort_offsets_, entries * 4));
-        BP_TRY(hipMalloc(&sort_status_, (entries / kScanTile + 2) * 8));
-        BP_TRY(hipMemset(sort_status_, 0, (entries / kScanTile + 2) * 8));
-        BP_TRY(hipMalloc(&coarse_, std::max<uint64_t>(n_slots, 1) * 48));
+        BP_TRY(sort_matrix_.ensure(entries * 4));
+        BP_TRY(sort_offsets_.ensure(entries * 4));
+        BP_TRY(sort_status_.ensure((entries / kScanTile + 2) * 8));
+        BP_TRY(hipMemset(sort_status_.p, 0, (entries / kScanTile + 2) * 8));
+        BP_TRY(coarse_.ensure(std::max<uint64_t>(n_slots, 1) * 48));
         // the transposing coarse pass wants 2 x buckets words + a 128 KiB window of LDS: more than the 64 KiB a kernel gets
         // without asking, and more than some devices have
         const size_t base_lds = (2 * static_cast<size_t>(sort_buckets_) + 16 + 4) * 4;
@@ -1815,6 +1806,9 @@ int Broadphase::configure(uint64_t n_slots, uint64_t pair_capacity)
             transposed_coarse_ = false;
         }
     }
+    n_slots_ = n_slots;
+    capacity_ = pair_capacity;
+    table_size_ = table_size;
     return BGE_OK;
 }
 
@@ -1826,20 +1820,20 @@ int Broadphase::run(hipStream_t stream, const WorldView& w, uint64_t n, const ui
         error_ = "broadphase not configured for this many slots";
         return BGE_ERR_STATE;
     }
-    Accum* acc = static_cast<Accum*>(counters_);
-    uint32_t* cell_count = static_cast<uint32_t*>(cell_count_);
-    uint32_t* cell_start = static_cast<uint32_t*>(cell_start_);
-    uint32_t* body_rank = static_cast<uint32_t*>(sorted_slot_);
-    uint32_t* body_cell = static_cast<uint32_t*>(body_cell_);
-    uint32_t* large_list = static_cast<uint32_t*>(large_list_);
-    float4* sorted = static_cast<float4*>(sorted_aabb_);
+    Accum* acc = counters_.as<Accum>();
+    uint32_t* cell_count = cell_count_.as<uint32_t>();
+    uint32_t* cell_start = cell_start_.as<uint32_t>();
+    uint32_t* body_rank = sorted_slot_.as<uint32_t>();
+    uint32_t* body_cell = body_cell_.as<uint32_t>();
+    uint32_t* large_list = large_list_.as<uint32_t>();
+    float4* sorted = sorted_aabb_.as<float4>();
     const uint64_t shard_cap = shard_capacity(capacity_);
-    const PairSink sink{&acc->shard_count[0][0], static_cast<uint2*>(scan_stage_), shard_cap,
+    const PairSink sink{&acc->shard_count[0][0], scan_stage_.as<uint2>(), shard_cap,
                         window ? window->axis : 0u, window ? window->lo : -INFINITY, window ? window->hi : INFINITY};
     ran_ = true;
     last_compact_ = compact_records;
     if (n == 0) {
-        BP_TRY(hipMemsetAsync(counters_, 0, sizeof(Accum), stream));
+        BP_TRY(hipMemsetAsync(counters_.p, 0, sizeof(Accum), stream));
         return BGE_OK;
     }
     // the scan covers table_size_ + 2 entries (cell_start[c + 2] is read for the last cell)
@@ -1859,16 +1853,16 @@ int Broadphase::run(hipStream_t stream, const WorldView& w, uint64_t n, const ui
     if (lds_sort_) {
         const uint32_t groups = std::min<uint32_t>(sort_groups_, blocks_for(n, kSortThreads));
         const uint64_t chunk = (n + groups - 1) / groups;
-        uint32_t* matrix = static_cast<uint32_t*>(sort_matrix_);
-        uint32_t* offsets = static_cast<uint32_t*>(sort_offsets_);
-        float4* coarse = static_cast<float4*>(coarse_);
+        uint32_t* matrix = sort_matrix_.as<uint32_t>();
+        uint32_t* offsets = sort_offsets_.as<uint32_t>();
+        float4* coarse = coarse_.as<float4>();
         const uint32_t n_scan = sort_buckets_ * groups;
         hipLaunchKernelGGL(k_sort_hist, dim3(groups), dim3(kSortThreads), 0, stream, n, chunk, w.flags, w.aabb, acc, sort_shift_,
                            sort_buckets_, matrix, large_list);
         scan_epoch_ = (scan_epoch_ + 1u) & 0x3fffffffu;
         if (scan_epoch_ == 0u) scan_epoch_ = 1u;
         hipLaunchKernelGGL(k_scan_lookback, dim3(blocks_for(n_scan, kScanTile)), dim3(256), 0, stream, matrix, offsets,
-                           static_cast<unsigned long long*>(sort_status_), acc, n_scan, scan_epoch_, 0u);
+                           sort_status_.as<unsigned long long>(), acc, n_scan, scan_epoch_, 0u);
         const size_t fine_lds = (static_cast<size_t>(1) << sort_shift_) * 4;
         if (transposed_coarse_) {
             const uint32_t* no_u32 = nullptr;
@@ -1903,7 +1897,7 @@ int Broadphase::run(hipStream_t stream, const WorldView& w, uint64_t n, const ui
         scan_epoch_ = (scan_epoch_ + 1u) & 0x3fffffffu;
         if (scan_epoch_ == 0u) scan_epoch_ = 1u; // 0 is what a never-written status word holds
         hipLaunchKernelGGL(k_scan_lookback, dim3(blocks_for(scan_n, kScanTile)), dim3(256), 0, stream, cell_count, cell_start,
-                           static_cast<unsigned long long*>(scan_status_), acc, scan_n, scan_epoch_, 1u);
+                           scan_status_.as<unsigned long long>(), acc, scan_n, scan_epoch_, 1u);
         if (compact_records) {
             hipLaunchKernelGGL(k_bp_scatter<true>, dim3(slot_blocks), dim3(256), 0, stream, n, w.flags, w.aabb, cell_start, body_cell,
                                body_rank, w.group, w.mask, palette->class_of_slot, entity_of_slot, sorted);
@@ -1944,13 +1938,13 @@ int Broadphase::query_boxes(hipStream_t stream, const WorldView& w, const uint32
         return BGE_ERR_STATE;
     }
     if (q.n_boxes == 0) return BGE_OK;
-    const Accum* acc = static_cast<const Accum*>(counters_);
+    const Accum* acc = counters_.as<const Accum>();
     hipLaunchKernelGGL(k_bp_classify_boxes, dim3(blocks_for(q.n_boxes, 256)), dim3(256), 0, stream, acc, q.n_boxes, q.aabb, q.counters,
                        q.big_list, q.grid_list);
     const dim3 grid(std::min<uint32_t>(blocks_for(q.n_boxes, 4), 2048u));
-    const uint32_t* cell_start = static_cast<const uint32_t*>(cell_start_);
-    const float4* sorted = static_cast<const float4*>(sorted_aabb_);
-    const uint32_t* large_list = static_cast<const uint32_t*>(large_list_);
+    const uint32_t* cell_start = cell_start_.as<const uint32_t>();
+    const float4* sorted = sorted_aabb_.as<const float4>();
+    const uint32_t* large_list = large_list_.as<const uint32_t>();
     if (last_compact_) {
         hipLaunchKernelGGL(k_bp_query_boxes<true>, grid, dim3(256), 0, stream, acc, cell_start, sorted, palette->table, q.aabb, q.group, q.mask,
                            q.entity, q.grid_list, q.counters, large_list, w.aabb, w.flags, w.group, w.mask, entity_of_slot, q.out, q.cap);
@@ -1965,15 +1959,15 @@ int Broadphase::query_boxes(hipStream_t stream, const WorldView& w, const uint32
 
 PairSlices Broadphase::slices() const
 {
-    const Accum* acc = static_cast<const Accum*>(counters_);
-    return PairSlices{static_cast<const uint2*>(scan_stage_), &acc->shard_count[0][0], shard_capacity(capacity_), kShards};
+    const Accum* acc = counters_.as<const Accum>();
+    return PairSlices{scan_stage_.as<const uint2>(), &acc->shard_count[0][0], shard_capacity(capacity_), kShards};
 }
 
 int Broadphase::compact(hipStream_t stream)
 {
     if (!ran_ || compacted_) return BGE_OK;
-    hipLaunchKernelGGL(k_bp_compact, dim3(kShards * kCompactParts), dim3(256), 0, stream, static_cast<Accum*>(counters_),
-                       static_cast<const uint2*>(scan_stage_), shard_capacity(capacity_), static_cast<uint2*>(pairs_), capacity_);
+    hipLaunchKernelGGL(k_bp_compact, dim3(kShards * kCompactParts), dim3(256), 0, stream, counters_.as<Accum>(),
+                       scan_stage_.as<const uint2>(), shard_capacity(capacity_), pairs_.as<uint2>(), capacity_);
     BP_TRY(hipGetLastError());
     compacted_ = true;
     return BGE_OK;
@@ -1983,7 +1977,7 @@ int Broadphase::download(hipStream_t stream, uint32_t* pairs2, uint64_t cap, uin
 {
     *total = 0;
     if (!ran_) return BGE_OK;
-    const Accum* acc = static_cast<const Accum*>(counters_);
+    const Accum* acc = counters_.as<const Accum>();
     unsigned long long counts[kShards][8];
     uint32_t scan_error = 0;
     BP_TRY(hipMemcpyAsync(counts, acc->shard_count, sizeof counts, hipMemcpyDeviceToHost, stream));
@@ -2010,7 +2004,7 @@ int Broadphase::download(hipStream_t stream, uint32_t* pairs2, uint64_t cap, uin
     const uint64_t take = std::min<uint64_t>(std::min<uint64_t>(both[1], cap), capacity_);
     if (take && pairs2) {
         if (int rc = compact(stream)) return rc;
-        BP_TRY(hipMemcpyAsync(pairs2, pairs_, take * 8, hipMemcpyDeviceToHost, stream));
+        BP_TRY(hipMemcpyAsync(pairs2, pairs_.p, take * 8, hipMemcpyDeviceToHost, stream));
         BP_TRY(hipStreamSynchronize(stream));
     }
     return BGE_OK;

@@ -6,6 +6,7 @@
 #include <cstdint>
 #include <string>
 
+#include "bge_device_buffer.hpp"
 #include "bge_kernels.hpp"
 
 namespace bge {
@@ -61,9 +62,8 @@ public:
     int download(hipStream_t stream, uint32_t* pairs2, uint64_t cap, uint64_t* total);
     // The search leaves the pairs in 64 shard slices; this builds the compact list (idempotent until the next run).
     int compact(hipStream_t stream);
-    void release();
     const char* error() const { return error_.c_str(); }
-    void* pairs_device() const { return pairs_; }
+    void* pairs_device() const { return pairs_.p; }
     uint64_t capacity() const { return capacity_; }
     uint64_t configured_slots() const { return n_slots_; }
 
@@ -73,27 +73,27 @@ private:
     uint64_t n_slots_ = 0;
     uint64_t capacity_ = 0;
     uint32_t table_size_ = 0;
-    void* pairs_ = nullptr;      // uint32[capacity][2] compact list
-    void* scan_stage_ = nullptr; // sharded staging of the pair list
-    void* counters_ = nullptr;   // device scalars (pair count, bounds, ...)
-    void* cell_count_ = nullptr; // uint32[table_size + 1]
-    void* cell_start_ = nullptr; // uint32[table_size + 1]
-    void* scan_status_ = nullptr; // uint64[tiles] status words of the single-pass scan
+    DevBuf pairs_;       // uint32[capacity][2] compact list
+    DevBuf scan_stage_;  // sharded staging of the pair list
+    DevBuf counters_;    // device scalars (pair count, bounds, ...)
+    DevBuf cell_count_;  // uint32[table_size + 1]
+    DevBuf cell_start_;  // uint32[table_size + 1]
+    DevBuf scan_status_; // uint64[tiles] status words of the single-pass scan
     uint32_t scan_epoch_ = 0;
     bool full_records_ = false;
     // two-level LDS counting sort (k_sort_*)
     bool lds_sort_ = false;
     uint32_t sort_shift_ = 12, sort_buckets_ = 0;
-    void *sort_matrix_ = nullptr, *sort_offsets_ = nullptr, *sort_status_ = nullptr, *coarse_ = nullptr;
+    DevBuf sort_matrix_, sort_offsets_, sort_status_, coarse_;
     bool fused_bounds_ = true;      // grid from the tick kernel's per-wave partials (TickParams::bp_partial) when the caller has them; BGE_BP_BOUNDS=pass for A/B
     uint32_t sort_groups_ = 512;    // chunk workgroups of the coarse passes (BGE_BP_SORT_GROUPS lowers it: tests)
     uint32_t fine_window_[2] = {0, 0}; // records in k_sort_fine_t's LDS window: [0] 48-byte records, [1] 32-byte records
     bool small_palette_ = true;     // wave search: one compatibility word per class when the palette has <= 32 classes
     bool transposed_coarse_ = true; // k_sort_coarse_t (bucket-ordered write-out) instead of k_sort_coarse<true>; BGE_BP_COARSE=scatter for A/B
-    void* sorted_slot_ = nullptr; // uint32[n_slots]
-    void* sorted_aabb_ = nullptr; // float4[n_slots][3] sorted records
-    void* body_cell_ = nullptr;   // int32[n_slots][4]
-    void* large_list_ = nullptr;  // uint32[n_slots]
+    DevBuf sorted_slot_; // uint32[n_slots]
+    DevBuf sorted_aabb_; // float4[n_slots][3] sorted records
+    DevBuf body_cell_;   // int32[n_slots][4]
+    DevBuf large_list_;  // uint32[n_slots]
     bool ran_ = false;
     bool last_compact_ = false;   // record format of the last run (32-byte records with a filter class)
     bool compacted_ = false;

@@ -126,9 +126,9 @@ int RootComm::init(int nranks, int rank, const void* id128, uint64_t rows_per_ra
     frame_ = 0;
     COMM_HIP(hipStreamCreateWithFlags(&side_, hipStreamNonBlocking));
     for (int b = 0; b < kRing; ++b) {
-        COMM_HIP(hipMalloc(reinterpret_cast<void**>(&send_[b]), rows_ * kRowFloats * 4));
-        COMM_HIP(hipMalloc(reinterpret_cast<void**>(&table_[b]), rows_ * kRowFloats * 4 * static_cast<size_t>(nranks)));
-        COMM_HIP(hipMemset(send_[b], 0, rows_ * kRowFloats * 4));
+        COMM_HIP(send_[b].ensure(rows_ * kRowFloats * 4));
+        COMM_HIP(table_[b].ensure(rows_ * kRowFloats * 4 * static_cast<size_t>(nranks)));
+        COMM_HIP(hipMemset(send_[b].p, 0, rows_ * kRowFloats * 4));
         COMM_HIP(hipEventCreateWithFlags(&packed_[b], hipEventDisableTiming));
         COMM_HIP(hipEventCreateWithFlags(&gathered_[b], hipEventDisableTiming));
         in_flight_[b] = false;
@@ -145,7 +145,7 @@ int RootComm::begin_frame(hipStream_t compute, float** send)
         const int done = static_cast<int>((frame_ - kWaitEvery) % kRing);
         if (in_flight_[done]) COMM_HIP(hipStreamWaitEvent(compute, gathered_[done], 0));
     }
-    *send = send_[b];
+    *send = send_[b].as<float>();
     return BGE_OK;
 }
 
@@ -160,19 +160,19 @@ int RootComm::gather(hipStream_t compute, void** table_device)
         COMM_NCCL(rccl().GroupStart());
         ncclResult_t first_error = ncclSuccess;
         for (int p = 0; p < nranks_; ++p) {
-            ncclResult_t e = rccl().Send(send_[b], words, ncclFloat32, p, static_cast<ncclComm_t>(comm_), side_);
+            ncclResult_t e = rccl().Send(send_[b].p, words, ncclFloat32, p, static_cast<ncclComm_t>(comm_), side_);
             if (e != ncclSuccess && first_error == ncclSuccess) first_error = e;
-            e = rccl().Recv(table_[b] + static_cast<size_t>(p) * words, words, ncclFloat32, p, static_cast<ncclComm_t>(comm_), side_);
+            e = rccl().Recv(table_[b].as<float>() + static_cast<size_t>(p) * words, words, ncclFloat32, p, static_cast<ncclComm_t>(comm_), side_);
             if (e != ncclSuccess && first_error == ncclSuccess) first_error = e;
         }
         COMM_NCCL(rccl().GroupEnd());
         if (first_error != ncclSuccess) return fail(BGE_ERR_HIP, std::string("ncclSend/ncclRecv: ") + rccl().GetErrorString(first_error));
     } else {
-        COMM_NCCL(rccl().AllGather(send_[b], table_[b], rows_ * kRowFloats, ncclFloat32, static_cast<ncclComm_t>(comm_), side_));
+        COMM_NCCL(rccl().AllGather(send_[b].p, table_[b].p, rows_ * kRowFloats, ncclFloat32, static_cast<ncclComm_t>(comm_), side_));
     }
     COMM_HIP(hipEventRecord(gathered_[b], side_));
     in_flight_[b] = true;
-    if (table_device) *table_device = table_[b];
+    if (table_device) *table_device = table_[b].p;
     ++frame_;
     return BGE_OK;
 }
@@ -240,11 +240,10 @@ void RootComm::destroy()
     if (comm_) (void)rccl().CommDestroy(static_cast<ncclComm_t>(comm_));
     comm_ = nullptr;
     for (int b = 0; b < kRing; ++b) {
-        if (send_[b]) (void)hipFree(send_[b]);
-        if (table_[b]) (void)hipFree(table_[b]);
+        send_[b].release(); // (init() sizes them anew for its rows and ranks)
+        table_[b].release();
         if (packed_[b]) (void)hipEventDestroy(packed_[b]);
         if (gathered_[b]) (void)hipEventDestroy(gathered_[b]);
-        send_[b] = table_[b] = nullptr;
         packed_[b] = gathered_[b] = nullptr;
         in_flight_[b] = false;
     }

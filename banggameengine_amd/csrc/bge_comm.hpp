@@ -6,6 +6,8 @@
 #include <cstdint>
 #include <string>
 
+#include "bge_device_buffer.hpp"
+
 namespace bge {
 
 class RootComm {
@@ -15,7 +17,7 @@ public:
     bool ready() const { return comm_ != nullptr; }
     uint64_t rows_per_rank() const { return rows_; }
     int nranks() const { return nranks_; }
-    const void* last_table() const { return frame_ ? table_[(frame_ - 1) % kRing] : nullptr; }
+    const void* last_table() const { return frame_ ? table_[(frame_ - 1) % kRing].p : nullptr; }
     // Buffer ring: frame t uses pair t % kRing.  The compute stream waits on the side stream only every kWaitEvery
     // frames (on the gather of frame t - kWaitEvery); a pair is therefore reused no earlier than kRing - kWaitEvery + 1
     // frames after a gather that is known to be complete.  A cross-stream wait costs ~4 us of dispatch gap on the
@@ -57,8 +59,8 @@ private:
     uint64_t rows_ = 0;
     uint64_t frame_ = 0;
     hipStream_t side_ = nullptr;
-    float* send_[kRing] = {};
-    float* table_[kRing] = {};
+    DevBuf send_[kRing];  // float[rows][kRowFloats]
+    DevBuf table_[kRing]; // ... of every rank
     hipEvent_t packed_[kRing] = {};   // compute -> side: roots of the frame are packed
     hipEvent_t gathered_[kRing] = {}; // side -> compute: the gather of that frame is complete
     bool in_flight_[kRing] = {};

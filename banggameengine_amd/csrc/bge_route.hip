@@ -246,32 +246,10 @@ int ShardRouter::fail(int code, const char* what, hipError_t e)
         if (e_ != hipSuccess) return fail(e_ == hipErrorOutOfMemory ? BGE_ERR_OOM : BGE_ERR_HIP, #expr, e_); \
     } while (0)
 
-int ShardRouter::ensure(void** p, size_t* have, size_t need)
-{
-    if (*have >= need && *p) return BGE_OK;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    *have = 0;
-    const size_t bytes = std::max<size_t>(need + need / 4, 256);
-    RT_TRY(hipMalloc(p, bytes));
-    *have = bytes;
-    return BGE_OK;
-}
-
-void ShardRouter::release()
-{
-    for (void** p : {&scalars_, &hist_, &rx_flags_, &rx_aabb_, &rx_group_, &rx_mask_, &rx_entity_}) {
-        if (*p) (void)hipFree(*p);
-        *p = nullptr;
-    }
-    rx_flags_b_ = rx_aabb_b_ = rx_group_b_ = rx_mask_b_ = rx_entity_b_ = 0;
-    counted_ = false;
-}
-
 int ShardRouter::bounds(hipStream_t stream, const WorldView& w, uint64_t n_slots, float mn[3], float mx[3], uint64_t* n_bodies)
 {
-    if (!scalars_) RT_TRY(hipMalloc(&scalars_, sizeof(RouteScalars)));
-    RouteScalars* sc = static_cast<RouteScalars*>(scalars_);
+    RT_TRY(scalars_.ensure(sizeof(RouteScalars)));
+    RouteScalars* sc = scalars_.as<RouteScalars>();
     hipLaunchKernelGGL(k_route_reset, dim3(1), dim3(256), 0, stream, sc);
     if (n_slots) hipLaunchKernelGGL(k_route_bounds, dim3(std::min<uint32_t>(grid_for_slots(n_slots), 1024)), dim3(256), 0, stream, n_slots, w.flags, w.aabb, sc);
     RT_TRY(hipGetLastError());
@@ -293,18 +271,18 @@ int ShardRouter::histogram(hipStream_t stream, const WorldView& w, uint64_t n_sl
         error_ = "histogram needs axis 0..2, 1 <= bins <= 4096 and lo <= hi";
         return BGE_ERR_INVALID;
     }
-    if (!hist_) RT_TRY(hipMalloc(&hist_, kMaxHistBins * sizeof(unsigned long long)));
-    RT_TRY(hipMemsetAsync(hist_, 0, bins * sizeof(unsigned long long), stream));
+    RT_TRY(hist_.ensure(kMaxHistBins * sizeof(unsigned long long)));
+    RT_TRY(hipMemsetAsync(hist_.p, 0, bins * sizeof(unsigned long long), stream));
     const float width = (hi - lo) / static_cast<float>(bins);
     const float inv_width = width > 0.0f ? 1.0f / width : 0.0f;
     if (n_slots) {
         // 256 workgroups: each merges up to `bins` LDS counters into the global histogram with atomics
         hipLaunchKernelGGL(k_route_hist, dim3(std::min<uint32_t>(grid_for_slots(n_slots), 256)), dim3(256), 0, stream, n_slots, w.flags,
-                           w.aabb, axis, lo, inv_width, bins, static_cast<unsigned long long*>(hist_));
+                           w.aabb, axis, lo, inv_width, bins, hist_.as<unsigned long long>());
         RT_TRY(hipGetLastError());
     }
     static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "64-bit counters");
-    RT_TRY(hipMemcpyAsync(hist_host, hist_, bins * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+    RT_TRY(hipMemcpyAsync(hist_host, hist_.p, bins * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
     RT_TRY(hipStreamSynchronize(stream));
     return BGE_OK;
 }
@@ -323,8 +301,8 @@ int ShardRouter::count(hipStream_t stream, const WorldView& w, uint64_t n_slots,
             return BGE_ERR_INVALID;
         }
     }
-    if (!scalars_) RT_TRY(hipMalloc(&scalars_, sizeof(RouteScalars)));
-    RouteScalars* sc = static_cast<RouteScalars*>(scalars_);
+    RT_TRY(scalars_.ensure(sizeof(RouteScalars)));
+    RouteScalars* sc = scalars_.as<RouteScalars>();
     hipLaunchKernelGGL(k_route_reset, dim3(1), dim3(256), 0, stream, sc);
     float cuts[kMaxSlabs + 1];
     for (uint32_t k = 0; k <= kMaxSlabs; ++k) cuts[k] = (k >= 1 && k < nranks) ? cuts_host[k] : (k == 0 ? -INFINITY : INFINITY);
@@ -364,7 +342,7 @@ int ShardRouter::pack(hipStream_t stream, const WorldView& w, uint64_t n_slots, 
         return BGE_ERR_INVALID;
     }
     hipLaunchKernelGGL(k_route_pack, dim3(grid_for_slots(n_slots)), dim3(256), 0, stream, n_slots, w.flags, w.aabb, w.group, w.mask,
-                       global_of_slot, axis_, nranks_, static_cast<RouteScalars*>(scalars_), static_cast<float4*>(send_device));
+                       global_of_slot, axis_, nranks_, scalars_.as<RouteScalars>(), static_cast<float4*>(send_device));
     RT_TRY(hipGetLastError());
     return BGE_OK;
 }
@@ -372,23 +350,25 @@ int ShardRouter::pack(hipStream_t stream, const WorldView& w, uint64_t n_slots, 
 int ShardRouter::unpack(hipStream_t stream, const void* records_device, uint64_t n, WorldView* view, const uint32_t** entity_ids)
 {
     const size_t m = std::max<uint64_t>(n, 1);
-    if (int rc = ensure(&rx_flags_, &rx_flags_b_, m * 4)) return rc;
-    if (int rc = ensure(&rx_aabb_, &rx_aabb_b_, m * 24)) return rc;
-    if (int rc = ensure(&rx_group_, &rx_group_b_, m * 4)) return rc;
-    if (int rc = ensure(&rx_mask_, &rx_mask_b_, m * 4)) return rc;
-    if (int rc = ensure(&rx_entity_, &rx_entity_b_, m * 4)) return rc;
+    // the number of records changes from tick to tick: grow with 25 % headroom, at least 256 bytes
+    auto grow = [](DevBuf& b, size_t need) { return need <= b.bytes ? hipSuccess : b.ensure(std::max<size_t>(need + need / 4, 256)); };
+    RT_TRY(grow(rx_flags_, m * 4));
+    RT_TRY(grow(rx_aabb_, m * 24));
+    RT_TRY(grow(rx_group_, m * 4));
+    RT_TRY(grow(rx_mask_, m * 4));
+    RT_TRY(grow(rx_entity_, m * 4));
     if (n) {
         hipLaunchKernelGGL(k_route_unpack, dim3(static_cast<uint32_t>((n + 255) / 256)), dim3(256), 0, stream, n,
-                           static_cast<const float4*>(records_device), static_cast<uint32_t*>(rx_flags_), static_cast<float*>(rx_aabb_),
-                           static_cast<uint32_t*>(rx_group_), static_cast<uint32_t*>(rx_mask_), static_cast<uint32_t*>(rx_entity_));
+                           static_cast<const float4*>(records_device), rx_flags_.as<uint32_t>(), rx_aabb_.as<float>(),
+                           rx_group_.as<uint32_t>(), rx_mask_.as<uint32_t>(), rx_entity_.as<uint32_t>());
         RT_TRY(hipGetLastError());
     }
     *view = WorldView{};
-    view->flags = static_cast<uint32_t*>(rx_flags_);
-    view->aabb = static_cast<float*>(rx_aabb_);
-    view->group = static_cast<uint32_t*>(rx_group_);
-    view->mask = static_cast<uint32_t*>(rx_mask_);
-    *entity_ids = static_cast<const uint32_t*>(rx_entity_);
+    view->flags = rx_flags_.as<uint32_t>();
+    view->aabb = rx_aabb_.as<float>();
+    view->group = rx_group_.as<uint32_t>();
+    view->mask = rx_mask_.as<uint32_t>();
+    *entity_ids = rx_entity_.as<const uint32_t>();
     return BGE_OK;
 }
 

@@ -6,6 +6,7 @@
 #include <cstdint>
 #include <string>
 
+#include "bge_device_buffer.hpp"
 #include "bge_kernels.hpp"
 
 namespace bge {
@@ -29,22 +30,19 @@ public:
     // Histogram of the bodies' min corner along `axis` over [lo, hi] in `bins` equal bins (<= kMaxHistBins), for balanced cuts.
     int histogram(hipStream_t stream, const WorldView& w, uint64_t n_slots, uint32_t axis, float lo, float hi, uint32_t bins,
                   uint64_t* hist_host);
-    void release();
     const char* error() const { return error_.c_str(); }
     uint64_t total_routed() const { return total_; }
 
 private:
     int fail(int code, const char* what, hipError_t e);
-    int ensure(void** p, size_t* have, size_t need);
     std::string error_;
-    void* scalars_ = nullptr; // counts[64] | cursor[64] | cuts[65] | bounds[6] | n
-    void* hist_ = nullptr;    // unsigned long long[kMaxHistBins]
+    DevBuf scalars_; // counts[64] | cursor[64] | cuts[65] | bounds[6] | n
+    DevBuf hist_;    // unsigned long long[kMaxHistBins]
     uint32_t axis_ = 0, nranks_ = 0;
     uint64_t total_ = 0;
     bool counted_ = false;
     // receive-side arrays
-    void *rx_flags_ = nullptr, *rx_aabb_ = nullptr, *rx_group_ = nullptr, *rx_mask_ = nullptr, *rx_entity_ = nullptr;
-    size_t rx_flags_b_ = 0, rx_aabb_b_ = 0, rx_group_b_ = 0, rx_mask_b_ = 0, rx_entity_b_ = 0;
+    DevBuf rx_flags_, rx_aabb_, rx_group_, rx_mask_, rx_entity_;
 };
 
 } // namespace bge

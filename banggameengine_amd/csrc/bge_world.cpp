@@ -20,6 +20,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "bge_device_buffer.hpp"
 #include "bge_broadphase.hpp"
 #include "bge_route.hpp"
 #include "bge_comm.hpp"
@@ -74,42 +75,10 @@ int fail(int code, const char* fmt, ...)
         }                                                                                                  \
     } while (0)
 
-struct DevBuf {
-    void* p = nullptr;
-    size_t bytes = 0;
-    hipError_t ensure(size_t need)
-    {
-        if (need <= bytes) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        bytes = 0;
-        const hipError_t e = hipMalloc(&p, need);
-        if (e == hipSuccess) bytes = need;
-        return e;
-    }
-    void release()
-    {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        bytes = 0;
-    }
-    template <class T> T* as() const { return static_cast<T*>(p); }
-};
-
-// A DevBuf that frees itself: temporaries of one call (an early HIP_TRY return must not leak them).
-struct TmpBuf : DevBuf {
-    TmpBuf() = default;
-    TmpBuf(const TmpBuf&) = delete;
-    TmpBuf& operator=(const TmpBuf&) = delete;
-    TmpBuf(TmpBuf&& o) noexcept
-    {
-        p = o.p;
-        bytes = o.bytes;
-        o.p = nullptr;
-        o.bytes = 0;
-    }
-    ~TmpBuf() { release(); }
-};
+// Every device block of the world is a DevBuf, every page-locked one a PinnedBuf (bge_device_buffer.hpp): members and the
+// temporaries of one call alike free themselves (an early HIP_TRY return must not leak them).
+using bge::DevBuf;
+using bge::PinnedBuf;
 
 // A per-slot device array and its format, set once where the member is declared: upload, download, allocation and the carry of
 // bge_world_set_topology read it from here.
@@ -147,14 +116,13 @@ struct EntityBuf : DevBuf {
         if (!p) return BGE_OK;
         const size_t row = words * 4;
         if (n > rows) {
-            TmpBuf grown;
+            DevBuf grown;
             HIP_TRY(grown.ensure(n * row));
             HIP_TRY(hipMemsetAsync(grown.p, 0xff, n * row, stream));
             const uint64_t keep = std::min(old_n, rows);
             if (keep) HIP_TRY(hipMemcpyAsync(grown.p, p, keep * row, hipMemcpyDeviceToDevice, stream));
             HIP_TRY(hipStreamSynchronize(stream));
-            std::swap(p, grown.p);
-            std::swap(bytes, grown.bytes);
+            std::swap<DevBuf>(*this, grown);
             rows = n;
         } else if (n < old_n) {
             HIP_TRY(hipMemsetAsync(static_cast<char*>(p) + n * row, 0xff, (std::min(old_n, rows) - n) * row, stream));
@@ -342,7 +310,7 @@ struct bge_world {
     bge::Broadphase island_bp;
     DevBuf isl_slot_words, isl_counts, isl_identity, isl_gen, isl_keys_raw, isl_keys[2], isl_man[2], isl_body_keys_raw, isl_body_slot_raw,
         isl_body_keys, isl_body_slot, isl_solver_bodies, isl_rows, isl_sort_tmp, isl_big_list, isl_body_words, isl_ints;
-    uint32_t* isl_counts_host = nullptr; // pinned
+    PinnedBuf isl_counts_host;
     int isl_cur = 0;
     uint32_t isl_n_prev = 0;
     uint64_t isl_identity_n = 0;
@@ -467,7 +435,7 @@ struct bge_world {
     // table holds exactly them — it is rebuilt from them after every tick that went the long way or changed them on the host.
     DevBuf trig_tab[2], trig_delta_dev, trig_keys_dev;
     uint32_t trig_tab_log2 = 0;
-    void* trig_delta_host = nullptr;      // hipHostMalloc
+    PinnedBuf trig_delta_host;
     bool trig_mirror_valid = false;
     bool trig_device_diff = true;         // BGE_TRIGGER_DEVICE_DIFF=0 keeps every tick on the host's path (A/B, tests)
     bool trig_stay_events = true;         // bge_world_set_trigger_stay_events
@@ -536,32 +504,12 @@ struct bge_world {
         view.rs_word = rs_word.as<uint32_t>();
         view.adv = adv.as<uint32_t>();
     }
-    void release_all()
+    // What is not memory; every buffer above frees itself after this body.  The caller has set the world's device and destroys
+    // the world's own stream afterwards (bge_world_destroy).
+    ~bge_world()
     {
-        for (SlotBuf* a : carried) a->release();
-        for (DevBuf* b : std::initializer_list<DevBuf*>{&flags, &parent, &tile_hdr, &slot_of_entity, &entity_of_slot, &root_slots, &root_index, &root_worlds, &counter, &stage,
-                          &stage2, &mass_palette, &normal, &filter_table, &grav_palette, &bp_partials, &obstacle_slots, &obstacle_gen, &obstacles, &obstacle_grid, &box_list, &box_count, &frozen, &rs_word, &adv, &trig_slot, &trig_entity, &trig_he, &trig_group,
-                          &trig_mask, &trig_active, &trig_aabb, &trig_pairs, &trig_count, &trig_lists, &ground_list, &ground_count, &trig_tab[0], &trig_tab[1],
-                          &trig_delta_dev, &trig_keys_dev, &trig_pose, &query_in, &query_out, &query_keys, &query_all, &query_all_count, &query_ghosts, &qi_count, &qi_start, &qi_cell, &qi_rec_a, &qi_rec_b, &qi_rec_c, &qi_scan, &qi_words, &qi_far, &move_in, &move_out, &move_state, &move_casts, &move_hits, &step_in, &step_out, &step_state, &step_casts, &step_hits, &recover_in, &recover_out, &recover_state, &recover_queries, &recover_hits, &char_desc, &char_input, &char_state, &char_recover_in, &char_recover_out, &char_step_in, &char_step_out, &char_scratch, &char_ride, &crowd_in, &crowd_out, &crowd_rec_a, &crowd_rec_b, &crowd_cell, &crowd_count, &crowd_start, &crowd_scan, &crowd_rmax, &char_crowd_hits, &char_crowd_group, &char_crowd_mask, &imp_in, &imp_status, &imp_keys[0], &imp_keys[1], &imp_vals[0], &imp_vals[1], &imp_sort, &char_push_records, &ct_group, &ct_mask, &ct_bits[0], &ct_bits[1], &ct_counts, &ct_row_total, &ct_row_base, &ct_ghost_rec, &ct_events, &ct_count, &ct_src_row, &dbg_block_sum, &dbg_block_off,
-                          &dbg_lines, &dbg_total, &bounds, &cull_ballots, &cull_block_sum, &cull_block_off, &cull_out, &cull_total, &draw_keys,
-                          &batch_sort, &batch_hist, &batch_out}) {
-            b->release();
-        }
-        if (trig_delta_host) (void)hipHostFree(trig_delta_host);
-        trig_delta_host = nullptr;
-        broadphase.release();
-        slab_broadphase.release();
-        island_bp.release();
-        for (DevBuf* b : {&isl_slot_words, &isl_counts, &isl_identity, &isl_gen, &isl_keys_raw, &isl_keys[0], &isl_keys[1], &isl_man[0], &isl_man[1], &isl_body_keys_raw,
-                          &isl_body_slot_raw, &isl_body_keys, &isl_body_slot, &isl_solver_bodies, &isl_rows, &isl_sort_tmp, &isl_big_list, &isl_body_words, &isl_ints})
-            b->release();
-        if (isl_counts_host) (void)hipHostFree(isl_counts_host);
-        isl_counts_host = nullptr;
-        router.release();
-        for (DevBuf* b : {&global_of_slot, &bp_send, &bp_recv, &bp_small, &bp_hist}) b->release();
         comm.destroy();
         for (hipEvent_t e : prof_events) (void)hipEventDestroy(e);
-        prof_events.clear();
     }
 };
 
@@ -904,7 +852,7 @@ int rebuild_trigger_mirror(bge_world* w)
     const size_t bytes = sizeof(uint64_t) << w->trig_tab_log2;
     for (DevBuf& b : w->trig_tab) HIP_TRY(b.ensure(bytes));
     HIP_TRY(w->trig_delta_dev.ensure(kTrigHeaderWords * 4 + static_cast<size_t>(kTrigDeltaCap) * 8));
-    if (!w->trig_delta_host) HIP_TRY(hipHostMalloc(&w->trig_delta_host, kTrigHeaderWords * 4 + static_cast<size_t>(kTrigDeltaCap) * 8, hipHostMallocDefault));
+    HIP_TRY(w->trig_delta_host.ensure(kTrigHeaderWords * 4 + static_cast<size_t>(kTrigDeltaCap) * 8));
     HIP_TRY(hipMemsetAsync(w->trig_tab[0].p, 0xff, bytes, w->stream)); // this tick's table for the next diff
     HIP_TRY(hipMemsetAsync(w->trig_tab[1].p, 0xff, bytes, w->stream)); // last tick's
     HIP_TRY(hipMemsetAsync(w->trig_delta_dev.p, 0, kTrigHeaderWords * 4, w->stream));
@@ -941,7 +889,7 @@ int process_trigger_pairs_fast(bge_world* w)
     HIP_TRY(bge::launch_trigger_diff(w->stream, d));
     // the header and the first 1,024 deltas in one copy; a tick with more changes fetches the rest in a second one
     constexpr uint32_t kFirst = 1024;
-    uint32_t* host = static_cast<uint32_t*>(w->trig_delta_host);
+    uint32_t* host = w->trig_delta_host.as<uint32_t>();
     HIP_TRY(hipMemcpyAsync(host, w->trig_delta_dev.p, kTrigHeaderWords * 4 + kFirst * 8, hipMemcpyDeviceToHost, w->stream));
     HIP_TRY(hipStreamSynchronize(w->stream));
     const uint32_t n_delta = host[0], n_pairs = host[3];
@@ -1136,7 +1084,8 @@ int island_substep(bge_world* w, bge::GroundParams& gp, uint64_t n_slots, bool b
         HIP_TRY(w->isl_counts.ensure(64));
         HIP_TRY(hipMemsetAsync(w->isl_counts.p, 0, 64, w->stream));
     }
-    if (!w->isl_counts_host) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&w->isl_counts_host), 64));
+    HIP_TRY(w->isl_counts_host.ensure(64));
+    const uint32_t* const counts_host = w->isl_counts_host.as<uint32_t>();
     if (w->isl_identity_n < n_slots) {
         std::vector<uint32_t> iota(n_slots);
         for (uint64_t i = 0; i < n_slots; ++i) iota[i] = static_cast<uint32_t>(i);
@@ -1205,14 +1154,14 @@ int island_substep(bge_world* w, bge::GroundParams& gp, uint64_t n_slots, bool b
         ip.bp_shard_cap = sl.shard_cap;
         ip.bp_shards = sl.shards;
         HIP_TRY(bge::launch_island_pair_keys(w->stream, w->view, ip));
-        HIP_TRY(hipMemcpyAsync(w->isl_counts_host, w->isl_counts.p, 16, hipMemcpyDeviceToHost, w->stream));
+        HIP_TRY(hipMemcpyAsync(w->isl_counts_host.p, w->isl_counts.p, 16, hipMemcpyDeviceToHost, w->stream));
         HIP_TRY(hipStreamSynchronize(w->stream));
-        if (w->isl_counts_host[3] & 5u) {
+        if (counts_host[3] & 5u) {
             HIP_TRY(hipMemsetAsync(w->isl_counts.p, 0, 64, w->stream));
             return fail(BGE_ERR_HIP, "internal error in the island solver of the previous sub-step (bits %#x): row pool exhausted or an obstacle record missing",
-                        w->isl_counts_host[3]);
+                        counts_host[3]);
         }
-        if (!(w->isl_counts_host[3] & 2u) && w->isl_counts_host[0] <= ip.pair_cap) {
+        if (!(counts_host[3] & 2u) && counts_host[0] <= ip.pair_cap) {
             w->bp_shared = shared;
             break;
         }
@@ -1227,7 +1176,7 @@ int island_substep(bge_world* w, bge::GroundParams& gp, uint64_t n_slots, bool b
         }
         w->isl_pair_cap = cap * 2; // (the pair search is repeated on the same boxes: nothing else of the sub-step has run yet)
     }
-    const uint32_t n_pairs = w->isl_counts_host[0];
+    const uint32_t n_pairs = counts_host[0];
     w->isl_last_pairs = n_pairs;
     w->isl_last_bodies = 0;
     const int cur = w->isl_cur, prev = cur ^ 1;
@@ -1255,9 +1204,9 @@ int island_substep(bge_world* w, bge::GroundParams& gp, uint64_t n_slots, bool b
     w->isl_n_prev = n_pairs;
     if (n_pairs == 0 && !later_sub_step) return BGE_OK;
     HIP_TRY(bge::launch_island_build(w->stream, w->view, ip, later_sub_step));
-    HIP_TRY(hipMemcpyAsync(w->isl_counts_host, w->isl_counts.p, 16, hipMemcpyDeviceToHost, w->stream));
+    HIP_TRY(hipMemcpyAsync(w->isl_counts_host.p, w->isl_counts.p, 16, hipMemcpyDeviceToHost, w->stream));
     HIP_TRY(hipStreamSynchronize(w->stream));
-    const uint32_t n_bodies = w->isl_counts_host[1];
+    const uint32_t n_bodies = counts_host[1];
     w->isl_last_bodies = n_bodies;
     if (n_bodies == 0) return BGE_OK;
     HIP_TRY(w->isl_body_keys.ensure(static_cast<size_t>(n_bodies) * 8));
@@ -1381,9 +1330,9 @@ void bge_world_destroy(bge_world* w)
         std::fprintf(stderr, "[bge] trigger diff on the device: %llu ticks, %.3f ms per tick until the deltas were on the host, %.3f ms applying %.0f of them\n",
                      (unsigned long long)w->trig_fast_ticks, w->trig_wait_ms / w->trig_fast_ticks, w->trig_apply_ms / w->trig_fast_ticks,
                      double(w->trig_deltas_seen) / w->trig_fast_ticks);
-    w->release_all();
-    if (w->own_stream) (void)hipStreamDestroy(w->stream);
-    delete w;
+    const hipStream_t own = w->own_stream ? w->stream : nullptr;
+    delete w; // frees every buffer, inside the guard
+    if (own) (void)hipStreamDestroy(own);
 }
 
 // Character platform riding: the anchors on entities [first, first + count) are cleared, on the stream (bge_world_set_topology: all
@@ -1465,13 +1414,13 @@ try {
     const uint64_t n_keep = carry ? std::min<uint64_t>(n, w->flat.n_entities) : 0;
     struct Carry {
         SlotBuf* buf;
-        TmpBuf tmp;
+        DevBuf tmp;
     };
     std::vector<Carry> carries;
-    TmpBuf old_flags_tmp;
+    DevBuf old_flags_tmp;
     if (n_keep) {
         for (SlotBuf* a : w->carried) {
-            if (a->p) carries.push_back(Carry{a, TmpBuf{}}); // (an optional store that was never made has nothing to carry)
+            if (a->p) carries.push_back(Carry{a, DevBuf{}}); // (an optional store that was never made has nothing to carry)
         }
         for (Carry& c : carries) {
             HIP_TRY(c.tmp.ensure(c.buf->bytes_for(n_keep)));
@@ -1614,7 +1563,7 @@ try {
         for (uint64_t i = 0; i < n_keep; ++i) {
             if (keep_mask[i]) carry_map[i] = nf.slot_of_entity[i];
         }
-        TmpBuf map_dev;
+        DevBuf map_dev;
         HIP_TRY(map_dev.ensure(n_keep * 4));
         HIP_TRY(hipMemcpyAsync(map_dev.p, carry_map.data(), n_keep * 4, hipMemcpyHostToDevice, w->stream));
         for (Carry& c : carries) {
@@ -2655,6 +2604,12 @@ try {
 }
 BGE_CATCH_ALL("bge_host_free")
 
+void bge_device_memory(uint64_t* allocations, uint64_t* bytes)
+{
+    if (allocations) *allocations = bge::live_memory().allocations.load(std::memory_order_relaxed);
+    if (bytes) *bytes = bge::live_memory().bytes.load(std::memory_order_relaxed);
+}
+
 int bge_world_download_dirty(bge_world* w, uint64_t first, uint64_t count, uint8_t* dirty)
 try {
     if (int rc = check_range(w, first, count)) return rc;
@@ -2957,12 +2912,12 @@ int chartrig_settle(bge_world* w, uint64_t min_cap, uint32_t* count_out)
     if (count == 0xffffffffu) return fail(BGE_ERR_UNSUPPORTED, "more than 2^32 - 2 character trigger events in one call");
     const uint64_t need = std::max<uint64_t>(count, min_cap);
     if (need <= w->ct_cap) return BGE_OK;
-    TmpBuf grown;
+    DevBuf grown;
     HIP_TRY(grown.ensure(need * sizeof(bge_character_trigger_event)));
     if (count <= w->ct_cap) { // (complete as it is)
         if (count) HIP_TRY(hipMemcpy(grown.p, w->ct_events.p, uint64_t(count) * sizeof(bge_character_trigger_event), hipMemcpyDeviceToDevice));
     }
-    std::swap(static_cast<DevBuf&>(grown), w->ct_events);
+    std::swap(grown, w->ct_events);
     const bool remake = count > w->ct_cap;
     w->ct_cap = need;
     if (remake) {
@@ -3012,7 +2967,7 @@ int chartrig_permute_rows(bge_world* w, const std::vector<uint32_t>& src_row)
     const uint64_t rows = src_row.size();
     if (int rc = chartrig_size_rows(w, rows)) return rc;
     const uint64_t bytes = std::max<uint64_t>(rows * w->ct_words * 8, 8);
-    TmpBuf next;
+    DevBuf next;
     HIP_TRY(next.ensure(bytes));
     if (rows) {
         HIP_TRY(hipMemcpyAsync(w->ct_src_row.p, src_row.data(), rows * 4, hipMemcpyHostToDevice, w->stream));
@@ -3020,7 +2975,7 @@ int chartrig_permute_rows(bge_world* w, const std::vector<uint32_t>& src_row)
                                             w->ct_bits[w->ct_rem].as<unsigned long long>(), next.as<unsigned long long>()));
         HIP_TRY(hipStreamSynchronize(w->stream)); // (src_row and the old bitmap die here)
     }
-    std::swap(static_cast<DevBuf&>(next), w->ct_bits[w->ct_rem]);
+    std::swap(next, w->ct_bits[w->ct_rem]);
     DevBuf& other = w->ct_bits[1 - w->ct_rem];
     if (other.bytes < bytes) HIP_TRY(other.ensure(bytes));
     w->ct_rows = rows;

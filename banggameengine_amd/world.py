@@ -1159,6 +1159,13 @@ class PinnedArray:
             pass
 
 
+def device_memory():
+    """(allocations, bytes) the library holds in this process over all worlds (bge_device_memory); (0, 0) once every world is closed."""
+    allocations, nbytes = C.c_uint64(), C.c_uint64()
+    lib().bge_device_memory(C.byref(allocations), C.byref(nbytes))
+    return int(allocations.value), int(nbytes.value)
+
+
 def balanced_cuts(hist, lo, hi, nranks):
     """Host-only: slab boundaries at the k/nranks quantiles of an (all-reduced) axis histogram."""
     hist = _arr(hist, np.uint64)

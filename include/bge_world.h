@@ -257,6 +257,10 @@ BGE_API int bge_world_profile_read(bge_world* world, double* tick_kernel_ms, uin
  * (pageable memory: roughly a fifth of it).  Optional — every entry point accepts any host pointer. */
 BGE_API int bge_host_alloc(uint64_t bytes, void** out);
 BGE_API int bge_host_free(void* p);
+/* What the library itself holds in this process, over all worlds: the number of live blocks and their bytes (device memory and the
+ * few page-locked blocks of the worlds; bge_host_alloc memory belongs to the caller and is not counted).  Both are 0 once every
+ * world is destroyed.  Either pointer may be NULL.  Costs two atomic loads; safe from any thread. */
+BGE_API void bge_device_memory(uint64_t* allocations, uint64_t* bytes);
 
 /* Results.  `Transform::world` after TransformSystem::Update; position/rotationEuler after PhysicsSystem::Update. */
 BGE_API int bge_world_download_world(bge_world* world, uint64_t first, uint64_t count, float* out16);
